@@ -21,6 +21,11 @@ In both the accumulated parameter gradients are SUM-all-reduced ONCE per step in
 region and the densification statistics of the step are synchronised (SUM / MAX) so that every
 replica would densify identically.
 
+`--steps K` is the number of timed steps of the headline figure, in all: `--repeats` deals them to back-to-back
+regions and `value` is the median region's.  `--dump-outputs DIR` writes what the last timed step computed (images,
+radii, gradients; a fixed, seeded sample of the larger ones, <= 64 MB) as DIR/<name>.npy; the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
+
 Prints ONE JSON line on rank 0 (contract in the task statement) carrying `roofline`
 (dominant kernel, HIP events measured live on the launch stream) and `cpu_baseline`
 (the CPU oracle timed on this host's cores on the same workload: warm-up + 3 frames, median/min,
@@ -42,6 +47,58 @@ import torch.distributed as dist  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 BREAKDOWN_STEPS = 20   # untimed steps that collect the per-stage table (and bring the clocks up)
+SECONDARY_STEPS = 20   # timed steps of each secondary leg (per-view loop, multi-stream); --steps counts the headline's steps only
+DUMP_BYTES = 64_000_000   # --dump-outputs: at most this many bytes of .npy files in all
+
+
+def timed_regions(steps: int, repeats: int) -> list:
+    """The `steps` timed steps dealt to min(repeats, steps) back-to-back regions, as evenly as possible: every region
+    gets its own step time, `value` is the median region's, and the regions together run exactly `steps` steps."""
+    n = max(1, min(repeats, steps))
+    return [steps // n + (1 if k < steps % n else 0) for k in range(n)]
+
+
+def dump_outputs(dirname: str, views, params, P: int, HW: int) -> dict:
+    """--dump-outputs: what the last timed step handed its caller, as DIR/<name>.npy in float32 — per view k the image,
+    depth, alpha and radii the forward returned and the gradient of its means2D carrier (view<k>_*), and the accumulated
+    parameter gradients (grad_*) — so that two builds can be compared output for output.  At most DUMP_BYTES in all: the
+    per-Gaussian arrays (rows of [P, ...]) share ONE fixed, seeded sample of Gaussians and the per-pixel arrays (written as
+    [channels, pixels]) one of pixels, each within half the budget, indices ascending; a workload small enough is written
+    whole.  The sampled indices are written too (gaussian_index.npy, pixel_index.npy, float64)."""
+    import numpy as np
+    per_g, per_px = {}, {}
+    for k, (color, depth, alpha, radii, m2) in enumerate(views):
+        per_px.update({f"view{k}_color": color, f"view{k}_depth": depth, f"view{k}_alpha": alpha})
+        per_g[f"view{k}_radii"] = radii
+        if m2.grad is not None:
+            per_g[f"view{k}_grad_means2D"] = m2.grad
+    for name, p in zip(("means3D", "colors", "opacities", "scales", "rotations"), params):
+        if p.grad is not None:
+            per_g[f"grad_{name}"] = p.grad
+    half = DUMP_BYTES // 2 - (1 << 16)      # (the .npy headers: ~128 bytes per file)
+
+    def sample(n_all, floats_per_item, seed):
+        n = min(n_all, half // (4 * floats_per_item + 8))
+        if n == n_all:
+            return np.arange(n_all, dtype=np.int64)
+        return np.sort(np.random.default_rng(seed).choice(n_all, n, replace=False)).astype(np.int64)
+
+    gi = sample(P, sum(t.numel() // P for t in per_g.values()), 0)
+    pi = sample(HW, sum(t.numel() // HW for t in per_px.values()), 1)
+    arrays = {"gaussian_index": gi.astype(np.float64), "pixel_index": pi.astype(np.float64)}
+    with torch.no_grad():
+        for name, t in per_g.items():
+            arrays[name] = t.detach()[torch.from_numpy(gi).to(t.device)].float().cpu().numpy()
+        for name, t in per_px.items():
+            arrays[name] = t.detach().reshape(-1, HW)[:, torch.from_numpy(pi).to(t.device)].float().cpu().numpy()
+    os.makedirs(dirname, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        path = os.path.join(dirname, name + ".npy")
+        np.save(path, a)
+        total += os.path.getsize(path)
+    assert total <= DUMP_BYTES, f"--dump-outputs wrote {total} bytes (budget {DUMP_BYTES})"
+    return {"dir": dirname, "files": len(arrays), "bytes": total, "gaussians": [len(gi), P], "pixels": [len(pi), HW]}
 
 
 def algorithmic_bytes(P, R, W, H, C, tiles):
@@ -997,7 +1054,7 @@ def launch_ranks(n: int, argv) -> int:
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (in all; --repeats splits them into regions)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="S2")
     ap.add_argument("--views", type=int, default=5,
@@ -1030,11 +1087,18 @@ def main():
                     help="do not start tools/gpu_sampler.py (amdsmi activity / clock / power samples across the timed regions)")
     ap.add_argument("--truth", type=int, default=200_000, help="--stage scene: Gaussians of the synthetic ground-truth room")
     ap.add_argument("--repeats", type=int, default=5,
-                    help="the timed region of K steps is repeated this many times; value = the MEDIAN region (min / max reported)")
+                    help="the K timed steps are split into this many back-to-back regions (at most K); value = the MEDIAN "
+                         "region's step time (min / max reported)")
     ap.add_argument("--stage", default="raster",
                     choices=["raster", "activations", "loss", "map_step", "refine_step", "scene", "eval_rendering", "pose_refine"],
                     help="raster = the BASELINE metric (default); activations = the fused front-end stage alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (raster stage; rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs is not None and args.stage != "raster":
+        ap.error("--dump-outputs: the raster stage only")
 
     # stdout carries ONE JSON line.  Native libraries write banners to file descriptor 1 (RCCL under NCCL_DEBUG=VERSION: five lines per
     # process group; gloo: "[Gloo] Rank 0 is connected to ..."): Python's own stdout moves to a duplicate of the real one and fd 1 is
@@ -1147,8 +1211,10 @@ def main():
 
     side = [torch.cuda.Stream(device=dev) for _ in range(args.streams)] if args.streams > 1 else []
     mode = {"window": not args.no_window and args.streams <= 1}
+    dump = args.dump_outputs is not None and rank == 0
+    last = {"views": []}     # --dump-outputs: (color, depth, alpha, radii, means2D carrier) per view of the last timed step
 
-    def window_step(record):
+    def window_step(record, keep):
         # the whole window as ONE launch sequence: forward of the V views, ONE backward that sums their parameter
         # gradients in-kernel, then the per-view densification statistics (train_gaussians.py:238-245)
         block = torch.zeros((len(views),) + tuple(means3D.shape), dtype=means3D.dtype, device=means3D.device)
@@ -1156,6 +1222,8 @@ def main():
         span = [] if DIST_ON else None    # N > 1: the backward's gradient allocation ends with a [2, P] tail for the statistics increments
         outs = rasterize_window([rs for _, _, rs in views], means3D, carriers, colors, opac, scales=scales, rotations=rots,
                                 grad_span=span)
+        if keep:
+            last["views"] = [tuple(o[:4]) + (m2,) for o, m2 in zip(outs, carriers)]
         if record:
             for k in range(0, len(outs), 8):
                 info["R"] += [int(r) for r in outs[k][0].grad_fn.R]
@@ -1171,10 +1239,12 @@ def main():
             add_densification_stats_window([m2.grad for m2 in carriers], [o[3] for o in outs], accum, denom, max_radii)
         return None
 
-    def one_view(rast, g_out, record):
+    def one_view(rast, g_out, record, keep):
         means2D = torch.zeros_like(means3D, requires_grad=True)   # per-view grad carrier (render(): screenspace_points)
         color, depth, alpha, radii = rast(means3D=means3D, means2D=means2D, shs=None, colors_precomp=colors,
                                           opacities=opac, scales=scales, rotations=rots, cov3D_precomp=None)
+        if keep:
+            last["views"].append((color, depth, alpha, radii, means2D))
         if record:
             info["R"].append(int(color.grad_fn.num_rendered))
             info["V"].append(int((radii > 0).sum().item()))
@@ -1183,15 +1253,17 @@ def main():
             # the step's densification statistics (train_gaussians.py:238-245): the same per-frame work at every N
             add_densification_stats(means2D.grad, radii, accum, denom, max_radii)
 
-    def step(record=False):
+    def step(record=False, keep=False):
         for p in params:
             p.grad = None
+        if keep:
+            last["views"] = []
         inc = None
         if DIST_ON and not (mode["window"] and views):
             accum.zero_()      # the per-view paths accumulate the step's increments here (summed over the ranks below)
             denom.zero_()
         if mode["window"] and views:
-            inc = window_step(record)
+            inc = window_step(record, keep)
         elif side:
             # the views of a window are independent until their gradients are summed: view j runs on HIP stream
             # j % K, so the latency-bound kernels of a small frame overlap with another view's (autograd runs
@@ -1201,12 +1273,12 @@ def main():
                 st.wait_stream(main)
             for j, (rast, g_out, _) in enumerate(views):
                 with torch.cuda.stream(side[j % len(side)]):
-                    one_view(rast, g_out, record)
+                    one_view(rast, g_out, record, keep)
             for st in side:
                 main.wait_stream(st)
         else:
             for rast, g_out, _ in views:   # every frame one forward + one backward, parameter gradients accumulate
-                one_view(rast, g_out, record)
+                one_view(rast, g_out, record, keep)
         if not args.fwd_only and DIST_ON:
             # TWO collectives per step (frame_parallel.reduce_step): ONE SUM all-reduce over [accumulated parameter gradients |
             # increments of xyz_gradient_accum, denom] — in place in the backward's own allocation on the window path — and
@@ -1252,25 +1324,36 @@ def main():
     stages = _native.timing_collect()
     dom = max(stages, key=lambda s: stages[s][0]) if views else "composite_bwd"
     # (2) timed region: only the dominant kernel is bracketed (roofline.achieved is measured live
-    #     here, on the launch stream)
+    #     here, on the launch stream).  The K steps run back to back between ONE barrier + synchronize before and one
+    #     after; HIP events on the launch stream delimit the regions, so a region boundary does not drain the pipeline
     _native.timing_select([dom])
-    regions, regions_unix = [], []
-    for _ in range(max(args.repeats, 1)):       # every region: barrier + synchronize, EXACTLY K steps, barrier + synchronize
-        barrier()
-        t0, u0 = time.perf_counter(), time.time()
-        for _ in range(args.steps):
-            step()
-        barrier()
-        regions.append(time.perf_counter() - t0)
-        regions_unix.append([u0, time.time()])
+    region_steps = timed_regions(args.steps, args.repeats)
+    marks = [torch.cuda.Event(enable_timing=True) for _ in range(len(region_steps) + 1)]
+    done = 0
+    barrier()
+    u0 = time.time()
+    marks[0].record()
+    for r, n in enumerate(region_steps):
+        for _ in range(n):
+            done += 1
+            step(keep=dump and done == args.steps)
+        marks[r + 1].record()
+    barrier()
+    u1 = time.time()
+    regions = [1e-3 * marks[r].elapsed_time(marks[r + 1]) for r in range(len(region_steps))]
+    ends = [u0 + sum(regions[:r + 1]) for r in range(len(regions))]
+    regions_unix = [[a, b] for a, b in zip([u0] + ends[:-1], ends[:-1] + [u1])]
     _native.timing_enable(False)
     stages[dom] = _native.timing_collect()[dom]
     if DIST_ON:       # MAX over the ranks, region by region
         t = torch.tensor(regions, dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         regions = [float(x) for x in t.tolist()]
-    elapsed = sorted(regions)[len(regions) // 2]     # value = the MEDIAN region
+    ms_all = [1e3 * r / n for r, n in zip(regions, region_steps)]
+    ms_per_step = sorted(ms_all)[len(ms_all) // 2]     # value = the MEDIAN region
     telemetry = stop_gpu_sampler(sampler, regions_unix) if sampler is not None else None
+    dumped = dump_outputs(args.dump_outputs, last["views"], params, P, H * W) if dump else None
+    last.clear()
 
     # Secondary figure (N = 1): the same step with the window's views spread over K HIP streams
     # (splatloc_amd.fused.render_window does this for the product path).  Not `value`: kernel durations
@@ -1285,13 +1368,13 @@ def main():
                 step()
             barrier()
             ts = time.perf_counter()
-            for _ in range(args.steps):
+            for _ in range(SECONDARY_STEPS):
                 step()
             barrier()
             el = time.perf_counter() - ts
-            multi_stream.append({"path": "per-view GaussianRasterizer calls", "streams": K,
-                                 "value": round(frames_per_step * args.steps / el, 3),
-                                 "ms_per_step": round(1e3 * el / args.steps, 4)})
+            multi_stream.append({"path": "per-view GaussianRasterizer calls", "streams": K, "steps": SECONDARY_STEPS,
+                                 "value": round(frames_per_step * SECONDARY_STEPS / el, 3),
+                                 "ms_per_step": round(1e3 * el / SECONDARY_STEPS, 4)})
         side[:] = []
         mode["window"] = was_window
 
@@ -1302,8 +1385,7 @@ def main():
         tiles = ((W + 15) // 16) * ((H + 15) // 16)
         st_bytes, frame_bytes, n_pass = algorithmic_bytes(P, R, W, H, C, tiles)
         act_bytes = actual_bytes(P, V, R, W, H, C, tiles)
-        ms_per_step = 1e3 * elapsed / args.steps
-        value = frames_per_step * args.steps / elapsed
+        value = frames_per_step * 1e3 / ms_per_step
         # units per launch: a window-batched launch processes the frames of all the rank's views at once
         vpl = max(len(views), 1) if mode["window"] else 1
         per_stage = {}
@@ -1372,10 +1454,10 @@ def main():
             "value": round(value, 3), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
             "scaling": args.scaling, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "repeats": {"regions": len(regions), "steps_per_region": args.steps, "value_is": "median region",
-                        "frames_per_s_min": round(frames_per_step * args.steps / max(regions), 3),
-                        "frames_per_s_max": round(frames_per_step * args.steps / min(regions), 3),
-                        "ms_per_step_all": [round(1e3 * r / args.steps, 4) for r in regions]},
+            "repeats": {"regions": len(regions), "steps_per_region": region_steps, "value_is": "median region",
+                        "frames_per_s_min": round(frames_per_step * 1e3 / max(ms_all), 3),
+                        "frames_per_s_max": round(frames_per_step * 1e3 / min(ms_all), 3),
+                        "ms_per_step_all": [round(m, 4) for m in ms_all]},
             "timed_regions_unix": [[round(a, 3), round(b, 3)] for a, b in regions_unix],   # for tools/clock_trace.py
             # what the GPU did DURING the timed regions, from an independent source (amdsmi, sampled by a separate process)
             "gpu_busy_in_timed_regions": (telemetry or {}).get("busy_pct_mean"),
@@ -1425,6 +1507,8 @@ def main():
             out["reduce_path"] = red.get("sum_path")
             out["collectives_per_step"] = red.get("collectives")
             out["config"]["grad_allreduce_path"] = red
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if args.fwd_only:
             out["metric"] = "DEBUG fwd-only frames/s (not the BASELINE metric)"
         if world == 1 and not args.no_cpu_baseline:

@@ -155,7 +155,9 @@ def test_bench_two_ranks_on_one_gpu_gloo(scaling):
     # the gradients AND the statistics increments were reduced where the backward left them, as ONE SUM; + ONE MAX
     assert path["sum_path"] == "in-place span" and path["collectives"] == 2, path
     assert out["rccl_ranks"] == 2 and out["collectives_per_step"] == 2 and out["reduce_path"] == "in-place span"
-    assert out["repeats"]["regions"] == 5 and len(out["repeats"]["ms_per_step_all"]) == 5
+    # --steps 3 = 3 timed steps in all: --repeats' 5 regions are capped at one step each
+    assert out["repeats"]["regions"] == 3 and out["repeats"]["steps_per_region"] == [1, 1, 1]
+    assert len(out["repeats"]["ms_per_step_all"]) == 3
     assert out["value"] > 0 and out["steps"] == 3 and "roofline" in out and "cpu_baseline" not in out
     assert len(set(out["config"]["tile_instances_R_per_view"])) == 2   # different cameras -> different lists
 
@@ -176,6 +178,40 @@ def test_bench_gpus_flag_alone_launches_the_ranks():
     assert out["n_gpus"] == 2 and out["rccl_ranks"] == 2 and out["config"]["frames_per_step"] == 1
     assert out["collectives_per_step"] == 2 and out["reduce_path"] == "in-place span"
     assert out["value"] > 0
+
+
+def test_bench_dump_outputs_repeat_run_to_run(tmp_path):
+    """`bench.py --dump-outputs DIR`: the last timed step's outputs as .npy files within the budget; two runs with the same
+    arguments see the same inputs, so the forward outputs agree bit for bit and the gradients up to the atomics' order."""
+    from tests.helpers import assert_grad_close
+    outs, dirs = [], []
+    for k in range(2):
+        d = str(tmp_path / f"run{k}")
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--workload", "S0",
+               "--no-cpu-baseline", "--no-multi-stream", "--no-telemetry", "--dump-outputs", d]
+        r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        outs.append(json.loads(lines[0]))
+        dirs.append(d)
+    info = outs[0]["dump_outputs"]
+    assert sum(outs[0]["repeats"]["steps_per_region"]) == 3
+    assert info["bytes"] <= 64_000_000 and info["gaussians"] == [10_000, 10_000] and info["pixels"][0] < info["pixels"][1]
+    names = sorted(f[:-4] for f in os.listdir(dirs[0]))
+    assert len(names) == info["files"] and names == sorted(f[:-4] for f in os.listdir(dirs[1]))
+    for v in range(5):
+        assert {f"view{v}_{n}" for n in ("color", "depth", "alpha", "radii", "grad_means2D")} <= set(names)
+    for n in ("means3D", "colors", "opacities", "scales", "rotations"):
+        assert f"grad_{n}" in names
+    for n in names:
+        a, b = (np.load(os.path.join(d, n + ".npy")) for d in dirs)
+        assert a.dtype in (np.float32, np.float64) and a.shape == b.shape, n
+        if "grad" in n:
+            assert_grad_close(n, a, b)
+        else:
+            assert np.array_equal(a, b), n
+    assert np.load(os.path.join(dirs[0], "view0_radii.npy")).max() > 0
 
 
 def test_replicas_stay_bit_identical_when_a_rank_has_no_view():

@@ -112,10 +112,18 @@ def test_reset_opacity_nonvisible_matches_reference(golden_dir):
     gm = types.SimpleNamespace(_opacity=p, optimizer=opt)
     reset_opacity_nonvisible(gm, [torch.from_numpy(d["filter0"]), torch.from_numpy(d["filter1"])])
     assert isinstance(gm._opacity, torch.nn.Parameter) and gm._opacity is opt.param_groups[1]["params"][0] and gm._opacity is not p
-    assert np.array_equal(gm._opacity.detach().numpy(), d["opacity_after"])
+    got = gm._opacity.detach().numpy()
+    seen = d["filter0"] | d["filter1"]
+    assert got.shape == d["opacity_after"].shape and np.array_equal(got[seen], d["opacity_after"][seen])
+    # the reset value is inverse_sigmoid(0.4) = torch.log(x / (1 - x)) (general_utils.py:20-21): the last bit of a float32 log
+    # on the CPU depends on the host's CPU (the fixture's host rounds it correctly to -0.40546516, some give -0.4054652).
+    # Bit-exact against the reference's expression evaluated on THIS host at the same length, within one ulp of the fixture.
+    x = torch.ones(got.shape) * 0.4
+    reset = torch.log(x / (1 - x)).numpy()
+    assert np.array_equal(got[~seen], reset[~seen])
+    assert (np.abs(d["opacity_after"][~seen] - reset[~seen]) <= np.spacing(np.abs(reset[~seen]))).all()
     st = opt.state[gm._opacity]
     assert np.array_equal(st["exp_avg"].numpy(), d["m_after"]) and np.array_equal(st["exp_avg_sq"].numpy(), d["v_after"])
     assert float(st["step"]) == float(d["step_after"]) == float(d["step_before"]) and not d["m_after"].any()
-    seen = d["filter0"] | d["filter1"]
     assert np.allclose(d["opacity_after"][~seen], np.log(0.4 / 0.6), atol=1e-6)       # the reset value
     assert (d["opacity_after"][seen] > 0).all() and (d["opacity_after"][seen] < 1).all()  # the reference's quirk: sigmoid kept as logit

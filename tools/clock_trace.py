@@ -6,7 +6,7 @@
 Starts a SEPARATE monitoring process that samples the GPU's shader clock, power and (when exposed) throttle status at
 >= 10 Hz — straight from sysfs (hwmon `freq1_input`, `power1_average` / `power1_input`, `pp_dpm_sclk`), with
 `amd-smi metric --json` every `--smi-every` samples as a second, independent source — then runs
-`bench.py --steps 300 --repeats 5 --no-cpu-baseline --no-multi-stream` (>= 10 s of back-to-back S2 windows) as a child
+`bench.py --steps 1500 --repeats 5 --no-cpu-baseline --no-multi-stream` (>= 10 s of back-to-back S2 windows) as a child
 process, stops the monitor and writes the samples that fall inside the bench's timed regions (the bench line carries
 their unix time stamps) with min / median / max.  This process never touches the GPU.  Nothing here needs root; every
 source that is missing on the box is recorded as such instead of guessed.
@@ -164,7 +164,7 @@ def _smi_numbers(entry):
 
 def main():
     out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "gpurun_out", "clocks.json")
-    bench_args = sys.argv[2:] or ["--steps", "300", "--repeats", "5", "--warmup", "5", "--no-cpu-baseline", "--no-multi-stream"]
+    bench_args = sys.argv[2:] or ["--steps", "1500", "--repeats", "5", "--warmup", "5", "--no-cpu-baseline", "--no-multi-stream"]
     os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
     raw = out_path + ".raw"
     stop = mp.Event()

@@ -6,10 +6,11 @@ usage: timeline.py <dir with *.db> [bench JSON written by the same run]
 
 A step starts at every preprocess_kernel launch.  bench.py runs, in this order: `warmup` steps, one recording step,
 BREAKDOWN_STEPS = 20 steps with EVERY stage bracketed by HIP events (an event record idles the GPU ~10 us: those steps are
-longer and are not what `value` measures), then `repeats` timed regions of `steps` steps (only the dominant kernel bracketed),
+longer and are not what `value` measures), then the `steps` timed steps in `repeats` regions (only the dominant kernel bracketed),
 then — unless --no-multi-stream — secondary legs.  The step printed is the middle step of the middle timed region, located
 from the counts in the bench JSON (round 4 printed "the 2nd step from the end", which was a secondary-leg step: its span did
-not reconcile with ms_per_step).  Without a JSON the counts of tools/profile_round.sh are assumed (3 warm-up, 10 steps, 5 regions)."""
+not reconcile with ms_per_step).  Without a JSON the counts of tools/profile_round.sh are assumed (3 warm-up, 10 steps, 5 regions).
+A bench JSON whose `steps_per_region` is a number is from before `steps` counted all timed steps: `regions` x `steps`."""
 import glob
 import json
 import sqlite3
@@ -27,12 +28,18 @@ def main():
         meta = json.loads(line)
     warmup, steps = int(meta["warmup"]), int(meta["steps"])
     regions = int(meta.get("repeats", {}).get("regions", 5))
+    per_region = meta.get("repeats", {}).get("steps_per_region")
+    if per_region is None:
+        per_region = [steps // regions + (1 if r < steps % regions else 0) for r in range(regions)]
+    elif isinstance(per_region, int):
+        per_region = [per_region] * regions
+    mid = len(per_region) // 2
     db = sorted(glob.glob(root + "/**/*.db", recursive=True))[0]
     con = sqlite3.connect(db)
     rows = con.execute("select name, start, end from kernels order by start").fetchall()
     starts = [i for i, r in enumerate(rows) if "preprocess_kernel" in r[0] and "bwd" not in r[0]]
     first_timed = warmup + 1 + BREAKDOWN_STEPS
-    k = first_timed + steps * (regions // 2) + steps // 2
+    k = first_timed + sum(per_region[:mid]) + per_region[mid] // 2
     if k + 1 >= len(starts):
         raise SystemExit(f"timeline.py: {len(starts)} steps in the trace, the timed step {k} is not among them (wrong bench JSON?)")
     a, b = starts[k], starts[k + 1]
@@ -40,8 +47,8 @@ def main():
     t0 = step[0][1]
     busy = 0
     prev_end = t0
-    print(f"# step {k} of {len(starts)} in the trace = step {steps // 2} of timed region {regions // 2} "
-          f"(warm-up {warmup}, 1 recording, {BREAKDOWN_STEPS} event-bracketed, then {regions} x {steps} timed)")
+    print(f"# step {k} of {len(starts)} in the trace = step {per_region[mid] // 2} of timed region {mid} "
+          f"(warm-up {warmup}, 1 recording, {BREAKDOWN_STEPS} event-bracketed, then {sum(per_region)} timed in regions of {per_region})")
     print(f"{'kernel':40s} {'start_us':>9s} {'dur_us':>8s} {'gap_us':>7s}")
     for name, s, e in step:
         n = name.split("(")[0].replace("void sr::", "").replace("sr::", "").replace("void ", "")[:40]
