@@ -12,6 +12,8 @@
  *       backward   triggered by train_gaussians.py:229 and :286 (loss.backward())
  *   simple_knn._C.distCUDA2
  *       call site  gaussian_splatting/scene/gaussian_model.py:18,206
+ *   tinycudann.Encoding (the multiresolution grid encodings of FeatureDecoder)
+ *       call site  models/encoding.py:3,33-46 (built), models/decoders.py:63 (called)
  *
  * Everything here is plain C: raw device pointers, sizes, an opaque stream handle
  * (hipStream_t passed as void*), int status codes.  No torch types, no exceptions.
@@ -36,7 +38,7 @@ extern "C" {
 /* bumped on every change of a signature or buffer layout; the Python binding refuses a library
  * whose splatraster_abi_version() differs (a stale in-tree .so would otherwise be called through
  * ctypes with mismatched arguments) */
-#define SPLATRASTER_ABI_VERSION 13
+#define SPLATRASTER_ABI_VERSION 14
 
 #define SPLATRASTER_TILE 16 /* tile edge in pixels (16x16 = 256 pixels = 4 wave64) */
 
@@ -548,6 +550,47 @@ int splatknn_dist2(int32_t N, const float* points /* [N,3] */, float* out /* [N]
 
 /* test hook: point count from which splatknn_dist2 takes the grid search (< 0 restores the default 10 000) */
 int splatknn_debug_set_grid_min(int32_t n);
+
+/* ---- tinycudann.Encoding: multiresolution grid encoding (models/encoding.py:33-46) -------------------------------------
+ * Restatement of tiny-cuda-nn's public grid-encoding definition.  Level l of L:
+ *   scale_l = exp2f(l * log2f(per_level_scale)) * base_res - 1,  res_l = ceilf(scale_l) + 1          (f32, on the host, once)
+ *   size_l  = next_multiple(res_l^D, 8) (at most 2^31 - 1 before rounding), then capped: Hash at 2^log2_T, Tiled at base_res^D,
+ *             Dense not at all;  offset_l = sum of the sizes below l;  n_params = F * sum of all sizes
+ *   params[(offset_l + index) * F + f]  (level-major table)
+ * A point x [D] (not clamped to [0, 1]) at level l: pos = fmaf(scale_l, x_d, 0.5f), cell = (uint32)(int)floorf(pos),
+ * frac = pos - floorf(pos); each of the 2^D corners is indexed densely (sum cell_d * res_l^d, stopping once the stride passes
+ * size_l) or, for Hash when res_l^D > size_l, by XOR_d cell_d * {1, 2654435761, 805459861}_d; then % size_l.  The output row
+ * of a point holds level l's F features in columns [l*F, l*F + F): the sum over corners of prod_d (frac_d | 1 - frac_d) *
+ * corner feature.  D in {2, 3}, F in {1, 2, 4, 8}, 1 <= L <= 32, 1 <= log2_T <= 30, linear interpolation only. */
+#define SPLATRASTER_GRID_MAX_LEVELS 32
+#define SPLATRASTER_GRID_HASH 0
+#define SPLATRASTER_GRID_DENSE 1
+#define SPLATRASTER_GRID_TILED 2
+typedef struct splatraster_grid_layout {
+    int32_t n_dims;        /* D */
+    int32_t n_levels;      /* L */
+    int32_t n_features;    /* F per level */
+    int32_t grid_type;     /* SPLATRASTER_GRID_* */
+    uint32_t offset[SPLATRASTER_GRID_MAX_LEVELS];      /* in table entries of F floats */
+    uint32_t size[SPLATRASTER_GRID_MAX_LEVELS];        /* entries of level l */
+    uint32_t resolution[SPLATRASTER_GRID_MAX_LEVELS];  /* res_l */
+    float scale[SPLATRASTER_GRID_MAX_LEVELS];          /* scale_l */
+    int64_t n_params;      /* floats in the parameter table */
+} splatraster_grid_layout;
+
+/* Host only (never touches the GPU): fills `out` for the configuration; SPLATRASTER_ERR_UNSUPPORTED outside the limits above
+ * or when the table would exceed 2^31 entries, SPLATRASTER_ERR_BAD_ARG for non-positive base_res / per_level_scale. */
+int splatraster_grid_encoding_layout(int32_t n_dims, int32_t n_levels, int32_t n_features, int32_t log2_hashmap_size,
+                                     int32_t base_resolution, double per_level_scale, int32_t grid_type,
+                                     splatraster_grid_layout* out);
+/* out [N, L*F] = encoding of x [N, D].  `layout` as filled by splatraster_grid_encoding_layout (re-validated: its offsets must
+ * be the running sum of its sizes); params [n_params].  params must be 16-byte aligned.  No host synchronisation. */
+int splatraster_grid_encoding_forward(const splatraster_grid_layout* layout, int64_t N, const float* x, const float* params,
+                                      float* out, void* stream);
+/* Gradients of a loss L given dL_dout [N, L*F]: dL_dparams [n_params] (may be NULL) is ACCUMULATED with float atomics
+ * (zero it first; the last bits depend on arrival order), dL_dx [N, D] (may be NULL) is written. */
+int splatraster_grid_encoding_backward(const splatraster_grid_layout* layout, int64_t N, const float* x, const float* params,
+                                       const float* dL_dout, float* dL_dparams, float* dL_dx, void* stream);
 
 /* ---- pose refinement on the device (build extension, DESIGN.md §6.8: the reference's rasterizer returns no camera gradient
  * and nothing calls its utils/optimization_utils.py:5-66 pose helpers) ------------------------------------------------------

@@ -11,7 +11,7 @@ import os
 from . import build as _build
 
 _LIB = None
-ABI_VERSION = 13   # == SPLATRASTER_ABI_VERSION of include/splatraster.h
+ABI_VERSION = 14   # == SPLATRASTER_ABI_VERSION of include/splatraster.h
 
 OK = 0
 WARN_LOOKBACK_STALL = 5   # splatraster_poll_errors() only; not an error of any frame
@@ -97,6 +97,17 @@ class AdamGroup(C.Structure):
                 ("step", C.c_double)]
 
 
+GRID_MAX_LEVELS = 32   # SPLATRASTER_GRID_MAX_LEVELS
+GRID_HASH, GRID_DENSE, GRID_TILED = 0, 1, 2   # SPLATRASTER_GRID_*
+
+
+class GridLayout(C.Structure):
+    """struct splatraster_grid_layout"""
+    _fields_ = [("n_dims", C.c_int32), ("n_levels", C.c_int32), ("n_features", C.c_int32), ("grid_type", C.c_int32),
+                ("offset", C.c_uint32 * GRID_MAX_LEVELS), ("size", C.c_uint32 * GRID_MAX_LEVELS),
+                ("resolution", C.c_uint32 * GRID_MAX_LEVELS), ("scale", C.c_float * GRID_MAX_LEVELS), ("n_params", C.c_int64)]
+
+
 # every symbol include/splatraster.h declares: (name, restype, argtypes)
 _vp, _i32, _i64, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t
 SYMBOLS = {
@@ -141,6 +152,9 @@ SYMBOLS = {
     "splatknn_workspace_bytes": (_sz, [_i32]),
     "splatknn_dist2": (C.c_int, [_i32, _vp, _vp, _vp, _vp]),
     "splatknn_debug_set_grid_min": (C.c_int, [_i32]),
+    "splatraster_grid_encoding_layout": (C.c_int, [_i32] * 5 + [C.c_double, _i32, C.POINTER(GridLayout)]),
+    "splatraster_grid_encoding_forward": (C.c_int, [C.POINTER(GridLayout), _i64, _vp, _vp, _vp, _vp]),
+    "splatraster_grid_encoding_backward": (C.c_int, [C.POINTER(GridLayout), _i64] + [_vp] * 6),
     "splatraster_activate_forward": (C.c_int, [_i32] * 5 + [_vp] * 13),
     "splatraster_activate_backward": (C.c_int, [_i32] * 5 + [_vp] * 19),
     "splatraster_densification_stats": (C.c_int, [_i32] + [_vp] * 6),

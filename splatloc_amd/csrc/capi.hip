@@ -1120,4 +1120,22 @@ int splatknn_dist2(int32_t N, const float* points, float* out, void* workspace, 
     return knn_dist2(N, points, out, workspace, reinterpret_cast<hipStream_t>(stream));
 }
 
+int splatraster_grid_encoding_layout(int32_t n_dims, int32_t n_levels, int32_t n_features, int32_t log2_hashmap_size,
+                                     int32_t base_resolution, double per_level_scale, int32_t grid_type, splatraster_grid_layout* out)
+{
+    return grid_layout(n_dims, n_levels, n_features, log2_hashmap_size, base_resolution, per_level_scale, grid_type, out);
+}
+
+int splatraster_grid_encoding_forward(const splatraster_grid_layout* layout, int64_t N, const float* x, const float* params,
+                                      float* out, void* stream)
+{
+    return grid_forward(layout, N, x, params, out, reinterpret_cast<hipStream_t>(stream));
+}
+
+int splatraster_grid_encoding_backward(const splatraster_grid_layout* layout, int64_t N, const float* x, const float* params,
+                                       const float* dL_dout, float* dL_dparams, float* dL_dx, void* stream)
+{
+    return grid_backward(layout, N, x, params, dL_dout, dL_dparams, dL_dx, reinterpret_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

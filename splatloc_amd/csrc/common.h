@@ -384,6 +384,13 @@ int launch_pose_step(const float* dL_dview, const float* dL_dproj, const float* 
 
 int knn_dist2(int32_t N, const float* points, float* out, void* workspace, hipStream_t stream);
 size_t knn_workspace_bytes(int32_t N);
-void knn_set_grid_min(int n);   // point count from which the exact grid search replaces the tiled brute force (< 0: default)
+void knn_set_grid_min(int n);
+
+// grid_encoding.hip (tinycudann.Encoding)
+int grid_layout(int32_t D, int32_t L, int32_t F, int32_t log2_T, int32_t base_res, double per_level_scale, int32_t grid_type,
+                splatraster_grid_layout* out);
+int grid_forward(const splatraster_grid_layout* lay, int64_t N, const float* x, const float* params, float* out, hipStream_t s);
+int grid_backward(const splatraster_grid_layout* lay, int64_t N, const float* x, const float* params, const float* dL_dout,
+                  float* dL_dparams, float* dL_dx, hipStream_t s);   // point count from which the exact grid search replaces the tiled brute force (< 0: default)
 
 }  // namespace sr
