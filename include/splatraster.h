@@ -14,6 +14,8 @@
  *       call site  gaussian_splatting/scene/gaussian_model.py:18,206
  *   tinycudann.Encoding (the multiresolution grid encodings of FeatureDecoder)
  *       call site  models/encoding.py:3,33-46 (built), models/decoders.py:63 (called)
+ *   utils.selection.gaussian_selectition (landmark selection)
+ *       call site  test.py:39 (import), test.py:564 (called by --eval_selection)
  *
  * Everything here is plain C: raw device pointers, sizes, an opaque stream handle
  * (hipStream_t passed as void*), int status codes.  No torch types, no exceptions.
@@ -38,7 +40,7 @@ extern "C" {
 /* bumped on every change of a signature or buffer layout; the Python binding refuses a library
  * whose splatraster_abi_version() differs (a stale in-tree .so would otherwise be called through
  * ctypes with mismatched arguments) */
-#define SPLATRASTER_ABI_VERSION 14
+#define SPLATRASTER_ABI_VERSION 15
 
 #define SPLATRASTER_TILE 16 /* tile edge in pixels (16x16 = 256 pixels = 4 wave64) */
 
@@ -591,6 +593,29 @@ int splatraster_grid_encoding_forward(const splatraster_grid_layout* layout, int
  * (zero it first; the last bits depend on arrival order), dL_dx [N, D] (may be NULL) is written. */
 int splatraster_grid_encoding_backward(const splatraster_grid_layout* layout, int64_t N, const float* x, const float* params,
                                        const float* dL_dout, float* dL_dparams, float* dL_dx, void* stream);
+
+/* ---- landmark selection: utils/selection.py:91-157 (gaussian_selectition), INTEGRATION.md §16 ----------------------------
+ * Scores.  Point p [N,3] against view i of w2c [M,4,4] (row-major world-to-camera) and K [3,3] (f64, row-major, HOST memory),
+ * all arithmetic f64 from the f32 inputs, no FP contraction:
+ *   pc = R_i p + t_i; visible iff !(pc.z < 0.01) and, with (u, v) = (K pc)_{0,1} / (K pc)_2, 0 < u < width, 0 < v < height
+ *   d = depths[i, (int)v, (int)u] ([M, height, width] f32); diff = |pc.z - d| kept iff diff < 0.3 and d > 0.02
+ *   depth_mean / depth_std (ddof 0) over the kept diffs, NaN when none was kept
+ *   b = R_i^T (p - t_i) / |.|, H = mean over visible views of (I - b b^T), span = acos(clip(1 - 2 lmin/lmax, 0, 1)), 0 if none
+ *   score = min(2, 0.05/mean) + min(2, 0.05/std) + span with python's min (NaN -> 2; a zero mean or std -> 2)
+ * n_visible / n_depth [N] i32, the others [N] f64.  No host synchronisation. */
+int splatraster_landmark_scores(int64_t N, int32_t M, const float* points, const float* w2c, const double* K,
+                                const float* depths, int32_t width, int32_t height, int32_t* n_visible, int32_t* n_depth,
+                                double* depth_mean, double* depth_std, double* span, double* score, void* stream);
+/* device workspace of splatraster_landmark_select for N points and num landmarks */
+size_t splatraster_landmark_workspace_bytes(int64_t N, int32_t num);
+/* Greedy pick of `num` landmarks among points [N,3] (f32) by score [N] (f64), as the reference's loop: candidates walked by
+ * score descending, ties the larger index first; rank 0 is taken; then passes at radius, radius/2, ...: a candidate is taken
+ * unless a landmark taken before it lies at f64 distance sqrt((dx^2 + dy^2) + dz^2) < radius; stop at num.  out_idx [num]
+ * (device) receives the point indices in pick order; *n_passes (host, may be NULL) the passes run.  Synchronises the stream
+ * once per pass (the landmark count is read back).  SPLATRASTER_ERR_BAD_ARG for num outside [1, N], a radius that is not
+ * positive and finite, or when the radius underflows to 0 first (fewer than num distinct positions). */
+int splatraster_landmark_select(int64_t N, const float* points, const double* score, int32_t num, double radius,
+                                int32_t* out_idx, int32_t* n_passes, void* workspace, void* stream);
 
 /* ---- pose refinement on the device (build extension, DESIGN.md §6.8: the reference's rasterizer returns no camera gradient
  * and nothing calls its utils/optimization_utils.py:5-66 pose helpers) ------------------------------------------------------

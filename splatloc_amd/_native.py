@@ -11,7 +11,7 @@ import os
 from . import build as _build
 
 _LIB = None
-ABI_VERSION = 14   # == SPLATRASTER_ABI_VERSION of include/splatraster.h
+ABI_VERSION = 15   # == SPLATRASTER_ABI_VERSION of include/splatraster.h
 
 OK = 0
 WARN_LOOKBACK_STALL = 5   # splatraster_poll_errors() only; not an error of any frame
@@ -155,6 +155,9 @@ SYMBOLS = {
     "splatraster_grid_encoding_layout": (C.c_int, [_i32] * 5 + [C.c_double, _i32, C.POINTER(GridLayout)]),
     "splatraster_grid_encoding_forward": (C.c_int, [C.POINTER(GridLayout), _i64, _vp, _vp, _vp, _vp]),
     "splatraster_grid_encoding_backward": (C.c_int, [C.POINTER(GridLayout), _i64] + [_vp] * 6),
+    "splatraster_landmark_scores": (C.c_int, [_i64, _i32] + [_vp] * 4 + [_i32, _i32] + [_vp] * 7),
+    "splatraster_landmark_workspace_bytes": (_sz, [_i64, _i32]),
+    "splatraster_landmark_select": (C.c_int, [_i64, _vp, _vp, _i32, C.c_double, _vp, _vp, _vp, _vp]),
     "splatraster_activate_forward": (C.c_int, [_i32] * 5 + [_vp] * 13),
     "splatraster_activate_backward": (C.c_int, [_i32] * 5 + [_vp] * 19),
     "splatraster_densification_stats": (C.c_int, [_i32] + [_vp] * 6),

@@ -1138,4 +1138,20 @@ int splatraster_grid_encoding_backward(const splatraster_grid_layout* layout, in
     return grid_backward(layout, N, x, params, dL_dout, dL_dparams, dL_dx, reinterpret_cast<hipStream_t>(stream));
 }
 
+int splatraster_landmark_scores(int64_t N, int32_t M, const float* points, const float* w2c, const double* K,
+                                const float* depths, int32_t width, int32_t height, int32_t* n_visible, int32_t* n_depth,
+                                double* depth_mean, double* depth_std, double* span, double* score, void* stream)
+{
+    return landmark_scores(N, M, points, w2c, K, depths, width, height, n_visible, n_depth, depth_mean, depth_std, span, score,
+                           reinterpret_cast<hipStream_t>(stream));
+}
+
+size_t splatraster_landmark_workspace_bytes(int64_t N, int32_t num) { return landmark_workspace_bytes(N, num); }
+
+int splatraster_landmark_select(int64_t N, const float* points, const double* score, int32_t num, double radius,
+                                int32_t* out_idx, int32_t* n_passes, void* workspace, void* stream)
+{
+    return landmark_select(N, points, score, num, radius, out_idx, n_passes, workspace, reinterpret_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

@@ -393,4 +393,12 @@ int grid_forward(const splatraster_grid_layout* lay, int64_t N, const float* x, 
 int grid_backward(const splatraster_grid_layout* lay, int64_t N, const float* x, const float* params, const float* dL_dout,
                   float* dL_dparams, float* dL_dx, hipStream_t s);   // point count from which the exact grid search replaces the tiled brute force (< 0: default)
 
+// selection.hip (landmark selection)
+int landmark_scores(int64_t N, int32_t M, const float* points, const float* w2c, const double* K, const float* depths,
+                    int32_t width, int32_t height, int32_t* n_visible, int32_t* n_depth, double* depth_mean,
+                    double* depth_std, double* span, double* score, hipStream_t stream);
+size_t landmark_workspace_bytes(int64_t N, int32_t num);
+int landmark_select(int64_t N, const float* points, const double* score, int32_t num, double radius, int32_t* out_idx,
+                    int32_t* n_passes, void* workspace, hipStream_t stream);
+
 }  // namespace sr

@@ -29,6 +29,7 @@ WHAT = [   # (file name regex, description; {placeholders} are filled by the ext
     (r"r\d+_hostprof_.*\.txt$", "cProfile of the host side of a refinement / map step (`tools/hostprof_steps.py`)"),
     (r"r\d+_ab_probes\.txt$", "A/B and timing-probe log of the round (one box per block)"),
     (r"r\d+_knn\.json$", "`distCUDA2` wall times, brute force vs exact grid"),
+    (r"^landmark_selection_time\.json$", "landmark selection (`gaussian_selectition`) at Replica scale on a synthetic room, HIP events per stage (`tools/landmark_selection_time.py`): {landmark}"),
     (r"r\d+_scene_lists.*\.json$", "one `color_refinement` iteration on a RECONSTRUCTED room (list-length distribution, per-kernel table; `tools/scene_lists.py`; suffix = the forced variant): {scenelists}"),
     (r"r\d+_scene.*\.json$", "`bench.py --stage scene`: the whole reconstruction schedule as one run (suffix: `replica_scale` = 180 key-frames of a 600k-Gaussian room, `radix_front_end` = SPLATRASTER_FRONT_END=0): {bench}{scene}"),
     (r"r\d+_ab_.*\.json$", "`tools/ab.py`: interleaved same-box A/B of variant libraries, paired statistics: {ab}"),
@@ -181,7 +182,18 @@ def rccl(path):
     return f"backend {j.get('backend')}, RCCL {j.get('rccl_version')}, HSA_ENABLE_IPC_MODE_LEGACY={((j.get('env') or {}).get('HSA_ENABLE_IPC_MODE_LEGACY'))}, ok = {j.get('ok')}"
 
 
-EXTRACT = {"scenelists": scenelists, "scene": scene, "ab": ab, "perview": perview, "mapidle": mapidle, "rccl": rccl, "kstats": kstats, "hbm": hbm, "sq": sq, "timeline": timeline, "bench": bench, "clocks": clocks, "gradbars": gradbars, "idle": idle}
+def landmark(path):
+    j = _load(path) or {}
+    rows = j.get("rows") or []
+    if not rows:
+        return "(no rows)"
+    sc = [r["scores_ms"] for r in rows]
+    se = [r["select_ms"] for r in rows]
+    return (f"{j.get('visible_pairs', '?')} visible (point, view) pairs; scores {min(sc):.2f}-{max(sc):.2f} ms, sort + greedy pick "
+            f"{min(se):.0f}-{max(se):.0f} ms ({rows[0].get('passes', '?')} passes) over {len(rows)} runs")
+
+
+EXTRACT = {"scenelists": scenelists, "scene": scene, "ab": ab, "perview": perview, "mapidle": mapidle, "rccl": rccl, "kstats": kstats, "hbm": hbm, "sq": sq, "timeline": timeline, "bench": bench, "clocks": clocks, "gradbars": gradbars, "idle": idle, "landmark": landmark}
 
 
 def describe(name, path):
