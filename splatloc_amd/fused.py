@@ -19,78 +19,92 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+from types import SimpleNamespace
 from typing import Optional
 
 import torch
 
 from . import _native
-from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, _on_device, _prep, _ptr, _require_gpu, _stream,
-                         _window_compatible, rasterize_window)
+from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, _on_device, _prep, _ptr, _require_gpu, _save,
+                         _saved, _stream, _window_compatible, rasterize_window)
+
+
+def activate_forward(xyz, f_dc, f_rest, scaling, rotation, opacity, extra, campos, active_sh_degree: int):
+    """(xyz, f_dc, f_rest, scaling, rotation, opacity, extra, campos) -> ((scales [P,3], rotations [P,4], opacities [P,1],
+    colors [P,3+E]), the frame `activate_backward` reads)."""
+    lib = _native.load()
+    _require_gpu(xyz, "xyz")
+    dev = xyz.device
+    P = int(xyz.shape[0])
+    K = 1 + (0 if f_rest is None else int(f_rest.shape[1]))
+    E = 0 if extra is None else int(extra.shape[1])
+    SC = int(scaling.shape[1])
+    if campos is not None and campos.requires_grad:
+        raise RuntimeError("activate_pack: the camera centre gets no gradient on the fused path")
+    x, fd, fr, sc, ro, op, ex, cp = (_prep(t, dev) for t in (xyz, f_dc, f_rest, scaling, rotation, opacity,
+                                                             extra, campos))
+    f32 = dict(dtype=torch.float32, device=dev)
+    scales = torch.empty((P, 3), **f32)
+    rotations = torch.empty((P, 4), **f32)
+    opacities = torch.empty((P, 1), **f32)
+    colors = torch.empty((P, 3 + E), **f32)
+    with _on_device(dev):
+        _native.check(lib.splatraster_activate_forward(
+            P, K, int(active_sh_degree), SC, E, _ptr(x), _ptr(fd), _ptr(fr), _ptr(sc), _ptr(ro), _ptr(op),
+            _ptr(ex), _ptr(cp), _ptr(scales), _ptr(rotations), _ptr(opacities), _ptr(colors), _stream(dev)),
+            "activate_forward")
+    frame = SimpleNamespace(dev=dev, cfg=(P, K, int(active_sh_degree), SC, E),
+                            shapes=(tuple(f_dc.shape), None if f_rest is None else tuple(f_rest.shape)),
+                            x=x, fd=fd, fr=fr, sc=sc, ro=ro, op=op, cp=cp)
+    return (scales, rotations, opacities, colors), frame
+
+
+def activate_backward(f, g_scales, g_rotations, g_opacities, g_colors):
+    """Gradients of (xyz — None at SH degree 0 —, f_dc, f_rest, scaling, rotation, opacity, extra); None: a zero gradient."""
+    lib = _native.load()
+    dev = f.dev
+    P, K, deg, SC, E = f.cfg
+    f32 = dict(dtype=torch.float32, device=dev)
+    zeros = lambda shp: torch.zeros(shp, **f32)  # noqa: E731
+    gs = _prep(g_scales, dev) if g_scales is not None else zeros((P, 3))
+    gr = _prep(g_rotations, dev) if g_rotations is not None else zeros((P, 4))
+    go = _prep(g_opacities, dev) if g_opacities is not None else zeros((P, 1))
+    gc = _prep(g_colors, dev) if g_colors is not None else zeros((P, 3 + E))
+    if P == 0:
+        gs = gr = go = gc = None
+    d_xyz = torch.empty((P, 3), **f32) if deg > 0 else None
+    d_fd = torch.empty(f.shapes[0], **f32)
+    d_fr = torch.empty(f.shapes[1], **f32) if f.shapes[1] is not None else None
+    d_sc = torch.empty((P, SC), **f32)
+    d_ro = torch.empty((P, 4), **f32)
+    d_op = torch.empty((P, 1), **f32)
+    d_ex = torch.empty((P, E), **f32) if E else None
+    with _on_device(dev):
+        _native.check(lib.splatraster_activate_backward(
+            P, K, deg, SC, E, _ptr(f.x), _ptr(f.fd), _ptr(f.fr), _ptr(f.sc), _ptr(f.ro), _ptr(f.op), _ptr(f.cp),
+            _ptr(gs), _ptr(gr), _ptr(go), _ptr(gc), _ptr(d_xyz), _ptr(d_fd),
+            _ptr(d_fr) if (d_fr is not None and d_fr.numel()) else None, _ptr(d_sc), _ptr(d_ro), _ptr(d_op),
+            _ptr(d_ex), _stream(dev)), "activate_backward")
+    return d_xyz, d_fd, d_fr, d_sc, d_ro, d_op, d_ex
+
+
+_ACT_INPUTS = ("x", "fd", "fr", "sc", "ro", "op", "cp")
 
 
 class _ActivatePack(torch.autograd.Function):
-    """(xyz, f_dc, f_rest, scaling, rotation, opacity, extra, campos) ->
-    (scales [P,3], rotations [P,4], opacities [P,1], colors [P,3+E])."""
+    """The autograd adapter of `activate_forward` / `activate_backward`."""
 
     @staticmethod
     def forward(ctx, xyz, f_dc, f_rest, scaling, rotation, opacity, extra, campos, active_sh_degree: int):
-        lib = _native.load()
-        _require_gpu(xyz, "xyz")
-        dev = xyz.device
-        P = int(xyz.shape[0])
-        K = 1 + (0 if f_rest is None else int(f_rest.shape[1]))
-        E = 0 if extra is None else int(extra.shape[1])
-        SC = int(scaling.shape[1])
-        if campos is not None and campos.requires_grad:
-            raise RuntimeError("activate_pack: the camera centre gets no gradient on the fused path")
-        x, fd, fr, sc, ro, op, ex, cp = (_prep(t, dev) for t in (xyz, f_dc, f_rest, scaling, rotation, opacity,
-                                                                 extra, campos))
-        f32 = dict(dtype=torch.float32, device=dev)
-        scales = torch.empty((P, 3), **f32)
-        rotations = torch.empty((P, 4), **f32)
-        opacities = torch.empty((P, 1), **f32)
-        colors = torch.empty((P, 3 + E), **f32)
-        with _on_device(dev):
-            _native.check(lib.splatraster_activate_forward(
-                P, K, int(active_sh_degree), SC, E, _ptr(x), _ptr(fd), _ptr(fr), _ptr(sc), _ptr(ro), _ptr(op),
-                _ptr(ex), _ptr(cp), _ptr(scales), _ptr(rotations), _ptr(opacities), _ptr(colors), _stream(dev)),
-                "activate_forward")
-        ctx.cfg = (P, K, int(active_sh_degree), SC, E)
-        ctx.shapes = (tuple(f_dc.shape), None if f_rest is None else tuple(f_rest.shape))
-        ctx.save_for_backward(*[t if t is not None else torch.empty(0, device=dev) for t in
-                                (x, fd, fr, sc, ro, op, cp)])
-        return scales, rotations, opacities, colors
+        out, f = activate_forward(xyz, f_dc, f_rest, scaling, rotation, opacity, extra, campos, active_sh_degree)
+        ctx.dev, ctx.cfg, ctx.shapes = f.dev, f.cfg, f.shapes
+        _save(ctx, f, [getattr(f, k) for k in _ACT_INPUTS], buffers=())
+        return out
 
     @staticmethod
     def backward(ctx, g_scales, g_rotations, g_opacities, g_colors):
-        lib = _native.load()
-        x, fd, fr, sc, ro, op, cp = ctx.saved_tensors
-        dev = x.device
-        P, K, deg, SC, E = ctx.cfg
-        opt = lambda t: t if t.numel() else None  # noqa: E731
-        fr, cp = opt(fr), opt(cp)
-        f32 = dict(dtype=torch.float32, device=dev)
-        zeros = lambda shp: torch.zeros(shp, **f32)  # noqa: E731
-        gs = _prep(g_scales, dev) if g_scales is not None else zeros((P, 3))
-        gr = _prep(g_rotations, dev) if g_rotations is not None else zeros((P, 4))
-        go = _prep(g_opacities, dev) if g_opacities is not None else zeros((P, 1))
-        gc = _prep(g_colors, dev) if g_colors is not None else zeros((P, 3 + E))
-        if P == 0:
-            gs = gr = go = gc = None
-        d_xyz = torch.empty((P, 3), **f32) if deg > 0 else None
-        d_fd = torch.empty(ctx.shapes[0], **f32)
-        d_fr = torch.empty(ctx.shapes[1], **f32) if ctx.shapes[1] is not None else None
-        d_sc = torch.empty((P, SC), **f32)
-        d_ro = torch.empty((P, 4), **f32)
-        d_op = torch.empty((P, 1), **f32)
-        d_ex = torch.empty((P, E), **f32) if E else None
-        with _on_device(dev):
-            _native.check(lib.splatraster_activate_backward(
-                P, K, deg, SC, E, _ptr(x), _ptr(fd), _ptr(fr), _ptr(sc), _ptr(ro), _ptr(op), _ptr(cp),
-                _ptr(gs), _ptr(gr), _ptr(go), _ptr(gc), _ptr(d_xyz), _ptr(d_fd),
-                _ptr(d_fr) if (d_fr is not None and d_fr.numel()) else None, _ptr(d_sc), _ptr(d_ro), _ptr(d_op),
-                _ptr(d_ex), _stream(dev)), "activate_backward")
-        return d_xyz, d_fd, d_fr, d_sc, d_ro, d_op, d_ex, None, None
+        f = SimpleNamespace(dev=ctx.dev, cfg=ctx.cfg, shapes=ctx.shapes, **dict(zip(_ACT_INPUTS, _saved(ctx, ())[0])))
+        return activate_backward(f, g_scales, g_rotations, g_opacities, g_colors) + (None, None)
 
 
 def activate_pack(xyz, f_dc, f_rest, scaling, rotation, opacity, extra=None, campos=None, active_sh_degree: int = 0):

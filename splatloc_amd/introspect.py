@@ -55,6 +55,13 @@ def image_views(img: torch.Tensor, W: int, H: int) -> dict:
     )
 
 
+def forward_buffers(grad_fn):
+    """(geom, binning, img) of the per-view or window forward behind an output's grad_fn."""
+    from .rasterizer import _saved
+    b = _saved(grad_fn)[1]
+    return b["geom"], b["binning"], b["img"]
+
+
 def forward_state(fn_ctx_tensors, P: int, W: int, H: int, R: int) -> dict:
     """Views for the (geom, binning, img) tensors saved by _RasterizeGaussians.forward."""
     geom, binning, img = fn_ctx_tensors

@@ -246,24 +246,31 @@ def l1_loss(network_output, gt):
     return _RefinementLoss.apply(network_output, gt, 0.0, 2)
 
 
+def isotropic_forward(scaling, marker):
+    """splatraster_isotropic_loss: (row_grad [P], out [2]) — out[0] the regulariser's value, and its gradient w.r.t.
+    scaling[i, :] is out[1] * row_grad[i] in every column."""
+    lib = _native.load()
+    _require_gpu(scaling, "scaling")
+    dev = scaling.device
+    P, SC = int(scaling.shape[0]), int(scaling.shape[1])
+    if SC not in (1, 3) or marker.numel() != P:
+        raise RuntimeError("isotropic_loss: expected scaling [P,3] (or [P,1]) and marker [P,1]")
+    s, mk = _prep(scaling, dev), _prep(marker, dev)
+    row_grad = torch.empty((P,), dtype=torch.float32, device=dev)
+    out = torch.empty((2,), dtype=torch.float32, device=dev)
+    ws = torch.empty((lib.splatraster_isotropic_loss_workspace_bytes(P),), dtype=torch.uint8, device=dev)
+    with _on_device(dev):
+        _native.check(lib.splatraster_isotropic_loss(P, SC, _ptr(s), _ptr(mk), _ptr(row_grad), _ptr(out), _ptr(ws),
+                                                     _stream(dev)), "isotropic_loss")
+    return row_grad, out
+
+
 class _IsotropicLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, scaling, marker):
-        lib = _native.load()
-        _require_gpu(scaling, "scaling")
-        dev = scaling.device
-        P, SC = int(scaling.shape[0]), int(scaling.shape[1])
-        if SC not in (1, 3) or marker.numel() != P:
-            raise RuntimeError("isotropic_loss: expected scaling [P,3] (or [P,1]) and marker [P,1]")
-        s, mk = _prep(scaling, dev), _prep(marker, dev)
-        row_grad = torch.empty((P,), dtype=torch.float32, device=dev)
-        out = torch.empty((2,), dtype=torch.float32, device=dev)
-        ws = torch.empty((lib.splatraster_isotropic_loss_workspace_bytes(P),), dtype=torch.uint8, device=dev)
-        with _on_device(dev):
-            _native.check(lib.splatraster_isotropic_loss(P, SC, _ptr(s), _ptr(mk), _ptr(row_grad), _ptr(out), _ptr(ws),
-                                                         _stream(dev)), "isotropic_loss")
+        row_grad, out = isotropic_forward(scaling, marker)
         ctx.save_for_backward(row_grad, out)
-        ctx.SC = SC
+        ctx.SC = int(scaling.shape[1])
         return out[0]
 
     @staticmethod

@@ -136,8 +136,8 @@ def refine_pose(render_target, gaussians: dict, camera, W2C_init: torch.Tensor, 
     tanfovx / tanfovy and `projection_matrix` (splatloc_amd.camera.PinholeCamera or the reference's Camera).
     Returns (W2C [4,4] detached, history of loss values as one device tensor [iterations]).
 
-    `graph_free` (default): an iteration is ONE launch sequence with no torch operator in it — the rasterizer's forward and
-    backward called directly (`PlainCtx`, like training.color_refinement_step), `splatraster_l1_rgbd_loss` for the loss and
+    `graph_free` (default): an iteration is ONE launch sequence with no torch operator in it — the rasterizer's launch functions
+    called directly (rasterizer.view_forward / view_backward, no autograd graph), `splatraster_l1_rgbd_loss` for the loss and
     its gradient planes, `splatraster_pose_step` for the chain rule to (w, t), the Adam step and the next camera tensors
     (csrc/pose.hip): no autograd graph, no torch.optim, the 6 numbers never visit the host.  `graph_free=False` is round
     4's loop (autograd through the 4x4 algebra + torch.optim.Adam): the same iterates to float32 rounding
@@ -147,7 +147,7 @@ def refine_pose(render_target, gaussians: dict, camera, W2C_init: torch.Tensor, 
                                      background, on_step)
     import ctypes as C
     from . import _native
-    from .rasterizer import GaussianRasterizationSettings, PlainCtx, _RasterizeGaussians, _stream
+    from .rasterizer import GaussianRasterizationSettings, _stream, view_backward, view_forward
     lib = _native.load()
     dev = gaussians["means3D"].device
     tgt_c, tgt_d = render_target
@@ -162,7 +162,6 @@ def refine_pose(render_target, gaussians: dict, camera, W2C_init: torch.Tensor, 
     view, proj, campos = torch.empty(4, 4, **f32), torch.empty(4, 4, **f32), torch.empty(3, **f32)
     hist = torch.zeros(iterations, **f32)
     g_color, g_depth = torch.empty_like(tgt_c), torch.empty((1, H, W), **f32)
-    carrier = torch.zeros_like(gaussians["means3D"])
     ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
     b1, b2, eps = 0.9, 0.999, 1e-8          # torch.optim.Adam's defaults, as round 4's loop used them
 
@@ -176,15 +175,14 @@ def refine_pose(render_target, gaussians: dict, camera, W2C_init: torch.Tensor, 
     n_c, n_d = tgt_c.numel(), H * W
     with torch.no_grad():
         for it in range(iterations):
-            ctx = PlainCtx()
-            color, depth, _alpha, _radii = _RasterizeGaussians.forward(
-                ctx, gaussians["means3D"], carrier, None, gaussians["colors"], gaussians["opacities"], gaussians["scales"],
-                gaussians["rotations"], None, rs, view, proj, campos)
-            _native.check(lib.splatraster_l1_rgbd_loss(n_c, ptr(color), ptr(tgt_c), n_d, ptr(depth), ptr(tgt_d), float(depth_weight),
+            f = view_forward(gaussians["means3D"], None, gaussians["colors"], gaussians["opacities"], gaussians["scales"],
+                             gaussians["rotations"], None, rs, view, proj, campos)
+            _native.check(lib.splatraster_l1_rgbd_loss(n_c, ptr(f.color), ptr(tgt_c), n_d, ptr(f.depth), ptr(tgt_d), float(depth_weight),
                                                        ptr(g_color), ptr(g_depth), C.c_void_p(hist.data_ptr() + 4 * it),
                                                        _stream(dev)), "l1_rgbd_loss")
-            grads = _RasterizeGaussians.backward(ctx, g_color, g_depth if tgt_d is not None else None, None)
-            step(1, grads[9:12])
+            d = view_backward(f, g_color, g_depth if tgt_d is not None else None, None, want_pose=True)
+            del f       # (the frame's buffers go back to the allocator before the next forward takes its own)
+            step(1, (d["view"], d["proj"], d["campos"]))
             if on_step:
                 on_step(it, hist[it])
         w, t = state[:3].clone()[None], state[3:6].clone()[None]

@@ -67,66 +67,94 @@ def _raw_backward_ok(gaussians) -> bool:
             and int(g._kp_score.shape[1]) == 1)     # (C = 4: the accumulator rows' colour columns share the moments' 64-byte line)
 
 
-def _color_refinement_step_direct(viewpoint_cam, gaussians, background, lambda_dssim, iteration, primitive_reg):
-    """The iteration of `color_refinement_step` with the SAME forward / backward code (`_ActivatePack`, `_RasterizeWindow`:
-    their static forward / backward called directly with a plain context) but without building an autograd graph: the
-    refinement iteration is HOST-bound at SplatLoc's frame size (tools/refine_idle.py: 0.42 ms of Python per iteration against
-    0.25 - 0.55 ms of kernels), and a third of that host time was the autograd engine handing the two backward nodes to its
-    worker thread.  Gradients land in `.grad` exactly as autograd would leave them: `_xyz` <- dL/dmeans3D, `_features_rest`
-    <- its empty gradient, `_kp_score` <- the zero column, `_marker` <- nothing (tests/test_gpu_refine.py, both paths)."""
-    from .fused import _ActivatePack, _view_settings
-    from .rasterizer import PlainCtx, _RasterizeWindow
-    with torch.no_grad():
-        xyz = gaussians._xyz
-        settings = _view_settings(viewpoint_cam, gaussians, background, 1.0)
-        c_ras = PlainCtx()
-        raw_ok = _raw_backward_ok(gaussians) and int(xyz.shape[0]) > 0
-        if raw_ok:
-            # the activations run inside the projection kernel (rasterizer.py: ctx.raw_fwd): it fills these four tensors
-            P = int(xyz.shape[0])
-            f32 = dict(dtype=torch.float32, device=xyz.device)
-            scales, rotations, opacity = torch.empty((P, 3), **f32), torch.empty((P, 4), **f32), torch.empty((P, 1), **f32)
-            colors = torch.empty((P, 3 + int(gaussians._kp_score.shape[1])), **f32)
-            c_ras.raw_fwd = (gaussians._scaling.detach(), gaussians._rotation.detach(), gaussians._opacity.detach(),
-                             gaussians._features_dc.detach(), gaussians._kp_score.detach())
-            c_act = None
+_PARAMS = ("_xyz", "_features_dc", "_features_rest", "_scaling", "_rotation", "_opacity", "_kp_score")
+
+
+def _grads_direct(gaussians, settings, loss_grads, with_reg: bool):
+    """The gradient part of a refinement iteration or a map step WITHOUT an autograd graph: the launch functions the graph
+    path runs through its autograd Functions (fused.activate_forward / _backward, rasterizer.window_forward / _backward,
+    losses.isotropic_forward), called directly.  At SplatLoc's frame size both steps are HOST-bound (tools/refine_idle.py,
+    tools/hostprof_steps.py), and the autograd engine's hand-off of the backward nodes to its worker thread and its
+    validation of the output gradients were a third of their host time.
+
+        activations -> ONE window forward over `settings` -> loss_grads(outs) -> 0.01 * isotropic regulariser (with_reg)
+        -> ONE window backward -> activation backward -> .grad
+
+    With `_raw_backward_ok` the activations run inside the rasterizer's per-Gaussian kernels instead (raw-parameter mode
+    of window_forward / window_backward: two launches and the activated-gradient tensors less, bit-identical values,
+    tests/test_gpu_refine.py).  `outs`: (rgb, kp_prob, depth, opacity, radii) per view; `loss_grads` returns (loss,
+    [(g_rgb, g_kp_prob, g_depth) per view]).  Gradients land in `.grad` exactly as autograd would leave them: `_xyz` <-
+    dL/dmeans3D, `_features_rest` <- its empty gradient, `_kp_score` <- its gradient (a zero column when only RGB reaches
+    the loss), `_marker` <- nothing.
+    Returns (outs, loss, dL/dmeans2D [V, P, 3])."""
+    from .fused import activate_backward, activate_forward
+    from .losses import isotropic_forward
+    from .rasterizer import window_backward, window_forward, window_outputs
+    g = gaussians
+    xyz = g._xyz
+    raw = act = None
+    if _raw_backward_ok(g):
+        raw = (g._scaling.detach(), g._rotation.detach(), g._opacity.detach(), g._features_dc.detach(), g._kp_score.detach())
+        frame = window_forward(xyz, None, None, None, None, None, settings, raw=raw)
+    else:
+        (scales, rotations, opacity, colors), act = activate_forward(xyz, g._features_dc, g._features_rest, g._scaling,
+                                                                     g._rotation, g._opacity, g._kp_score, None, 0)
+        frame = window_forward(xyz, colors, opacity, scales, rotations, None, settings)
+    outs = window_outputs(frame, 3)
+    loss, grads = loss_grads(outs)
+    reg = None
+    if with_reg:
+        # 0.01 * isotropic regulariser on exp(_scaling) (train_gaussians.py:221-228): its gradient w.r.t. the ACTIVATED scales
+        # joins the rasterizer's before the activation backward multiplies by exp(s)
+        row_grad, out = isotropic_forward(frame.sca, g._marker.detach())
+        reg = (row_grad, out, 0.01)
+        loss = 0.01 * out[0] if loss is None else loss + 0.01 * out[0]
+    d = window_backward(frame, [(g_rgb, g_kp, g_depth, None) for g_rgb, g_kp, g_depth in grads], 3, raw=raw, reg=reg)
+    if raw is not None:
+        fresh = (d["m3"], d["f_dc"], torch.empty_like(g._features_rest), d["scaling"], d["rotation"], d["opacity"], d["extra"])
+    else:
+        d_sca = d["sca"]
+        if reg is not None:
+            d_sca = d_sca + ((reg[2] * reg[1][1]) * reg[0]).view(-1, 1)
+        _dx, d_fd, d_fr, d_sc, d_ro, d_op, d_ex = activate_backward(act, d_sca, d["rot"], d["op"], d["col"])
+        fresh = (d["m3"], d_fd, d_fr, d_sc, d_ro, d_op, d_ex)
+    for k, gr in zip(_PARAMS, fresh):
+        if gr is not None:
+            p = getattr(g, k)
+            p.grad = gr if p.grad is None else p.grad + gr
+    return outs, loss, d["m2"]
+
+
+def _key_gate(gaussians, on: bool) -> None:
+    """The key-primitive gate on xyz.grad (rows whose _marker exceeds 0.005 do not move): inside the fused Adam launch when
+    the optimizer is splatloc_amd.optim.Adam, else the reference's masked assignment."""
+    opt = gaussians.optimizer
+    if hasattr(opt, "set_key_gate"):
+        if on:
+            opt.set_key_gate(gaussians._marker, 0.005)
         else:
-            c_act = PlainCtx()
-            scales, rotations, opacity, colors = _ActivatePack.forward(
-                c_act, xyz, gaussians._features_dc, gaussians._features_rest, gaussians._scaling, gaussians._rotation,
-                gaussians._opacity, gaussians._kp_score, None, 0)
-        rgb, _kp, _depth, _alpha, radii = _RasterizeWindow.forward(c_ras, xyz, colors, opacity, scales, rotations, None, (settings,),
-                                                                 3, None, xyz)     # (means2D is a gradient carrier only)
+            opt.set_key_gate(None)
+    elif on and gaussians._xyz.grad is not None:
+        gaussians._xyz.grad[gaussians._marker.detach().squeeze() > 0.005] = 0
+
+
+def _color_refinement_step_direct(viewpoint_cam, gaussians, background, lambda_dssim, iteration, primitive_reg):
+    """The iteration of `color_refinement_step` without an autograd graph (`_grads_direct`)."""
+    from .fused import _view_settings
+
+    def loss_grads(outs):
+        rgb = outs[0][0]
         gt_image = viewpoint_cam.original_image
         if gt_image.device != rgb.device:
             gt_image = gt_image.to(rgb.device)
         loss, g_image = refinement_loss_and_grad(rgb, gt_image, lambda_dssim)
-        if raw_ok:
-            # the rasterizer's backward writes the RAW parameters' gradients itself (rasterizer.py: ctx.raw): two launches and the
-            # activated-gradient tensors less per iteration, bit-identical values (tests/test_gpu_refine.py)
-            c_ras.raw = (gaussians._scaling.detach(), gaussians._rotation.detach(), gaussians._opacity.detach(),
-                         gaussians._features_dc.detach(), gaussians._kp_score.detach())
-            d = _RasterizeWindow.backward(c_ras, g_image, None, None, None, None)
-            d_m3 = d[0]
-            d_sc, d_ro, d_opa, d_fd, d_ex = c_ras.raw_out
-            d_fr = torch.empty_like(gaussians._features_rest)
-        else:
-            d = _RasterizeWindow.backward(c_ras, g_image, None, None, None, None)
-            d_m3, d_col, d_op, d_sca, d_rot = d[0], d[1], d[2], d[3], d[4]
-            _dx, d_fd, d_fr, d_sc, d_ro, d_opa, d_ex, _, _ = _ActivatePack.backward(c_act, d_sca, d_rot, d_op, d_col)
-        for p, g in ((gaussians._xyz, d_m3), (gaussians._features_dc, d_fd), (gaussians._features_rest, d_fr),
-                     (gaussians._scaling, d_sc), (gaussians._rotation, d_ro), (gaussians._opacity, d_opa), (gaussians._kp_score, d_ex)):
-            if g is not None:
-                p.grad = g if p.grad is None else p.grad + g
+        return loss, [(g_image, None, None)]
+
+    with torch.no_grad():
+        outs, loss, _m2 = _grads_direct(gaussians, [_view_settings(viewpoint_cam, gaussians, background, 1.0)], loss_grads, False)
+        radii = outs[0][4]
         opt = gaussians.optimizer
-        if primitive_reg:
-            if hasattr(opt, "set_key_gate"):
-                opt.set_key_gate(gaussians._marker, 0.005)
-            else:
-                key_mask = gaussians._marker.detach().squeeze() > 0.005
-                gaussians._xyz.grad[key_mask] = 0
-        elif hasattr(opt, "set_key_gate"):
-            opt.set_key_gate(None)
+        _key_gate(gaussians, primitive_reg)
         if hasattr(opt, "set_radii_update") and radii.dtype == torch.int32 and radii.is_contiguous():
             opt.set_radii_update(radii, gaussians.max_radii2D)      # the statistics line rides the fused Adam launch
         else:
@@ -169,14 +197,7 @@ def color_refinement_step(viewpoint_cam, gaussians, pipe, background, lambda_dss
     image.backward(g_image)
     opt = gaussians.optimizer
     with torch.no_grad():
-        if primitive_reg:
-            if hasattr(opt, "set_key_gate"):
-                opt.set_key_gate(gaussians._marker, 0.005)
-            else:
-                key_mask = gaussians._marker.detach().squeeze() > 0.005
-                gaussians._xyz.grad[key_mask] = 0
-        elif hasattr(opt, "set_key_gate"):
-            opt.set_key_gate(None)
+        _key_gate(gaussians, primitive_reg)
         add_densification_stats_window(None, [radii], None, None, gaussians.max_radii2D)
         opt.step()
         opt.zero_grad(set_to_none=True)
@@ -185,82 +206,31 @@ def color_refinement_step(viewpoint_cam, gaussians, pipe, background, lambda_dss
 
 
 def _map_grads_direct(mine, gaussians, pipe, background, config, with_reg: bool):
-    """The gradient part of `map_step` without an autograd graph (same forward / backward code as the graph path: the static
-    `forward` / `backward` of `_ActivatePack`, `_RasterizeWindow`, `_IsotropicLoss` with a plain context; the per-view losses
-    already carry their gradients).  At SplatLoc's frame size a map step is ~2 ms of kernels under ~3 ms of Python (tools/
-    hostprof_steps.py): the engine's hand-off of three backward nodes and its validation of 16 explicit gradient tensors were a
-    third of it.  Leaves the raw-parameter gradients in `.grad`.  Returns (pkgs, loss, [dL/dmeans2D per view]) or None when the
+    """The gradient part of `map_step` without an autograd graph (`_grads_direct`; the per-view losses already carry their
+    gradients).  Leaves the raw-parameter gradients in `.grad`.  Returns (pkgs, loss, [dL/dmeans2D per view]) or None when the
     configuration needs the general path (view-dependent colours, python covariance, mixed image sizes, an empty model)."""
-    from .fused import _ActivatePack, _view_settings
-    from .losses import _IsotropicLoss, mapping_loss_window
-    from .rasterizer import PlainCtx, _RasterizeWindow, _window_compatible
+    from .fused import _view_settings
+    from .losses import mapping_loss_window
+    from .rasterizer import _window_compatible
     from . import _native
     if not _direct_refine_ok(gaussians, pipe) or len(mine) > _native.MAX_WINDOW_VIEWS:
         return None
-    P = int(gaussians._xyz.shape[0])
-    if P * len(mine) > (1 << 24):          # (rasterize_window would chunk the window: general path)
+    if int(gaussians._xyz.shape[0]) * len(mine) > (1 << 24):          # (rasterize_window would chunk the window: general path)
         return None
     settings = [_view_settings(vp, gaussians, background, 1.0) for vp in mine]
     if not _window_compatible(settings):
         return None
-    with torch.no_grad():
-        xyz = gaussians._xyz
-        c_ras = PlainCtx()
-        V = len(mine)
-        raw_ok = _raw_backward_ok(gaussians) and P > 0
-        raw_in = (gaussians._scaling.detach(), gaussians._rotation.detach(), gaussians._opacity.detach(),
-                  gaussians._features_dc.detach(), gaussians._kp_score.detach()) if raw_ok else None
-        if raw_ok:
-            # the activations run inside the projection kernel (rasterizer.py: ctx.raw_fwd), which fills these four tensors
-            f32 = dict(dtype=torch.float32, device=xyz.device)
-            scales, rotations, opacity = torch.empty((P, 3), **f32), torch.empty((P, 4), **f32), torch.empty((P, 1), **f32)
-            colors = torch.empty((P, 3 + int(gaussians._kp_score.shape[1])), **f32)
-            c_ras.raw_fwd = raw_in
-            c_act = None
-        else:
-            c_act = PlainCtx()
-            scales, rotations, opacity, colors = _ActivatePack.forward(
-                c_act, xyz, gaussians._features_dc, gaussians._features_rest, gaussians._scaling, gaussians._rotation,
-                gaussians._opacity, gaussians._kp_score, None, 0)
-        outs = _RasterizeWindow.forward(c_ras, xyz, colors, opacity, scales, rotations, None, tuple(settings), 3, None,
-                                        *([xyz] * V))
-        pkgs = []
-        for v in range(V):
-            rgb, kp, depth, alpha, radii = outs[5 * v:5 * v + 5]
+    pkgs = []
+
+    def loss_grads(outs):
+        for rgb, kp, depth, alpha, radii in outs:
             pkgs.append({"render": rgb, "kp_prob": kp, "depth": depth, "opacity": alpha, "radii": radii})
         _t, g, loss = mapping_loss_window(config, pkgs, mine)      # g = [g_render, g_depth, g_kp] per view
-        gouts = []
-        for v in range(V):
-            gouts += [g[3 * v], g[3 * v + 2], g[3 * v + 1], None, None]      # (rgb, last, depth, alpha, radii)
-        reg = None
-        if with_reg:
-            # 0.01 * isotropic regulariser on exp(_scaling) (train_gaussians.py:221-228): its gradient w.r.t. the ACTIVATED scales
-            # joins the rasterizer's before the activation backward multiplies by exp(s)
-            c_reg = PlainCtx()
-            value = _IsotropicLoss.forward(c_reg, scales, gaussians._marker.detach())
-            row_grad, out = c_reg.saved_tensors
-            reg = (row_grad, out, 0.01)
-            loss = 0.01 * value if loss is None else loss + 0.01 * value
-        if raw_ok:
-            # the rasterizer's backward writes the RAW parameters' gradients itself, the regulariser's term included (ctx.raw)
-            c_ras.raw = raw_in + ((reg,) if reg is not None else ())
-            d = _RasterizeWindow.backward(c_ras, *gouts)
-            d_m3 = d[0]
-            grads2d = list(d[9:9 + V])
-            d_sc, d_ro, d_opa, d_fd, d_ex = c_ras.raw_out
-            d_fr = torch.empty_like(gaussians._features_rest)
-        else:
-            d = _RasterizeWindow.backward(c_ras, *gouts)
-            d_m3, d_col, d_op, d_sca, d_rot = d[0], d[1], d[2], d[3], d[4]
-            grads2d = list(d[9:9 + V])
-            if reg is not None:
-                d_sca = d_sca + ((reg[2] * reg[1][1]) * reg[0]).view(-1, 1)
-            _dx, d_fd, d_fr, d_sc, d_ro, d_opa, d_ex, _, _ = _ActivatePack.backward(c_act, d_sca, d_rot, d_op, d_col)
-        for p, gr in ((gaussians._xyz, d_m3), (gaussians._features_dc, d_fd), (gaussians._features_rest, d_fr),
-                      (gaussians._scaling, d_sc), (gaussians._rotation, d_ro), (gaussians._opacity, d_opa), (gaussians._kp_score, d_ex)):
-            if gr is not None:
-                p.grad = gr if p.grad is None else p.grad + gr
-    return pkgs, loss, grads2d
+        return loss, [(g[3 * v], g[3 * v + 2], g[3 * v + 1]) for v in range(len(mine))]
+
+    with torch.no_grad():
+        _outs, loss, m2 = _grads_direct(gaussians, settings, loss_grads, with_reg)
+    return pkgs, loss, [m2[v] for v in range(len(mine))]
 
 
 # how a multi-GPU map_step sums its payload: "ring" (one all-reduce) or "rs_ag" (reduce-scatter + all-gather);
@@ -372,13 +342,7 @@ def map_step(viewpoints, gaussians, pipe, background, config, iteration_count: i
             if pkgs:
                 add_densification_stats_window(grads2d, radii, gaussians.xyz_gradient_accum, gaussians.denom, gaussians.max_radii2D)
         LAST_STEP_INFO["render_path"] = ran
-        if primitive_reg:
-            if hasattr(opt, "set_key_gate"):
-                opt.set_key_gate(gaussians._marker, 0.005)
-            elif gaussians._xyz.grad is not None:
-                gaussians._xyz.grad[gaussians._marker.detach().squeeze() > 0.005] = 0
-        elif hasattr(opt, "set_key_gate"):
-            opt.set_key_gate(None)
+        _key_gate(gaussians, primitive_reg)
         if update_gaussian:
             densify_and_prune(gaussians, densify["grad_threshold"], densify["min_opacity"], densify["extent"],
                               densify["size_threshold"], seed=seed, draw_id=iteration_count)

@@ -61,8 +61,7 @@ class HipRun:
                                           cov3D_precomp=self.cov3D)
         self.color, self.depth, self.alpha, self.radii = color, depth, alpha, radii
         fn = color.grad_fn
-        saved = fn.saved_tensors
-        geom, binning, img = saved[12], saved[13], saved[14]
+        geom, binning, img = introspect.forward_buffers(fn)
         P = sc.means3D.shape[0]
         W, H = sc.camera.image_width, sc.camera.image_height
         self.num_rendered = fn.num_rendered

@@ -133,8 +133,7 @@ def test_window_of_views_binned_equals_radix():
         res = rasterize_window(settings, m3, m2, sc.features.to(dev), sc.opacities.to(dev), sc.scales.to(dev),
                                sc.rotations.to(dev))
         fn = res[0][0].grad_fn
-        saved = fn.saved_tensors
-        st = introspect.window_state((saved[7], saved[8], saved[9]), 30_000, 5, 320, 240, fn.R)
+        st = introspect.window_state(introspect.forward_buffers(fn), 30_000, 5, 320, 240, fn.R)
         outs[mode] = (res, st)
     torch.cuda.synchronize()
     for v in range(5):

@@ -223,6 +223,48 @@ def test_raw_parameter_backward_is_the_two_kernel_chain_bit_for_bit(workload):
 
 
 @pytest.mark.parametrize("workload", ["S0", "S2-ref-layout"])
+def test_graph_free_refinement_step_is_the_autograd_window_step_bit_for_bit(workload):
+    """`color_refinement_step` without an autograd graph (render_path "auto": the rasterizer's launch functions called
+    directly, raw-parameter kernels) and under autograd (render_path "window": _ActivatePack + _RasterizeWindow) take the SAME
+    step from the same state: with the deterministic-sum compositing the loss, every parameter, both Adam moments and
+    max_radii2D are identical bit for bit."""
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+    import map_idle
+    from splatloc_amd import _native, training
+    dev = torch.device(DEV)
+    bg = torch.zeros(3, device=dev)
+    pipe = types.SimpleNamespace(convert_SHs_python=True, compute_cov3D_python=False)
+    res = {}
+    _native.set_deterministic(True)
+    try:
+        for path in ("auto", "window"):
+            pc, views = map_idle.build(workload, dev)
+            for grp in pc.optimizer.param_groups:
+                grp["lr"] = 1e-3        # (map_idle's rates are 0: here the parameters have to move)
+            assert training._direct_refine_ok(pc, pipe)
+            loss = training.color_refinement_step(views[1], pc, pipe, bg, 0.2, 7, primitive_reg=True, render_path=path)
+            torch.cuda.synchronize()
+            out = {"loss": loss.detach().reshape(1).clone(), "max_radii2D": pc.max_radii2D.clone()}
+            for k in ATTR.values():
+                p = getattr(pc, k)
+                out[k] = p.detach().clone()
+                st = pc.optimizer.state.get(p, {})
+                for m in ("exp_avg", "exp_avg_sq"):
+                    if m in st:
+                        out[f"{k} {m}"] = st[m].clone()
+            res[path] = out
+            del pc, views
+    finally:
+        _native.set_deterministic(False)
+    a, b = res["auto"], res["window"]
+    assert a.keys() == b.keys() and "_xyz exp_avg" in a
+    for k in a:
+        assert a[k].shape == b[k].shape and torch.equal(a[k].view(torch.int32), b[k].view(torch.int32)), (k, float((a[k] - b[k]).abs().max()))
+    assert float(a["_scaling exp_avg"].abs().max()) > 0 and float(a["max_radii2D"].max()) > 0
+
+
+@pytest.mark.parametrize("workload", ["S0", "S2-ref-layout"])
 def test_map_step_raw_parameter_path_is_the_two_kernel_chain_bit_for_bit(workload):
     """The same for the graph-free MAP step (five views, the isotropic regulariser's term joining dL/dscales inside the per-Gaussian
     backward before the chain through exp): gradients of every parameter group, the per-view dL/dmeans2D and the loss identical bit for

@@ -57,8 +57,7 @@ def _serial(sc, views, dev, cov=None, use=(True, True, True)):
             means3D=L["means3D"], means2D=m2, shs=None, colors_precomp=L["colors"], opacities=L["opac"],
             scales=L["scales"], rotations=L["rots"], cov3D_precomp=L["cov"])
         fn = color.grad_fn
-        sv = fn.saved_tensors
-        states.append((introspect.forward_state((sv[12], sv[13], sv[14]), sc.means3D.shape[0], cam.image_width,
+        states.append((introspect.forward_state(introspect.forward_buffers(fn), sc.means3D.shape[0], cam.image_width,
                                                 cam.image_height, fn.num_rendered), fn.num_rendered))
         outs.append((color, depth, alpha, radii))
         m2s.append(m2)
@@ -82,10 +81,9 @@ def _window(sc, views, dev, cov=None, use=(True, True, True)):
     K = 8
     for a in range(0, len(views), K):
         fn = outs[a][0].grad_fn
-        sv = fn.saved_tensors
         V = min(K, len(views) - a)
         cam = views[0][0]
-        states += [(st, R) for st, R in zip(introspect.window_state((sv[7], sv[8], sv[9]), sc.means3D.shape[0], V,
+        states += [(st, R) for st, R in zip(introspect.window_state(introspect.forward_buffers(fn), sc.means3D.shape[0], V,
                                                                    cam.image_width, cam.image_height, fn.R), fn.R)]
     loss = 0
     for (color, depth, alpha, radii), (_, _, g) in zip(outs, views):

@@ -44,8 +44,7 @@ def main():
             means3D=m3, means2D=torch.zeros_like(m3), shs=None, colors_precomp=act["colors"], opacities=act["opacities"],
             scales=act["scales"], rotations=act["rotations"], cov3D_precomp=None)
         fn = color.grad_fn
-        sv = fn.saved_tensors
-        st = introspect.forward_state((sv[12], sv[13], sv[14]), P, W, H, fn.num_rendered)
+        st = introspect.forward_state(introspect.forward_buffers(fn), P, W, H, fn.num_rendered)
         lens = (st["ranges"][:, 1] - st["ranges"][:, 0]).long().cpu()
         out["views"].append({"uid": f.uid, "R": int(fn.num_rendered), "mean": round(float(lens.float().mean()), 1),
                              "max": int(lens.max()), "over_1024": int((lens > 1024).sum()), "over_2048": int((lens > 2048).sum()),
