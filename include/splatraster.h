@@ -16,6 +16,8 @@
  *       call site  models/encoding.py:3,33-46 (built), models/decoders.py:63 (called)
  *   utils.selection.gaussian_selectition (landmark selection)
  *       call site  test.py:39 (import), test.py:564 (called by --eval_selection)
+ *   utils.match_utils.HungarianMatcher / hungarian_solve, LocalizeQuery.get_frusm_pts (2D-3D matching)
+ *       call site  test.py:247-378 (match_feature, --eval_pose)
  *
  * Everything here is plain C: raw device pointers, sizes, an opaque stream handle
  * (hipStream_t passed as void*), int status codes.  No torch types, no exceptions.
@@ -40,7 +42,7 @@ extern "C" {
 /* bumped on every change of a signature or buffer layout; the Python binding refuses a library
  * whose splatraster_abi_version() differs (a stale in-tree .so would otherwise be called through
  * ctypes with mismatched arguments) */
-#define SPLATRASTER_ABI_VERSION 15
+#define SPLATRASTER_ABI_VERSION 16
 
 #define SPLATRASTER_TILE 16 /* tile edge in pixels (16x16 = 256 pixels = 4 wave64) */
 
@@ -616,6 +618,58 @@ size_t splatraster_landmark_workspace_bytes(int64_t N, int32_t num);
  * positive and finite, or when the radius underflows to 0 first (fewer than num distinct positions). */
 int splatraster_landmark_select(int64_t N, const float* points, const double* score, int32_t num, double radius,
                                 int32_t* out_idx, int32_t* n_passes, void* workspace, void* stream);
+
+/* ---- 2D-3D matching: test.py:247-378 (get_frusm_pts, match_feature), utils/match_utils.py (hungarian_solve), INTEGRATION.md §17
+ * Exact rectangular assignment (scipy.optimize.linear_sum_assignment, Crouse's shortest augmenting path): for the same f64 cost
+ * matrix the same assignment as scipy, ties included.  Problem b is the ORIENTED [nr, nc] f64 matrix (nr <= nc, row-major) at
+ * element `offset` of `costs`; `transposed` != 0 says it is the transpose of the caller's matrix.  Limits: 1 <= nr <= nc <=
+ * SPLATRASTER_LSAP_MAX_NC and nr * nc < 2^31 (SPLATRASTER_ERR_OVERFLOW beyond them, SPLATRASTER_ERR_BAD_ARG for nr < 1 or nc < nr).
+ * maximize != 0 solves on -cost.  Problem b writes nr pairs at row_ind / col_ind [sum of nr] (int64, device) from slot
+ * sum_{b' < b} nr_b', in the caller's orientation: untransposed (i, col of row i) for i = 0..nr-1; transposed the caller's rows
+ * ascending and their columns.  status[b] (device) receives SPLATRASTER_LSAP_OK, _INVALID (a NaN or, after the sign, a -inf
+ * entry) or _INFEASIBLE (no finite assignment), steps[b] the Dijkstra steps taken.  The problem table is host memory; no host
+ * synchronisation.  The column / row state lives in LDS when nc <= 4096 (splatraster_debug_set_lsap_lds(1), the default) and
+ * in `workspace` otherwise (splatraster_lsap_workspace_bytes; 0 bytes when every problem fits the LDS). */
+#define SPLATRASTER_LSAP_MAX_NC 65535
+#define SPLATRASTER_LSAP_OK 0
+#define SPLATRASTER_LSAP_INVALID 1
+#define SPLATRASTER_LSAP_INFEASIBLE 2
+typedef struct splatraster_lsap_problem {
+    int64_t offset;
+    int32_t nr, nc;
+    int32_t transposed;
+    int32_t reserved;
+} splatraster_lsap_problem;
+size_t splatraster_lsap_workspace_bytes(int32_t B, const splatraster_lsap_problem* problems);
+int splatraster_lsap(int32_t B, const splatraster_lsap_problem* problems, const double* costs, int32_t maximize,
+                     int64_t* row_ind, int64_t* col_ind, int32_t* status, int32_t* steps, void* workspace, void* stream);
+/* test hook: 1 (default) keeps the solver state of problems with nc <= 4096 in LDS, 0 forces the global workspace for every
+ * problem.  Results never depend on it. */
+int splatraster_debug_set_lsap_lds(int mode);
+/* hungarian_solve's cost: d1 [D, N1], d2 [D, N2] f32 (columns are descriptors), each column divided by max(||x||, 1e-12)
+ * (F.normalize(p=2, dim=0)); sim = d1^T d2 in f32 (one FMA chain over D per entry), sim < threshold -> 0, cost = 1 - sim (f32),
+ * written widened to f64 in the solver's orientation: [N1, N2] when N1 <= N2, else [N2, N1] (its transpose).  norms [N1 + N2]
+ * (device) receives the denominators.  splatraster_match_sims gathers the thresholded similarity of K pairs (i1[k], i2[k])
+ * (int64 indices into d1 / d2, device) with the same arithmetic as the matrix.  No host synchronisation. */
+int splatraster_match_cost(int32_t D, int32_t N1, int32_t N2, const float* d1, const float* d2, float threshold, float* norms,
+                           double* cost, void* stream);
+int splatraster_match_sims(int32_t D, int32_t N1, int32_t N2, const float* d1, const float* d2, const float* norms,
+                           float threshold, int64_t K, const int64_t* i1, const int64_t* i2, float* sims, void* stream);
+/* get_frusm_pts without the decoder.  points [N,3] f32 (device); w2c [4,4] and K [3,3] f64 row-major (HOST).  All arithmetic in
+ * f64 from the f32 inputs: pc = R p + t, (u, v) = (K pc)_{0,1} / (K pc)_2; kept iff pc.z > 0.05, 0 <= u < width, 0 <= v < height
+ * and, in key-Gaussian mode (marker != NULL, [N] f32), marker > marker_threshold (compared in f32 like the reference).
+ * Subset mode (marker == NULL): the kept points in index order.  Key-Gaussian mode: every pixel of kp_mask [height, width] (u8,
+ * 1 = keypoint; row-major order) is back-projected with depth [height, width] f32, c2w [4,4] (f64, HOST) and kp_K = (fx, fy,
+ * cx, cy) (HOST): x = (col - cx) * d / fx, y = (row - cy) * d / fy, z = d, q = R x + t; its nearest kept point (distance
+ * sqrt((dx^2 + dy^2) + dz^2) in f64, ties the smaller index) is emitted, in keypoint order, when closer than 0.1.
+ * Outputs (device): out_idx [n] i32 point indices, out_xyz [n,3] f32, out_uv [n,2] f64 projections, *out_count (int64, device) =
+ * n; capacity N (subset) or width * height (key mode).  workspace: splatraster_frustum_workspace_bytes(N, width, height).  No
+ * host synchronisation. */
+size_t splatraster_frustum_workspace_bytes(int64_t N, int32_t width, int32_t height);
+int splatraster_frustum_candidates(int64_t N, const float* points, const float* marker, float marker_threshold, const double* w2c,
+                                   const double* K, int32_t width, int32_t height, const uint8_t* kp_mask, const float* depth,
+                                   const double* c2w, const double* kp_K, int32_t* out_idx, float* out_xyz, double* out_uv,
+                                   int64_t* out_count, void* workspace, void* stream);
 
 /* ---- pose refinement on the device (build extension, DESIGN.md §6.8: the reference's rasterizer returns no camera gradient
  * and nothing calls its utils/optimization_utils.py:5-66 pose helpers) ------------------------------------------------------

@@ -1154,4 +1154,44 @@ int splatraster_landmark_select(int64_t N, const float* points, const double* sc
     return landmark_select(N, points, score, num, radius, out_idx, n_passes, workspace, reinterpret_cast<hipStream_t>(stream));
 }
 
+size_t splatraster_lsap_workspace_bytes(int32_t B, const splatraster_lsap_problem* problems)
+{
+    return lsap_workspace_bytes(B, problems);
+}
+
+int splatraster_lsap(int32_t B, const splatraster_lsap_problem* problems, const double* costs, int32_t maximize,
+                     int64_t* row_ind, int64_t* col_ind, int32_t* status, int32_t* steps, void* workspace, void* stream)
+{
+    return lsap_solve(B, problems, costs, maximize, row_ind, col_ind, status, steps, workspace,
+                      reinterpret_cast<hipStream_t>(stream));
+}
+
+int splatraster_debug_set_lsap_lds(int mode) { return lsap_set_lds(mode); }
+
+int splatraster_match_cost(int32_t D, int32_t N1, int32_t N2, const float* d1, const float* d2, float threshold, float* norms,
+                           double* cost, void* stream)
+{
+    return match_cost(D, N1, N2, d1, d2, threshold, norms, cost, reinterpret_cast<hipStream_t>(stream));
+}
+
+int splatraster_match_sims(int32_t D, int32_t N1, int32_t N2, const float* d1, const float* d2, const float* norms,
+                           float threshold, int64_t K, const int64_t* i1, const int64_t* i2, float* sims, void* stream)
+{
+    return match_sims(D, N1, N2, d1, d2, norms, threshold, K, i1, i2, sims, reinterpret_cast<hipStream_t>(stream));
+}
+
+size_t splatraster_frustum_workspace_bytes(int64_t N, int32_t width, int32_t height)
+{
+    return frustum_workspace_bytes(N, width, height);
+}
+
+int splatraster_frustum_candidates(int64_t N, const float* points, const float* marker, float marker_threshold, const double* w2c,
+                                   const double* K, int32_t width, int32_t height, const uint8_t* kp_mask, const float* depth,
+                                   const double* c2w, const double* kp_K, int32_t* out_idx, float* out_xyz, double* out_uv,
+                                   int64_t* out_count, void* workspace, void* stream)
+{
+    return frustum_candidates(N, points, marker, marker_threshold, w2c, K, width, height, kp_mask, depth, c2w, kp_K, out_idx,
+                              out_xyz, out_uv, out_count, workspace, reinterpret_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

@@ -401,4 +401,19 @@ size_t landmark_workspace_bytes(int64_t N, int32_t num);
 int landmark_select(int64_t N, const float* points, const double* score, int32_t num, double radius, int32_t* out_idx,
                     int32_t* n_passes, void* workspace, hipStream_t stream);
 
+// matching.hip (2D-3D matching: assignment solver, descriptor cost, frustum candidates)
+size_t lsap_workspace_bytes(int32_t B, const splatraster_lsap_problem* problems);
+int lsap_solve(int32_t B, const splatraster_lsap_problem* problems, const double* costs, int32_t maximize, int64_t* row_ind,
+               int64_t* col_ind, int32_t* status, int32_t* steps, void* workspace, hipStream_t stream);
+int lsap_set_lds(int mode);
+int match_cost(int32_t D, int32_t N1, int32_t N2, const float* d1, const float* d2, float threshold, float* norms,
+               double* cost, hipStream_t stream);
+int match_sims(int32_t D, int32_t N1, int32_t N2, const float* d1, const float* d2, const float* norms, float threshold,
+               int64_t K, const int64_t* i1, const int64_t* i2, float* sims, hipStream_t stream);
+size_t frustum_workspace_bytes(int64_t N, int32_t width, int32_t height);
+int frustum_candidates(int64_t N, const float* points, const float* marker, float marker_threshold, const double* w2c,
+                       const double* K, int32_t width, int32_t height, const uint8_t* kp_mask, const float* depth,
+                       const double* c2w, const double* kp_K, int32_t* out_idx, float* out_xyz, double* out_uv,
+                       int64_t* out_count, void* workspace, hipStream_t stream);
+
 }  // namespace sr

@@ -29,6 +29,7 @@ WHAT = [   # (file name regex, description; {placeholders} are filled by the ext
     (r"r\d+_hostprof_.*\.txt$", "cProfile of the host side of a refinement / map step (`tools/hostprof_steps.py`)"),
     (r"r\d+_ab_probes\.txt$", "A/B and timing-probe log of the round (one box per block)"),
     (r"r\d+_knn\.json$", "`distCUDA2` wall times, brute force vs exact grid"),
+    (r"^matching_time\.json$", "2D-3D matching (`hungarian_solve` cost + exact assignment, batched solver, frustum candidates) against torch-CPU + scipy on the same host, HIP events (`tools/matching_time.py`): {matching}"),
     (r"^landmark_selection_time\.json$", "landmark selection (`gaussian_selectition`) at Replica scale on a synthetic room, HIP events per stage (`tools/landmark_selection_time.py`): {landmark}"),
     (r"r\d+_scene_lists.*\.json$", "one `color_refinement` iteration on a RECONSTRUCTED room (list-length distribution, per-kernel table; `tools/scene_lists.py`; suffix = the forced variant): {scenelists}"),
     (r"r\d+_scene.*\.json$", "`bench.py --stage scene`: the whole reconstruction schedule as one run (suffix: `replica_scale` = 180 key-frames of a 600k-Gaussian room, `radix_front_end` = SPLATRASTER_FRONT_END=0): {bench}{scene}"),
@@ -193,7 +194,20 @@ def landmark(path):
             f"{min(se):.0f}-{max(se):.0f} ms ({rows[0].get('passes', '?')} passes) over {len(rows)} runs")
 
 
-EXTRACT = {"scenelists": scenelists, "scene": scene, "ab": ab, "perview": perview, "mapidle": mapidle, "rccl": rccl, "kstats": kstats, "hbm": hbm, "sq": sq, "timeline": timeline, "bench": bench, "clocks": clocks, "gradbars": gradbars, "idle": idle, "landmark": landmark}
+def matching(path):
+    j = _load(path) or {}
+    rows = j.get("rows") or []
+    if not rows:
+        return "(no rows)"
+    parts = [f"({r['N1']}, {r['N2']}) {min(r['cost_plus_solve_ms']):.1f} ms vs CPU {r['cpu_matmul_ms'] + r['cpu_scipy_ms']:.0f} ms"
+             for r in rows]
+    b = j.get("batch") or {}
+    c = j.get("candidates") or {}
+    return (", ".join(parts) + f"; B = {b.get('B', '?')} batch {b.get('problems_per_s', '?')} problems/s; candidates "
+            f"{min(c.get('ms') or [0]):.2f} ms")
+
+
+EXTRACT = {"scenelists": scenelists, "scene": scene, "ab": ab, "perview": perview, "mapidle": mapidle, "rccl": rccl, "kstats": kstats, "hbm": hbm, "sq": sq, "timeline": timeline, "bench": bench, "clocks": clocks, "gradbars": gradbars, "idle": idle, "landmark": landmark, "matching": matching}
 
 
 def describe(name, path):
