@@ -18,6 +18,8 @@
  *       call site  test.py:39 (import), test.py:564 (called by --eval_selection)
  *   utils.match_utils.HungarianMatcher / hungarian_solve, LocalizeQuery.get_frusm_pts (2D-3D matching)
  *       call site  test.py:247-378 (match_feature, --eval_pose)
+ *   pycolmap.absolute_pose_estimation via solve_pose (absolute pose: P3P LO-RANSAC and refinement)
+ *       call site  test.py:64-84 (solve_pose), test.py:345 (called by match_feature, --eval_pose)
  *
  * Everything here is plain C: raw device pointers, sizes, an opaque stream handle
  * (hipStream_t passed as void*), int status codes.  No torch types, no exceptions.
@@ -42,7 +44,7 @@ extern "C" {
 /* bumped on every change of a signature or buffer layout; the Python binding refuses a library
  * whose splatraster_abi_version() differs (a stale in-tree .so would otherwise be called through
  * ctypes with mismatched arguments) */
-#define SPLATRASTER_ABI_VERSION 16
+#define SPLATRASTER_ABI_VERSION 17
 
 #define SPLATRASTER_TILE 16 /* tile edge in pixels (16x16 = 256 pixels = 4 wave64) */
 
@@ -670,6 +672,74 @@ int splatraster_frustum_candidates(int64_t N, const float* points, const float* 
                                    const double* K, int32_t width, int32_t height, const uint8_t* kp_mask, const float* depth,
                                    const double* c2w, const double* kp_K, int32_t* out_idx, float* out_xyz, double* out_uv,
                                    int64_t* out_count, void* workspace, void* stream);
+
+/* ---- absolute pose: test.py:64-84 (solve_pose -> pycolmap.absolute_pose_estimation), INTEGRATION.md §18 -------------------
+ * P3P LO-RANSAC and a robust refinement for B problems of different sizes.  Problem b holds n correspondences at element
+ * `offset` of points2d [*, 2] and points3d [*, 3] (f64, device) and a pinhole camera (fx, fy, cx, cy).  The pose is
+ * world-to-camera: x_cam = R X + t.  Everything is f64 and compiled without FP contraction; the definitions below are exact.
+ *
+ * Residual of (R, t) at correspondence i: (x, y, z) = R X + t with x = ((R00*X0 + R01*X1) + R02*X2) + t0 (same for y, z);
+ *   du = u - (fx * (x / z) + cx), dv = v - (fy * (y / z) + cy), r = du*du + dv*dv (no +0.5 shift of the keypoints).
+ *   i is an inlier iff z > 0 and r <= thr2, thr2 = max_error_px * max_error_px.
+ * Support: (inlier count, sum of r over the inliers).  A model is better with more inliers; at equal counts with the smaller
+ *   sum; then the lower trial, then the lower solution index (slot = 4 * trial + solution).
+ * Sampler (stateless): mix(x) = splitmix64's finaliser: x += 0x9E3779B97F4A7C15; x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9;
+ *   x = (x ^ (x >> 27)) * 0x94D049BB133111EB; x ^ (x >> 31) (uint64 wrap-around).  h_d = mix(mix(seed) ^ (3 * trial + d))
+ *   for draw d = 0, 1, 2.  i0 = h_0 mod n; i1 = h_1 mod (n - 1), +1 if >= i0; i2 = h_2 mod (n - 2), +1 if >= min(i0, i1),
+ *   +1 more if then >= max(i0, i1).  The problem's position in the batch is not hashed, so a problem draws the same samples
+ *   alone or in a batch.
+ * Minimal solver: Grunert's P3P on the bearings normalize((u - cx) / fx, (v - cy) / fy, 1): the quartic in v = s3 / s1
+ *   (Haralick et al. 1994), its real roots by Ferrari's resolvent (largest cubic root in closed form, 2 Newton steps on the
+ *   cubic, 2 on the quartic), u = s2 / s1 from v, the depths polished by 3 Newton steps on the three cosine-law equations, and
+ *   (R, t) from the orthonormal frames of the two triangles (t from the centroids).  Up to 4 models per trial; v <= 0, u <= 0, a
+ *   degenerate triangle (|e1 x e2| <= 1e-10 |e1| |e2|, a zero side) or a non-finite entry drops a model.  Never NaN.
+ * Trials run in batches of SPLATRASTER_PNP_BATCH.  After each batch, with k the best inlier count: required = max_num_trials
+ *   if k == 0 or k / n < min_inlier_ratio; else p3 = (k / n)^3, required = min_num_trials if p3 >= 1, else
+ *   ceil(log(1 - confidence) / log(1 - p3)) clipped to [min_num_trials, max_num_trials] (max_num_trials if the log is 0).
+ *   A problem finishes when its trials (a multiple of the batch) reach the required count.
+ * LO: when a batch's best model beats the running best, up to 4 rounds of { up to 10 Gauss-Newton steps of sum r over the
+ *   inliers of the round's start model (rotation by the so(3) exponential, left-multiplied; t additive), re-score on all n };
+ *   a round is kept if its support is better, and LO stops at the first round that is not.
+ * Success: a best model with >= 4 inliers.  Final refinement: Levenberg-Marquardt on sum log(1 + r) over the RANSAC inliers,
+ *   at most 100 iterations, stopping when the relative cost change or the step norm falls below 1e-10; a non-finite result is
+ *   SPLATRASTER_PNP_NONFINITE.  num_inliers / inlier_mask are those of the RANSAC model, before refinement.
+ * Every reduction has a fixed order (no atomics): outputs are bit-identical from run to run and between a batch and single
+ *   calls.  n < 4 gives SPLATRASTER_PNP_NO_MODEL without any trial.
+ * Outputs (device): R_out [B, 9] (row-major), t_out [B, 3] f64, num_inliers [B] i32, inlier_mask [sum n] u8, status [B] i32,
+ *   trials [B] i32.  One stream synchronisation per batch of trials (the "all finished" flag).  workspace:
+ *   splatraster_pnp_workspace_bytes.  Limits: n <= SPLATRASTER_PNP_MAX_N, B <= 65535, 1 <= min_num_trials <= max_num_trials. */
+#define SPLATRASTER_PNP_BATCH 1024
+#define SPLATRASTER_PNP_MAX_N (1 << 20)
+#define SPLATRASTER_PNP_OK 0
+#define SPLATRASTER_PNP_NO_MODEL 1
+#define SPLATRASTER_PNP_NONFINITE 2
+typedef struct splatraster_pnp_problem {
+    int64_t offset;
+    int32_t n;
+    int32_t reserved;
+    double fx, fy, cx, cy;
+} splatraster_pnp_problem;
+typedef struct splatraster_pnp_options {
+    double max_error_px;
+    double min_inlier_ratio;
+    double confidence;
+    uint64_t seed;
+    int32_t min_num_trials, max_num_trials;
+} splatraster_pnp_options;
+size_t splatraster_pnp_workspace_bytes(int32_t B, const splatraster_pnp_problem* problems, const splatraster_pnp_options* options);
+int splatraster_pnp(int32_t B, const splatraster_pnp_problem* problems, const splatraster_pnp_options* options,
+                    const double* points2d, const double* points3d, double* R_out, double* t_out, int32_t* num_inliers,
+                    uint8_t* inlier_mask, int32_t* status, int32_t* trials, void* workspace, void* stream);
+/* test entries (same workspace, no host synchronisation).  hypotheses: trials trial0 .. trial0 + ntrials - 1 of every problem
+ * (ntrials <= SPLATRASTER_PNP_BATCH): samples [B, ntrials, 3] i32, models [B, ntrials, 4, 12] f64 (R row-major, t; slots past
+ * nmodels unwritten), nmodels [B, ntrials] i32.  score: the support of M given models [B, M, 12] per problem: count [B, M] i32,
+ * sum [B, M] f64. */
+int splatraster_pnp_hypotheses(int32_t B, const splatraster_pnp_problem* problems, const splatraster_pnp_options* options,
+                               int64_t trial0, int32_t ntrials, const double* points2d, const double* points3d, int32_t* samples,
+                               double* models, int32_t* nmodels, void* workspace, void* stream);
+int splatraster_pnp_score(int32_t B, const splatraster_pnp_problem* problems, const splatraster_pnp_options* options, int32_t M,
+                          const double* models, const double* points2d, const double* points3d, int32_t* count, double* sum,
+                          void* workspace, void* stream);
 
 /* ---- pose refinement on the device (build extension, DESIGN.md §6.8: the reference's rasterizer returns no camera gradient
  * and nothing calls its utils/optimization_utils.py:5-66 pose helpers) ------------------------------------------------------

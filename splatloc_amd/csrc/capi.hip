@@ -1194,4 +1194,33 @@ int splatraster_frustum_candidates(int64_t N, const float* points, const float* 
                               out_xyz, out_uv, out_count, workspace, reinterpret_cast<hipStream_t>(stream));
 }
 
+size_t splatraster_pnp_workspace_bytes(int32_t B, const splatraster_pnp_problem* problems, const splatraster_pnp_options* options)
+{
+    return pnp_workspace_bytes(B, problems, options);
+}
+
+int splatraster_pnp(int32_t B, const splatraster_pnp_problem* problems, const splatraster_pnp_options* options,
+                    const double* points2d, const double* points3d, double* R_out, double* t_out, int32_t* num_inliers,
+                    uint8_t* inlier_mask, int32_t* status, int32_t* trials, void* workspace, void* stream)
+{
+    return pnp_solve(B, problems, options, points2d, points3d, R_out, t_out, num_inliers, inlier_mask, status, trials, workspace,
+                     reinterpret_cast<hipStream_t>(stream));
+}
+
+int splatraster_pnp_hypotheses(int32_t B, const splatraster_pnp_problem* problems, const splatraster_pnp_options* options,
+                               int64_t trial0, int32_t ntrials, const double* points2d, const double* points3d, int32_t* samples,
+                               double* models, int32_t* nmodels, void* workspace, void* stream)
+{
+    return pnp_hypotheses(B, problems, options, trial0, ntrials, points2d, points3d, samples, models, nmodels, workspace,
+                          reinterpret_cast<hipStream_t>(stream));
+}
+
+int splatraster_pnp_score(int32_t B, const splatraster_pnp_problem* problems, const splatraster_pnp_options* options, int32_t M,
+                          const double* models, const double* points2d, const double* points3d, int32_t* count, double* sum,
+                          void* workspace, void* stream)
+{
+    return pnp_score(B, problems, options, M, models, points2d, points3d, count, sum, workspace,
+                     reinterpret_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

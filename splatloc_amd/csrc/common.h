@@ -416,4 +416,16 @@ int frustum_candidates(int64_t N, const float* points, const float* marker, floa
                        const double* c2w, const double* kp_K, int32_t* out_idx, float* out_xyz, double* out_uv,
                        int64_t* out_count, void* workspace, hipStream_t stream);
 
+// pnp.hip (absolute pose: P3P LO-RANSAC and refinement)
+size_t pnp_workspace_bytes(int32_t B, const splatraster_pnp_problem* problems, const splatraster_pnp_options* options);
+int pnp_solve(int32_t B, const splatraster_pnp_problem* problems, const splatraster_pnp_options* options, const double* points2d,
+              const double* points3d, double* R_out, double* t_out, int32_t* num_inliers, uint8_t* inlier_mask,
+              int32_t* status, int32_t* trials, void* workspace, hipStream_t stream);
+int pnp_hypotheses(int32_t B, const splatraster_pnp_problem* problems, const splatraster_pnp_options* options, int64_t trial0,
+                   int32_t ntrials, const double* points2d, const double* points3d, int32_t* samples, double* models,
+                   int32_t* nmodels, void* workspace, hipStream_t stream);
+int pnp_score(int32_t B, const splatraster_pnp_problem* problems, const splatraster_pnp_options* options, int32_t M,
+              const double* models, const double* points2d, const double* points3d, int32_t* count, double* sum,
+              void* workspace, hipStream_t stream);
+
 }  // namespace sr

@@ -29,6 +29,7 @@ WHAT = [   # (file name regex, description; {placeholders} are filled by the ext
     (r"r\d+_hostprof_.*\.txt$", "cProfile of the host side of a refinement / map step (`tools/hostprof_steps.py`)"),
     (r"r\d+_ab_probes\.txt$", "A/B and timing-probe log of the round (one box per block)"),
     (r"r\d+_knn\.json$", "`distCUDA2` wall times, brute force vs exact grid"),
+    (r"^pnp_time\.json$", "absolute pose (`solve_pose`: P3P LO-RANSAC + Cauchy refinement) on planted scenes, HIP events (`tools/pnp_time.py`): {pnp}"),
     (r"^matching_time\.json$", "2D-3D matching (`hungarian_solve` cost + exact assignment, batched solver, frustum candidates) against torch-CPU + scipy on the same host, HIP events (`tools/matching_time.py`): {matching}"),
     (r"^landmark_selection_time\.json$", "landmark selection (`gaussian_selectition`) at Replica scale on a synthetic room, HIP events per stage (`tools/landmark_selection_time.py`): {landmark}"),
     (r"r\d+_scene_lists.*\.json$", "one `color_refinement` iteration on a RECONSTRUCTED room (list-length distribution, per-kernel table; `tools/scene_lists.py`; suffix = the forced variant): {scenelists}"),
@@ -207,7 +208,17 @@ def matching(path):
             f"{min(c.get('ms') or [0]):.2f} ms")
 
 
-EXTRACT = {"scenelists": scenelists, "scene": scene, "ab": ab, "perview": perview, "mapidle": mapidle, "rccl": rccl, "kstats": kstats, "hbm": hbm, "sq": sq, "timeline": timeline, "bench": bench, "clocks": clocks, "gradbars": gradbars, "idle": idle, "landmark": landmark, "matching": matching}
+def pnp(path):
+    j = _load(path) or {}
+    rows = j.get("rows") or []
+    if not rows:
+        return "(no rows)"
+    parts = [f"N = {r['N']} at {r['outlier_share']} outliers {min(r['ms']):.2f} ms" for r in rows]
+    b = j.get("batch") or {}
+    return ", ".join(parts) + f"; B = {b.get('B', '?')} batch {min(b.get('ms') or [0]):.1f} ms"
+
+
+EXTRACT = {"scenelists": scenelists, "scene": scene, "ab": ab, "perview": perview, "mapidle": mapidle, "rccl": rccl, "kstats": kstats, "hbm": hbm, "sq": sq, "timeline": timeline, "bench": bench, "clocks": clocks, "gradbars": gradbars, "idle": idle, "landmark": landmark, "matching": matching, "pnp": pnp}
 
 
 def describe(name, path):
