@@ -177,7 +177,8 @@ static BinLayout bin_layout(int32_t P, int32_t V, int64_t R, int32_t W, int32_t 
     L.ipack = take(4 * n);
     // padded feature table only when the rows are not already 16-byte aligned (shared by the views)
     L.featp = take((C % 4) ? (size_t)(P > 0 ? P : 1) * padded_channels(C) * sizeof(float) : 16);
-    L.gacc = take((size_t)(P > 0 ? P : 1) * nv * gacc_row_floats(C) * sizeof(float));
+    // (the shared colour rows and the per-(view, Gaussian) rows are ONE section: GaccLayout, common.h)
+    L.gacc = take(gacc_total_floats(C, (size_t)(P > 0 ? P : 1), nv) * sizeof(float));
     L.pose_acc = take(POSE_ACC_BYTES);      // (directly behind gacc: the backward zeroes both with one fill)
     // (the deterministic debug mode's 64-bit accumulator is NOT part of this buffer: it is a stream-ordered
     //  allocation made by the backward only while that mode is on)
@@ -230,11 +231,13 @@ ImgView img_view(void* base, int32_t W, int32_t H, int32_t V)
 // The compositing kernels index feature / accumulator rows with 24-bit x 24-bit multiplies (one
 // full-rate instruction instead of a 64-bit multiply-add pair per address): Gaussian ids must fit 24
 // bits and a row's float offset 32 bits.  16.7 M Gaussians per scene — SplatLoc maps hold < 1 M.
+// The accumulator's two tables (GaccLayout, common.h) are addressed as mul24(row, stride) + base + column modulo 2^32: right
+// whenever the element's index itself — at most the accumulator's size — fits 32 bits.
 static int check_row_index_range(int32_t P, int32_t V, int32_t C)
 {
-    const uint64_t row = (uint64_t)(gacc_row_floats(C) > padded_channels(C) ? gacc_row_floats(C) : padded_channels(C));
     const uint64_t n = (uint64_t)P * (uint64_t)V;   // rows of the window
-    if (n > (1ull << 24) || n * row >= (1ull << 32)) return SPLATRASTER_ERR_UNSUPPORTED;
+    if (n > (1ull << 24) || n * (uint64_t)padded_channels(C) >= (1ull << 32)) return SPLATRASTER_ERR_UNSUPPORTED;
+    if ((uint64_t)gacc_total_floats(C, (size_t)P, (size_t)V) >= (1ull << 32)) return SPLATRASTER_ERR_UNSUPPORTED;
     return SPLATRASTER_OK;
 }
 
@@ -645,7 +648,7 @@ static int window_backward(const splatraster_settings* s, int32_t V, const splat
     }
     // zero the accumulator rows (outside the stage bracket: the stage is the kernel alone, so its
     // figure can be held against the per-kernel rocprofv3 average)
-    const size_t gacc_n = (size_t)gacc_row_floats(C) * (size_t)P * (size_t)V;
+    const size_t gacc_n = gacc_total_floats(C, (size_t)P, (size_t)V);   // shared colour rows + per-(view, Gaussian) rows
     const bool det = g_deterministic != 0;
     long long* gacc64 = nullptr;   // debug mode only: stream-ordered scratch, freed below (never part of `binning`)
     if (det) {
@@ -667,7 +670,7 @@ static int window_backward(const splatraster_settings* s, int32_t V, const splat
         if (!st) st = launch_composite_bwd(*s, P, V, R, g, b, im, (C % 4) ? b.featp : feat, C, grads, b.gacc, gacc64, 1, stream);
     }
     if (det) {
-        if (!st) st = launch_fixed_to_float((int64_t)gacc_n, gacc64, b.gacc, stream);
+        if (!st) st = launch_fixed_to_float((int64_t)gacc_n, gacc64, b.gacc, gacc_det_headroom_drop(C, V), stream);
         (void)hipFreeAsync(gacc64, stream);
     }
     if (st) return st;

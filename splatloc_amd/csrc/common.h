@@ -113,7 +113,7 @@ struct BinView {
     uint32_t* ipack;      // [R] point_list[j] (a row id < 2^24) | reach bits << 24 (bit q: the Gaussian may reach quadrant q of its tile):
                           //     ONE word per entry is all a compositing wave prefetches
     float* featp;         // [P * CP] feature rows padded to CP = roundup4(C) floats (16-byte aligned rows); shared by the views
-    float* gacc;          // [V * P * gacc_row_floats(C)] backward gradient accumulator rows (one per row)
+    float* gacc;          // [gacc_total_floats(C, P, V)] backward gradient accumulator: the shared colour rows, then one row per (view, Gaussian) (GaccLayout)
     float* pose_acc;      // right behind gacc (one fill zeroes both): POSE_SETS replicated accumulator sets of the camera gradients + the ticket word
     uint32_t* nparts;     // [V * tiles] parts of every (view, tile) list in a split launch (written with the launch order; common.h)
     float* ckpt;          // [V][SPLIT_PARTS_MAX][C + 2][H * W] segment records of the forward (T in front of the segment, its own colours, depth), split launches only
@@ -256,8 +256,48 @@ static inline int padded_channels(int C) { return (C + 3) & ~3; }
 // sixteen 256-byte lines instead of 27 words every block hits), the LAST block to finish (ticket) sums the sets and writes the outputs
 constexpr int POSE_SETS = 16, POSE_SET_FLOATS = 64;
 constexpr size_t POSE_ACC_BYTES = (size_t)POSE_SETS * POSE_SET_FLOATS * sizeof(float) + 256;   // + the ticket's own line
-__host__ __device__ static inline int gacc_moment_offset(int C) { return ((C & 15) + 7 <= 16) ? C : ((C + 15) & ~15); }
-__host__ __device__ static inline int gacc_row_floats(int C) { return (gacc_moment_offset(C) + 7 + 15) & ~15; }
+__host__ __device__ constexpr int gacc_moment_offset(int C) { return ((C & 15) + 7 <= 16) ? C : ((C + 15) & ~15); }
+__host__ __device__ constexpr int gacc_row_floats(int C) { return (gacc_moment_offset(C) + 7 + 15) & ~15; }
+// Where the columns [0, gacc_row_floats(C)) of such a row live.  The feature table is shared by the views of a window, so the only
+// thing ever done with the views' dL/dfeature columns is their sum over the views — which the float atomics form for free when the
+// views add into the same place.  For the layouts the wide backward serves (C >= 32) the colour columns that fill whole 64-byte
+// lines are therefore ONE row per Gaussian, shared by the V views; only the line(s) with the tail colours and the moments stay per
+// (view, Gaussian):
+//   shared table   [P][SH],      SH = largest multiple of 16 not above C: column c < SH of Gaussian i, whatever the view, at i * SH + c;
+//   per-view table [V * P][PV],  right behind it: columns SH .. of row g = v * P + i at P * SH + g * PV + (c - SH)
+//                                (C = 35: [c32 c33 c34 | 7 moments | pad] = one line; C = 32: the moments only; PV = 16 or 32).
+// C < 32: SH = 0, PV = gacc_row_floats(C) — the per-(view, Gaussian) rows as they always were.  A single view holds SH + PV =
+// gacc_row_floats(C) floats per Gaussian either way; a window of V views (V - 1) * P * SH fewer than V single views.
+// (480 MB -> 224 MB to clear and to read back per 5-view window of 500k Gaussians at C = 35.)
+__host__ __device__ constexpr int gacc_shared_floats(int C) { return C >= 32 ? (C & ~15) : 0; }
+__host__ __device__ constexpr int gacc_view_floats(int C) { return gacc_row_floats(C) - gacc_shared_floats(C); }
+__host__ __device__ static inline size_t gacc_total_floats(int C, size_t P, size_t V)
+{
+    return P * (size_t)gacc_shared_floats(C) + V * P * (size_t)gacc_view_floats(C);
+}
+// float index of column `col` of row g = v * P + i (THE mapping: every pass addresses the accumulator through it)
+struct GaccLayout {
+    uint32_t SH, PV;   // gacc_shared_floats, gacc_view_floats
+    uint32_t P;        // Gaussians of the scene = rows per view
+    __host__ __device__ size_t index(size_t g, size_t i, uint32_t col) const
+    {
+        return col < SH ? i * SH + col : (size_t)P * SH + g * PV + (col - SH);
+    }
+    // The same mapping for the compositing kernels' 24-bit multiplies, as  mul24(i, stride) + base + col  (the index fits 32
+    // bits: check_row_index_range): stride / base of the table the column lives in.  row0 = v * P, the view's first row, is
+    // wave-uniform there, so the view's part of the per-view address is folded into the base once per wave.
+    __host__ __device__ uint32_t view_base24(uint32_t row0) const { return P * SH + row0 * PV - SH; }
+    __host__ __device__ uint32_t stride24(uint32_t col) const { return col < SH ? SH : PV; }
+    __host__ __device__ uint32_t base24(uint32_t col, uint32_t row0) const { return col < SH ? 0u : view_base24(row0); }
+};
+// Deterministic mode (composite_bwd.hip acc_add): an element of the shared table receives the partials of ALL V <= MAX_VIEWS = 8
+// views of the window, 8 times as many as an element of a per-(view, Gaussian) row, so launches of such a layout scale their
+// fixed point 3 bits lower (the compositing kernel and fixed_to_float_kernel evaluate the same function).
+__host__ __device__ constexpr int gacc_det_headroom_drop(int C, int V) { return (gacc_shared_floats(C) > 0 && V > 1) ? 3 : 0; }
+__host__ __device__ static inline GaccLayout gacc_layout(int C, int32_t P)
+{
+    return GaccLayout{(uint32_t)gacc_shared_floats(C), (uint32_t)gacc_view_floats(C), (uint32_t)P};
+}
 // One small frame alone (SplatLoc's color_refinement: 640x480, one view) is 4 800 quadrant-waves on a machine with room
 // for ~8 000: every wave starts at once and the compositing kernel lasts as long as its LONGEST list.  For such launches
 // (narrow layouts, at most SPLIT_MAX_WAVES quadrant-waves: measured 233 -> 180 us at 4 800 waves, 201 -> 187 us at 12 900,
@@ -333,7 +373,7 @@ int launch_tile_order(const splatraster_settings& s, int32_t V, const BinView& b
 int launch_composite_bwd(const splatraster_settings& s, int32_t P, int32_t V, int64_t R, const GeomView& g,
                          const BinView& b, const ImgView& im, const float* feat, int feat_stride,
                          const WinGrad& grads,
-                         float* gacc /*[V * P, gacc_row_floats(C)]: dL/dfeature | moments sum E dx, E dy, E dx^2,
+                         float* gacc /*GaccLayout: dL/dfeature | moments sum E dx, E dy, E dx^2,
                                       E dx dy, E dy^2, E, w g_D*/,
                          long long* gacc64 /*non-NULL: deterministic fixed-point accumulation into this buffer*/,
                          int det_pass /*deterministic mode: 0 = max pass, 1 = sum pass; else ignored*/,
@@ -341,7 +381,7 @@ int launch_composite_bwd(const splatraster_settings& s, int32_t P, int32_t V, in
 // test / A-B hook: frames with at most this many quadrant-waves take the small-layout panel variant of the backward
 // (< 0: the built-in default)
 void set_small_panel_max_waves(int waves);
-int launch_fixed_to_float(int64_t n, const long long* src, float* dst, hipStream_t stream);
+int launch_fixed_to_float(int64_t n, const long long* src, float* dst, int headroom_drop /*gacc_det_headroom_drop*/, hipStream_t stream);
 
 int launch_activate_fwd(int32_t P, int32_t K, int32_t deg, int32_t SC, int32_t E, const float* xyz,
                         const float* f_dc, const float* f_rest, const float* scaling, const float* rotation,

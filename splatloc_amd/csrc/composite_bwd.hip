@@ -81,8 +81,8 @@ struct BwdCfg {
     // (S1, 1200x680: 0.198 vs 0.238 ms), and below 4 channels the flush costs what it saves.
     static constexpr bool SMALLP = NC <= 15 && SP;
     static constexpr bool MFMA = NC >= 32 || SMALLP;
-    // NC in (32, 47]: the channels beyond 32 and the depth weight are a THIRD 16-column block of the flush (16 more
-    // MFMAs per 16 Gaussians) instead of 4 of the 10 butterfly values per Gaussian
+    // NC >= 32: channels 0-31 are the TWO 16-column blocks of the flush (NB = 2); the channels beyond 32 and the depth
+    // weight are butterfly values (NV, KV below)
     static constexpr int NM = NC >= 32 ? 32 : (SMALLP ? NC : 0);   // channels reduced on the matrix pipe
     static constexpr int NB = NC >= 32 ? 2 : 1;         // 16-column blocks of the contraction
     static constexpr bool XD = SMALLP && AUX;              // column NC of the blocks = the depth weight
@@ -113,9 +113,12 @@ struct BwdCfg {
 // which is 1e-3 of a gradient of 1e-9 — with mean-reduced losses, dL/dout ~ 1 / (H W), most rows of a 500k-Gaussian
 // scene are that small).  The kernel therefore runs TWICE in this mode:
 //   det_pass 0: atomicMax of the bit pattern of |partial| into the (zeroed) float accumulator — max is associative too;
-//   det_pass 1: partial * 2^(170 - biased exponent of that max) added as int64: |partial| * scale < 2^44, and up to 2^18
-//               partials per element (4 quadrant-waves per tile a Gaussian touches) cannot overflow 2^62; the resolution
-//               is 2^-44 of the element's LARGEST partial — twenty bits below a float's;
+//   det_pass 1: partial * 2^(170 - det_drop - biased exponent of that max) added as int64.  det_drop = 0 (one row per (view,
+//               Gaussian)): |partial| * scale < 2^44, and up to 2^18 partials per element (4 quadrant-waves per tile a Gaussian
+//               touches) cannot overflow 2^62; the resolution is 2^-44 of the element's LARGEST partial — twenty bits below a
+//               float's.  det_drop = 3 (C >= 32, V > 1: an element of the shared colour table receives the partials of all V <= 8
+//               views, up to 2^21): |partial| * scale < 2^41, the same 2^62 bound, resolution 2^-41 (common.h:
+//               gacc_det_headroom_drop; the whole launch uses it, per-view rows included);
 //   fixed_to_float_kernel (preprocess_bwd.hip) reads the same exponent and converts back.
 constexpr int DET_HEADROOM_EXP = 170;   // scale exponent = DET_HEADROOM_EXP - biased exponent of max |partial|
 __device__ __forceinline__ int det_scale_exp(unsigned max_bits)
@@ -124,7 +127,7 @@ __device__ __forceinline__ int det_scale_exp(unsigned max_bits)
     return DET_HEADROOM_EXP - (eb > 0 ? eb : 1);
 }
 template <bool DET>
-__device__ __forceinline__ void acc_add(float* gacc, long long* gacc64, size_t idx, float v, int det_pass)
+__device__ __forceinline__ void acc_add(float* gacc, long long* gacc64, size_t idx, float v, int det_pass, int det_drop)
 {
     if (DET) {
         if (det_pass == 0) {
@@ -139,11 +142,12 @@ __device__ __forceinline__ void acc_add(float* gacc, long long* gacc64, size_t i
                 if (__builtin_isinf(v)) atomicAdd(reinterpret_cast<unsigned long long*>(gacc64) + idx, v > 0.f ? 1ull : (1ull << 32));
                 return;
             }
-            const double scaled = ldexp((double)v, det_scale_exp(mb));
+            const double scaled = ldexp((double)v, det_scale_exp(mb) - det_drop);
             atomicAdd(reinterpret_cast<unsigned long long*>(gacc64) + idx, (unsigned long long)__double2ll_rn(scaled));
         }
     } else {
         (void)det_pass;
+        (void)det_drop;
         atomicAdd(gacc + idx, v);
     }
 }
@@ -159,8 +163,8 @@ composite_bwd_kernel(int W, int H, int C_total, int CP4, int c0, int first_pass,
                      const float4* __restrict__ irec, const float4* __restrict__ featp4,
                      WinGrad grads,
                      const float* __restrict__ final_T_all, const uint32_t* __restrict__ n_contrib_all,
-                     float* __restrict__ gacc /*[V * P, GROW]*/, int GROW,
-                     int MO, long long* __restrict__ gacc64 /*[V * P, GROW] fixed point, DET only*/,
+                     float* __restrict__ gacc /*GaccLayout (common.h)*/, GaccLayout GL,
+                     int MO /*column of the moments*/, long long* __restrict__ gacc64 /*same layout, fixed point, DET only*/,
                      const float* __restrict__ ckpt_all /*split launches (common.h; gridDim.y == SPLIT_PARTS): the forward's segment
                                                           records [V][SPLIT_PARTS_MAX][NC + 2][H * W], else null*/,
                      const uint32_t* __restrict__ nparts /*split launches: parts of every (view, tile) list, or null: SPLIT_PARTS*/,
@@ -213,7 +217,23 @@ composite_bwd_kernel(int W, int H, int C_total, int CP4, int c0, int first_pass,
     }
     const int view = (V == 1) ? 0 : gtile / tiles;      // wave-uniform (scalar)
     const int tile = gtile - view * tiles;
-    const uint32_t row0 = (uint32_t)view * (uint32_t)P;  // accumulator rows are per (view, Gaussian), feature rows shared
+    const uint32_t row0 = (uint32_t)view * (uint32_t)P;  // the view's first row: feature rows (and the accumulator's shared colour rows) are per Gaussian
+    // accumulator addressing (GaccLayout, common.h): column col of Gaussian i at mul24(i, stride) + base + col.  A kernel of
+    // NC >= 32 channels only exists for c0 + 32 <= C, so its flush columns [c0, c0 + 32) all lie in the shared table and its
+    // butterfly values (channels c0 + 32 .., moments) in the per-view one: known at compile time, nothing is selected per pair.
+    // The narrower kernels serve any column range (the chunked passes of C = 40, 48 ...; C < 32: everything per view).
+    constexpr bool WIDE = NC >= 32;
+    const int det_drop = DET ? gacc_det_headroom_drop(C_total, V) : 0;   // fixed-point headroom of a shared table (acc_add, common.h)
+    // what the WIDE shortcuts below rest on: the flush covers exactly the 32 columns [c0, c0 + 32) (c0 + 32 <= C, so <= SH for any
+    // multiple-of-16 SH >= 32 reached in steps of 32 or with NC < 48), every butterfly column is >= c0 + 32 >= SH or a moment
+    static_assert(!WIDE || (Cfg::NM == 32 && NC < 48), "a wide kernel's flush columns are the shared table's, its butterfly columns the per-view row's");
+    // (the headline kernel, NC = 35, covers all of C = 35, or of C = 36 without its last channel: gacc_shared_floats = 32 and
+    //  gacc_view_floats = 16 for both — constants here instead of two more scalars held through the loops; the launcher checks them)
+    constexpr bool FIXED = NC == 35;
+    static_assert(!FIXED || (gacc_shared_floats(NC) == 32 && gacc_view_floats(NC) == 16 && gacc_shared_floats(NC + 1) == 32 &&
+                             gacc_view_floats(NC + 1) == 16), "the constants of the headline kernel");
+    if constexpr (FIXED) { GL.SH = 32u; GL.PV = 16u; }
+    const uint32_t pv_base = GL.view_base24(row0);
     const float* __restrict__ dL_dcolor = grads.dL_dcolor[view];
     const float* __restrict__ dL_ddepth = grads.dL_ddepth[view];
     const float* __restrict__ dL_dalpha = grads.dL_dalpha[view];
@@ -337,7 +357,10 @@ composite_bwd_kernel(int W, int H, int C_total, int CP4, int c0, int first_pass,
     uint32_t wave_last = last;
 #pragma unroll
     for (int d = 1; d < WAVE; d <<= 1) wave_last = max(wave_last, (uint32_t)__shfl_xor((int)wave_last, d, WAVE));
-    const uint32_t end = min(end0, list0 + wave_last);
+    uint32_t end = min(end0, list0 + wave_last);
+    // WIDE only: the value is wave-uniform after the reduction; said so, the list's end and the chunk counter derived from it
+    // live in scalar registers, which keeps the headline kernel <35> inside its 128-VGPR budget (tests/test_codegen_budget.py)
+    if constexpr (WIDE) end = (uint32_t)__builtin_amdgcn_readfirstlane((int)end);
     if (NC <= 4) { if (split && beg >= end) return; }   // nothing of this half contributes
 
     // wave_reduce_pack leaves total k in lane bitreverse6(k); values [0, KV) belong to the first
@@ -347,7 +370,9 @@ composite_bwd_kernel(int W, int H, int C_total, int CP4, int c0, int first_pass,
     const int sv = slot_second ? slotv - KV : slotv;
     const bool slot_col = sv < NV;
     const bool slot_ok = slotv < 2 * KV;
-    const int slot_off = slot_col ? (c0 + NM + sv) : (TM ? MO + 6 : MO + sv - NV);  // float offset inside the Gaussian's row
+    const uint32_t slot_colv = (uint32_t)(slot_col ? (c0 + NM + sv) : (TM ? MO + 6 : MO + sv - NV));  // column of the Gaussian's row
+    const uint32_t slot_stride = WIDE ? GL.PV : GL.stride24(slot_colv);
+    const uint32_t slot_off = (WIDE ? pv_base : GL.base24(slot_colv, row0)) + slot_colv;
     int nslot = 0;  // Gaussians parked in the weight panel (wave-uniform)
     int e0 = 0;     // weight-panel slot of the E panel's column 0 (wave-uniform)
 
@@ -374,14 +399,15 @@ composite_bwd_kernel(int W, int H, int C_total, int CP4, int c0, int first_pass,
         for (int r = 0; r < 4; ++r) {
             const int gs = 4 * (lane >> 4) + r;
             if (gs < count) {
-                const uint32_t rowi = __umul24(s_gid[gs], (uint32_t)GROW);
+                const uint32_t gid = s_gid[gs];
 #pragma unroll
                 for (int t = 0; t < NB; ++t) {
                     const int c = 16 * t + j0c;
                     const bool full = 16 * t + 16 <= NM;   // every column of the block is a channel
                     const bool col_ok = full || c < NM || (XD && c == NM && first_pass);
-                    const uint32_t col_off = (full || c < NM) ? (uint32_t)(c0 + c) : (uint32_t)(MO + 6);
-                    if (col_ok) acc_add<DET>(gacc, gacc64, (size_t)(rowi + col_off), D[t][r], det_pass);
+                    const uint32_t col = (full || c < NM) ? (uint32_t)(c0 + c) : (uint32_t)(MO + 6);
+                    const uint32_t rowi = WIDE ? __umul24(gid, GL.SH) : __umul24(gid, GL.stride24(col)) + GL.base24(col, row0);
+                    if (col_ok) acc_add<DET>(gacc, gacc64, (size_t)(rowi + col), D[t][r], det_pass, det_drop);
                 }
             }
         }
@@ -415,8 +441,8 @@ composite_bwd_kernel(int W, int H, int C_total, int CP4, int c0, int first_pass,
             const float outv = wave_reduce_hi3<6>(m, lane);
             const int vi = ((lane >> 5) & 1) + 2 * ((lane >> 4) & 1) + 4 * ((lane >> 3) & 1);
             if (eg < count && vi < 6) {
-                const size_t di = (size_t)(__umul24(s_gid[e0 + eg], (uint32_t)GROW) + (uint32_t)(MO + vi));
-                acc_add<DET>(gacc, gacc64, di, outv, det_pass);
+                const size_t di = (size_t)(__umul24(s_gid[e0 + eg], GL.PV) + pv_base + (uint32_t)(MO + vi));   // (the moments: per view)
+                acc_add<DET>(gacc, gacc64, di, outv, det_pass, det_drop);
             }
             __builtin_amdgcn_wave_barrier();
         }
@@ -446,7 +472,7 @@ composite_bwd_kernel(int W, int H, int C_total, int CP4, int c0, int first_pass,
         const uint32_t base = beg + (uint32_t)chunk * WAVE;
         const bool cur_reach = (pw >> (24 + quad)) & 1u;
         uint64_t cand = __builtin_amdgcn_ballot_w64(cur_reach);
-        const uint32_t cur_gid = pw & 0xFFFFFFu;
+        const uint32_t cur_gid = (pw & 0xFFFFFFu) - row0;   // the Gaussian's index in its view: what the feature and accumulator rows are addressed with
         // the chunk in front: requested now, consumed after this one (the loop's last iteration requests nothing: the guard
         // is per lane, so there is no wave-uniform branch around the loads)
         fetch(chunk > 0 ? base - WAVE : 0xFFFFFF00u, pw);
@@ -470,7 +496,7 @@ composite_bwd_kernel(int W, int H, int C_total, int CP4, int c0, int first_pass,
 #pragma unroll SR_BWD_STAGE_UNROLL
             for (int e = lane; e < ncand * PPR; e += WAVE) {
                 const int row = e / PPR, pc = e - row * PPR;
-                reinterpret_cast<float4*>(s_feat)[e] = featp4[(size_t)(__umul24(s_cgid[row] - row0, (uint32_t)CP4) + (uint32_t)((c0 >> 2) + pc))];
+                reinterpret_cast<float4*>(s_feat)[e] = featp4[(size_t)(__umul24(s_cgid[row], (uint32_t)CP4) + (uint32_t)((c0 >> 2) + pc))];
             }
             if (mine) {
                 s_rec0[rank] = rec_a;
@@ -576,8 +602,8 @@ composite_bwd_kernel(int W, int H, int C_total, int CP4, int c0, int first_pass,
                     {
                         const float outv = wave_reduce_pack<2 * KV>(red, lane);
                         const uint32_t gi = slot_second ? gi1 : gi0;
-                        const size_t di = (size_t)(__umul24(gi, (uint32_t)GROW) + (uint32_t)slot_off);   // gi < 2^24 (checked on the host)
-                        if (slot_ok && (has1 || !slot_second)) acc_add<DET>(gacc, gacc64, di, outv, det_pass);
+                        const size_t di = (size_t)(__umul24(gi, slot_stride) + slot_off);   // gi < 2^24 (checked on the host)
+                        if (slot_ok && (has1 || !slot_second)) acc_add<DET>(gacc, gacc64, di, outv, det_pass, det_drop);
                     }
                 }
                 if constexpr (MFMA) {
@@ -697,6 +723,8 @@ static int launch_one_bwd(const splatraster_settings& s, int c0, int first, cons
     const int tiles = gx * gy;
     const unsigned blocks = quadrant_blocks(L.V * tiles, gx);  // 4 quadrants per (view, tile) (+ padding of the id space)
     const float* ckpt = (NC <= 4 && c0 == 0 && first) ? L.ckpt : nullptr;
+    const GaccLayout GL = gacc_layout(s.channels, L.P);
+    if (NC == 35 && (c0 != 0 || GL.SH != 32u || GL.PV != 16u)) return SPLATRASTER_ERR_UNSUPPORTED;   // (the headline kernel's constants)
     // split launches with a launch order: three groups of extra workgroups (parts 4 .. 15 of the SPLIT_EXTRA_TILES longest lists) lead the grid
     const bool extras = ckpt != nullptr && use_tile_order(L.V, tiles);
     const unsigned extra_blocks = extras ? (unsigned)(SPLIT_PARTS_MAX / SPLIT_PARTS - 1) * quadrant_blocks(SPLIT_EXTRA_TILES, gx) : 0u;
@@ -705,7 +733,7 @@ static int launch_one_bwd(const splatraster_settings& s, int c0, int first, cons
     hipLaunchKernelGGL((composite_bwd_kernel<NC, DET, SPV, AUX>), grid, dim3(WAVE), 0, stream, s.image_width,           \
                        s.image_height, feat_stride, padded_channels(feat_stride) / 4, c0, first, tiles, L.V, L.P,      \
                        b.ranges, b.ipack, b.irec, reinterpret_cast<const float4*>(feat), *L.grads,       \
-                       im.final_T, im.n_contrib, gacc, gacc_row_floats(s.channels),                                    \
+                       im.final_T, im.n_contrib, gacc, GL,                                                             \
                        gacc_moment_offset(s.channels), gacc64, ckpt, extras ? b.nparts : nullptr, (int)extra_blocks,               \
                        use_tile_order(L.V, tiles) ? b.tile_order : nullptr, L.det_pass)
     if constexpr (NC >= 4 && NC <= 15 && AUX) {   // C = 3 and below: the flush costs what the 8 saved butterfly values gain (A/B: S0 0.036 vs 0.041 ms)

@@ -87,15 +87,19 @@ __device__ void sh_backward(int deg, int M, const float* sh, float* dsh, const u
 // row g = v * P + i, forward record rec[g], the view's camera) are summed in view order into ONE set of parameter
 // gradients, written once — no per-view gradient tensors, no accumulation kernels, a deterministic sum.
 // dL/dmeans2D stays per view (GaussianModel.add_densification_stats reads it per view).
-template <bool POSE, bool RAW = false>
+// TQ > 0 (C >= 32 with C % 16 != 0; GaccLayout, common.h): the colour columns that are not in the shared table lie in front of the
+// moments in the per-view row this kernel reads anyway — they are summed here, in view order, and written to dL_dcolors[i][SH ..]
+// (copy_shared_dcolors_kernel copies the shared columns).  TQ = 16-byte pieces of the row that hold them (the row is 64-byte
+// aligned): 1 for the headline's three tail channels (C = 35, 36), 4 for any longer tail.
+template <bool POSE, bool RAW = false, int TQ = 0>
 __global__ void __launch_bounds__(256)
 preprocess_bwd_kernel(int P, int V, int W, int H, float mod, int sh_degree, int M, WinCams cams, WinGrad grads,
                       const float* __restrict__ means3D, const float* __restrict__ shs,
                       const float* __restrict__ scales, const float* __restrict__ rotations,
                       const float* __restrict__ cov3D_precomp,
                       const uint8_t* __restrict__ clamped,
-                      const float4* __restrict__ rec, const float* __restrict__ gacc, int C, int GROW, int MO,
-                      float* __restrict__ dL_dmeans3D,
+                      const float4* __restrict__ rec, const float* __restrict__ gacc, int C, GaccLayout GL, int MO,
+                      float* __restrict__ dL_dcolors /*TQ > 0 only*/, float* __restrict__ dL_dmeans3D,
                       float* __restrict__ dL_dopacities, float* __restrict__ dL_dscales,
                       float* __restrict__ dL_drotations, float* __restrict__ dL_dcov3D,
                       float* __restrict__ dL_dshs, float* __restrict__ dL_dview, float* __restrict__ dL_dproj,
@@ -113,6 +117,11 @@ preprocess_bwd_kernel(int P, int V, int W, int H, float mod, int sh_degree, int 
     float dcov[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     float dop = 0.f;
     float csum[4] = {0.f, 0.f, 0.f, 0.f};   // RAW: dL/dcolours of this Gaussian (a view that does not see it left its row at +0: skipping it is exact)
+    constexpr int NT = TQ > 0 ? 4 * TQ : 1;    // TQ > 0: the same for the colour columns of the per-view row
+    float tsum[NT];
+#pragma unroll
+    for (int k = 0; k < NT; ++k) tsum[k] = 0.f;
+    [[maybe_unused]] const int ntail = C - (int)GL.SH;
     if (i < P) {
     bool any_visible = false;
     const float px = means3D[3 * i], py = means3D[3 * i + 1], pz = means3D[3 * i + 2];
@@ -159,10 +168,18 @@ preprocess_bwd_kernel(int P, int V, int W, int H, float mod, int sh_degree, int 
     const bool visible = cams.radii[v][i] > 0;
     if (visible) {
         any_visible = true;
-        const float* mrow = gacc + gr * GROW + MO;  // moment record of this row
+        const float* mrow = gacc + GL.index(gr, (size_t)i, (uint32_t)MO);  // moment record of this row
         if constexpr (RAW) {    // the row's colour columns (C <= 4: the moments' own 64-byte line), summed in view order like gather_dcolors_kernel
-            const float4 cr = *reinterpret_cast<const float4*>(gacc + gr * GROW);
+            const float4 cr = *reinterpret_cast<const float4*>(gacc + GL.index(gr, (size_t)i, 0u));
             csum[0] += cr.x; csum[1] += cr.y; csum[2] += cr.z; csum[3] += cr.w;
+        }
+        if constexpr (TQ > 0) {
+            const float4* trow = reinterpret_cast<const float4*>(gacc + GL.index(gr, (size_t)i, GL.SH));
+#pragma unroll
+            for (int q = 0; q < TQ; ++q) {
+                const float4 t = trow[q];   // (columns behind the tail — moments, padding — are summed along and never written)
+                tsum[4 * q] += t.x; tsum[4 * q + 1] += t.y; tsum[4 * q + 2] += t.z; tsum[4 * q + 3] += t.w;
+            }
         }
         const float4 g0 = make_float4(mrow[0], mrow[1], mrow[2], mrow[3]);
         const float4 g1 = make_float4(mrow[4], mrow[5], mrow[6], 0.f);
@@ -283,7 +300,7 @@ preprocess_bwd_kernel(int P, int V, int W, int H, float mod, int sh_degree, int 
         if (shs) {   // single-view calls only
             const float sm0 = dmean[0], sm1 = dmean[1], sm2 = dmean[2];
             sh_backward(sh_degree, M, shs + (size_t)i * 3 * M, dL_dshs + (size_t)i * 3 * M, clamped + 3 * (size_t)i,
-                        gacc + gr * GROW, px - campos_p[0], py - campos_p[1], pz - campos_p[2], dmean);
+                        gacc + GL.index(gr, (size_t)i, 0u), px - campos_p[0], py - campos_p[1], pz - campos_p[2], dmean);
             if (POSE) {  // direction = normalize(p - campos)
                 pose[24] = -(dmean[0] - sm0);
                 pose[25] = -(dmean[1] - sm1);
@@ -382,6 +399,11 @@ preprocess_bwd_kernel(int P, int V, int W, int H, float mod, int sh_degree, int 
     if (i < P) {
 #pragma unroll
     for (int k = 0; k < 3; ++k) dL_dmeans3D[3 * i + k] = dmean[k];
+    if constexpr (TQ > 0) {
+#pragma unroll
+        for (int k = 0; k < NT; ++k)
+            if (k < ntail) dL_dcolors[(size_t)i * C + GL.SH + k] = tsum[k];
+    }
     if constexpr (RAW) {
         // the chain through the activations, with activations.hip's own arithmetic (activation_math.h): bit-identical to
         // gather_dcolors_kernel + activate_bwd_kernel behind the plain kernel
@@ -421,9 +443,9 @@ preprocess_bwd_kernel(int P, int V, int W, int H, float mod, int sh_degree, int 
 // contiguous reads inside a row, fully coalesced writes.
 // deterministic debug mode: the fixed-point accumulator rows -> the float rows the kernels below read
 // (dst holds, per element, the bit pattern of the largest |partial| that went into src — composite_bwd.hip acc_add:
-//  the fixed point of the element is 2^-(170 - its biased exponent); the same expression is evaluated here)
+//  the fixed point of the element is 2^-(170 - headroom_drop - its biased exponent); the same expression is evaluated here)
 __global__ void __launch_bounds__(256)
-fixed_to_float_kernel(int64_t n, const long long* __restrict__ src, float* __restrict__ dst)
+fixed_to_float_kernel(int64_t n, const long long* __restrict__ src, float* __restrict__ dst, int headroom_drop)
 {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n) return;
@@ -435,28 +457,40 @@ fixed_to_float_kernel(int64_t n, const long long* __restrict__ src, float* __res
         dst[e] = ((mb & 0x7fffffu) || pos == neg) ? __builtin_nanf("") : (neg ? -__builtin_inff() : __builtin_inff());
         return;
     }
-    dst[e] = (float)ldexp((double)src[e], -(170 - (eb > 0 ? eb : 1)));
+    dst[e] = (float)ldexp((double)src[e], -(170 - headroom_drop - (eb > 0 ? eb : 1)));
 }
 
-int launch_fixed_to_float(int64_t n, const long long* src, float* dst, hipStream_t stream)
+int launch_fixed_to_float(int64_t n, const long long* src, float* dst, int headroom_drop, hipStream_t stream)
 {
     if (n <= 0) return SPLATRASTER_OK;
-    hipLaunchKernelGGL(fixed_to_float_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, src, dst);
+    hipLaunchKernelGGL(fixed_to_float_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, src, dst, headroom_drop);
     SR_LAUNCH_CHECK();
     return SPLATRASTER_OK;
 }
 
+// C < 32 (SH = 0): the colour columns of the V per-view rows of every Gaussian, summed in view order.
 __global__ void __launch_bounds__(256)
-gather_dcolors_kernel(int64_t n, int C, int GROW, int V, int64_t P, const float* __restrict__ gacc,
+gather_dcolors_kernel(int64_t n, int C, GaccLayout GL, int V, const float* __restrict__ gacc,
                       float* __restrict__ dL_dcolors)
 {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n) return;
     const int64_t i = e / C;
     const int ch = (int)(e - i * C);
-    float sum = gacc[i * GROW + ch];
-    for (int v = 1; v < V; ++v) sum += gacc[(v * P + i) * GROW + ch];   // the feature table is shared by the views
+    float sum = gacc[GL.index((size_t)i, (size_t)i, (uint32_t)ch)];
+    for (int v = 1; v < V; ++v) sum += gacc[GL.index((size_t)v * GL.P + (size_t)i, (size_t)i, (uint32_t)ch)];   // the feature table is shared by the views
     dL_dcolors[e] = sum;
+}
+// C >= 32: the views already added into ONE row per Gaussian (the atomics formed the sum over the views): a coalesced copy
+// [P][SH] -> dL_dcolors[:, :SH], no view loop; the columns SH .. C - 1 are preprocess_bwd_kernel<.., TQ>'s
+__global__ void __launch_bounds__(256)
+copy_shared_dcolors_kernel(int64_t n /*P * SH*/, int C, GaccLayout GL, const float* __restrict__ gacc, float* __restrict__ dL_dcolors)
+{
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    const int64_t i = e / GL.SH;
+    const uint32_t ch = (uint32_t)(e - i * GL.SH);
+    dL_dcolors[i * C + ch] = gacc[GL.index((size_t)i, (size_t)i, ch)];
 }
 
 int launch_preprocess_bwd(const splatraster_settings& s, int32_t P, int32_t V, const WinCams& cams, const WinGrad& grads,
@@ -467,26 +501,37 @@ int launch_preprocess_bwd(const splatraster_settings& s, int32_t P, int32_t V, c
                           float* dL_dproj, float* dL_dcampos, float* pose_acc, hipStream_t stream, const RawBwd* raw)
 {
     if (P == 0) return SPLATRASTER_OK;
+    const GaccLayout GL = gacc_layout(C, P);
+    const int ntail = (dL_dcolors && !raw && GL.SH > 0) ? C - (int)GL.SH : 0;   // colour columns of the per-view rows: summed by the kernel below
     if (dL_dcolors && !raw) {
-        const int64_t n = (int64_t)P * C;
-        hipLaunchKernelGGL(gather_dcolors_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, C,
-                           gacc_row_floats(C), V, (int64_t)P, gacc, dL_dcolors);
+        const int64_t n = (int64_t)P * (GL.SH ? (int)GL.SH : C);
+        if (GL.SH)
+            hipLaunchKernelGGL(copy_shared_dcolors_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, C, GL, gacc,
+                               dL_dcolors);
+        else
+            hipLaunchKernelGGL(gather_dcolors_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, C, GL, V, gacc,
+                               dL_dcolors);
         SR_LAUNCH_CHECK();
     }
     const bool pose = dL_dview && dL_dproj;      // (the accumulator sets behind gacc were zeroed with the rows: capi.hip)
     if (pose && !pose_acc) return SPLATRASTER_ERR_BAD_ARG;
 #define SR_PBWD_ARGS                                                                                              \
     P, V, s.image_width, s.image_height, s.scale_modifier, s.sh_degree, s.sh_coeffs, cams, grads, means3D,         \
-        shs, scales, rotations, cov3D_precomp, clamped, rec, gacc, C, gacc_row_floats(C),                          \
-        gacc_moment_offset(C), dL_dmeans3D, dL_dopacities, dL_dscales, dL_drotations,                              \
+        shs, scales, rotations, cov3D_precomp, clamped, rec, gacc, C, GL,                                          \
+        gacc_moment_offset(C), dL_dcolors, dL_dmeans3D, dL_dopacities, dL_dscales, dL_drotations,                              \
         dL_dcov3D, dL_dshs, dL_dview, dL_dproj, dL_dcampos, pose_acc, (raw ? *raw : RawBwd{})
     if (raw) {
         if (pose || shs || cov3D_precomp || !scales || !rotations || raw->E > 1) return SPLATRASTER_ERR_UNSUPPORTED;   // (C <= 4: the colour columns share the moments' line)
         hipLaunchKernelGGL((preprocess_bwd_kernel<false, true>), dim3((P + 255) / 256), dim3(256), 0, stream, SR_PBWD_ARGS);
-    } else if (pose)
-        hipLaunchKernelGGL(preprocess_bwd_kernel<true>, dim3((P + 255) / 256), dim3(256), 0, stream, SR_PBWD_ARGS);
-    else
-        hipLaunchKernelGGL(preprocess_bwd_kernel<false>, dim3((P + 255) / 256), dim3(256), 0, stream, SR_PBWD_ARGS);
+    } else if (pose) {
+        if (ntail > 4) hipLaunchKernelGGL((preprocess_bwd_kernel<true, false, 4>), dim3((P + 255) / 256), dim3(256), 0, stream, SR_PBWD_ARGS);
+        else if (ntail > 0) hipLaunchKernelGGL((preprocess_bwd_kernel<true, false, 1>), dim3((P + 255) / 256), dim3(256), 0, stream, SR_PBWD_ARGS);
+        else hipLaunchKernelGGL(preprocess_bwd_kernel<true>, dim3((P + 255) / 256), dim3(256), 0, stream, SR_PBWD_ARGS);
+    } else {
+        if (ntail > 4) hipLaunchKernelGGL((preprocess_bwd_kernel<false, false, 4>), dim3((P + 255) / 256), dim3(256), 0, stream, SR_PBWD_ARGS);
+        else if (ntail > 0) hipLaunchKernelGGL((preprocess_bwd_kernel<false, false, 1>), dim3((P + 255) / 256), dim3(256), 0, stream, SR_PBWD_ARGS);
+        else hipLaunchKernelGGL(preprocess_bwd_kernel<false>, dim3((P + 255) / 256), dim3(256), 0, stream, SR_PBWD_ARGS);
+    }
 #undef SR_PBWD_ARGS
     SR_LAUNCH_CHECK();
     return SPLATRASTER_OK;
