@@ -44,7 +44,7 @@ extern "C" {
 /* bumped on every change of a signature or buffer layout; the Python binding refuses a library
  * whose splatraster_abi_version() differs (a stale in-tree .so would otherwise be called through
  * ctypes with mismatched arguments) */
-#define SPLATRASTER_ABI_VERSION 17
+#define SPLATRASTER_ABI_VERSION 18
 
 #define SPLATRASTER_TILE 16 /* tile edge in pixels (16x16 = 256 pixels = 4 wave64) */
 
@@ -597,6 +597,55 @@ int splatraster_grid_encoding_forward(const splatraster_grid_layout* layout, int
  * (zero it first; the last bits depend on arrival order), dL_dx [N, D] (may be NULL) is written. */
 int splatraster_grid_encoding_backward(const splatraster_grid_layout* layout, int64_t N, const float* x, const float* params,
                                        const float* dL_dout, float* dL_dparams, float* dL_dx, void* stream);
+
+/* ---- FeatureDecoder: models/decoders.py:43-68 and the training step of train_decoder.py:20-25,48-51,64-78; INTEGRATION.md §19 ----
+ * out[n] = f / |f|,  f = W_{n-1} relu(... relu(W_0 enc(xn)) ...),  xn = (float)((x - lo) / (hi - lo)) computed in f64 from the f64
+ * (or exactly widened f32) point and rounded once; enc = the grid encoding above (bit-identical to
+ * splatraster_grid_encoding_forward); W_l [dims[l+1], dims[l]] row-major f32 without bias (torch.nn.Linear.weight).  Every dot
+ * product is an f32 fmaf chain from a zero accumulator with k ascending (v_mfma_f32_32x32x2_f32).  |f| = sqrtf(sum of squares), the
+ * squares summed per block of 32 columns by a butterfly over lane distances 16, 8, 4, 2, 1 and the blocks' sums added in ascending
+ * column order; the quotient is a division, so a zero row gives NaN as the reference does.
+ * Supported shapes: the grid configurations above with dims[0] = L*F a multiple of 16 up to 64; 2 <= n_layers <= 8; one hidden width
+ * dims[1] = ... = dims[n_layers-1] in {32, 64, 128}; dims[n_layers] a multiple of 32 up to 256.  Anything else:
+ * SPLATRASTER_ERR_BAD_ARG, before any launch. */
+#define SPLATRASTER_DECODER_MAX_LAYERS 8
+typedef struct splatraster_decoder_layout {
+    splatraster_grid_layout grid;
+    double bound[3][2];    /* scene.bound: {lo, hi} per dimension (the first n_dims rows are read) */
+    int32_t n_layers;      /* Linear layers */
+    int32_t dims[SPLATRASTER_DECODER_MAX_LAYERS + 1];   /* dims[0] = L*F, dims[l+1] = rows of W_l */
+} splatraster_decoder_layout;
+
+/* Host only.  *workspace_bytes: the backward's workspace for N points (per-workgroup weight-gradient slabs, per-tile loss terms,
+ * dL/d(encoded)); *activation_bytes: the activation record of a training forward over N points, floats in this order:
+ * encoded [N, dims[0]], post-ReLU h_1 .. h_{n-1} [N, H] each, unnormalised f [N, O], |f| [N], xn [N, D].  Either may be NULL. */
+int splatraster_decoder_workspace_bytes(const splatraster_decoder_layout* layout, int64_t N, size_t* workspace_bytes,
+                                        size_t* activation_bytes);
+/* out [N, O].  x [N, D] f32, or f64 when x_is_f64; table [grid.n_params]; weights: HOST array of n_layers device pointers.
+ * activations: NULL (inference: nothing but `out` is written) or activation_bytes of device memory, filled for the backward.
+ * table, out, activations and every weight must be 16-byte aligned.  One launch, no host synchronisation. */
+int splatraster_decoder_forward(const splatraster_decoder_layout* layout, int64_t N, const void* x, int32_t x_is_f64,
+                                const float* table, const float* const* weights, float* out, float* activations, void* stream);
+/* Backward of the forward that filled `activations` (N >= 1).  Exactly one of dL_dout [N, O] and targets [N, O] is given.
+ * With targets the loss is train_decoder.py's cos_loss, 1 - mean_i cos(out_i, t_i) with
+ * cos = (y . t) / (max(|y|, 1e-8) max(|t|, 1e-8)) as torch.cosine_similarity defines it; *loss (device, may be NULL) receives it,
+ * summed in a fixed order (per row: 8 ascending chains over O/8 columns, butterfly 1, 2, 4; rows of a 32-point tile ascending;
+ * tiles in 256 strided ascending chains and a binary tree), and dL/dout is formed in the same pass.
+ * dL_dweights [sum_l dims[l+1]*dims[l]] (layer 0 first, each laid out like its weight) is WRITTEN: per-workgroup partial sums in
+ * the workspace, added in ascending workgroup order, so it is bit-reproducible run to run.  dL_dtable [grid.n_params] (may be
+ * NULL) is ACCUMULATED by the float atomics of splatraster_grid_encoding_backward (zero it first; arrival-ordered).  dL_dx [N, D]
+ * (may be NULL) is written, with respect to the NORMALISED point xn.  Three launches, no host synchronisation. */
+int splatraster_decoder_backward(const splatraster_decoder_layout* layout, int64_t N, const float* table,
+                                 const float* const* weights, const float* activations, const float* dL_dout, const float* targets,
+                                 float* loss, float* dL_dweights, float* dL_dtable, float* dL_dx, void* workspace, void* stream);
+/* One torch.optim.Adam step (no amsgrad) over both parameter groups of train_decoder.py:48-51 in one launch, `step` = 1 for the
+ * first: g += weight_decay * p (weights only); m += (g - m)(1 - beta1); v = v beta2 + (1 - beta2) g g;
+ * p -= lr / (1 - beta1^step) * m / (sqrt(v) / sqrt(1 - beta2^step) + eps).  Dense over the table (an entry with zero gradient
+ * still moves through its momentum).  w_grad / w_m / w_v: flat, laid out as dL_dweights; t_*: [grid.n_params].  Every gradient
+ * read is written back as zero, so the next backward needs no memset. */
+int splatraster_decoder_adam(const splatraster_decoder_layout* layout, float* const* weights, float* w_grad, float* w_m, float* w_v,
+                             float* table, float* t_grad, float* t_m, float* t_v, int64_t step, double lr_weights, double lr_table,
+                             double beta1, double beta2, double eps_weights, double eps_table, double weight_decay, void* stream);
 
 /* ---- landmark selection: utils/selection.py:91-157 (gaussian_selectition), INTEGRATION.md §16 ----------------------------
  * Scores.  Point p [N,3] against view i of w2c [M,4,4] (row-major world-to-camera) and K [3,3] (f64, row-major, HOST memory),

@@ -11,7 +11,7 @@ import os
 from . import build as _build
 
 _LIB = None
-ABI_VERSION = 17   # == SPLATRASTER_ABI_VERSION of include/splatraster.h
+ABI_VERSION = 18   # == SPLATRASTER_ABI_VERSION of include/splatraster.h
 
 OK = 0
 WARN_LOOKBACK_STALL = 5   # splatraster_poll_errors() only; not an error of any frame
@@ -108,6 +108,15 @@ class GridLayout(C.Structure):
                 ("resolution", C.c_uint32 * GRID_MAX_LEVELS), ("scale", C.c_float * GRID_MAX_LEVELS), ("n_params", C.c_int64)]
 
 
+DECODER_MAX_LAYERS = 8   # SPLATRASTER_DECODER_MAX_LAYERS
+
+
+class DecoderLayout(C.Structure):
+    """struct splatraster_decoder_layout"""
+    _fields_ = [("grid", GridLayout), ("bound", (C.c_double * 2) * 3), ("n_layers", C.c_int32),
+                ("dims", C.c_int32 * (DECODER_MAX_LAYERS + 1))]
+
+
 # every symbol include/splatraster.h declares: (name, restype, argtypes)
 _vp, _i32, _i64, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t
 SYMBOLS = {
@@ -155,6 +164,10 @@ SYMBOLS = {
     "splatraster_grid_encoding_layout": (C.c_int, [_i32] * 5 + [C.c_double, _i32, C.POINTER(GridLayout)]),
     "splatraster_grid_encoding_forward": (C.c_int, [C.POINTER(GridLayout), _i64, _vp, _vp, _vp, _vp]),
     "splatraster_grid_encoding_backward": (C.c_int, [C.POINTER(GridLayout), _i64] + [_vp] * 6),
+    "splatraster_decoder_workspace_bytes": (C.c_int, [C.POINTER(DecoderLayout), _i64, C.POINTER(_sz), C.POINTER(_sz)]),
+    "splatraster_decoder_forward": (C.c_int, [C.POINTER(DecoderLayout), _i64, _vp, _i32, _vp, C.POINTER(_vp), _vp, _vp, _vp]),
+    "splatraster_decoder_backward": (C.c_int, [C.POINTER(DecoderLayout), _i64, _vp, C.POINTER(_vp)] + [_vp] * 9),
+    "splatraster_decoder_adam": (C.c_int, [C.POINTER(DecoderLayout), C.POINTER(_vp)] + [_vp] * 7 + [_i64] + [C.c_double] * 7 + [_vp]),
     "splatraster_landmark_scores": (C.c_int, [_i64, _i32] + [_vp] * 4 + [_i32, _i32] + [_vp] * 7),
     "splatraster_landmark_workspace_bytes": (_sz, [_i64, _i32]),
     "splatraster_landmark_select": (C.c_int, [_i64, _vp, _vp, _i32, C.c_double, _vp, _vp, _vp, _vp]),

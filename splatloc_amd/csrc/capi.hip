@@ -1141,6 +1141,34 @@ int splatraster_grid_encoding_backward(const splatraster_grid_layout* layout, in
     return grid_backward(layout, N, x, params, dL_dout, dL_dparams, dL_dx, reinterpret_cast<hipStream_t>(stream));
 }
 
+int splatraster_decoder_workspace_bytes(const splatraster_decoder_layout* layout, int64_t N, size_t* workspace_bytes,
+                                        size_t* activation_bytes)
+{
+    return decoder_workspace_bytes(layout, N, workspace_bytes, activation_bytes);
+}
+
+int splatraster_decoder_forward(const splatraster_decoder_layout* layout, int64_t N, const void* x, int32_t x_is_f64,
+                                const float* table, const float* const* weights, float* out, float* activations, void* stream)
+{
+    return decoder_forward(layout, N, x, x_is_f64, table, weights, out, activations, reinterpret_cast<hipStream_t>(stream));
+}
+
+int splatraster_decoder_backward(const splatraster_decoder_layout* layout, int64_t N, const float* table,
+                                 const float* const* weights, const float* activations, const float* dL_dout, const float* targets,
+                                 float* loss, float* dL_dweights, float* dL_dtable, float* dL_dx, void* workspace, void* stream)
+{
+    return decoder_backward(layout, N, table, weights, activations, dL_dout, targets, loss, dL_dweights, dL_dtable, dL_dx, workspace,
+                            reinterpret_cast<hipStream_t>(stream));
+}
+
+int splatraster_decoder_adam(const splatraster_decoder_layout* layout, float* const* weights, float* w_grad, float* w_m, float* w_v,
+                             float* table, float* t_grad, float* t_m, float* t_v, int64_t step, double lr_weights, double lr_table,
+                             double beta1, double beta2, double eps_weights, double eps_table, double weight_decay, void* stream)
+{
+    return decoder_adam(layout, weights, w_grad, w_m, w_v, table, t_grad, t_m, t_v, step, lr_weights, lr_table, beta1, beta2,
+                        eps_weights, eps_table, weight_decay, reinterpret_cast<hipStream_t>(stream));
+}
+
 int splatraster_landmark_scores(int64_t N, int32_t M, const float* points, const float* w2c, const double* K,
                                 const float* depths, int32_t width, int32_t height, int32_t* n_visible, int32_t* n_depth,
                                 double* depth_mean, double* depth_std, double* span, double* score, void* stream)

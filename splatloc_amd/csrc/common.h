@@ -433,6 +433,17 @@ int grid_forward(const splatraster_grid_layout* lay, int64_t N, const float* x, 
 int grid_backward(const splatraster_grid_layout* lay, int64_t N, const float* x, const float* params, const float* dL_dout,
                   float* dL_dparams, float* dL_dx, hipStream_t s);   // point count from which the exact grid search replaces the tiled brute force (< 0: default)
 
+// decoder.hip (fused FeatureDecoder: forward, backward, cosine loss, Adam)
+int decoder_workspace_bytes(const splatraster_decoder_layout* lay, int64_t N, size_t* workspace_bytes, size_t* activation_bytes);
+int decoder_forward(const splatraster_decoder_layout* lay, int64_t N, const void* x, int32_t x_is_f64, const float* table,
+                    const float* const* weights, float* out, float* acts, hipStream_t s);
+int decoder_backward(const splatraster_decoder_layout* lay, int64_t N, const float* table, const float* const* weights,
+                     const float* acts, const float* dL_dout, const float* targets, float* loss, float* dL_dweights,
+                     float* dL_dtable, float* dL_dx, void* workspace, hipStream_t s);
+int decoder_adam(const splatraster_decoder_layout* lay, float* const* weights, float* w_grad, float* w_m, float* w_v, float* table,
+                 float* t_grad, float* t_m, float* t_v, int64_t step, double lr_w, double lr_t, double beta1, double beta2,
+                 double eps_w, double eps_t, double weight_decay, hipStream_t s);
+
 // selection.hip (landmark selection)
 int landmark_scores(int64_t N, int32_t M, const float* points, const float* w2c, const double* K, const float* depths,
                     int32_t width, int32_t height, int32_t* n_visible, int32_t* n_depth, double* depth_mean,

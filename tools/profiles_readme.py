@@ -29,6 +29,7 @@ WHAT = [   # (file name regex, description; {placeholders} are filled by the ext
     (r"r\d+_hostprof_.*\.txt$", "cProfile of the host side of a refinement / map step (`tools/hostprof_steps.py`)"),
     (r"r\d+_ab_probes\.txt$", "A/B and timing-probe log of the round (one box per block)"),
     (r"r\d+_knn\.json$", "`distCUDA2` wall times, brute force vs exact grid"),
+    (r"^decoder_time\.json$", "fused FeatureDecoder against the composed path (`tinycudann.Encoding` + torch layers + `torch.optim.Adam`), HIP events, interleaved regions (`tools/decoder_time.py`): {decoder}"),
     (r"^pnp_time\.json$", "absolute pose (`solve_pose`: P3P LO-RANSAC + Cauchy refinement) on planted scenes, HIP events (`tools/pnp_time.py`): {pnp}"),
     (r"^matching_time\.json$", "2D-3D matching (`hungarian_solve` cost + exact assignment, batched solver, frustum candidates) against torch-CPU + scipy on the same host, HIP events (`tools/matching_time.py`): {matching}"),
     (r"^landmark_selection_time\.json$", "landmark selection (`gaussian_selectition`) at Replica scale on a synthetic room, HIP events per stage (`tools/landmark_selection_time.py`): {landmark}"),
@@ -218,7 +219,18 @@ def pnp(path):
     return ", ".join(parts) + f"; B = {b.get('B', '?')} batch {min(b.get('ms') or [0]):.1f} ms"
 
 
-EXTRACT = {"scenelists": scenelists, "scene": scene, "ab": ab, "perview": perview, "mapidle": mapidle, "rccl": rccl, "kstats": kstats, "hbm": hbm, "sq": sq, "timeline": timeline, "bench": bench, "clocks": clocks, "gradbars": gradbars, "idle": idle, "landmark": landmark, "matching": matching, "pnp": pnp}
+def decoder(path):
+    j = _load(path) or {}
+    names = (("train_step_batch_256", "training step at batch 256"), ("inference_5000", "inference at N = 5 000"),
+             ("inference_1000000", "inference at N = 1 000 000"))
+    parts = [f"{label} {j[k]['fused_ms']:.3f} vs {j[k]['composed_ms']:.3f} ms" for k, label in names if k in j]
+    if not parts:
+        return "(no rows)"
+    tf = (j.get("inference_1000000") or {}).get("fused_TFLOPS")
+    return ", ".join(parts) + (f" ({tf} TFLOPS)" if tf is not None else "")
+
+
+EXTRACT = {"scenelists": scenelists, "scene": scene, "ab": ab, "perview": perview, "mapidle": mapidle, "rccl": rccl, "kstats": kstats, "hbm": hbm, "sq": sq, "timeline": timeline, "bench": bench, "clocks": clocks, "gradbars": gradbars, "idle": idle, "landmark": landmark, "matching": matching, "pnp": pnp, "decoder": decoder}
 
 
 def describe(name, path):
