@@ -20,6 +20,8 @@
  *       call site  test.py:247-378 (match_feature, --eval_pose)
  *   pycolmap.absolute_pose_estimation via solve_pose (absolute pose: P3P LO-RANSAC and refinement)
  *       call site  test.py:64-84 (solve_pose), test.py:345 (called by match_feature, --eval_pose)
+ *   utils.fusion_utils.TSDFVolumeTorch.integrate / get_mesh's vertex gather (feature-TSDF fusion)
+ *       call site  pre_process/gen_3d_fusion_feature.py:70-94 (run_feature_fusion)
  *
  * Everything here is plain C: raw device pointers, sizes, an opaque stream handle
  * (hipStream_t passed as void*), int status codes.  No torch types, no exceptions.
@@ -44,7 +46,7 @@ extern "C" {
 /* bumped on every change of a signature or buffer layout; the Python binding refuses a library
  * whose splatraster_abi_version() differs (a stale in-tree .so would otherwise be called through
  * ctypes with mismatched arguments) */
-#define SPLATRASTER_ABI_VERSION 18
+#define SPLATRASTER_ABI_VERSION 19
 
 #define SPLATRASTER_TILE 16 /* tile edge in pixels (16x16 = 256 pixels = 4 wave64) */
 
@@ -669,6 +671,50 @@ size_t splatraster_landmark_workspace_bytes(int64_t N, int32_t num);
  * positive and finite, or when the radius underflows to 0 first (fewer than num distinct positions). */
 int splatraster_landmark_select(int64_t N, const float* points, const double* score, int32_t num, double radius,
                                 int32_t* out_idx, int32_t* n_passes, void* workspace, void* stream);
+
+/* ---- feature-TSDF fusion: utils/fusion_utils.py:112-181 (integrate), 277-288 (the vertex gather of get_mesh), INTEGRATION.md §20
+ * The volume in the reference's layout, all f32 and contiguous: tsdf [X,Y,Z], weight [X,Y,Z], color [X,Y,Z,3], feat [X,Y,Z,C]
+ * (16-byte aligned); axis[a] [dim[a]] f32 are the voxel centres along axis a (the host builds them with the reference's
+ * promotion chain).  dim[0]*dim[1]*dim[2] <= 2^30; feat_dim a multiple of 4 in [4, 256].  Element offsets are 64-bit. */
+#define SPLATRASTER_FUSION_MAX_FRAMES 8
+#define SPLATRASTER_FUSION_MAX_FEAT_DIM 256
+typedef struct splatraster_fusion_volume {
+    int32_t dim[3];
+    int32_t feat_dim;
+    const float* axis[3];
+    float* tsdf;
+    float* weight;
+    float* color;
+    float* feat;
+} splatraster_fusion_volume;
+/* Host only: bytes of the four volumes, and of the device workspace of splatraster_fusion_surface_count / _extract.
+ * SPLATRASTER_ERR_BAD_ARG (both set to 0) for a dimension < 1, more than 2^30 voxels or an unsupported feat_dim. */
+int splatraster_fusion_bytes(int32_t X, int32_t Y, int32_t Z, int32_t feat_dim, size_t* volume_bytes, size_t* surface_bytes);
+/* Integrates F <= 8 frames, in order, in one launch: depth [F,H,W], color_im [F,H,W,3], feat_im [F,H,W,C] (device f32, feat_im
+ * 16-byte aligned); world2cam [F,12] (rows 0..2 of the world-to-camera matrices) and intrinsics [F,4] (fx, fy, cx, cy) in HOST
+ * memory.  Per voxel centre p and frame, every operation rounded to f32 on its own:
+ *   cam = ((m0 px + m1 py) + m2 pz) + m3 per row; skipped unless cam.z > 0
+ *   pix = rint((cam.xy * f) / cam.z + c) (half to even); skipped outside [0, W) x [0, H)
+ *   d = depth[pix]; diff = d - cam.z; skipped unless d > 0 and diff >= -sdf_trunc; dist = min(diff / sdf_trunc, 1)
+ *   w' = w + obs_weight; tsdf = (w tsdf + obs dist) / w'; color = clamp(rint((w color + obs color_im[pix]) / w'), 0, 255);
+ *   feat = clamp((w feat + obs feat_im[pix]) / w', 0, 255); weight = w'
+ * A batch gives bit for bit what F single-frame calls give.  H, W <= 32768.  No host synchronisation. */
+int splatraster_fusion_integrate(const splatraster_fusion_volume* volume, int32_t F, int32_t H, int32_t W, const float* depth,
+                                 const float* color_im, const float* feat_im, const float* world2cam, const float* intrinsics,
+                                 float obs_weight, float sdf_trunc, void* stream);
+/* Surface vertices: one per grid edge (voxel n to its +x, +y or +z neighbour) whose end values a, b satisfy
+ * (a < level) != (b < level).  level = `level` when use_level, else 0.5f * (min + max) of tsdf (NaN ignored), reduced on the
+ * device; it is stored as the f32 at offset 0 of the workspace.  Counts the vertices, scans the counts and returns the total in
+ * *n_vertices (HOST); synchronises the stream once.  volume->feat and ->axis are not read. */
+int splatraster_fusion_surface_count(const splatraster_fusion_volume* volume, int32_t use_level, float level, void* workspace,
+                                     int64_t* n_vertices, void* stream);
+/* Writes the M = *n_vertices vertices of the preceding count (same workspace, unchanged tsdf), in ascending (voxel linear index,
+ * axis) order: verts [M,3] f32 in voxel units (i + (level - a) / (b - a) along the edge's axis), points [M,3] f64 =
+ * (double)(verts * (float)voxel_size) + origin (origin: 3 doubles in HOST memory), index [M] i64 = linear index of the voxel
+ * rint(verts) (half to even), colors [M,3] u8 = floor(color[index]), feats [M,C] = feat[index] (16-byte aligned). */
+int splatraster_fusion_surface_extract(const splatraster_fusion_volume* volume, const void* workspace, double voxel_size,
+                                       const double* origin, int64_t M, float* verts, double* points, int64_t* index,
+                                       uint8_t* colors, float* feats, void* stream);
 
 /* ---- 2D-3D matching: test.py:247-378 (get_frusm_pts, match_feature), utils/match_utils.py (hungarian_solve), INTEGRATION.md §17
  * Exact rectangular assignment (scipy.optimize.linear_sum_assignment, Crouse's shortest augmenting path): for the same f64 cost

@@ -11,7 +11,7 @@ import os
 from . import build as _build
 
 _LIB = None
-ABI_VERSION = 18   # == SPLATRASTER_ABI_VERSION of include/splatraster.h
+ABI_VERSION = 19   # == SPLATRASTER_ABI_VERSION of include/splatraster.h
 
 OK = 0
 WARN_LOOKBACK_STALL = 5   # splatraster_poll_errors() only; not an error of any frame
@@ -117,6 +117,16 @@ class DecoderLayout(C.Structure):
                 ("dims", C.c_int32 * (DECODER_MAX_LAYERS + 1))]
 
 
+FUSION_MAX_FRAMES = 8      # SPLATRASTER_FUSION_MAX_FRAMES
+FUSION_MAX_FEAT_DIM = 256  # SPLATRASTER_FUSION_MAX_FEAT_DIM
+
+
+class FusionVolume(C.Structure):
+    """struct splatraster_fusion_volume"""
+    _fields_ = [("dim", C.c_int32 * 3), ("feat_dim", C.c_int32), ("axis", C.c_void_p * 3), ("tsdf", C.c_void_p),
+                ("weight", C.c_void_p), ("color", C.c_void_p), ("feat", C.c_void_p)]
+
+
 # every symbol include/splatraster.h declares: (name, restype, argtypes)
 _vp, _i32, _i64, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t
 SYMBOLS = {
@@ -171,6 +181,10 @@ SYMBOLS = {
     "splatraster_landmark_scores": (C.c_int, [_i64, _i32] + [_vp] * 4 + [_i32, _i32] + [_vp] * 7),
     "splatraster_landmark_workspace_bytes": (_sz, [_i64, _i32]),
     "splatraster_landmark_select": (C.c_int, [_i64, _vp, _vp, _i32, C.c_double, _vp, _vp, _vp, _vp]),
+    "splatraster_fusion_bytes": (C.c_int, [_i32] * 4 + [C.POINTER(_sz), C.POINTER(_sz)]),
+    "splatraster_fusion_integrate": (C.c_int, [C.POINTER(FusionVolume), _i32, _i32, _i32] + [_vp] * 5 + [C.c_float, C.c_float, _vp]),
+    "splatraster_fusion_surface_count": (C.c_int, [C.POINTER(FusionVolume), _i32, C.c_float, _vp, C.POINTER(_i64), _vp]),
+    "splatraster_fusion_surface_extract": (C.c_int, [C.POINTER(FusionVolume), _vp, C.c_double, _vp, _i64] + [_vp] * 6),
     "splatraster_lsap_workspace_bytes": (_sz, [_i32, _vp]),
     "splatraster_lsap": (C.c_int, [_i32, _vp, _vp, _i32] + [_vp] * 6),
     "splatraster_debug_set_lsap_lds": (C.c_int, [C.c_int]),

@@ -1185,6 +1185,33 @@ int splatraster_landmark_select(int64_t N, const float* points, const double* sc
     return landmark_select(N, points, score, num, radius, out_idx, n_passes, workspace, reinterpret_cast<hipStream_t>(stream));
 }
 
+int splatraster_fusion_bytes(int32_t X, int32_t Y, int32_t Z, int32_t feat_dim, size_t* volume_bytes, size_t* surface_bytes)
+{
+    return fusion_bytes(X, Y, Z, feat_dim, volume_bytes, surface_bytes);
+}
+
+int splatraster_fusion_integrate(const splatraster_fusion_volume* volume, int32_t F, int32_t H, int32_t W, const float* depth,
+                                 const float* color_im, const float* feat_im, const float* world2cam, const float* intrinsics,
+                                 float obs_weight, float sdf_trunc, void* stream)
+{
+    return fusion_integrate(volume, F, H, W, depth, color_im, feat_im, world2cam, intrinsics, obs_weight, sdf_trunc,
+                            reinterpret_cast<hipStream_t>(stream));
+}
+
+int splatraster_fusion_surface_count(const splatraster_fusion_volume* volume, int32_t use_level, float level, void* workspace,
+                                     int64_t* n_vertices, void* stream)
+{
+    return fusion_surface_count(volume, use_level, level, workspace, n_vertices, reinterpret_cast<hipStream_t>(stream));
+}
+
+int splatraster_fusion_surface_extract(const splatraster_fusion_volume* volume, const void* workspace, double voxel_size,
+                                       const double* origin, int64_t M, float* verts, double* points, int64_t* index,
+                                       uint8_t* colors, float* feats, void* stream)
+{
+    return fusion_surface_extract(volume, workspace, voxel_size, origin, M, verts, points, index, colors, feats,
+                                  reinterpret_cast<hipStream_t>(stream));
+}
+
 size_t splatraster_lsap_workspace_bytes(int32_t B, const splatraster_lsap_problem* problems)
 {
     return lsap_workspace_bytes(B, problems);

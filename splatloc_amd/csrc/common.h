@@ -452,6 +452,17 @@ size_t landmark_workspace_bytes(int64_t N, int32_t num);
 int landmark_select(int64_t N, const float* points, const double* score, int32_t num, double radius, int32_t* out_idx,
                     int32_t* n_passes, void* workspace, hipStream_t stream);
 
+// fusion.hip (feature-TSDF fusion: batch integration, surface vertices and their feature rows)
+int fusion_bytes(int32_t X, int32_t Y, int32_t Z, int32_t C, size_t* volume_bytes, size_t* surface_bytes);
+int fusion_integrate(const splatraster_fusion_volume* v, int32_t F, int32_t H, int32_t W, const float* depth,
+                     const float* color_im, const float* feat_im, const float* world2cam, const float* intrinsics,
+                     float obs_weight, float sdf_trunc, hipStream_t stream);
+int fusion_surface_count(const splatraster_fusion_volume* v, int32_t use_level, float level, void* workspace, int64_t* n_vertices,
+                         hipStream_t stream);
+int fusion_surface_extract(const splatraster_fusion_volume* v, const void* workspace, double voxel_size, const double* origin,
+                           int64_t M, float* verts, double* points, int64_t* index, uint8_t* colors, float* feats,
+                           hipStream_t stream);
+
 // matching.hip (2D-3D matching: assignment solver, descriptor cost, frustum candidates)
 size_t lsap_workspace_bytes(int32_t B, const splatraster_lsap_problem* problems);
 int lsap_solve(int32_t B, const splatraster_lsap_problem* problems, const double* costs, int32_t maximize, int64_t* row_ind,

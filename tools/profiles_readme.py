@@ -30,6 +30,7 @@ WHAT = [   # (file name regex, description; {placeholders} are filled by the ext
     (r"r\d+_ab_probes\.txt$", "A/B and timing-probe log of the round (one box per block)"),
     (r"r\d+_knn\.json$", "`distCUDA2` wall times, brute force vs exact grid"),
     (r"^decoder_time\.json$", "fused FeatureDecoder against the composed path (`tinycudann.Encoding` + torch layers + `torch.optim.Adam`), HIP events, interleaved regions (`tools/decoder_time.py`): {decoder}"),
+    (r"^fusion_time\.json$", "feature-TSDF fusion at office_0's size (21.9 M voxels x 256 channels, 640 x 480 frames) against the same update composed from torch operators, HIP events, interleaved regions (`tools/fusion_timing.py`): {fusion}"),
     (r"^pnp_time\.json$", "absolute pose (`solve_pose`: P3P LO-RANSAC + Cauchy refinement) on planted scenes, HIP events (`tools/pnp_time.py`): {pnp}"),
     (r"^matching_time\.json$", "2D-3D matching (`hungarian_solve` cost + exact assignment, batched solver, frustum candidates) against torch-CPU + scipy on the same host, HIP events (`tools/matching_time.py`): {matching}"),
     (r"^landmark_selection_time\.json$", "landmark selection (`gaussian_selectition`) at Replica scale on a synthetic room, HIP events per stage (`tools/landmark_selection_time.py`): {landmark}"),
@@ -230,7 +231,16 @@ def decoder(path):
     return ", ".join(parts) + (f" ({tf} TFLOPS)" if tf is not None else "")
 
 
-EXTRACT = {"scenelists": scenelists, "scene": scene, "ab": ab, "perview": perview, "mapidle": mapidle, "rccl": rccl, "kstats": kstats, "hbm": hbm, "sq": sq, "timeline": timeline, "bench": bench, "clocks": clocks, "gradbars": gradbars, "idle": idle, "landmark": landmark, "matching": matching, "pnp": pnp, "decoder": decoder}
+def fusion(path):
+    j = _load(path) or {}
+    ms, tb = j.get("ms_per_frame") or {}, j.get("achieved_TB_per_s") or {}
+    if not ms:
+        return "(no rows)"
+    return (f"single frames {ms['single']:.2f} ms per frame ({tb.get('single')} TB/s), batches of 8 {ms['batch8']:.2f} ({tb.get('batch8')} TB/s), "
+            f"torch composition {ms['torch']:.1f}")
+
+
+EXTRACT = {"scenelists": scenelists, "scene": scene, "ab": ab, "perview": perview, "mapidle": mapidle, "rccl": rccl, "kstats": kstats, "hbm": hbm, "sq": sq, "timeline": timeline, "bench": bench, "clocks": clocks, "gradbars": gradbars, "idle": idle, "landmark": landmark, "matching": matching, "pnp": pnp, "decoder": decoder, "fusion": fusion}
 
 
 def describe(name, path):
