@@ -756,9 +756,11 @@ int splatraster_match_sims(int32_t D, int32_t N1, int32_t N2, const float* d1, c
  * f64 from the f32 inputs: pc = R p + t, (u, v) = (K pc)_{0,1} / (K pc)_2; kept iff pc.z > 0.05, 0 <= u < width, 0 <= v < height
  * and, in key-Gaussian mode (marker != NULL, [N] f32), marker > marker_threshold (compared in f32 like the reference).
  * Subset mode (marker == NULL): the kept points in index order.  Key-Gaussian mode: every pixel of kp_mask [height, width] (u8,
- * 1 = keypoint; row-major order) is back-projected with depth [height, width] f32, c2w [4,4] (f64, HOST) and kp_K = (fx, fy,
- * cx, cy) (HOST): x = (col - cx) * d / fx, y = (row - cy) * d / fy, z = d, q = R x + t; its nearest kept point (distance
+ * == 1 is a keypoint, every other value is not; row-major order) is back-projected with depth [height, width] f32, c2w [4,4]
+ * (f64, HOST) and kp_K = (fx, fy, cx, cy) (HOST): x = (col - cx) * d / fx, y = (row - cy) * d / fy, z = d, q = R x + t; its nearest kept point (distance
  * sqrt((dx^2 + dy^2) + dz^2) in f64, ties the smaller index) is emitted, in keypoint order, when closer than 0.1.
+ * A keypoint whose q is not finite (depth inf or NaN) or reaches 1e15 in magnitude is not searched and emits nothing; depth 0
+ * gives q = t and follows the rule.
  * Outputs (device): out_idx [n] i32 point indices, out_xyz [n,3] f32, out_uv [n,2] f64 projections, *out_count (int64, device) =
  * n; capacity N (subset) or width * height (key mode).  workspace: splatraster_frustum_workspace_bytes(N, width, height).  No
  * host synchronisation. */

@@ -596,6 +596,7 @@ fr_grid_fill_kernel(const uint64_t* __restrict__ total, const uint32_t* __restri
 }
 
 // per keypoint pixel (mask == 1): back-projection, nearest kept point (ties: the smaller point index), found if < 0.1 m
+// (a back-projection that is not finite or reaches 1e15, from a depth hole, is not searched: no cell index is formed from it)
 __global__ void __launch_bounds__(FR_THREADS)
 fr_query_kernel(int32_t W, int32_t H, const uint8_t* __restrict__ kp_mask, const float* __restrict__ depth, FrCam cam,
                 const float* __restrict__ points, const int32_t* __restrict__ cand, const uint32_t* __restrict__ starts,
@@ -606,7 +607,7 @@ fr_query_kernel(int32_t W, int32_t H, const uint8_t* __restrict__ kp_mask, const
     if (p >= (int64_t)W * H) return;
     uint32_t f = 0;
     int32_t bi = -1;
-    if (kp_mask[p]) {
+    if (kp_mask[p] == 1) {
         const double row = (double)(p / W), col = (double)(p % W);
         const double d = depth[p];
         const double xs = (col - cam.cx) * d / cam.fx;

@@ -194,6 +194,85 @@ def test_argument_errors_before_device_work():
         M.frustum_candidates(np.zeros((5, 3), np.float32), np.eye(4), np.eye(3), 64, 48, marker=np.zeros(4, np.float32))
 
 
+def test_frustum_restatement_reproduces_fixture():
+    from tests import matching_reference as R
+    g = golden()
+    W, H = (int(x) for x in g["f_size"])
+    idx, xyz, uv = R.frustum_restated(g["f_points"], g["f_w2c"], g["f_K"], W, H, marker=g["f_marker"], kp_mask=g["f_mask"],
+                                      depth=g["f_depth"], c2w=g["f_c2w"], kp_K=g["f_K"])
+    assert len(idx) == 600 and np.array_equal(idx, g["f_idx"])
+    assert xyz.dtype == np.float32 and np.array_equal(xyz, g["f_pts3d"])
+    assert np.abs(uv - g["f_pts2d"]).max() <= 1e-4   # the reference's key mode projects in f32
+    idx, xyz, uv = R.frustum_restated(g["s_subset"], g["f_w2c"], g["f_K"], W, H)
+    assert len(idx) == 1074 and np.array_equal(idx, g["s_idx"])
+    assert np.array_equal(xyz.astype(np.float64), g["s_pts3d"])
+    assert np.abs(uv - g["s_pts2d"]).max() <= 1e-12
+
+
+def test_frustum_restatement_equals_kdtree_away_from_the_edges():
+    """scipy's k-d tree (the reference's search) on duplicate-free scenes: equal pairs wherever the nearest distance is not
+    within 1e-9 of the 0.1 m bound and the runner-up is not within 1e-9 of the nearest"""
+    spatial = pytest.importorskip("scipy.spatial")
+    from tests import matching_reference as R
+    pairs = 0
+    for seed, N, W, H, density in ((1, 2049, 64, 48, 0.3), (2, 1025, 17, 9, 1.0), (3, 300, 250, 130, 0.3)):
+        s = R.room_scene(seed, N, W, H, density)
+        assert len(np.unique(s["points"], axis=0)) == N
+        idx, _, _, dist = R.frustum_restated(s["points"], s["w2c"], s["K"], W, H, return_distance=True, **R.key_args(s))
+        pz, u, v = R.project(s["points"], s["w2c"], s["K"])
+        kept = np.flatnonzero((pz > 0.05) & (u >= 0) & (u < W) & (v >= 0) & (v < H) & (s["marker"] > np.float32(0.005)))
+        q, ok = R.backproject(s["mask"], s["depth"], s["c2w"], s["K"])
+        assert ok.all()
+        d2, i2 = spatial.cKDTree(s["points"][kept].astype(np.float64)).query(q, k=2)
+        safe = (np.abs(d2[:, 0] - 0.1) > 1e-9) & (d2[:, 1] - d2[:, 0] > 1e-9)
+        assert safe.mean() > 0.99
+        dk, ik = spatial.cKDTree(s["points"][kept].astype(np.float64)).query(q, distance_upper_bound=0.1)
+        found = np.isfinite(dk)
+        want = np.where(found, kept[np.minimum(ik, len(kept) - 1)], -1)
+        # the restatement's pairs, one slot per keypoint
+        d1, p1 = R.nearest(s["points"][kept].astype(np.float64), q)
+        got = np.where(d1 < 0.1, kept[p1], -1)
+        assert np.array_equal(got[safe], want[safe]), seed
+        assert np.array_equal(idx, got[got >= 0]) and np.array_equal(dist, d1[got >= 0])
+        assert 0 < (got >= 0).sum() < len(q)   # both outcomes of d < 0.1
+        pairs += int((got >= 0).sum())
+    assert pairs > 500
+
+
+def test_cost_f64_reproduces_fixture_hungarian_cases():
+    from tests import matching_reference as R
+    g = golden()
+    for k in range(int(g["h_count"])):
+        d1, d2 = g[f"h{k}_d1"], g[f"h{k}_d2"]
+        want, s = reference_cost(d1, d2)
+        sim, cost = R.cost_f64(d1, d2, 0.4)
+        if d2.shape[1] < d1.shape[1]:
+            sim, cost = sim.T, cost.T
+        assert sim.shape == want.shape
+        s32 = sim.astype(np.float32)
+        s32[s32 < np.float32(0.4)] = 0
+        assert np.array_equal(s32, s) and np.array_equal((np.float32(1) - s32).astype(np.float64), want), k
+        assert np.abs(cost - want).max() <= 2.0 ** -24   # the f32 rounding of sim and of 1 - sim below 1
+        r, c = lsap_restated(cost)
+        assert np.array_equal(np.stack([r, c]), g[f"h{k}_matches"]), k
+
+
+def test_cost_cases_leave_the_threshold_band_nearly_empty():
+    """the differential cost test of tests/test_gpu_matching_edges.py may skip at most 0.1 % of a case's entries"""
+    from tests import matching_reference as R
+    assert R.cost_bound(256) == 520 * 2.0 ** -24
+    for D, N1, N2 in R.cost_cases():
+        d1, d2 = R.cost_case(D, N1, N2)
+        sim, cost = R.cost_f64(d1, d2, R.COST_THRESHOLD)
+        assert sim.shape == (min(N1, N2), max(N1, N2))
+        assert R.band(sim, R.COST_THRESHOLD, D).mean() <= R.BAND_SHARE, (D, N1, N2)
+        # numpy's own f32 evaluation stays inside the derived bound
+        a = (d1 / np.maximum(np.linalg.norm(d1, axis=0), np.float32(1e-12))).astype(np.float32)
+        b = (d2 / np.maximum(np.linalg.norm(d2, axis=0), np.float32(1e-12))).astype(np.float32)
+        s32 = (a.T @ b).astype(np.float64)
+        assert np.abs((s32.T if N2 < N1 else s32) - sim).max() <= R.cost_bound(D), (D, N1, N2)
+
+
 def _usage(src):
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
