@@ -2,7 +2,8 @@
 rule and local optimisation (include/splatraster.h), checked on planted poses; the argument errors of
 splatloc_amd.pnp, raised before any device work; solve_pose's conversion against the reference's on tests/golden/pnp.npz
 (make_golden_pnp.py); and the compiler's resource report of csrc/pnp.hip.  The restatement is also the CPU side of
-tests/test_gpu_pnp.py."""
+tests/test_gpu_pnp.py and tests/test_gpu_pnp_edges.py; its premises on the cases of tests/pnp_cases.py (decisions independent
+of the summation order, no residual on the threshold) are checked here."""
 import math
 import os
 
@@ -341,7 +342,8 @@ def refine(m, mask, p2d, p3d, intr):
 
 def estimate_restated(p2d, p3d, intr, thr=12.0, min_inlier_ratio=0.01, min_num_trials=1000, max_num_trials=100000,
                       confidence=0.9999, seed=0):
-    """the whole estimator: dict(success, R, t, inliers, num_inliers, trials)"""
+    """the whole estimator: dict(success, R, t, inliers, num_inliers, trials, model); model is the RANSAC model (R row-major,
+    t) before the refinement, the one whose inliers are reported"""
     n = len(p2d)
     if n < 4:
         return {"success": False}
@@ -366,7 +368,7 @@ def estimate_restated(p2d, p3d, intr, thr=12.0, min_inlier_ratio=0.01, min_num_t
     mask = inliers(best, p2d, p3d, intr, thr)
     m = refine(best, mask, p2d, p3d, intr)
     return {"success": bool(np.isfinite(m).all()), "R": m[:9].reshape(3, 3), "t": m[9:], "inliers": mask,
-            "num_inliers": int(sup[0]), "trials": trials}
+            "num_inliers": int(sup[0]), "trials": trials, "model": np.asarray(best, dtype=np.float64)}
 
 
 # ------------------------------------------------------------------------------------------------------- planted scenes
@@ -522,6 +524,79 @@ def test_argument_errors_before_device_work():
         P.absolute_pose_estimation(np.zeros((5, 2), np.int64), p3, SCENE12)
     with pytest.raises(ValueError, match="K must be"):
         P.estimate_absolute_pose(p2, p3, np.eye(4))
+
+
+def test_hypotheses_trial_range_errors_before_any_launch():
+    """ntrials above the batch and a negative trial0 are SPLATRASTER_ERR_BAD_ARG; every pointer is valid (host memory), so the
+    trial range alone decides, and the call returns before it touches a device"""
+    import ctypes as C
+    from splatloc_amd import _native
+    from splatloc_amd import pnp as P
+    lib = _native.load()
+    tab = (P.PnpProblem * 1)(P.PnpProblem(0, 5, 0, 572.0, 572.0, 320.0, 240.0))
+    opt = P.options()
+    buf = np.zeros(64)
+    ptr = C.c_void_p(buf.ctypes.data)
+
+    def call(trial0, ntrials):
+        return lib.splatraster_pnp_hypotheses(1, tab, C.byref(opt), trial0, ntrials, ptr, ptr, ptr, ptr, ptr, ptr, None)
+    assert call(0, BATCH + 1) == 1
+    assert call(-1, 1) == 1
+    assert call(0, 0) == 1
+    assert call(-(2 ** 40), BATCH) == 1
+    assert not buf.any()
+
+
+def pytest_generate_tests(metafunc):
+    if "pnp_case" in metafunc.fixturenames:   # tests/pnp_cases.py imports this module: its names are read at collection
+        from tests import pnp_cases
+        metafunc.parametrize("pnp_case", pnp_cases.NAMES)
+
+
+def test_case_reference_preconditions(pnp_case):
+    """what tests/test_gpu_pnp_edges.py relies on, for every case of tests/pnp_cases.py: the restatement runs the stated
+    number of trials, its decisions do not depend on the order of its sums (reversed: inliers, count, trials and success
+    identical, the pose within 1e-12), and no residual of its RANSAC model lies within 1e-6 relative of the threshold"""
+    from tests import pnp_cases
+    case = pnp_cases.BY_NAME[pnp_case]
+    p2d, p3d, intr, K = pnp_cases.scene(pnp_case)
+    assert p2d.shape == (case.n, 2) and p3d.shape == (case.n, 3)
+    assert p2d.dtype == p3d.dtype == (np.float32 if case.f32 else np.float64)
+    ref = pnp_cases.reference(pnp_case)
+    rev = pnp_cases.reordered_case(pnp_case)
+    assert ref["success"] and rev["success"]
+    assert ref["trials"] == rev["trials"] == case.trials
+    assert ref["num_inliers"] == rev["num_inliers"] == int(ref["inliers"].sum()) >= 4
+    assert np.array_equal(ref["inliers"], rev["inliers"])
+    assert np.abs(ref["R"] - rev["R"]).max() <= 1e-12
+    assert np.abs(ref["t"] - rev["t"]).max() <= 1e-12
+    thr2 = float(case.options.get("max_error_px", 12.0)) ** 2
+    r = pnp_cases.case_residuals(pnp_case)
+    assert r.shape == (case.n,) and not ref["inliers"][r > thr2].any()
+    assert np.abs(r - thr2).min() > 1e-6 * thr2, np.abs(r - thr2).min() / thr2
+
+
+def test_tie_scene_is_decided_by_the_residual_sum():
+    """the two-pose scene of tests/pnp_cases.py: the batch's best count is shared by models of both poses, the smallest and
+    the largest residual sum among them belong to different poses, and the restatement returns the pose of the smallest"""
+    from tests import pnp_cases
+    p2d, p3d, intr, _, first = pnp_cases.tie_scene()
+    sup = pnp_cases.batch_supports(p2d, p3d, intr)
+    top = max(c for c, _, _ in sup)
+    tied = sorted(((s, m) for c, s, m in sup if c == top), key=lambda x: x[0])
+    assert top == 20 and len(tied) >= 20
+    sums = sorted({s for s, _ in tied})   # a triplet drawn twice gives the same model and sum twice
+    assert len(sums) >= 20 and sums[1] - sums[0] > 1e-6 * sums[0]   # rounding cannot change which sum is the smallest
+    in_lo, in_hi = (inliers(m, p2d, p3d, intr, 12.0) for m in (tied[0][1], tied[-1][1]))
+    assert np.array_equal(in_lo, first) or np.array_equal(in_lo, ~first)
+    assert np.array_equal(in_hi, ~in_lo)
+    ref = pnp_cases.tie_reference()
+    rev = pnp_cases.reordered_reference(p2d, p3d, intr, seed=pnp_cases.SEED, **pnp_cases.TIE_OPTIONS)
+    assert ref["success"] and ref["trials"] == rev["trials"] == BATCH and ref["num_inliers"] == rev["num_inliers"] == 20
+    assert np.array_equal(ref["inliers"], in_lo) and np.array_equal(rev["inliers"], in_lo)
+    assert np.abs(ref["R"] - rev["R"]).max() <= 1e-12 and np.abs(ref["t"] - rev["t"]).max() <= 1e-12
+    r = pnp_cases.ransac_residuals(ref, p2d, p3d, intr)
+    assert np.abs(r - 144.0).min() > 1e-6 * 144.0
 
 
 def test_fewer_than_four_points_fail_without_a_device():
