@@ -46,7 +46,7 @@ extern "C" {
 /* bumped on every change of a signature or buffer layout; the Python binding refuses a library
  * whose splatraster_abi_version() differs (a stale in-tree .so would otherwise be called through
  * ctypes with mismatched arguments) */
-#define SPLATRASTER_ABI_VERSION 19
+#define SPLATRASTER_ABI_VERSION 20
 
 #define SPLATRASTER_TILE 16 /* tile edge in pixels (16x16 = 256 pixels = 4 wave64) */
 
@@ -837,6 +837,34 @@ int splatraster_pnp_hypotheses(int32_t B, const splatraster_pnp_problem* problem
 int splatraster_pnp_score(int32_t B, const splatraster_pnp_problem* problems, const splatraster_pnp_options* options, int32_t M,
                           const double* models, const double* points2d, const double* points3d, int32_t* count, double* sum,
                           void* workspace, void* stream);
+
+/* ---- localisation: retrieval and pose errors (pre_process/gen_netvlad_retrieval.py:32-34, utils/eval_utils.py:75-145,
+ * test.py:81-82), INTEGRATION.md §21 ------------------------------------------------------------------------------------------
+ * Retrieval: the k most similar database rows of every query row, similarity and selection fused (the Q x N matrix never exists
+ * in global memory).  query [Q, D], db [N, D] f32 row-major (device); rows need not be unit length.  sims [Q, k] (f32) is the dot
+ * product of the query row and the selected database row, accumulated in f32 (the order is the kernel's); idx [Q, k] (int64) the
+ * database rows.  Within a query row: similarity descending, equal similarities (-0 == +0) by database index ascending.
+ * Limits: 1 <= k <= min(N, SPLATRASTER_RETRIEVAL_MAX_K), D >= 1, Q >= 0, 1 <= N < 2^31; anything else is
+ * SPLATRASTER_ERR_BAD_ARG without a launch.  status [1] (i32, device) receives SPLATRASTER_RETRIEVAL_OK, or _NONFINITE when a
+ * computed similarity is NaN (idx / sims are then unspecified).  workspace (splatraster_retrieval_workspace_bytes; may be 0 bytes,
+ * then NULL is accepted) holds one k-entry list per (query, slice of the database): O(Q k slices), at most 64 slices, nothing
+ * that grows with Q * N.  No host synchronisation. */
+#define SPLATRASTER_RETRIEVAL_MAX_K 128
+#define SPLATRASTER_RETRIEVAL_OK 0
+#define SPLATRASTER_RETRIEVAL_NONFINITE 1
+size_t splatraster_retrieval_workspace_bytes(int64_t Q, int64_t N, int32_t D, int32_t k);
+int splatraster_retrieval_topk(int64_t Q, int64_t N, int32_t D, int32_t k, const float* query, const float* db, int64_t* idx,
+                               float* sims, int32_t* status, void* workspace, void* stream);
+/* eval_pose for B poses (f64 row-major rotations [B,3,3], translations [B,3], device).  Per pose and per rotation: the quaternion
+ * of SO3_to_quat in f64 (branch on R22 < 0, then R00 > R11; else on R00 < -R11; (v * 0.5) / sqrt(scale)), divided by
+ * max(norm, 1e-12), rounded to f32; d = |q_gt . q_est| in f32, d > (float)(1 - 1e-7) -> that bound;
+ * theta_deg = 2 * acos(d) * 180 / pi in f32 (never below 0.05595 degrees); dist = ||t_est - t_gt|| in f64.  valid (u8 [B] or NULL):
+ * rows with valid == 0 get NaN in both outputs.  No host synchronisation. */
+int splatraster_pose_errors(int64_t B, const double* R_est, const double* t_est, const double* R_gt, const double* t_gt,
+                            const uint8_t* valid, float* theta_deg, double* dist, void* stream);
+/* solve_pose's conversion for B poses: R_out = R^T, t_out[i] = fma(-R[2][i], t[2], fma(-R[1][i], t[1], -R[0][i] * t[0])) (f64,
+ * device; the rounding of a three-term FMA chain in ascending order).  No host synchronisation. */
+int splatraster_pose_invert(int64_t B, const double* R, const double* t, double* R_out, double* t_out, void* stream);
 
 /* ---- pose refinement on the device (build extension, DESIGN.md §6.8: the reference's rasterizer returns no camera gradient
  * and nothing calls its utils/optimization_utils.py:5-66 pose helpers) ------------------------------------------------------

@@ -11,7 +11,7 @@ import os
 from . import build as _build
 
 _LIB = None
-ABI_VERSION = 19   # == SPLATRASTER_ABI_VERSION of include/splatraster.h
+ABI_VERSION = 20   # == SPLATRASTER_ABI_VERSION of include/splatraster.h
 
 OK = 0
 WARN_LOOKBACK_STALL = 5   # splatraster_poll_errors() only; not an error of any frame
@@ -196,6 +196,10 @@ SYMBOLS = {
     "splatraster_pnp": (C.c_int, [_i32] + [_vp] * 12),
     "splatraster_pnp_hypotheses": (C.c_int, [_i32, _vp, _vp, _i64, _i32] + [_vp] * 7),
     "splatraster_pnp_score": (C.c_int, [_i32, _vp, _vp, _i32] + [_vp] * 7),
+    "splatraster_retrieval_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
+    "splatraster_retrieval_topk": (C.c_int, [_i64, _i64, _i32, _i32] + [_vp] * 7),
+    "splatraster_pose_errors": (C.c_int, [_i64] + [_vp] * 8),
+    "splatraster_pose_invert": (C.c_int, [_i64] + [_vp] * 5),
     "splatraster_activate_forward": (C.c_int, [_i32] * 5 + [_vp] * 13),
     "splatraster_activate_backward": (C.c_int, [_i32] * 5 + [_vp] * 19),
     "splatraster_densification_stats": (C.c_int, [_i32] + [_vp] * 6),

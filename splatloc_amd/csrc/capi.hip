@@ -1281,4 +1281,26 @@ int splatraster_pnp_score(int32_t B, const splatraster_pnp_problem* problems, co
                      reinterpret_cast<hipStream_t>(stream));
 }
 
+size_t splatraster_retrieval_workspace_bytes(int64_t Q, int64_t N, int32_t D, int32_t k)
+{
+    return retrieval_workspace_bytes(Q, N, D, k);
+}
+
+int splatraster_retrieval_topk(int64_t Q, int64_t N, int32_t D, int32_t k, const float* query, const float* db, int64_t* idx,
+                               float* sims, int32_t* status, void* workspace, void* stream)
+{
+    return retrieval_topk(Q, N, D, k, query, db, idx, sims, status, workspace, reinterpret_cast<hipStream_t>(stream));
+}
+
+int splatraster_pose_errors(int64_t B, const double* R_est, const double* t_est, const double* R_gt, const double* t_gt,
+                            const uint8_t* valid, float* theta_deg, double* dist, void* stream)
+{
+    return pose_errors(B, R_est, t_est, R_gt, t_gt, valid, theta_deg, dist, reinterpret_cast<hipStream_t>(stream));
+}
+
+int splatraster_pose_invert(int64_t B, const double* R, const double* t, double* R_out, double* t_out, void* stream)
+{
+    return pose_invert(B, R, t, R_out, t_out, reinterpret_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

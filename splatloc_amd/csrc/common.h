@@ -490,4 +490,12 @@ int pnp_score(int32_t B, const splatraster_pnp_problem* problems, const splatras
               const double* models, const double* points2d, const double* points3d, int32_t* count, double* sum,
               void* workspace, hipStream_t stream);
 
+// retrieval.hip (localisation: fused similarity + top-k, pose errors, pose inversion)
+size_t retrieval_workspace_bytes(int64_t Q, int64_t N, int32_t D, int32_t k);
+int retrieval_topk(int64_t Q, int64_t N, int32_t D, int32_t k, const float* query, const float* db, int64_t* idx, float* sims,
+                   int32_t* status, void* workspace, hipStream_t stream);
+int pose_errors(int64_t B, const double* R_est, const double* t_est, const double* R_gt, const double* t_gt, const uint8_t* valid,
+                float* theta_deg, double* dist, hipStream_t stream);
+int pose_invert(int64_t B, const double* R, const double* t, double* R_out, double* t_out, hipStream_t stream);
+
 }  // namespace sr

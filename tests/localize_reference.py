@@ -1,0 +1,165 @@
+"""numpy restatement of the localisation kernels (splatloc_amd/csrc/retrieval.hip) and the seeded retrieval cases the fixture
+tests/golden/localize.npz refers to.  f64 throughout except where the reference rounds to f32.
+
+retrieval_topk: f64 similarities, stable argsort of their negation (similarity descending, equal similarities by database
+index ascending: the project's tie rule; torch.topk leaves ties unspecified).
+pose_errors: utils/eval_utils.py:75-145 (SO3_to_quat, compute_quaternion_dist, eval_pose) for f64 inputs.
+
+The retrieval cases are rebuilt from their seeds with elementwise numpy only (no BLAS, no reductions on the data path), so the
+arrays are bit-identical everywhere; the fixture stores their sha256.
+"""
+import functools
+import hashlib
+import math
+
+import numpy as np
+
+# case: (seed, Q, N, D, k)
+RETRIEVAL_CASES = {
+    1: (101, 37, 180, 4096, 10),    # Replica's database and descriptor size; Q is not a multiple of the tile
+    2: (102, 1, 10, 4096, 10),      # k == N, a full sort
+    3: (103, 70, 333, 130, 5),      # odd D (zero-padded tail), odd N, several query tiles
+    4: (104, 3, 5000, 128, 10),     # many database steps; the split over N
+    5: (105, 33, 100, 64, 1),       # k == 1; Q one past a tile
+    6: (106, 2, 64, 4096, 32),      # wide k
+}
+MAX_REDRAWS = 1000
+
+
+def gamma(D):
+    """the forward-error constant of an f32 dot product of length D in any order (FMA included)"""
+    u = D * 2.0 ** -24
+    return u / (1.0 - u)
+
+
+def dots64(q, db):
+    """f64 similarities [Q, N] (elementwise products, numpy's pairwise sum)"""
+    q, db = np.asarray(q, np.float64), np.asarray(db, np.float64)
+    return np.stack([(db * q[i]).sum(axis=1) for i in range(q.shape[0])]) if q.shape[0] else np.zeros((0, db.shape[0]))
+
+
+def retrieval_topk(q, db, k):
+    s = dots64(q, db)
+    idx = np.argsort(-s, axis=1, kind="stable")[:, :k]
+    return idx.astype(np.int64), np.take_along_axis(s, idx, axis=1)
+
+
+def _noise(rng, shape, D):
+    return ((2 * rng.random(shape) - 1).astype(np.float32)) * np.float32(math.sqrt(3.0 / D))
+
+
+@functools.lru_cache(maxsize=None)
+def retrieval_case(case):
+    """(query f32 [Q, D], db f32 [N, D], k, draws): every consecutive gap among a row's top-(k + 1) f64 similarities exceeds
+    4 gamma_D ||q|| max ||d||, twice what any f32 summation order can move a pair, so the indices are pinned."""
+    seed, Q, N, D, k = RETRIEVAL_CASES[case]
+    rng = np.random.default_rng(seed)
+    db = _noise(rng, (N, D), D)
+    db64 = db.astype(np.float64)
+    dmax = float(np.sqrt((db64 * db64).sum(axis=1)).max())
+    m = min(k + 2, N)
+    w = [np.float32(1.0 - j / (m + 1)) for j in range(m)]
+    scale = np.float32(1.0 / math.sqrt(0.09 + sum(float(x) ** 2 for x in w)))
+    rows, draws = [], 0
+    for _ in range(Q):
+        while True:
+            draws += 1
+            assert draws <= MAX_REDRAWS, f"case {case}: more than {MAX_REDRAWS} draws"
+            row = np.float32(0.3) * _noise(rng, (D,), D)
+            p = rng.permutation(N)[:m]
+            for j in range(m):
+                row = row + w[j] * db[p[j]]
+            row = (row * scale).astype(np.float32)
+            r64 = row.astype(np.float64)
+            s = np.sort((db64 * r64).sum(axis=1))[::-1][:min(k + 1, N)]
+            margin = 4 * gamma(D) * math.sqrt(float((r64 * r64).sum())) * dmax
+            if len(s) < 2 or float((s[:-1] - s[1:]).min()) > margin:
+                break
+        rows.append(row)
+    return np.stack(rows), db, k, draws
+
+
+def case_hash(q, db):
+    return hashlib.sha256(np.ascontiguousarray(q).tobytes() + np.ascontiguousarray(db).tobytes()).hexdigest()
+
+
+@functools.lru_cache(maxsize=None)
+def exact_case(which):
+    """small-integer descriptors stored as f32: every order of summation is exact.  (q, db, k, idx, sims) with the expected
+    result from the int64 product and a stable argsort."""
+    if which == 0:
+        rng = np.random.default_rng(7001)
+        Q, N, D, k, lo, hi = 33, 300, 64, 128, -3, 3
+    else:
+        rng = np.random.default_rng(7002)
+        Q, N, D, k, lo, hi = 2, 130, 4096, 128, -1, 1
+    q = rng.integers(lo, hi + 1, size=(Q, D))
+    db = rng.integers(lo, hi + 1, size=(N, D))
+    s = np.stack([(db * q[i]).sum(axis=1) for i in range(Q)]).astype(np.int64)
+    idx = np.argsort(-s, axis=1, kind="stable")[:, :k].astype(np.int64)
+    return q.astype(np.float32), db.astype(np.float32), k, idx, np.take_along_axis(s, idx, axis=1).astype(np.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def wide_case(which):
+    """exact integer cases large enough for the kernel's 128-query tile (at least 512 tile x 128-row steps, k <= 32): the second
+    query tile is partial, the database is split into the maximum number of slices; D a multiple of 4 and not"""
+    Q, N, D, k = ((130, 33000, 12, 32), (129, 33111, 7, 5))[which]
+    rng = np.random.default_rng(7100 + which)
+    q = rng.integers(-3, 4, size=(Q, D))
+    db = rng.integers(-3, 4, size=(N, D))
+    s = np.stack([(db * q[i]).sum(axis=1) for i in range(Q)]).astype(np.int64)
+    idx = np.argsort(-s, axis=1, kind="stable")[:, :k].astype(np.int64)
+    return q.astype(np.float32), db.astype(np.float32), k, idx, np.take_along_axis(s, idx, axis=1).astype(np.float32)
+
+
+def so3_to_quat(R):
+    """SO3_to_quat for one f64 matrix, normalised (F.normalize)"""
+    R = np.asarray(R, np.float64)
+    if R[2, 2] < 0 and R[0, 0] > R[1, 1]:
+        s = 1.0 + R[0, 0] - R[1, 1] - R[2, 2]
+        q = np.array([R[1, 2] - R[2, 1], s, R[0, 1] + R[1, 0], R[2, 0] + R[0, 2]])
+    elif R[2, 2] < 0:
+        s = 1.0 - R[0, 0] + R[1, 1] - R[2, 2]
+        q = np.array([R[2, 0] - R[0, 2], R[0, 1] + R[1, 0], s, R[1, 2] + R[2, 1]])
+    elif R[0, 0] < -R[1, 1]:
+        s = 1.0 - R[0, 0] - R[1, 1] + R[2, 2]
+        q = np.array([R[0, 1] - R[1, 0], R[2, 0] + R[0, 2], R[1, 2] + R[2, 1], s])
+    else:
+        s = 1.0 + R[0, 0] + R[1, 1] + R[2, 2]
+        q = np.array([s, R[1, 2] - R[2, 1], R[2, 0] - R[0, 2], R[0, 1] - R[1, 0]])
+    q = q * 0.5 / math.sqrt(s)
+    return q / max(math.sqrt(float((q * q).sum())), 1e-12)
+
+
+def quat_branch(R):
+    """which of SO3_to_quat's four branches a matrix takes (1..4, the reference's numbering)"""
+    if R[2, 2] < 0:
+        return 1 if R[0, 0] > R[1, 1] else 2
+    return 3 if R[0, 0] < -R[1, 1] else 4
+
+
+def pose_errors(R_est, t_est, R_gt, t_gt, valid=None):
+    """(theta_deg f32 [B], dist f64 [B]); rows with valid == 0 are NaN"""
+    B = len(R_est)
+    theta, dist = np.full(B, np.nan, np.float32), np.full(B, np.nan, np.float64)
+    lim = np.float32(1.0 - 1e-7)
+    for b in range(B):
+        if valid is not None and not valid[b]:
+            continue
+        qg, qe = so3_to_quat(R_gt[b]).astype(np.float32), so3_to_quat(R_est[b]).astype(np.float32)
+        d = np.float32(0)
+        for i in range(4):
+            d = np.float32(d + qg[i] * qe[i])
+        d = min(np.float32(abs(d)), lim)
+        theta[b] = np.float32(np.float32(np.float32(2) * np.arccos(d)) * np.float32(180)) / np.float32(math.pi)
+        e = np.asarray(t_est[b], np.float64) - np.asarray(t_gt[b], np.float64)
+        dist[b] = math.sqrt(float((e * e).sum()))
+    return theta, dist
+
+
+def theta_bound(theta_ref):
+    """|theta - theta_ref| allowed between two conforming implementations: twelve f32 roundings of d (six each: two rounded
+    unit quaternions and a four-term dot) through the slope of acos, plus the ulps of acos itself"""
+    t = np.maximum(np.asarray(theta_ref, np.float64), 0.05595)
+    return (360 / math.pi) * 12 * 2.0 ** -24 / np.sin(np.radians(t) / 2) + 1e-5 * np.asarray(theta_ref, np.float64)

@@ -32,6 +32,7 @@ WHAT = [   # (file name regex, description; {placeholders} are filled by the ext
     (r"^decoder_time\.json$", "fused FeatureDecoder against the composed path (`tinycudann.Encoding` + torch layers + `torch.optim.Adam`), HIP events, interleaved regions (`tools/decoder_time.py`): {decoder}"),
     (r"^fusion_time\.json$", "feature-TSDF fusion at office_0's size (21.9 M voxels x 256 channels, 640 x 480 frames) against the same update composed from torch operators, HIP events, interleaved regions (`tools/fusion_timing.py`): {fusion}"),
     (r"^pnp_time\.json$", "absolute pose (`solve_pose`: P3P LO-RANSAC + Cauchy refinement) on planted scenes, HIP events (`tools/pnp_time.py`): {pnp}"),
+    (r"^localize_time\.json$", "localisation (`tools/localize_time.py`), HIP events, interleaved medians: fused retrieval against `torch.einsum(...).topk` and the batched `Localizer.localize` against the per-query loop: {localize}"),
     (r"^matching_time\.json$", "2D-3D matching (`hungarian_solve` cost + exact assignment, batched solver, frustum candidates) against torch-CPU + scipy on the same host, HIP events (`tools/matching_time.py`): {matching}"),
     (r"^landmark_selection_time\.json$", "landmark selection (`gaussian_selectition`) at Replica scale on a synthetic room, HIP events per stage (`tools/landmark_selection_time.py`): {landmark}"),
     (r"r\d+_scene_lists.*\.json$", "one `color_refinement` iteration on a RECONSTRUCTED room (list-length distribution, per-kernel table; `tools/scene_lists.py`; suffix = the forced variant): {scenelists}"),
@@ -220,6 +221,18 @@ def pnp(path):
     return ", ".join(parts) + f"; B = {b.get('B', '?')} batch {min(b.get('ms') or [0]):.1f} ms"
 
 
+def localize(path):
+    j = _load(path) or {}
+    rows = j.get("retrieval") or []
+    d = j.get("driver") or {}
+    if not rows or not d:
+        return "(no rows)"
+    parts = [f"Q = {r['Q']}, N = {r['N']}, D = {r['D']}, k = {r['k']}: {r['retrieve_ms']:.3f} ms vs torch {r['torch_einsum_topk_ms']:.3f} ms "
+             f"(workspace {r['workspace_bytes'] / 1e6:.2f} MB, matrix {r['similarity_matrix_bytes'] / 1e6:.1f} MB)" for r in rows]
+    return ("; ".join(parts) + f"; {d['queries']} queries on {d['frames']} frames: localize {d['localize_ms']:.0f} ms vs per-query loop "
+            f"{d['per_query_loop_ms']:.0f} ms ({d['ratio_loop_over_localize']:.2f} x), bit-identical {d['bit_identical_to_loop']}")
+
+
 def decoder(path):
     j = _load(path) or {}
     names = (("train_step_batch_256", "training step at batch 256"), ("inference_5000", "inference at N = 5 000"),
@@ -240,7 +253,7 @@ def fusion(path):
             f"torch composition {ms['torch']:.1f}")
 
 
-EXTRACT = {"scenelists": scenelists, "scene": scene, "ab": ab, "perview": perview, "mapidle": mapidle, "rccl": rccl, "kstats": kstats, "hbm": hbm, "sq": sq, "timeline": timeline, "bench": bench, "clocks": clocks, "gradbars": gradbars, "idle": idle, "landmark": landmark, "matching": matching, "pnp": pnp, "decoder": decoder, "fusion": fusion}
+EXTRACT = {"scenelists": scenelists, "scene": scene, "ab": ab, "perview": perview, "mapidle": mapidle, "rccl": rccl, "kstats": kstats, "hbm": hbm, "sq": sq, "timeline": timeline, "bench": bench, "clocks": clocks, "gradbars": gradbars, "idle": idle, "landmark": landmark, "matching": matching, "pnp": pnp, "decoder": decoder, "fusion": fusion, "localize": localize}
 
 
 def describe(name, path):
