@@ -262,6 +262,18 @@ composite_bwd_kernel(int W, int H, int C_total, int CP4, int c0, int first_pass,
     }
     // (the forward wrote C_total + 2 planes per checkpoint k, taken in front of list entry beg + (k + 1) part: T, its C_total
     //  colours so far, the depth so far — this pass may cover fewer channels)
+    // Leave early: this quadrant only needs the list up to its deepest contributor, and a quadrant without a list or
+    // without a contributor (empty regions of real frames, quadrants outside the image) has nothing to add — it returns
+    // here, before the set-up loads its NC + 3 planes.
+    uint32_t last = inside ? n_contrib[pix] : 0u;
+    uint32_t wave_last = last;
+#pragma unroll
+    for (int d = 1; d < WAVE; d <<= 1) wave_last = max(wave_last, (uint32_t)__shfl_xor((int)wave_last, d, WAVE));
+    uint32_t end = min(end0, list0 + wave_last);
+    // WIDE only: the value is wave-uniform after the reduction; said so, the list's end and the chunk counter derived from it
+    // live in scalar registers, which keeps the headline kernel <35> inside its 128-VGPR budget (tests/test_codegen_budget.py)
+    if constexpr (WIDE) end = (uint32_t)__builtin_amdgcn_readfirstlane((int)end);
+    if (beg >= end) return;   // (split launches: nothing of this part contributes)
     // per-pixel constants
     float g[NC];
     // state of the back-to-front walk: T = transmittance BEHIND the entry about to be processed, A = what lies behind it per
@@ -269,55 +281,81 @@ composite_bwd_kernel(int W, int H, int C_total, int CP4, int c0, int first_pass,
     ST A = 0;
     ST T = 1;
     float gD = 0.0f;
-    uint32_t last = 0;
     if (inside) {
-        last = n_contrib[pix];
         // a split launch's segment that ends in FRONT of this pixel's last contributor starts from the boundary state rebuilt
         // from the forward's segment records (common.h): T_b, and A_b = (what the later segments contribute) / T_b
         const bool from_ckpt = split && seg < np - 1 && list0 + last > end0;
         float s_end = 0.0f;
-        // planes [0, gc) behind dL_dcolor, the LAST channel's plane behind dL_dlast, nothing in between.  Branch-free on purpose:
-        // every channel loads from a valid address chosen by selects (plane 0 when the channel has no gradient) and the value
-        // is selected afterwards — with a branch per channel the set-up is 35 basic blocks and the compiler waits for every
-        // second load before issuing the next (seen in the .s: 21 x s_waitcnt vmcnt(0) between the plane loads, backward + 4 %).
-        float gvals[NC];
-#pragma unroll
-        for (int ch = 0; ch < NC; ++ch) {
-            const int c = c0 + ch;
-            const bool lastc = c == C_total - 1 && c >= gc && dL_dlast != nullptr;
-            const float* src = lastc ? dL_dlast : dL_dcolor + (size_t)(c < gc ? c : 0) * plane;
-            gvals[ch] = src[pix];
+        // planes [0, gc) behind dL_dcolor, the LAST channel's plane behind dL_dlast, nothing in between.  Which channel reads
+        // what is the same for every wave of the launch, so it is decided ONCE per wave by scalar compares and the planes are
+        // then walked with a pointer: a load and an add per channel.  (Until this form the source of every channel was selected
+        // on its own — a 64-bit multiply, two selects and spilled conditions per channel: ~1 300 scalar instructions per wave
+        // of the headline kernel)  The loads stay independent and in flight together: no branch BETWEEN them —
+        // with a branch per channel the compiler waits for every second load before issuing the next (seen in the .s: 21 x
+        // s_waitcnt vmcnt(0) between the plane loads, backward + 4 %).
+        // The pixel's other values are requested first and branch-free as well (an absent plane reads final_T and drops the
+        // value), so that they travel with the colour planes instead of one memory latency each behind them.
+        const float Tf = final_T[pix];
+        const bool has_gD = AUX && first_pass && dL_ddepth != nullptr, has_gA = AUX && first_pass && dL_dalpha != nullptr;
+        float vD = 0.0f, vA = 0.0f;
+        if constexpr (AUX) {
+            vD = (has_gD ? dL_ddepth : final_T)[pix];
+            vA = (has_gA ? dL_dalpha : final_T)[pix];
         }
+        const int cb = FIXED ? 0 : c0;                           // (the launcher enforces c0 == 0 for the headline kernel)
+        const int n_plain = min(max(gc - cb, 0), NC);            // channels [0, n_plain) of this pass have a plane behind dL_dcolor
+        // channel C_total - 1 travels apart when gc < C_total.  The passes of a launch tile [0, C) (launch_composite_bwd), so
+        // that channel is the LAST one of the pass that holds it
+        const bool last_apart = gc < C_total && cb + NC == C_total && dL_dlast != nullptr;
+        const float* const src0 = dL_dcolor + pix;               // plane 0: what a channel without a gradient reads (and drops)
+        const float* src = src0 + (size_t)(n_plain > 0 ? cb : 0) * plane;
+        if (n_plain >= NC - 1) {
+            // every channel is plain (the per-view drop-in, the benchmark), or all but the pass's last one (split_last = True)
 #pragma unroll
-        for (int ch = 0; ch < NC; ++ch) {
-            const int c = c0 + ch;
-            const bool take = c < gc || (c == C_total - 1 && dL_dlast != nullptr);
-            g[ch] = take ? gvals[ch] : 0.0f;
+            for (int ch = 0; ch < NC - 1; ++ch) {
+                g[ch] = *src;
+                src += plane;
+            }
+            const bool own = n_plain == NC;
+            const float v = *(own ? src : (last_apart ? dL_dlast + pix : src0));
+            g[NC - 1] = (own || last_apart) ? v : 0.0f;
+        } else {
+            // a few leading planes, zeros, then perhaps the plane that travels apart (the map step's split_last = 3 at C = 35;
+            // passes beyond gc): the walk stops at the last plain plane and the values behind it are dropped
+#pragma unroll
+            for (int ch = 0; ch < NC - 1; ++ch) {
+                const float v = *src;
+                g[ch] = ch < n_plain ? v : 0.0f;
+                src += ch + 1 < n_plain ? plane : (size_t)0;
+            }
+            const float v = *(last_apart ? dL_dlast + pix : src0);
+            g[NC - 1] = last_apart ? v : 0.0f;
         }
-        {   // s_end = bg . g: AFTER the plane loads and branch-free (clamped index + select) — a conditional scalar load inside the
-            // loop above put a branch between the plane loads and serialised them (measured: backward + 6 % on S2)
-            const float* bgp = grads.bg ? grads.bg : final_T_all;      // (any readable address; nb = 0 selects 0 below)
+        {   // s_end = bg . g over the background's entries that fall into this pass, in channel order (a term the old
+            // 35-way clamp-and-select form added for a channel beyond the background was fmaf(0, g, s) == s).  AFTER the plane
+            // loads: a conditional scalar load between them serialised them (measured: backward + 6 % on S2)
             const int nb = grads.bg ? grads.bg_channels : 0;
-            const int hi = nb > 0 ? nb - 1 : 0;
+            const float* __restrict__ bgp = grads.bg;
+            if (nb <= 4) {   // RGB (+ 1) backgrounds: at most the pass's first four channels
 #pragma unroll
-            for (int ch = 0; ch < NC; ++ch) {
-                const int c = c0 + ch;
-                const float b = bgp[c < hi ? c : hi];
-                s_end = fmaf(c < nb ? b : 0.0f, g[ch], s_end);
+                for (int ch = 0; ch < (NC < 4 ? NC : 4); ++ch)
+                    if (cb + ch < nb) s_end = fmaf(bgp[cb + ch], g[ch], s_end);
+            } else {
+#pragma unroll
+                for (int ch = 0; ch < NC; ++ch)
+                    if (cb + ch < nb) s_end = fmaf(bgp[cb + ch], g[ch], s_end);
             }
         }
-        float gA = 0.0f;
         if (AUX && first_pass) {
-            gD = dL_ddepth ? dL_ddepth[pix] : 0.0f;
-            gA = dL_dalpha ? dL_dalpha[pix] : 0.0f;
-            s_end -= gA;
+            gD = has_gD ? vD : 0.0f;
+            s_end -= has_gA ? vA : 0.0f;
         }
-        T = (ST)final_T[pix];
+        T = (ST)Tf;
         A = (ST)s_end;
         if constexpr (NC <= 4) {
             if (from_ckpt) {
                 // later segments first (the smallest contributions), this boundary's neighbour last
-                float sfx = final_T[pix] * s_end;
+                float sfx = Tf * s_end;
                 const float* rec0 = ckpt_all + (size_t)view * SPLIT_PARTS_MAX * (C_total + 2) * plane + pix;
                 for (int k = np - 1; k > seg; --k) {
                     const float* ck = rec0 + (size_t)k * (C_total + 2) * plane;
@@ -353,15 +391,6 @@ composite_bwd_kernel(int W, int H, int C_total, int CP4, int c0, int first_pass,
         }
         __builtin_amdgcn_wave_barrier();
     }
-    // this quadrant only needs the list up to its deepest contributor
-    uint32_t wave_last = last;
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) wave_last = max(wave_last, (uint32_t)__shfl_xor((int)wave_last, d, WAVE));
-    uint32_t end = min(end0, list0 + wave_last);
-    // WIDE only: the value is wave-uniform after the reduction; said so, the list's end and the chunk counter derived from it
-    // live in scalar registers, which keeps the headline kernel <35> inside its 128-VGPR budget (tests/test_codegen_budget.py)
-    if constexpr (WIDE) end = (uint32_t)__builtin_amdgcn_readfirstlane((int)end);
-    if (NC <= 4) { if (split && beg >= end) return; }   // nothing of this half contributes
 
     // wave_reduce_pack leaves total k in lane bitreverse6(k); values [0, KV) belong to the first
     // Gaussian of a pair, [KV, 2 KV) to the second; inside a Gaussian: NV colours then 7 geometric
@@ -462,7 +491,6 @@ composite_bwd_kernel(int W, int H, int C_total, int CP4, int c0, int first_pass,
     };
     // The list is walked from the quadrant's deepest contributor towards the camera, 64 entries at a time (chunk k = entries
     // [beg + 64 k, beg + 64 k + 64)), the candidates of a chunk from the highest list position down.
-    if (beg >= end) return;
     const uint64_t gt_mask = (lane == WAVE - 1) ? 0ull : (~0ull << (lane + 1));   // list positions behind this lane's
     const int nchunks = (int)((end - beg + (WAVE - 1)) / WAVE);
     fetch(beg + (uint32_t)(nchunks - 1) * WAVE, pw);
@@ -769,7 +797,10 @@ int launch_composite_bwd(const splatraster_settings& s, int32_t P, int32_t V, in
         any_last = any_last || grads.dL_dlast[v] != nullptr;
         any_aux = any_aux || grads.dL_ddepth[v] != nullptr || grads.dL_dalpha[v] != nullptr;
     }
-    if (grads.gc < C && !any_last) C = grads.gc;
+    // (not in the deterministic mode: there the passes — and with them every rounding — do not depend on which outputs reached the
+    //  loss; the kernel reads the last channel as the zeros a null dL_dlast stands for, and a launch is bit-identical to the one
+    //  given the same gradient as full planes: tests/test_gpu_bwd_sources.py)
+    if (grads.gc < C && !any_last && !det) C = grads.gc;
     if (C == 3 && !any_aux && !det)   // (the panel variant of this kernel measured equal at 640x480: 0.752 vs 0.760 ms per refinement iteration)
         return launch_one_bwd<3, false, false>(s, 0, 1, g, b, im, feat, feat_stride, L, gacc, gacc64, stream);
 #define SR_BWD_ARGS g, b, im, feat, feat_stride, L, gacc, gacc64, stream

@@ -44,6 +44,10 @@ WHAT = [   # (file name regex, description; {placeholders} are filled by the ext
     (r"r\d+_map_idle.*\.json$", "live GPU idle and raster / non-raster kernel split of one `training.map_step` (`tools/map_idle.py`): {mapidle}"),
     (r"r\d+_rccl_contact\.json$", "`tools/rccl_contact.py` on one MI355X: a world-size-1 `nccl` (RCCL) process group drives every collective call of the frame-parallel path (in-place span SUM, MAX, reduce-scatter + all-gather, header, broadcast_model): {rccl}"),
     (r"r\d+_bench_force_process_group.*\.json$", "`bench.py --gpus 1 --force-process-group`: the BASELINE step with its collectives issued on a world-size-1 RCCL group: {bench}"),
+    (r"^bwd_setup_isa\.txt$", "set-up of one quadrant wave of the headline backward, parent against the pointer-walk form (DESIGN §13.8): instruction classes per basic block in front of the chunk loop (`tools/isa_blocks.py` on `hipcc -S`), the compiler's resource report"),
+    (r"^bwd_setup_pmc\.json$", "`rocprofv3 --pmc SQ_INSTS_SALU SQ_INSTS_VALU SQ_WAVES` of the headline backward per launch, parent against the change, one run each: {setup_pmc}"),
+    (r"^bwd_setup_kernel_stats\.txt$", "`rocprofv3 --kernel-trace --stats` of the default bench, parent (first listing) and change (second): {kstats2}"),
+    (r"^bwd_setup_ab\.json$", "`tools/ab.py`, base = the change, variant `parent` = the parent commit's library (differences are parent minus change): {ab}; {setup_ab}"),
     (r"traffic\.json$", "per-stage HBM bytes per launch that `bench.py` replays as `roofline.traffic` (recorded workload / launch mode inside)"),
     (r"valu\.json$", "VALU / MFMA / SALU wave-instructions, busy fractions of the two compositing kernels per launch (replayed by `bench.py` as `frame_valu` / `roofline_valu`)"),
     (r"r01_v1_first_.*", "round 1: the first correct pipeline (per-value DPP reductions, no reach masks)"),
@@ -253,7 +257,26 @@ def fusion(path):
             f"torch composition {ms['torch']:.1f}")
 
 
-EXTRACT = {"scenelists": scenelists, "scene": scene, "ab": ab, "perview": perview, "mapidle": mapidle, "rccl": rccl, "kstats": kstats, "hbm": hbm, "sq": sq, "timeline": timeline, "bench": bench, "clocks": clocks, "gradbars": gradbars, "idle": idle, "landmark": landmark, "matching": matching, "pnp": pnp, "decoder": decoder, "fusion": fusion, "localize": localize}
+def setup_pmc(path):
+    j = _load(path) or {}
+    return "; ".join(f"{c} {j['parent'][c] / 1e6:.1f} M -> {j['change'][c] / 1e6:.1f} M ({j['delta_per_wave'][c]:+.0f} per wave)"
+                     for c in ("SQ_INSTS_SALU", "SQ_INSTS_VALU"))
+
+
+def kstats2(path):
+    rows = [ln.split() for ln in open(path) if ln.startswith("composite_bwd_kernel<35")]
+    return "`composite_bwd_kernel<35>` " + " -> ".join(f"{float(r[-6]):.2f}" for r in rows) + " us avg"
+
+
+def setup_ab(path):
+    c = (_load(path) or {})["change_vs_parent"]
+    k = c["bwd_kcycles_ms_x_mhz"]
+    return (f"change minus parent {c['fps_diff_pct_of_parent_mean']['mean']:+.2f} % of the parent's frames/s (CI "
+            f"{c['fps_diff_pct_of_parent_mean']['ci95'][0]:+.2f} .. {c['fps_diff_pct_of_parent_mean']['ci95'][1]:+.2f} %), backward "
+            f"{c['bwd_ms']['parent']:.4f} -> {c['bwd_ms']['change']:.4f} ms, ms x MHz {k['parent']['mean']:.0f} -> {k['change']['mean']:.0f}")
+
+
+EXTRACT = {"setup_pmc": setup_pmc, "kstats2": kstats2, "setup_ab": setup_ab, "scenelists": scenelists, "scene": scene, "ab": ab, "perview": perview, "mapidle": mapidle, "rccl": rccl, "kstats": kstats, "hbm": hbm, "sq": sq, "timeline": timeline, "bench": bench, "clocks": clocks, "gradbars": gradbars, "idle": idle, "landmark": landmark, "matching": matching, "pnp": pnp, "decoder": decoder, "fusion": fusion, "localize": localize}
 
 
 def describe(name, path):
