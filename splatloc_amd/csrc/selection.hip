@@ -27,7 +27,9 @@ constexpr int SEL_THREADS = 256;
 constexpr int SEL_VIEW_CHUNK = 64;
 constexpr int SEL_RESOLVE_THREADS = 1024;
 constexpr int SEL_RESOLVE_WAVES = SEL_RESOLVE_THREADS / WAVE;
-constexpr int SEL_LDS_LANDMARKS = 4096;   // landmarks of the current pass kept in LDS by the resolve kernel (48 KB)
+// landmarks of the current pass kept in LDS by the resolve kernel: 4096 float4 = 64 KB.  With the 1024 candidates (16 KB)
+// and the ballot masks (256 B) sel_resolve_kernel holds 82 176 B of static LDS; later landmarks are read from global memory
+constexpr int SEL_LDS_LANDMARKS = 4096;
 constexpr int SEL_JACOBI_SWEEPS = 16;      // cyclic Jacobi on 3x3 converges in <= 6 sweeps in f64; hard bound
 constexpr int SEL_MAX_PASSES = 1100;       // 18 * 2^-1100 == 0 in f64: the radius has underflowed long before
 
