@@ -260,6 +260,11 @@ activate_bwd_kernel(int P, int K, int deg, int SC, int E, const float* __restric
     }
 }
 
+struct StatsViews {
+    const float* vs_grad[MAX_VIEWS];   // [P,3] per view (unused when accum == null)
+    const int32_t* radii[MAX_VIEWS];   // [P] per view
+};
+
 // Per-view densification statistics, in place, one launch and no host round trip (the reference
 // indexes with boolean masks, i.e. a nonzero + device->host sync per statement):
 //   vis = radii > 0
@@ -293,7 +298,7 @@ densification_stats_kernel(int P, int V, StatsViews views, float* __restrict__ a
     }
 }
 
-int launch_densification_stats(int32_t P, int32_t V, const StatsViews& views, float* accum, float* denom,
+static int launch_densification_stats(int32_t P, int32_t V, const StatsViews& views, float* accum, float* denom,
                                float* max_radii, hipStream_t stream)
 {
     if (P == 0 || V == 0) return SPLATRASTER_OK;
@@ -303,7 +308,7 @@ int launch_densification_stats(int32_t P, int32_t V, const StatsViews& views, fl
     return SPLATRASTER_OK;
 }
 
-int launch_activate_fwd(int32_t P, int32_t K, int32_t deg, int32_t SC, int32_t E, const float* xyz,
+static int launch_activate_fwd(int32_t P, int32_t K, int32_t deg, int32_t SC, int32_t E, const float* xyz,
                         const float* f_dc, const float* f_rest, const float* scaling, const float* rotation,
                         const float* opacity, const float* extra, const float* campos, float* scales,
                         float* rotations, float* opacities, float* colors, hipStream_t stream)
@@ -318,7 +323,7 @@ int launch_activate_fwd(int32_t P, int32_t K, int32_t deg, int32_t SC, int32_t E
     return SPLATRASTER_OK;
 }
 
-int launch_activate_bwd(int32_t P, int32_t K, int32_t deg, int32_t SC, int32_t E, const float* xyz,
+static int launch_activate_bwd(int32_t P, int32_t K, int32_t deg, int32_t SC, int32_t E, const float* xyz,
                         const float* f_dc, const float* f_rest, const float* scaling, const float* rotation,
                         const float* opacity, const float* campos, const float* g_scales,
                         const float* g_rotations, const float* g_opacities, const float* g_colors, float* d_xyz,
@@ -336,3 +341,86 @@ int launch_activate_bwd(int32_t P, int32_t K, int32_t deg, int32_t SC, int32_t E
 }
 
 }  // namespace sr
+
+using namespace sr;
+
+extern "C" {
+
+static int check_activate(int32_t P, int32_t K, int32_t deg, int32_t SC, int32_t E, const void* f_rest,
+                          const void* extra)
+{
+    if (P < 0 || K < 1 || deg < 0 || E < 0) return SPLATRASTER_ERR_BAD_ARG;
+    if (deg > 3) return SPLATRASTER_ERR_UNSUPPORTED;
+    if ((deg + 1) * (deg + 1) > K) return SPLATRASTER_ERR_BAD_ARG;
+    if (SC != 1 && SC != 3) return SPLATRASTER_ERR_BAD_ARG;
+    if (P > 0 && K > 1 && !f_rest) return SPLATRASTER_ERR_BAD_ARG;
+    if (P > 0 && E > 0 && !extra) return SPLATRASTER_ERR_BAD_ARG;
+    return SPLATRASTER_OK;
+}
+
+int splatraster_activate_forward(int32_t P, int32_t sh_coeffs, int32_t active_sh_degree, int32_t scaling_cols,
+                                 int32_t extras, const float* xyz, const float* f_dc, const float* f_rest,
+                                 const float* scaling, const float* rotation, const float* opacity,
+                                 const float* extra, const float* campos, float* scales, float* rotations,
+                                 float* opacities, float* colors, void* stream)
+{
+    int st = check_activate(P, sh_coeffs, active_sh_degree, scaling_cols, extras, f_rest, extra);
+    if (st) return st;
+    if (P == 0) return SPLATRASTER_OK;
+    if (!xyz || !f_dc || !scaling || !rotation || !opacity || !scales || !rotations || !opacities || !colors)
+        return SPLATRASTER_ERR_BAD_ARG;
+    if (active_sh_degree > 0 && !campos) return SPLATRASTER_ERR_BAD_ARG;
+    return launch_activate_fwd(P, sh_coeffs, active_sh_degree, scaling_cols, extras, xyz, f_dc, f_rest, scaling,
+                               rotation, opacity, extra, campos, scales, rotations, opacities, colors,
+                               reinterpret_cast<hipStream_t>(stream));
+}
+
+int splatraster_activate_backward(int32_t P, int32_t sh_coeffs, int32_t active_sh_degree, int32_t scaling_cols,
+                                  int32_t extras, const float* xyz, const float* f_dc, const float* f_rest,
+                                  const float* scaling, const float* rotation, const float* opacity,
+                                  const float* campos, const float* dL_dscales, const float* dL_drotations,
+                                  const float* dL_dopacities, const float* dL_dcolors, float* dL_dxyz,
+                                  float* dL_df_dc, float* dL_df_rest, float* dL_dscaling, float* dL_drotation,
+                                  float* dL_dopacity, float* dL_dextra, void* stream)
+{
+    int st = check_activate(P, sh_coeffs, active_sh_degree, scaling_cols, extras, f_rest, dL_dextra);
+    if (st) return st;
+    if (P == 0) return SPLATRASTER_OK;
+    if (!xyz || !f_dc || !scaling || !rotation || !opacity || !dL_dscales || !dL_drotations || !dL_dopacities ||
+        !dL_dcolors || !dL_df_dc || !dL_dscaling || !dL_drotation || !dL_dopacity)
+        return SPLATRASTER_ERR_BAD_ARG;
+    if (sh_coeffs > 1 && !dL_df_rest) return SPLATRASTER_ERR_BAD_ARG;
+    if (active_sh_degree > 0 && !campos) return SPLATRASTER_ERR_BAD_ARG;
+    return launch_activate_bwd(P, sh_coeffs, active_sh_degree, scaling_cols, extras, xyz, f_dc, f_rest, scaling,
+                               rotation, opacity, campos, dL_dscales, dL_drotations, dL_dopacities, dL_dcolors,
+                               dL_dxyz, dL_df_dc, dL_df_rest, dL_dscaling, dL_drotation, dL_dopacity, dL_dextra,
+                               reinterpret_cast<hipStream_t>(stream));
+}
+
+int splatraster_densification_stats(int32_t P, const float* viewspace_grad, const int32_t* radii,
+                                    float* xyz_gradient_accum, float* denom, float* max_radii2D, void* stream)
+{
+    const float* g[1] = {viewspace_grad};
+    const int32_t* r[1] = {radii};
+    return splatraster_densification_stats_window(P, 1, g, r, xyz_gradient_accum, denom, max_radii2D, stream);
+}
+
+int splatraster_densification_stats_window(int32_t P, int32_t n_views, const float* const* viewspace_grads,
+                                           const int32_t* const* radii, float* xyz_gradient_accum, float* denom,
+                                           float* max_radii2D, void* stream)
+{
+    if (P < 0 || n_views < 0 || n_views > MAX_VIEWS) return SPLATRASTER_ERR_BAD_ARG;
+    if (P == 0 || n_views == 0) return SPLATRASTER_OK;
+    if (!radii || !max_radii2D || (xyz_gradient_accum == nullptr) != (denom == nullptr)) return SPLATRASTER_ERR_BAD_ARG;
+    if (xyz_gradient_accum && !viewspace_grads) return SPLATRASTER_ERR_BAD_ARG;
+    StatsViews sv{};
+    for (int v = 0; v < n_views; ++v) {
+        if (!radii[v] || (xyz_gradient_accum && !viewspace_grads[v])) return SPLATRASTER_ERR_BAD_ARG;
+        sv.radii[v] = radii[v];
+        sv.vs_grad[v] = viewspace_grads ? viewspace_grads[v] : nullptr;
+    }
+    return launch_densification_stats(P, n_views, sv, xyz_gradient_accum, denom, max_radii2D,
+                                      reinterpret_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"

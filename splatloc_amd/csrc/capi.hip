@@ -1,5 +1,7 @@
-// capi.hip — the C ABI declared in include/splatraster.h: buffer layouts, argument
-// validation and stage sequencing.  No torch types; everything is raw device pointers.
+// capi.hip — the raster part of the C ABI declared in include/splatraster.h: buffer layouts, the per-view / window / raw
+// raster pipeline (argument validation and stage sequencing), the sort and timing entry points, error strings and polling,
+// and the raster debug hooks.  Every other stage defines its splatraster_* / splatknn_* entry points in an extern "C" block
+// at the end of its own .hip (densify.hip, matching.hip, ...).  No torch types; everything is raw device pointers.
 #include <string.h>
 
 #include <mutex>
@@ -948,359 +950,6 @@ int splatraster_timing_collect(double* ms, int64_t* counts)
     }
     g_recs.clear();
     return SPLATRASTER_OK;
-}
-
-size_t splatknn_workspace_bytes(int32_t N) { return knn_workspace_bytes(N); }
-
-static int check_activate(int32_t P, int32_t K, int32_t deg, int32_t SC, int32_t E, const void* f_rest,
-                          const void* extra)
-{
-    if (P < 0 || K < 1 || deg < 0 || E < 0) return SPLATRASTER_ERR_BAD_ARG;
-    if (deg > 3) return SPLATRASTER_ERR_UNSUPPORTED;
-    if ((deg + 1) * (deg + 1) > K) return SPLATRASTER_ERR_BAD_ARG;
-    if (SC != 1 && SC != 3) return SPLATRASTER_ERR_BAD_ARG;
-    if (P > 0 && K > 1 && !f_rest) return SPLATRASTER_ERR_BAD_ARG;
-    if (P > 0 && E > 0 && !extra) return SPLATRASTER_ERR_BAD_ARG;
-    return SPLATRASTER_OK;
-}
-
-int splatraster_activate_forward(int32_t P, int32_t sh_coeffs, int32_t active_sh_degree, int32_t scaling_cols,
-                                 int32_t extras, const float* xyz, const float* f_dc, const float* f_rest,
-                                 const float* scaling, const float* rotation, const float* opacity,
-                                 const float* extra, const float* campos, float* scales, float* rotations,
-                                 float* opacities, float* colors, void* stream)
-{
-    int st = check_activate(P, sh_coeffs, active_sh_degree, scaling_cols, extras, f_rest, extra);
-    if (st) return st;
-    if (P == 0) return SPLATRASTER_OK;
-    if (!xyz || !f_dc || !scaling || !rotation || !opacity || !scales || !rotations || !opacities || !colors)
-        return SPLATRASTER_ERR_BAD_ARG;
-    if (active_sh_degree > 0 && !campos) return SPLATRASTER_ERR_BAD_ARG;
-    return launch_activate_fwd(P, sh_coeffs, active_sh_degree, scaling_cols, extras, xyz, f_dc, f_rest, scaling,
-                               rotation, opacity, extra, campos, scales, rotations, opacities, colors,
-                               reinterpret_cast<hipStream_t>(stream));
-}
-
-int splatraster_activate_backward(int32_t P, int32_t sh_coeffs, int32_t active_sh_degree, int32_t scaling_cols,
-                                  int32_t extras, const float* xyz, const float* f_dc, const float* f_rest,
-                                  const float* scaling, const float* rotation, const float* opacity,
-                                  const float* campos, const float* dL_dscales, const float* dL_drotations,
-                                  const float* dL_dopacities, const float* dL_dcolors, float* dL_dxyz,
-                                  float* dL_df_dc, float* dL_df_rest, float* dL_dscaling, float* dL_drotation,
-                                  float* dL_dopacity, float* dL_dextra, void* stream)
-{
-    int st = check_activate(P, sh_coeffs, active_sh_degree, scaling_cols, extras, f_rest, dL_dextra);
-    if (st) return st;
-    if (P == 0) return SPLATRASTER_OK;
-    if (!xyz || !f_dc || !scaling || !rotation || !opacity || !dL_dscales || !dL_drotations || !dL_dopacities ||
-        !dL_dcolors || !dL_df_dc || !dL_dscaling || !dL_drotation || !dL_dopacity)
-        return SPLATRASTER_ERR_BAD_ARG;
-    if (sh_coeffs > 1 && !dL_df_rest) return SPLATRASTER_ERR_BAD_ARG;
-    if (active_sh_degree > 0 && !campos) return SPLATRASTER_ERR_BAD_ARG;
-    return launch_activate_bwd(P, sh_coeffs, active_sh_degree, scaling_cols, extras, xyz, f_dc, f_rest, scaling,
-                               rotation, opacity, campos, dL_dscales, dL_drotations, dL_dopacities, dL_dcolors,
-                               dL_dxyz, dL_df_dc, dL_df_rest, dL_dscaling, dL_drotation, dL_dopacity, dL_dextra,
-                               reinterpret_cast<hipStream_t>(stream));
-}
-
-int splatraster_densification_stats(int32_t P, const float* viewspace_grad, const int32_t* radii,
-                                    float* xyz_gradient_accum, float* denom, float* max_radii2D, void* stream)
-{
-    const float* g[1] = {viewspace_grad};
-    const int32_t* r[1] = {radii};
-    return splatraster_densification_stats_window(P, 1, g, r, xyz_gradient_accum, denom, max_radii2D, stream);
-}
-
-int splatraster_densification_stats_window(int32_t P, int32_t n_views, const float* const* viewspace_grads,
-                                           const int32_t* const* radii, float* xyz_gradient_accum, float* denom,
-                                           float* max_radii2D, void* stream)
-{
-    if (P < 0 || n_views < 0 || n_views > MAX_VIEWS) return SPLATRASTER_ERR_BAD_ARG;
-    if (P == 0 || n_views == 0) return SPLATRASTER_OK;
-    if (!radii || !max_radii2D || (xyz_gradient_accum == nullptr) != (denom == nullptr)) return SPLATRASTER_ERR_BAD_ARG;
-    if (xyz_gradient_accum && !viewspace_grads) return SPLATRASTER_ERR_BAD_ARG;
-    StatsViews sv{};
-    for (int v = 0; v < n_views; ++v) {
-        if (!radii[v] || (xyz_gradient_accum && !viewspace_grads[v])) return SPLATRASTER_ERR_BAD_ARG;
-        sv.radii[v] = radii[v];
-        sv.vs_grad[v] = viewspace_grads ? viewspace_grads[v] : nullptr;
-    }
-    return launch_densification_stats(P, n_views, sv, xyz_gradient_accum, denom, max_radii2D,
-                                      reinterpret_cast<hipStream_t>(stream));
-}
-
-size_t splatraster_mapping_loss_workspace_bytes(int32_t pixels) { return mapping_loss_workspace_bytes(pixels); }
-
-int splatraster_mapping_loss(int32_t pixels, const float* image, const float* depth, const float* marker,
-                             const float* gt_image, const float* gt_depth, const float* kp,
-                             float rgb_boundary_threshold, const float* exposure, float* g_image, float* g_depth,
-                             float* g_marker, float* out, void* workspace, void* stream)
-{
-    if (pixels <= 0) return SPLATRASTER_ERR_BAD_ARG;
-    if (!image || !depth || !marker || !gt_image || !gt_depth || !kp || !g_image || !g_depth || !g_marker || !out ||
-        !workspace)
-        return SPLATRASTER_ERR_BAD_ARG;
-    return launch_mapping_loss(pixels, image, depth, marker, gt_image, gt_depth, kp, rgb_boundary_threshold, exposure,
-                               g_image, g_depth, g_marker, out, workspace, reinterpret_cast<hipStream_t>(stream));
-}
-
-int splatraster_mapping_loss_window(int32_t n_views, int32_t pixels, const splatraster_loss_view* views,
-                                    float rgb_boundary_threshold, float* out, void* workspace, void* stream)
-{
-    if (pixels <= 0 || n_views < 1 || n_views > SPLATRASTER_MAX_WINDOW_VIEWS || !views || !out || !workspace)
-        return SPLATRASTER_ERR_BAD_ARG;
-    for (int v = 0; v < n_views; ++v) {
-        const splatraster_loss_view& w = views[v];
-        if (!w.image || !w.depth || !w.marker || !w.gt_image || !w.gt_depth || !w.kp || !w.g_image || !w.g_depth || !w.g_marker)
-            return SPLATRASTER_ERR_BAD_ARG;
-    }
-    return launch_mapping_loss_window(n_views, pixels, views, rgb_boundary_threshold, out, workspace,
-                                      reinterpret_cast<hipStream_t>(stream));
-}
-
-size_t splatraster_refinement_loss_workspace_bytes(int32_t channels, int32_t height, int32_t width)
-{
-    if (channels <= 0 || height <= 0 || width <= 0) return 0;
-    return refinement_loss_workspace_bytes(channels, height, width);
-}
-
-int splatraster_refinement_loss(int32_t channels, int32_t height, int32_t width, float lambda_dssim,
-                                const float* image, const float* gt, float* g_image, float* out, void* workspace,
-                                void* stream)
-{
-    if (channels <= 0 || height <= 0 || width <= 0) return SPLATRASTER_ERR_BAD_ARG;
-    if (!image || !gt || !g_image || !out || !workspace) return SPLATRASTER_ERR_BAD_ARG;
-    return launch_refinement_loss(channels, height, width, lambda_dssim, image, gt, g_image, out, workspace,
-                                  reinterpret_cast<hipStream_t>(stream));
-}
-
-size_t splatraster_eval_metrics_workspace_bytes(int32_t channels, int32_t height, int32_t width)
-{
-    if (channels <= 0 || height <= 0 || width <= 0) return 0;
-    return eval_metrics_workspace_bytes(channels, height, width);
-}
-
-int splatraster_eval_metrics(int32_t channels, int32_t height, int32_t width, const float* render, const float* gt, float* out,
-                             void* workspace, void* stream)
-{
-    if (channels <= 0 || height <= 0 || width <= 0) return SPLATRASTER_ERR_BAD_ARG;
-    if (!render || !gt || !out || !workspace) return SPLATRASTER_ERR_BAD_ARG;
-    return launch_eval_metrics(channels, height, width, render, gt, out, workspace, reinterpret_cast<hipStream_t>(stream));
-}
-
-int splatraster_l1_rgbd_loss(int64_t n_color, const float* color, const float* target_color, int64_t n_depth, const float* depth,
-                             const float* target_depth, float depth_weight, float* g_color, float* g_depth, float* loss_out,
-                             void* stream)
-{
-    if (n_color <= 0 || n_depth < 0) return SPLATRASTER_ERR_BAD_ARG;
-    if (!color || !target_color || !g_color || !loss_out) return SPLATRASTER_ERR_BAD_ARG;
-    if (n_depth > 0 && target_depth && !depth) return SPLATRASTER_ERR_BAD_ARG;
-    return launch_l1_rgbd_loss(n_color, color, target_color, n_depth, depth, target_depth, depth_weight, g_color, g_depth, loss_out,
-                               reinterpret_cast<hipStream_t>(stream));
-}
-
-int splatraster_pose_step(const float* dL_dviewmatrix, const float* dL_dprojmatrix, const float* dL_dcampos, const float* W2C_init,
-                          const float* projection_matrix, float lr_rot, float lr_trans, float beta1, float beta2, float eps,
-                          int advance, float* state, float* viewmatrix, float* projmatrix, float* campos, void* stream)
-{
-    if (!W2C_init || !projection_matrix || !state || !viewmatrix || !projmatrix) return SPLATRASTER_ERR_BAD_ARG;
-    if (advance && (!dL_dviewmatrix || !dL_dprojmatrix)) return SPLATRASTER_ERR_BAD_ARG;
-    return launch_pose_step(dL_dviewmatrix, dL_dprojmatrix, dL_dcampos, W2C_init, projection_matrix, lr_rot, lr_trans, beta1, beta2,
-                            eps, advance, state, viewmatrix, projmatrix, campos, reinterpret_cast<hipStream_t>(stream));
-}
-
-int splatknn_debug_set_grid_min(int32_t n)
-{
-    knn_set_grid_min(n);
-    return SPLATRASTER_OK;
-}
-
-int splatknn_dist2(int32_t N, const float* points, float* out, void* workspace, void* stream)
-{
-    if (N < 0) return SPLATRASTER_ERR_BAD_ARG;
-    if (N == 0) return SPLATRASTER_OK;
-    if (!points || !out || !workspace) return SPLATRASTER_ERR_BAD_ARG;
-    return knn_dist2(N, points, out, workspace, reinterpret_cast<hipStream_t>(stream));
-}
-
-int splatraster_grid_encoding_layout(int32_t n_dims, int32_t n_levels, int32_t n_features, int32_t log2_hashmap_size,
-                                     int32_t base_resolution, double per_level_scale, int32_t grid_type, splatraster_grid_layout* out)
-{
-    return grid_layout(n_dims, n_levels, n_features, log2_hashmap_size, base_resolution, per_level_scale, grid_type, out);
-}
-
-int splatraster_grid_encoding_forward(const splatraster_grid_layout* layout, int64_t N, const float* x, const float* params,
-                                      float* out, void* stream)
-{
-    return grid_forward(layout, N, x, params, out, reinterpret_cast<hipStream_t>(stream));
-}
-
-int splatraster_grid_encoding_backward(const splatraster_grid_layout* layout, int64_t N, const float* x, const float* params,
-                                       const float* dL_dout, float* dL_dparams, float* dL_dx, void* stream)
-{
-    return grid_backward(layout, N, x, params, dL_dout, dL_dparams, dL_dx, reinterpret_cast<hipStream_t>(stream));
-}
-
-int splatraster_decoder_workspace_bytes(const splatraster_decoder_layout* layout, int64_t N, size_t* workspace_bytes,
-                                        size_t* activation_bytes)
-{
-    return decoder_workspace_bytes(layout, N, workspace_bytes, activation_bytes);
-}
-
-int splatraster_decoder_forward(const splatraster_decoder_layout* layout, int64_t N, const void* x, int32_t x_is_f64,
-                                const float* table, const float* const* weights, float* out, float* activations, void* stream)
-{
-    return decoder_forward(layout, N, x, x_is_f64, table, weights, out, activations, reinterpret_cast<hipStream_t>(stream));
-}
-
-int splatraster_decoder_backward(const splatraster_decoder_layout* layout, int64_t N, const float* table,
-                                 const float* const* weights, const float* activations, const float* dL_dout, const float* targets,
-                                 float* loss, float* dL_dweights, float* dL_dtable, float* dL_dx, void* workspace, void* stream)
-{
-    return decoder_backward(layout, N, table, weights, activations, dL_dout, targets, loss, dL_dweights, dL_dtable, dL_dx, workspace,
-                            reinterpret_cast<hipStream_t>(stream));
-}
-
-int splatraster_decoder_adam(const splatraster_decoder_layout* layout, float* const* weights, float* w_grad, float* w_m, float* w_v,
-                             float* table, float* t_grad, float* t_m, float* t_v, int64_t step, double lr_weights, double lr_table,
-                             double beta1, double beta2, double eps_weights, double eps_table, double weight_decay, void* stream)
-{
-    return decoder_adam(layout, weights, w_grad, w_m, w_v, table, t_grad, t_m, t_v, step, lr_weights, lr_table, beta1, beta2,
-                        eps_weights, eps_table, weight_decay, reinterpret_cast<hipStream_t>(stream));
-}
-
-int splatraster_landmark_scores(int64_t N, int32_t M, const float* points, const float* w2c, const double* K,
-                                const float* depths, int32_t width, int32_t height, int32_t* n_visible, int32_t* n_depth,
-                                double* depth_mean, double* depth_std, double* span, double* score, void* stream)
-{
-    return landmark_scores(N, M, points, w2c, K, depths, width, height, n_visible, n_depth, depth_mean, depth_std, span, score,
-                           reinterpret_cast<hipStream_t>(stream));
-}
-
-size_t splatraster_landmark_workspace_bytes(int64_t N, int32_t num) { return landmark_workspace_bytes(N, num); }
-
-int splatraster_landmark_select(int64_t N, const float* points, const double* score, int32_t num, double radius,
-                                int32_t* out_idx, int32_t* n_passes, void* workspace, void* stream)
-{
-    return landmark_select(N, points, score, num, radius, out_idx, n_passes, workspace, reinterpret_cast<hipStream_t>(stream));
-}
-
-int splatraster_fusion_bytes(int32_t X, int32_t Y, int32_t Z, int32_t feat_dim, size_t* volume_bytes, size_t* surface_bytes)
-{
-    return fusion_bytes(X, Y, Z, feat_dim, volume_bytes, surface_bytes);
-}
-
-int splatraster_fusion_integrate(const splatraster_fusion_volume* volume, int32_t F, int32_t H, int32_t W, const float* depth,
-                                 const float* color_im, const float* feat_im, const float* world2cam, const float* intrinsics,
-                                 float obs_weight, float sdf_trunc, void* stream)
-{
-    return fusion_integrate(volume, F, H, W, depth, color_im, feat_im, world2cam, intrinsics, obs_weight, sdf_trunc,
-                            reinterpret_cast<hipStream_t>(stream));
-}
-
-int splatraster_fusion_surface_count(const splatraster_fusion_volume* volume, int32_t use_level, float level, void* workspace,
-                                     int64_t* n_vertices, void* stream)
-{
-    return fusion_surface_count(volume, use_level, level, workspace, n_vertices, reinterpret_cast<hipStream_t>(stream));
-}
-
-int splatraster_fusion_surface_extract(const splatraster_fusion_volume* volume, const void* workspace, double voxel_size,
-                                       const double* origin, int64_t M, float* verts, double* points, int64_t* index,
-                                       uint8_t* colors, float* feats, void* stream)
-{
-    return fusion_surface_extract(volume, workspace, voxel_size, origin, M, verts, points, index, colors, feats,
-                                  reinterpret_cast<hipStream_t>(stream));
-}
-
-size_t splatraster_lsap_workspace_bytes(int32_t B, const splatraster_lsap_problem* problems)
-{
-    return lsap_workspace_bytes(B, problems);
-}
-
-int splatraster_lsap(int32_t B, const splatraster_lsap_problem* problems, const double* costs, int32_t maximize,
-                     int64_t* row_ind, int64_t* col_ind, int32_t* status, int32_t* steps, void* workspace, void* stream)
-{
-    return lsap_solve(B, problems, costs, maximize, row_ind, col_ind, status, steps, workspace,
-                      reinterpret_cast<hipStream_t>(stream));
-}
-
-int splatraster_debug_set_lsap_lds(int mode) { return lsap_set_lds(mode); }
-
-int splatraster_match_cost(int32_t D, int32_t N1, int32_t N2, const float* d1, const float* d2, float threshold, float* norms,
-                           double* cost, void* stream)
-{
-    return match_cost(D, N1, N2, d1, d2, threshold, norms, cost, reinterpret_cast<hipStream_t>(stream));
-}
-
-int splatraster_match_sims(int32_t D, int32_t N1, int32_t N2, const float* d1, const float* d2, const float* norms,
-                           float threshold, int64_t K, const int64_t* i1, const int64_t* i2, float* sims, void* stream)
-{
-    return match_sims(D, N1, N2, d1, d2, norms, threshold, K, i1, i2, sims, reinterpret_cast<hipStream_t>(stream));
-}
-
-size_t splatraster_frustum_workspace_bytes(int64_t N, int32_t width, int32_t height)
-{
-    return frustum_workspace_bytes(N, width, height);
-}
-
-int splatraster_frustum_candidates(int64_t N, const float* points, const float* marker, float marker_threshold, const double* w2c,
-                                   const double* K, int32_t width, int32_t height, const uint8_t* kp_mask, const float* depth,
-                                   const double* c2w, const double* kp_K, int32_t* out_idx, float* out_xyz, double* out_uv,
-                                   int64_t* out_count, void* workspace, void* stream)
-{
-    return frustum_candidates(N, points, marker, marker_threshold, w2c, K, width, height, kp_mask, depth, c2w, kp_K, out_idx,
-                              out_xyz, out_uv, out_count, workspace, reinterpret_cast<hipStream_t>(stream));
-}
-
-size_t splatraster_pnp_workspace_bytes(int32_t B, const splatraster_pnp_problem* problems, const splatraster_pnp_options* options)
-{
-    return pnp_workspace_bytes(B, problems, options);
-}
-
-int splatraster_pnp(int32_t B, const splatraster_pnp_problem* problems, const splatraster_pnp_options* options,
-                    const double* points2d, const double* points3d, double* R_out, double* t_out, int32_t* num_inliers,
-                    uint8_t* inlier_mask, int32_t* status, int32_t* trials, void* workspace, void* stream)
-{
-    return pnp_solve(B, problems, options, points2d, points3d, R_out, t_out, num_inliers, inlier_mask, status, trials, workspace,
-                     reinterpret_cast<hipStream_t>(stream));
-}
-
-int splatraster_pnp_hypotheses(int32_t B, const splatraster_pnp_problem* problems, const splatraster_pnp_options* options,
-                               int64_t trial0, int32_t ntrials, const double* points2d, const double* points3d, int32_t* samples,
-                               double* models, int32_t* nmodels, void* workspace, void* stream)
-{
-    return pnp_hypotheses(B, problems, options, trial0, ntrials, points2d, points3d, samples, models, nmodels, workspace,
-                          reinterpret_cast<hipStream_t>(stream));
-}
-
-int splatraster_pnp_score(int32_t B, const splatraster_pnp_problem* problems, const splatraster_pnp_options* options, int32_t M,
-                          const double* models, const double* points2d, const double* points3d, int32_t* count, double* sum,
-                          void* workspace, void* stream)
-{
-    return pnp_score(B, problems, options, M, models, points2d, points3d, count, sum, workspace,
-                     reinterpret_cast<hipStream_t>(stream));
-}
-
-size_t splatraster_retrieval_workspace_bytes(int64_t Q, int64_t N, int32_t D, int32_t k)
-{
-    return retrieval_workspace_bytes(Q, N, D, k);
-}
-
-int splatraster_retrieval_topk(int64_t Q, int64_t N, int32_t D, int32_t k, const float* query, const float* db, int64_t* idx,
-                               float* sims, int32_t* status, void* workspace, void* stream)
-{
-    return retrieval_topk(Q, N, D, k, query, db, idx, sims, status, workspace, reinterpret_cast<hipStream_t>(stream));
-}
-
-int splatraster_pose_errors(int64_t B, const double* R_est, const double* t_est, const double* R_gt, const double* t_gt,
-                            const uint8_t* valid, float* theta_deg, double* dist, void* stream)
-{
-    return pose_errors(B, R_est, t_est, R_gt, t_gt, valid, theta_deg, dist, reinterpret_cast<hipStream_t>(stream));
-}
-
-int splatraster_pose_invert(int64_t B, const double* R, const double* t, double* R_out, double* t_out, void* stream)
-{
-    return pose_invert(B, R, t, R_out, t_out, reinterpret_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

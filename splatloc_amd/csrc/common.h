@@ -383,119 +383,4 @@ int launch_composite_bwd(const splatraster_settings& s, int32_t P, int32_t V, in
 void set_small_panel_max_waves(int waves);
 int launch_fixed_to_float(int64_t n, const long long* src, float* dst, int headroom_drop /*gacc_det_headroom_drop*/, hipStream_t stream);
 
-int launch_activate_fwd(int32_t P, int32_t K, int32_t deg, int32_t SC, int32_t E, const float* xyz,
-                        const float* f_dc, const float* f_rest, const float* scaling, const float* rotation,
-                        const float* opacity, const float* extra, const float* campos, float* scales,
-                        float* rotations, float* opacities, float* colors, hipStream_t stream);
-int launch_activate_bwd(int32_t P, int32_t K, int32_t deg, int32_t SC, int32_t E, const float* xyz,
-                        const float* f_dc, const float* f_rest, const float* scaling, const float* rotation,
-                        const float* opacity, const float* campos, const float* g_scales,
-                        const float* g_rotations, const float* g_opacities, const float* g_colors, float* d_xyz,
-                        float* d_f_dc, float* d_f_rest, float* d_scaling, float* d_rotation, float* d_opacity,
-                        float* d_extra, hipStream_t stream);
-
-struct StatsViews {
-    const float* vs_grad[MAX_VIEWS];   // [P,3] per view (unused when accum == null)
-    const int32_t* radii[MAX_VIEWS];   // [P] per view
-};
-int launch_densification_stats(int32_t P, int32_t V, const StatsViews& views, float* accum /*or null*/,
-                               float* denom /*or null*/, float* max_radii, hipStream_t stream);
-size_t mapping_loss_workspace_bytes(int32_t HW);
-int launch_mapping_loss_window(int32_t V, int32_t HW, const splatraster_loss_view* views, float threshold, float* out,
-                               void* workspace, hipStream_t stream);
-int launch_mapping_loss(int32_t HW, const float* image, const float* depth, const float* marker,
-                        const float* gt_image, const float* gt_depth, const float* kp, float threshold,
-                        const float* exposure, float* g_image, float* g_depth, float* g_marker, float* out,
-                        void* workspace, hipStream_t stream);
-
-size_t refinement_loss_workspace_bytes(int32_t C, int32_t H, int32_t W);
-int launch_refinement_loss(int32_t C, int32_t H, int32_t W, float lambda, const float* image, const float* gt,
-                           float* g_image, float* out, void* workspace, hipStream_t stream);
-
-size_t eval_metrics_workspace_bytes(int32_t C, int32_t H, int32_t W);
-int launch_eval_metrics(int32_t C, int32_t H, int32_t W, const float* image, const float* gt, float* out, void* workspace,
-                        hipStream_t stream);
-
-int launch_l1_rgbd_loss(int64_t n_color, const float* color, const float* tgt_c, int64_t n_depth, const float* depth,
-                        const float* tgt_d, float depth_weight, float* g_color, float* g_depth, float* loss_out, hipStream_t stream);
-int launch_pose_step(const float* dL_dview, const float* dL_dproj, const float* dL_dcampos, const float* W2C0, const float* Pm,
-                     float lr_rot, float lr_trans, float beta1, float beta2, float eps, int advance, float* state, float* view_out,
-                     float* proj_out, float* campos_out, hipStream_t stream);
-
-int knn_dist2(int32_t N, const float* points, float* out, void* workspace, hipStream_t stream);
-size_t knn_workspace_bytes(int32_t N);
-void knn_set_grid_min(int n);
-
-// grid_encoding.hip (tinycudann.Encoding)
-int grid_layout(int32_t D, int32_t L, int32_t F, int32_t log2_T, int32_t base_res, double per_level_scale, int32_t grid_type,
-                splatraster_grid_layout* out);
-int grid_forward(const splatraster_grid_layout* lay, int64_t N, const float* x, const float* params, float* out, hipStream_t s);
-int grid_backward(const splatraster_grid_layout* lay, int64_t N, const float* x, const float* params, const float* dL_dout,
-                  float* dL_dparams, float* dL_dx, hipStream_t s);   // point count from which the exact grid search replaces the tiled brute force (< 0: default)
-
-// decoder.hip (fused FeatureDecoder: forward, backward, cosine loss, Adam)
-int decoder_workspace_bytes(const splatraster_decoder_layout* lay, int64_t N, size_t* workspace_bytes, size_t* activation_bytes);
-int decoder_forward(const splatraster_decoder_layout* lay, int64_t N, const void* x, int32_t x_is_f64, const float* table,
-                    const float* const* weights, float* out, float* acts, hipStream_t s);
-int decoder_backward(const splatraster_decoder_layout* lay, int64_t N, const float* table, const float* const* weights,
-                     const float* acts, const float* dL_dout, const float* targets, float* loss, float* dL_dweights,
-                     float* dL_dtable, float* dL_dx, void* workspace, hipStream_t s);
-int decoder_adam(const splatraster_decoder_layout* lay, float* const* weights, float* w_grad, float* w_m, float* w_v, float* table,
-                 float* t_grad, float* t_m, float* t_v, int64_t step, double lr_w, double lr_t, double beta1, double beta2,
-                 double eps_w, double eps_t, double weight_decay, hipStream_t s);
-
-// selection.hip (landmark selection)
-int landmark_scores(int64_t N, int32_t M, const float* points, const float* w2c, const double* K, const float* depths,
-                    int32_t width, int32_t height, int32_t* n_visible, int32_t* n_depth, double* depth_mean,
-                    double* depth_std, double* span, double* score, hipStream_t stream);
-size_t landmark_workspace_bytes(int64_t N, int32_t num);
-int landmark_select(int64_t N, const float* points, const double* score, int32_t num, double radius, int32_t* out_idx,
-                    int32_t* n_passes, void* workspace, hipStream_t stream);
-
-// fusion.hip (feature-TSDF fusion: batch integration, surface vertices and their feature rows)
-int fusion_bytes(int32_t X, int32_t Y, int32_t Z, int32_t C, size_t* volume_bytes, size_t* surface_bytes);
-int fusion_integrate(const splatraster_fusion_volume* v, int32_t F, int32_t H, int32_t W, const float* depth,
-                     const float* color_im, const float* feat_im, const float* world2cam, const float* intrinsics,
-                     float obs_weight, float sdf_trunc, hipStream_t stream);
-int fusion_surface_count(const splatraster_fusion_volume* v, int32_t use_level, float level, void* workspace, int64_t* n_vertices,
-                         hipStream_t stream);
-int fusion_surface_extract(const splatraster_fusion_volume* v, const void* workspace, double voxel_size, const double* origin,
-                           int64_t M, float* verts, double* points, int64_t* index, uint8_t* colors, float* feats,
-                           hipStream_t stream);
-
-// matching.hip (2D-3D matching: assignment solver, descriptor cost, frustum candidates)
-size_t lsap_workspace_bytes(int32_t B, const splatraster_lsap_problem* problems);
-int lsap_solve(int32_t B, const splatraster_lsap_problem* problems, const double* costs, int32_t maximize, int64_t* row_ind,
-               int64_t* col_ind, int32_t* status, int32_t* steps, void* workspace, hipStream_t stream);
-int lsap_set_lds(int mode);
-int match_cost(int32_t D, int32_t N1, int32_t N2, const float* d1, const float* d2, float threshold, float* norms,
-               double* cost, hipStream_t stream);
-int match_sims(int32_t D, int32_t N1, int32_t N2, const float* d1, const float* d2, const float* norms, float threshold,
-               int64_t K, const int64_t* i1, const int64_t* i2, float* sims, hipStream_t stream);
-size_t frustum_workspace_bytes(int64_t N, int32_t width, int32_t height);
-int frustum_candidates(int64_t N, const float* points, const float* marker, float marker_threshold, const double* w2c,
-                       const double* K, int32_t width, int32_t height, const uint8_t* kp_mask, const float* depth,
-                       const double* c2w, const double* kp_K, int32_t* out_idx, float* out_xyz, double* out_uv,
-                       int64_t* out_count, void* workspace, hipStream_t stream);
-
-// pnp.hip (absolute pose: P3P LO-RANSAC and refinement)
-size_t pnp_workspace_bytes(int32_t B, const splatraster_pnp_problem* problems, const splatraster_pnp_options* options);
-int pnp_solve(int32_t B, const splatraster_pnp_problem* problems, const splatraster_pnp_options* options, const double* points2d,
-              const double* points3d, double* R_out, double* t_out, int32_t* num_inliers, uint8_t* inlier_mask,
-              int32_t* status, int32_t* trials, void* workspace, hipStream_t stream);
-int pnp_hypotheses(int32_t B, const splatraster_pnp_problem* problems, const splatraster_pnp_options* options, int64_t trial0,
-                   int32_t ntrials, const double* points2d, const double* points3d, int32_t* samples, double* models,
-                   int32_t* nmodels, void* workspace, hipStream_t stream);
-int pnp_score(int32_t B, const splatraster_pnp_problem* problems, const splatraster_pnp_options* options, int32_t M,
-              const double* models, const double* points2d, const double* points3d, int32_t* count, double* sum,
-              void* workspace, hipStream_t stream);
-
-// retrieval.hip (localisation: fused similarity + top-k, pose errors, pose inversion)
-size_t retrieval_workspace_bytes(int64_t Q, int64_t N, int32_t D, int32_t k);
-int retrieval_topk(int64_t Q, int64_t N, int32_t D, int32_t k, const float* query, const float* db, int64_t* idx, float* sims,
-                   int32_t* status, void* workspace, hipStream_t stream);
-int pose_errors(int64_t B, const double* R_est, const double* t_est, const double* R_gt, const double* t_gt, const uint8_t* valid,
-                float* theta_deg, double* dist, hipStream_t stream);
-int pose_invert(int64_t B, const double* R, const double* t, double* R_out, double* t_out, hipStream_t stream);
-
 }  // namespace sr

@@ -577,18 +577,6 @@ static DecWorkspace dec_workspace(const DecArgs& d, int64_t N)
     return w;
 }
 
-int decoder_workspace_bytes(const splatraster_decoder_layout* lay, int64_t N, size_t* workspace_bytes, size_t* activation_bytes)
-{
-    GridArgs a;
-    DecArgs d;
-    const int st = dec_args(lay, &a, &d);
-    if (st) return st;
-    if (!dec_n_ok(N)) return SPLATRASTER_ERR_BAD_ARG;
-    if (workspace_bytes) *workspace_bytes = dec_workspace(d, N).total;
-    if (activation_bytes) *activation_bytes = (size_t)dec_acts_floats(d, N, lay->grid.n_dims) * sizeof(float);
-    return SPLATRASTER_OK;
-}
-
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 static int dec_weights(const DecArgs& d, const float* const* weights, DecWeights* W)
@@ -631,9 +619,29 @@ static void launch_dec_fwd(int64_t N, const GridArgs& a, const DecArgs& d, const
         }                                                      \
     } while (0)
 
-int decoder_forward(const splatraster_decoder_layout* lay, int64_t N, const void* x, int32_t x_is_f64, const float* table,
-                    const float* const* weights, float* out, float* acts, hipStream_t s)
+}  // namespace sr
+
+using namespace sr;
+
+extern "C" {
+
+int splatraster_decoder_workspace_bytes(const splatraster_decoder_layout* lay, int64_t N, size_t* workspace_bytes,
+                                        size_t* activation_bytes)
 {
+    GridArgs a;
+    DecArgs d;
+    const int st = dec_args(lay, &a, &d);
+    if (st) return st;
+    if (!dec_n_ok(N)) return SPLATRASTER_ERR_BAD_ARG;
+    if (workspace_bytes) *workspace_bytes = dec_workspace(d, N).total;
+    if (activation_bytes) *activation_bytes = (size_t)dec_acts_floats(d, N, lay->grid.n_dims) * sizeof(float);
+    return SPLATRASTER_OK;
+}
+
+int splatraster_decoder_forward(const splatraster_decoder_layout* lay, int64_t N, const void* x, int32_t x_is_f64,
+                                const float* table, const float* const* weights, float* out, float* acts, void* stream)
+{
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     GridArgs a;
     DecArgs d;
     int st = dec_args(lay, &a, &d);
@@ -654,10 +662,11 @@ int decoder_forward(const splatraster_decoder_layout* lay, int64_t N, const void
     return SPLATRASTER_OK;
 }
 
-int decoder_backward(const splatraster_decoder_layout* lay, int64_t N, const float* table, const float* const* weights,
-                     const float* acts, const float* dL_dout, const float* targets, float* loss, float* dL_dweights,
-                     float* dL_dtable, float* dL_dx, void* workspace, hipStream_t s)
+int splatraster_decoder_backward(const splatraster_decoder_layout* lay, int64_t N, const float* table,
+                                 const float* const* weights, const float* acts, const float* dL_dout, const float* targets,
+                                 float* loss, float* dL_dweights, float* dL_dtable, float* dL_dx, void* workspace, void* stream)
 {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     GridArgs a;
     DecArgs d;
     int st = dec_args(lay, &a, &d);
@@ -693,14 +702,15 @@ int decoder_backward(const splatraster_decoder_layout* lay, int64_t N, const flo
                        G, slabs, dL_dweights, tiles, loss_part, inv_N, targets ? loss : nullptr);
     SR_LAUNCH_CHECK();
     if (dL_dtable || dL_dx)
-        return grid_backward(&lay->grid, N, acts + acts_xn_offset(d, N), table, denc, dL_dtable, dL_dx, s);
+        return splatraster_grid_encoding_backward(&lay->grid, N, acts + acts_xn_offset(d, N), table, denc, dL_dtable, dL_dx, stream);
     return SPLATRASTER_OK;
 }
 
-int decoder_adam(const splatraster_decoder_layout* lay, float* const* weights, float* w_grad, float* w_m, float* w_v, float* table,
-                 float* t_grad, float* t_m, float* t_v, int64_t step, double lr_w, double lr_t, double beta1, double beta2,
-                 double eps_w, double eps_t, double weight_decay, hipStream_t s)
+int splatraster_decoder_adam(const splatraster_decoder_layout* lay, float* const* weights, float* w_grad, float* w_m, float* w_v,
+                             float* table, float* t_grad, float* t_m, float* t_v, int64_t step, double lr_w, double lr_t,
+                             double beta1, double beta2, double eps_w, double eps_t, double weight_decay, void* stream)
 {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     GridArgs a;
     DecArgs d;
     int st = dec_args(lay, &a, &d);
@@ -737,4 +747,4 @@ int decoder_adam(const splatraster_decoder_layout* lay, float* const* weights, f
     return SPLATRASTER_OK;
 }
 
-}  // namespace sr
+}  // extern "C"

@@ -152,45 +152,6 @@ static bool bad_volume(const splatraster_fusion_volume* v, bool need_feat)
     return false;
 }
 
-int fusion_bytes(int32_t X, int32_t Y, int32_t Z, int32_t C, size_t* volume_bytes, size_t* surface_bytes)
-{
-    if (volume_bytes) *volume_bytes = 0;
-    if (surface_bytes) *surface_bytes = 0;
-    if (X < 1 || Y < 1 || Z < 1 || !volume_bytes || !surface_bytes) return SPLATRASTER_ERR_BAD_ARG;
-    if ((int64_t)X * Y > FUS_MAX_VOXELS || (int64_t)X * Y * Z > FUS_MAX_VOXELS) return SPLATRASTER_ERR_BAD_ARG;
-    if (C < 4 || C > FUS_MAX_FEAT || C % 4) return SPLATRASTER_ERR_BAD_ARG;
-    const size_t N = (size_t)X * Y * Z;
-    *volume_bytes = N * sizeof(float) * (size_t)(1 + 1 + 3 + C);
-    // [level, total | counts N | min/max partials | scan state]
-    *surface_bytes = 256 + align_up(N * sizeof(uint32_t), 256) + align_up(2 * FUS_MINMAX_BLOCKS * sizeof(float), 256)
-                     + align_up(scan_tmp_bytes((int64_t)N), 256);
-    return SPLATRASTER_OK;
-}
-
-int fusion_integrate(const splatraster_fusion_volume* v, int32_t F, int32_t H, int32_t W, const float* depth,
-                     const float* color_im, const float* feat_im, const float* world2cam, const float* intrinsics,
-                     float obs_weight, float sdf_trunc, hipStream_t stream)
-{
-    if (bad_volume(v, true) || !v->axis[0] || !v->axis[1] || !v->axis[2]) return SPLATRASTER_ERR_BAD_ARG;
-    if (F < 0 || F > FUS_MAX_FRAMES || H < 1 || W < 1 || H > FUS_MAX_IMAGE || W > FUS_MAX_IMAGE) return SPLATRASTER_ERR_BAD_ARG;
-    if (F == 0) return SPLATRASTER_OK;
-    if (!depth || !color_im || !feat_im || !world2cam || !intrinsics) return SPLATRASTER_ERR_BAD_ARG;
-    if (reinterpret_cast<uintptr_t>(feat_im) & 15) return SPLATRASTER_ERR_BAD_ARG;
-    if (!(sdf_trunc > 0.f) || obs_weight != obs_weight) return SPLATRASTER_ERR_BAD_ARG;
-    FusFrames fr;
-    for (int f = 0; f < FUS_MAX_FRAMES; ++f) {
-        for (int k = 0; k < 12; ++k) fr.w2c[f][k] = f < F ? world2cam[f * 12 + k] : 0.f;
-        for (int k = 0; k < 4; ++k) fr.intr[f][k] = f < F ? intrinsics[f * 4 + k] : 0.f;
-    }
-    const int64_t N = (int64_t)v->dim[0] * v->dim[1] * v->dim[2];
-    const unsigned nb = (unsigned)((N + FUS_THREADS - 1) / FUS_THREADS);
-    hipLaunchKernelGGL(fusion_integrate_kernel, dim3(nb), dim3(FUS_THREADS), 0, stream, N, v->dim[1], v->dim[2], v->feat_dim,
-                       v->axis[0], v->axis[1], v->axis[2], v->tsdf, v->weight, v->color, v->feat, F, H, W, depth, color_im, feat_im,
-                       fr, obs_weight, sdf_trunc);
-    SR_LAUNCH_CHECK();
-    return SPLATRASTER_OK;
-}
-
 // ---- surface -------------------------------------------------------------------------------------------------------------
 struct FusWs {
     float* level;
@@ -361,9 +322,56 @@ fusion_gather_kernel(int64_t M, int64_t N, int32_t C, const float* __restrict__ 
     reinterpret_cast<float4*>(out + m * C)[lane] = reinterpret_cast<const float4*>(feat + src * C)[lane];
 }
 
-int fusion_surface_count(const splatraster_fusion_volume* v, int32_t use_level, float level, void* workspace, int64_t* n_vertices,
-                         hipStream_t stream)
+}  // namespace sr
+
+using namespace sr;
+
+extern "C" {
+
+int splatraster_fusion_bytes(int32_t X, int32_t Y, int32_t Z, int32_t C, size_t* volume_bytes, size_t* surface_bytes)
 {
+    if (volume_bytes) *volume_bytes = 0;
+    if (surface_bytes) *surface_bytes = 0;
+    if (X < 1 || Y < 1 || Z < 1 || !volume_bytes || !surface_bytes) return SPLATRASTER_ERR_BAD_ARG;
+    if ((int64_t)X * Y > FUS_MAX_VOXELS || (int64_t)X * Y * Z > FUS_MAX_VOXELS) return SPLATRASTER_ERR_BAD_ARG;
+    if (C < 4 || C > FUS_MAX_FEAT || C % 4) return SPLATRASTER_ERR_BAD_ARG;
+    const size_t N = (size_t)X * Y * Z;
+    *volume_bytes = N * sizeof(float) * (size_t)(1 + 1 + 3 + C);
+    // [level, total | counts N | min/max partials | scan state]
+    *surface_bytes = 256 + align_up(N * sizeof(uint32_t), 256) + align_up(2 * FUS_MINMAX_BLOCKS * sizeof(float), 256)
+                     + align_up(scan_tmp_bytes((int64_t)N), 256);
+    return SPLATRASTER_OK;
+}
+
+int splatraster_fusion_integrate(const splatraster_fusion_volume* v, int32_t F, int32_t H, int32_t W, const float* depth,
+                                 const float* color_im, const float* feat_im, const float* world2cam, const float* intrinsics,
+                                 float obs_weight, float sdf_trunc, void* stream_)
+{
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    if (bad_volume(v, true) || !v->axis[0] || !v->axis[1] || !v->axis[2]) return SPLATRASTER_ERR_BAD_ARG;
+    if (F < 0 || F > FUS_MAX_FRAMES || H < 1 || W < 1 || H > FUS_MAX_IMAGE || W > FUS_MAX_IMAGE) return SPLATRASTER_ERR_BAD_ARG;
+    if (F == 0) return SPLATRASTER_OK;
+    if (!depth || !color_im || !feat_im || !world2cam || !intrinsics) return SPLATRASTER_ERR_BAD_ARG;
+    if (reinterpret_cast<uintptr_t>(feat_im) & 15) return SPLATRASTER_ERR_BAD_ARG;
+    if (!(sdf_trunc > 0.f) || obs_weight != obs_weight) return SPLATRASTER_ERR_BAD_ARG;
+    FusFrames fr;
+    for (int f = 0; f < FUS_MAX_FRAMES; ++f) {
+        for (int k = 0; k < 12; ++k) fr.w2c[f][k] = f < F ? world2cam[f * 12 + k] : 0.f;
+        for (int k = 0; k < 4; ++k) fr.intr[f][k] = f < F ? intrinsics[f * 4 + k] : 0.f;
+    }
+    const int64_t N = (int64_t)v->dim[0] * v->dim[1] * v->dim[2];
+    const unsigned nb = (unsigned)((N + FUS_THREADS - 1) / FUS_THREADS);
+    hipLaunchKernelGGL(fusion_integrate_kernel, dim3(nb), dim3(FUS_THREADS), 0, stream, N, v->dim[1], v->dim[2], v->feat_dim,
+                       v->axis[0], v->axis[1], v->axis[2], v->tsdf, v->weight, v->color, v->feat, F, H, W, depth, color_im, feat_im,
+                       fr, obs_weight, sdf_trunc);
+    SR_LAUNCH_CHECK();
+    return SPLATRASTER_OK;
+}
+
+int splatraster_fusion_surface_count(const splatraster_fusion_volume* v, int32_t use_level, float level, void* workspace,
+                                     int64_t* n_vertices, void* stream_)
+{
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     if (n_vertices) *n_vertices = 0;
     if (bad_volume(v, false) || !workspace || !n_vertices || (use_level && level != level)) return SPLATRASTER_ERR_BAD_ARG;
     const int64_t N = (int64_t)v->dim[0] * v->dim[1] * v->dim[2];
@@ -391,10 +399,11 @@ int fusion_surface_count(const splatraster_fusion_volume* v, int32_t use_level, 
     return SPLATRASTER_OK;
 }
 
-int fusion_surface_extract(const splatraster_fusion_volume* v, const void* workspace, double voxel_size, const double* origin,
-                           int64_t M, float* verts, double* points, int64_t* index, uint8_t* colors, float* feats,
-                           hipStream_t stream)
+int splatraster_fusion_surface_extract(const splatraster_fusion_volume* v, const void* workspace, double voxel_size,
+                                       const double* origin, int64_t M, float* verts, double* points, int64_t* index,
+                                       uint8_t* colors, float* feats, void* stream_)
 {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     if (bad_volume(v, true) || !workspace || !origin || M < 0) return SPLATRASTER_ERR_BAD_ARG;
     const int64_t N = (int64_t)v->dim[0] * v->dim[1] * v->dim[2];
     if (M > 3 * N) return SPLATRASTER_ERR_BAD_ARG;
@@ -415,4 +424,4 @@ int fusion_surface_extract(const splatraster_fusion_volume* v, const void* works
     return SPLATRASTER_OK;
 }
 
-}  // namespace sr
+}  // extern "C"

@@ -106,7 +106,7 @@ __device__ __forceinline__ float corner_weight(const Locus<D>& q, int c)
     return w;
 }
 
-// a layout the kernels can index safely: the one grid_layout() makes (offsets = running sum of sizes, sizes > 0)
+// a layout the kernels can index safely: the one splatraster_grid_encoding_layout() makes (offsets = running sum of sizes, sizes > 0)
 static inline int grid_args(const splatraster_grid_layout* lay, GridArgs* a)
 {
     if (!lay) return SPLATRASTER_ERR_BAD_ARG;

@@ -117,8 +117,56 @@ grid_encode_bwd_kernel(int64_t N, GridArgs a, const float* __restrict__ x, const
 
 // ---- host ------------------------------------------------------------------------------------------------------------
 
-int grid_layout(int32_t D, int32_t L, int32_t F, int32_t log2_T, int32_t base_res, double per_level_scale, int32_t grid_type,
-                splatraster_grid_layout* out)
+static dim3 grid_blocks(int64_t N, const GridArgs& a)
+{
+    return dim3((unsigned)(((N << a.lp_log2) + GRID_THREADS - 1) / GRID_THREADS));
+}
+
+// lanes of all N points fit one 1-D grid (2^31 - 1 blocks): N <= 2^31 * 256 / 32 covers any table-sized batch
+static bool grid_n_ok(int64_t N) { return N >= 0 && N <= (int64_t(1) << 36); }
+
+template <int D, int F>
+static void launch_fwd(int64_t N, const GridArgs& a, const float* x, const float* params, float* out, hipStream_t s)
+{
+    hipLaunchKernelGGL((grid_encode_fwd_kernel<D, F>), grid_blocks(N, a), dim3(GRID_THREADS), 0, s, N, a, x, params, out);
+}
+
+template <int D, int F>
+static void launch_bwd(int64_t N, const GridArgs& a, const float* x, const float* params, const float* g, float* dp, float* dx,
+                       hipStream_t s)
+{
+    const dim3 b = grid_blocks(N, a);
+    if (dp && dx)
+        hipLaunchKernelGGL((grid_encode_bwd_kernel<D, F, true, true>), b, dim3(GRID_THREADS), 0, s, N, a, x, params, g, dp, dx);
+    else if (dp)
+        hipLaunchKernelGGL((grid_encode_bwd_kernel<D, F, true, false>), b, dim3(GRID_THREADS), 0, s, N, a, x, params, g, dp, dx);
+    else
+        hipLaunchKernelGGL((grid_encode_bwd_kernel<D, F, false, true>), b, dim3(GRID_THREADS), 0, s, N, a, x, params, g, dp, dx);
+}
+
+#define SR_GRID_DISPATCH(D, F, CALL)                           \
+    do {                                                       \
+        switch ((D) * 16 + (F)) {                              \
+        case 2 * 16 + 1: CALL(2, 1); break;                    \
+        case 2 * 16 + 2: CALL(2, 2); break;                    \
+        case 2 * 16 + 4: CALL(2, 4); break;                    \
+        case 2 * 16 + 8: CALL(2, 8); break;                    \
+        case 3 * 16 + 1: CALL(3, 1); break;                    \
+        case 3 * 16 + 2: CALL(3, 2); break;                    \
+        case 3 * 16 + 4: CALL(3, 4); break;                    \
+        case 3 * 16 + 8: CALL(3, 8); break;                    \
+        default: return SPLATRASTER_ERR_UNSUPPORTED;           \
+        }                                                      \
+    } while (0)
+
+}  // namespace sr
+
+using namespace sr;
+
+extern "C" {
+
+int splatraster_grid_encoding_layout(int32_t D, int32_t L, int32_t F, int32_t log2_T, int32_t base_res, double per_level_scale,
+                                     int32_t grid_type, splatraster_grid_layout* out)
 {
 #pragma clang fp contract(off)   // the level table rounds each f32 operation on its own (no fused multiply-add)
     if (!out) return SPLATRASTER_ERR_BAD_ARG;
@@ -165,50 +213,10 @@ int grid_layout(int32_t D, int32_t L, int32_t F, int32_t log2_T, int32_t base_re
     return SPLATRASTER_OK;
 }
 
-static dim3 grid_blocks(int64_t N, const GridArgs& a)
+int splatraster_grid_encoding_forward(const splatraster_grid_layout* lay, int64_t N, const float* x, const float* params, float* out,
+                                      void* stream)
 {
-    return dim3((unsigned)(((N << a.lp_log2) + GRID_THREADS - 1) / GRID_THREADS));
-}
-
-// lanes of all N points fit one 1-D grid (2^31 - 1 blocks): N <= 2^31 * 256 / 32 covers any table-sized batch
-static bool grid_n_ok(int64_t N) { return N >= 0 && N <= (int64_t(1) << 36); }
-
-template <int D, int F>
-static void launch_fwd(int64_t N, const GridArgs& a, const float* x, const float* params, float* out, hipStream_t s)
-{
-    hipLaunchKernelGGL((grid_encode_fwd_kernel<D, F>), grid_blocks(N, a), dim3(GRID_THREADS), 0, s, N, a, x, params, out);
-}
-
-template <int D, int F>
-static void launch_bwd(int64_t N, const GridArgs& a, const float* x, const float* params, const float* g, float* dp, float* dx,
-                       hipStream_t s)
-{
-    const dim3 b = grid_blocks(N, a);
-    if (dp && dx)
-        hipLaunchKernelGGL((grid_encode_bwd_kernel<D, F, true, true>), b, dim3(GRID_THREADS), 0, s, N, a, x, params, g, dp, dx);
-    else if (dp)
-        hipLaunchKernelGGL((grid_encode_bwd_kernel<D, F, true, false>), b, dim3(GRID_THREADS), 0, s, N, a, x, params, g, dp, dx);
-    else
-        hipLaunchKernelGGL((grid_encode_bwd_kernel<D, F, false, true>), b, dim3(GRID_THREADS), 0, s, N, a, x, params, g, dp, dx);
-}
-
-#define SR_GRID_DISPATCH(D, F, CALL)                           \
-    do {                                                       \
-        switch ((D) * 16 + (F)) {                              \
-        case 2 * 16 + 1: CALL(2, 1); break;                    \
-        case 2 * 16 + 2: CALL(2, 2); break;                    \
-        case 2 * 16 + 4: CALL(2, 4); break;                    \
-        case 2 * 16 + 8: CALL(2, 8); break;                    \
-        case 3 * 16 + 1: CALL(3, 1); break;                    \
-        case 3 * 16 + 2: CALL(3, 2); break;                    \
-        case 3 * 16 + 4: CALL(3, 4); break;                    \
-        case 3 * 16 + 8: CALL(3, 8); break;                    \
-        default: return SPLATRASTER_ERR_UNSUPPORTED;           \
-        }                                                      \
-    } while (0)
-
-int grid_forward(const splatraster_grid_layout* lay, int64_t N, const float* x, const float* params, float* out, hipStream_t s)
-{
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     GridArgs a;
     const int st = grid_args(lay, &a);
     if (st) return st;
@@ -223,9 +231,10 @@ int grid_forward(const splatraster_grid_layout* lay, int64_t N, const float* x, 
     return SPLATRASTER_OK;
 }
 
-int grid_backward(const splatraster_grid_layout* lay, int64_t N, const float* x, const float* params, const float* dL_dout,
-                  float* dL_dparams, float* dL_dx, hipStream_t s)
+int splatraster_grid_encoding_backward(const splatraster_grid_layout* lay, int64_t N, const float* x, const float* params,
+                                       const float* dL_dout, float* dL_dparams, float* dL_dx, void* stream)
 {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     GridArgs a;
     const int st = grid_args(lay, &a);
     if (st) return st;
@@ -242,4 +251,4 @@ int grid_backward(const splatraster_grid_layout* lay, int64_t N, const float* x,
     return SPLATRASTER_OK;
 }
 
-}  // namespace sr
+}  // extern "C"

@@ -87,7 +87,6 @@ knn_merge_kernel(int N, int slices, const float* __restrict__ partial, float* __
 // ---- exact grid search ------------------------------------------------------------------------------------------
 constexpr int KNN_GRID_MIN_DEFAULT = 10000;   // measured crossover on MI355X (profiles/r03_knn.json): 5 k 0.11 vs 0.16 ms, 20 k 0.34 vs 0.19 ms
 static int g_knn_grid_min = KNN_GRID_MIN_DEFAULT;
-void knn_set_grid_min(int n) { g_knn_grid_min = n < 0 ? KNN_GRID_MIN_DEFAULT : n; }
 
 struct KnnGrid {            // written by knn_grid_setup_kernel, read by the others (device memory)
     float ox, oy, oz;       // origin (bounding-box minimum)
@@ -295,7 +294,7 @@ static int knn_slices(int N)
 // flag word of the grid path (largest overloaded cell, see KnnGrid): the last 256 bytes of the workspace
 static uint32_t* knn_flag_word(void* workspace, int32_t N)
 {
-    return reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(workspace) + knn_workspace_bytes(N) - 256);
+    return reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(workspace) + splatknn_workspace_bytes(N) - 256);
 }
 
 // the tiled brute force; `gate` non-null: every block returns at once unless *gate > gate_limit
@@ -342,7 +341,13 @@ static int knn_grid_dist2(int32_t N, const float* points, float* out, void* work
     return knn_brute_dist2(N, points, out, workspace, flag, knn_overload_limit(N), stream);
 }
 
-size_t knn_workspace_bytes(int32_t N)
+}  // namespace sr
+
+using namespace sr;
+
+extern "C" {
+
+size_t splatknn_workspace_bytes(int32_t N)
 {
     const size_t n = (size_t)(N > 0 ? N : 1);
     const size_t brute = align_up((size_t)knn_slices((int)n) * n * 3 * sizeof(float), 256);
@@ -350,10 +355,20 @@ size_t knn_workspace_bytes(int32_t N)
     return (brute > grid ? brute : grid) + 256;     // either path may be taken (the threshold is a run-time knob); + the flag word
 }
 
-int knn_dist2(int32_t N, const float* points, float* out, void* workspace, hipStream_t stream)
+int splatknn_debug_set_grid_min(int32_t n)
 {
+    g_knn_grid_min = n < 0 ? KNN_GRID_MIN_DEFAULT : n;
+    return SPLATRASTER_OK;
+}
+
+int splatknn_dist2(int32_t N, const float* points, float* out, void* workspace, void* stream_)
+{
+    if (N < 0) return SPLATRASTER_ERR_BAD_ARG;
+    if (N == 0) return SPLATRASTER_OK;
+    if (!points || !out || !workspace) return SPLATRASTER_ERR_BAD_ARG;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     if (N >= g_knn_grid_min && N >= 8) return knn_grid_dist2(N, points, out, workspace, stream);
     return knn_brute_dist2(N, points, out, workspace, nullptr, 0u, stream);
 }
 
-}  // namespace sr
+}  // extern "C"

@@ -132,10 +132,10 @@ static int loss_blocks(int32_t HW)
     return blocks;
 }
 
-size_t mapping_loss_workspace_bytes(int32_t HW) { return (size_t)loss_blocks(HW) * LOSS_SUMS * sizeof(double); }
+static size_t mapping_loss_workspace_bytes(int32_t HW) { return (size_t)loss_blocks(HW) * LOSS_SUMS * sizeof(double); }
 
 // V views (host array of per-view pointers), out [V][4], workspace V x mapping_loss_workspace_bytes(HW)
-int launch_mapping_loss_window(int32_t V, int32_t HW, const splatraster_loss_view* views, float threshold, float* out,
+static int launch_mapping_loss_window(int32_t V, int32_t HW, const splatraster_loss_view* views, float threshold, float* out,
                                void* workspace, hipStream_t stream)
 {
     LossViews lv{};
@@ -154,7 +154,7 @@ int launch_mapping_loss_window(int32_t V, int32_t HW, const splatraster_loss_vie
     return SPLATRASTER_OK;
 }
 
-int launch_mapping_loss(int32_t HW, const float* image, const float* depth, const float* marker,
+static int launch_mapping_loss(int32_t HW, const float* image, const float* depth, const float* marker,
                         const float* gt_image, const float* gt_depth, const float* kp, float threshold,
                         const float* exposure, float* g_image, float* g_depth, float* g_marker, float* out,
                         void* workspace, hipStream_t stream)
@@ -393,7 +393,7 @@ static RefineWindow refine_window()
     return win;
 }
 
-size_t refinement_loss_workspace_bytes(int32_t C, int32_t H, int32_t W)
+static size_t refinement_loss_workspace_bytes(int32_t C, int32_t H, int32_t W)
 {
     const size_t blocks = (size_t)((W + FW - 1) / FW) * ((H + FH - 1) / FH) * (size_t)C;
     return align_up(3 * sizeof(float) * (size_t)C * H * W, 256) + blocks * 2 * sizeof(double);
@@ -512,13 +512,13 @@ eval_metrics_finish_kernel(int blocks, double n_total, const double* __restrict_
     }
 }
 
-size_t eval_metrics_workspace_bytes(int32_t C, int32_t H, int32_t W)
+static size_t eval_metrics_workspace_bytes(int32_t C, int32_t H, int32_t W)
 {
     const size_t blocks = (size_t)((W + RT - 1) / RT) * ((H + RT - 1) / RT) * (size_t)C;
     return blocks * EVAL_SUMS * sizeof(double);
 }
 
-int launch_eval_metrics(int32_t C, int32_t H, int32_t W, const float* image, const float* gt, float* out, void* workspace,
+static int launch_eval_metrics(int32_t C, int32_t H, int32_t W, const float* image, const float* gt, float* out, void* workspace,
                         hipStream_t stream)
 {
     const dim3 grid((W + RT - 1) / RT, (H + RT - 1) / RT, C);
@@ -531,7 +531,7 @@ int launch_eval_metrics(int32_t C, int32_t H, int32_t W, const float* image, con
     return SPLATRASTER_OK;
 }
 
-int launch_refinement_loss(int32_t C, int32_t H, int32_t W, float lambda, const float* image, const float* gt,
+static int launch_refinement_loss(int32_t C, int32_t H, int32_t W, float lambda, const float* image, const float* gt,
                            float* g_image, float* out, void* workspace, hipStream_t stream)
 {
     const size_t n = (size_t)C * H * W;
@@ -550,3 +550,68 @@ int launch_refinement_loss(int32_t C, int32_t H, int32_t W, float lambda, const 
 }
 
 }  // namespace sr
+
+using namespace sr;
+
+extern "C" {
+
+size_t splatraster_mapping_loss_workspace_bytes(int32_t pixels) { return mapping_loss_workspace_bytes(pixels); }
+
+int splatraster_mapping_loss(int32_t pixels, const float* image, const float* depth, const float* marker,
+                             const float* gt_image, const float* gt_depth, const float* kp,
+                             float rgb_boundary_threshold, const float* exposure, float* g_image, float* g_depth,
+                             float* g_marker, float* out, void* workspace, void* stream)
+{
+    if (pixels <= 0) return SPLATRASTER_ERR_BAD_ARG;
+    if (!image || !depth || !marker || !gt_image || !gt_depth || !kp || !g_image || !g_depth || !g_marker || !out ||
+        !workspace)
+        return SPLATRASTER_ERR_BAD_ARG;
+    return launch_mapping_loss(pixels, image, depth, marker, gt_image, gt_depth, kp, rgb_boundary_threshold, exposure,
+                               g_image, g_depth, g_marker, out, workspace, reinterpret_cast<hipStream_t>(stream));
+}
+
+int splatraster_mapping_loss_window(int32_t n_views, int32_t pixels, const splatraster_loss_view* views,
+                                    float rgb_boundary_threshold, float* out, void* workspace, void* stream)
+{
+    if (pixels <= 0 || n_views < 1 || n_views > SPLATRASTER_MAX_WINDOW_VIEWS || !views || !out || !workspace)
+        return SPLATRASTER_ERR_BAD_ARG;
+    for (int v = 0; v < n_views; ++v) {
+        const splatraster_loss_view& w = views[v];
+        if (!w.image || !w.depth || !w.marker || !w.gt_image || !w.gt_depth || !w.kp || !w.g_image || !w.g_depth || !w.g_marker)
+            return SPLATRASTER_ERR_BAD_ARG;
+    }
+    return launch_mapping_loss_window(n_views, pixels, views, rgb_boundary_threshold, out, workspace,
+                                      reinterpret_cast<hipStream_t>(stream));
+}
+
+size_t splatraster_refinement_loss_workspace_bytes(int32_t channels, int32_t height, int32_t width)
+{
+    if (channels <= 0 || height <= 0 || width <= 0) return 0;
+    return refinement_loss_workspace_bytes(channels, height, width);
+}
+
+int splatraster_refinement_loss(int32_t channels, int32_t height, int32_t width, float lambda_dssim,
+                                const float* image, const float* gt, float* g_image, float* out, void* workspace,
+                                void* stream)
+{
+    if (channels <= 0 || height <= 0 || width <= 0) return SPLATRASTER_ERR_BAD_ARG;
+    if (!image || !gt || !g_image || !out || !workspace) return SPLATRASTER_ERR_BAD_ARG;
+    return launch_refinement_loss(channels, height, width, lambda_dssim, image, gt, g_image, out, workspace,
+                                  reinterpret_cast<hipStream_t>(stream));
+}
+
+size_t splatraster_eval_metrics_workspace_bytes(int32_t channels, int32_t height, int32_t width)
+{
+    if (channels <= 0 || height <= 0 || width <= 0) return 0;
+    return eval_metrics_workspace_bytes(channels, height, width);
+}
+
+int splatraster_eval_metrics(int32_t channels, int32_t height, int32_t width, const float* render, const float* gt, float* out,
+                             void* workspace, void* stream)
+{
+    if (channels <= 0 || height <= 0 || width <= 0) return SPLATRASTER_ERR_BAD_ARG;
+    if (!render || !gt || !out || !workspace) return SPLATRASTER_ERR_BAD_ARG;
+    return launch_eval_metrics(channels, height, width, render, gt, out, workspace, reinterpret_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"

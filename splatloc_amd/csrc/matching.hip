@@ -317,75 +317,6 @@ static int lsap_check(int32_t B, const splatraster_lsap_problem* p)
     return SPLATRASTER_OK;
 }
 
-size_t lsap_workspace_bytes(int32_t B, const splatraster_lsap_problem* problems)
-{
-    if (lsap_check(B, problems) != SPLATRASTER_OK) return 0;
-    size_t bytes = 0;
-    for (int32_t b = 0; b < B; ++b)
-        if (!lsap_uses_lds(problems[b].nc)) bytes += lsap_state_bytes(problems[b].nr, problems[b].nc);
-    return bytes;
-}
-
-int lsap_set_lds(int mode)
-{
-    g_lsap_lds = mode ? 1 : 0;
-    return SPLATRASTER_OK;
-}
-
-int lsap_solve(int32_t B, const splatraster_lsap_problem* problems, const double* costs, int32_t maximize, int64_t* row_ind,
-               int64_t* col_ind, int32_t* status, int32_t* steps, void* workspace, hipStream_t stream)
-{
-    int chk = lsap_check(B, problems);
-    if (chk != SPLATRASTER_OK) return chk;
-    if (B == 0) return SPLATRASTER_OK;
-    if (!costs || !row_ind || !col_ind || !status || !steps) return SPLATRASTER_ERR_BAD_ARG;
-    if (lsap_workspace_bytes(B, problems) > 0 && !workspace) return SPLATRASTER_ERR_BAD_ARG;
-    // three groups, one kernel variant each, launched in chunks of LSAP_BATCH problems
-    std::vector<LsapEntry> groups[3];
-    int64_t out = 0, ws = 0;
-    for (int32_t b = 0; b < B; ++b) {
-        const splatraster_lsap_problem& p = problems[b];
-        LsapEntry e;
-        e.cost_off = p.offset;
-        e.out_off = out;
-        e.ws_off = 0;
-        e.nr = p.nr;
-        e.nc = p.nc;
-        e.transposed = p.transposed ? 1 : 0;
-        e.index = b;
-        out += p.nr;
-        int g;
-        if (!lsap_uses_lds(p.nc)) {
-            g = 2;
-            e.ws_off = ws;
-            ws += (int64_t)lsap_state_bytes(p.nr, p.nc);
-        } else {
-            g = p.nc <= LSAP_LDS_SMALL ? 0 : 1;
-        }
-        groups[g].push_back(e);
-    }
-    char* wsp = reinterpret_cast<char*>(workspace);
-    for (int g = 0; g < 3; ++g) {
-        for (size_t c0 = 0; c0 < groups[g].size(); c0 += LSAP_BATCH) {
-            const size_t n = std::min((size_t)LSAP_BATCH, groups[g].size() - c0);
-            LsapBatch batch;
-            memset(&batch, 0, sizeof(batch));
-            for (size_t k = 0; k < n; ++k) batch.e[k] = groups[g][c0 + k];
-            if (g == 0)
-                hipLaunchKernelGGL(lsap_kernel<LSAP_LDS_SMALL>, dim3((unsigned)n), dim3(LSAP_THREADS), 0, stream, batch, costs,
-                                   maximize, row_ind, col_ind, status, steps, wsp);
-            else if (g == 1)
-                hipLaunchKernelGGL(lsap_kernel<LSAP_LDS_LARGE>, dim3((unsigned)n), dim3(LSAP_THREADS), 0, stream, batch, costs,
-                                   maximize, row_ind, col_ind, status, steps, wsp);
-            else
-                hipLaunchKernelGGL(lsap_kernel<0>, dim3((unsigned)n), dim3(LSAP_THREADS), 0, stream, batch, costs, maximize,
-                                   row_ind, col_ind, status, steps, wsp);
-            SR_LAUNCH_CHECK();
-        }
-    }
-    return SPLATRASTER_OK;
-}
-
 // ---- descriptor cost ----------------------------------------------------------------------------------------------------
 constexpr int MC_TILE = 64;      // output tile edge
 constexpr int MC_KC = 16;        // descriptor dimensions staged per round
@@ -472,38 +403,6 @@ match_sims_kernel(int32_t D, int32_t N1, int32_t N2, const float* __restrict__ d
     float acc = 0.f;
     for (int q = 0; q < D; ++q) acc = fmaf(d1[(int64_t)q * N1 + a] / na, d2[(int64_t)q * N2 + b] / nb, acc);
     sims[k] = mc_sim_tail(acc, thr);
-}
-
-int match_cost(int32_t D, int32_t N1, int32_t N2, const float* d1, const float* d2, float threshold, float* norms,
-               double* cost, hipStream_t stream)
-{
-    if (D < 1 || N1 < 1 || N2 < 1 || !d1 || !d2 || !norms || !cost) return SPLATRASTER_ERR_BAD_ARG;
-    hipLaunchKernelGGL(match_norm_kernel, dim3((N1 + 255) / 256), dim3(256), 0, stream, D, N1, d1, norms);
-    SR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(match_norm_kernel, dim3((N2 + 255) / 256), dim3(256), 0, stream, D, N2, d2, norms + N1);
-    SR_LAUNCH_CHECK();
-    const bool tr = N2 < N1;   // the solver's orientation: rows = the smaller set
-    const int NR = tr ? N2 : N1, NC = tr ? N1 : N2;
-    const float* R = tr ? d2 : d1;
-    const float* Cm = tr ? d1 : d2;
-    const float* nR = tr ? norms + N1 : norms;
-    const float* nC = tr ? norms : norms + N1;
-    const dim3 grid((unsigned)((NC + MC_TILE - 1) / MC_TILE), (unsigned)((NR + MC_TILE - 1) / MC_TILE));
-    hipLaunchKernelGGL(match_cost_kernel, grid, dim3(MC_THREADS), 0, stream, D, NR, NC, R, nR, Cm, nC, threshold, cost);
-    SR_LAUNCH_CHECK();
-    return SPLATRASTER_OK;
-}
-
-int match_sims(int32_t D, int32_t N1, int32_t N2, const float* d1, const float* d2, const float* norms, float threshold,
-               int64_t K, const int64_t* i1, const int64_t* i2, float* sims, hipStream_t stream)
-{
-    if (D < 1 || N1 < 1 || N2 < 1 || K < 0 || !d1 || !d2 || !norms) return SPLATRASTER_ERR_BAD_ARG;
-    if (K == 0) return SPLATRASTER_OK;
-    if (!i1 || !i2 || !sims) return SPLATRASTER_ERR_BAD_ARG;
-    hipLaunchKernelGGL(match_sims_kernel, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, stream, D, N1, N2, d1, d2, norms,
-                       threshold, K, i1, i2, sims);
-    SR_LAUNCH_CHECK();
-    return SPLATRASTER_OK;
 }
 
 // ---- frustum candidates -------------------------------------------------------------------------------------------------
@@ -699,18 +598,129 @@ static FrWs fr_layout(char* base, int64_t N, int64_t P)
     return w;
 }
 
-size_t frustum_workspace_bytes(int64_t N, int32_t width, int32_t height)
+static inline unsigned fr_blocks(int64_t n) { return (unsigned)((n + FR_THREADS - 1) / FR_THREADS); }
+
+}  // namespace sr
+
+using namespace sr;
+
+extern "C" {
+
+size_t splatraster_lsap_workspace_bytes(int32_t B, const splatraster_lsap_problem* problems)
+{
+    if (lsap_check(B, problems) != SPLATRASTER_OK) return 0;
+    size_t bytes = 0;
+    for (int32_t b = 0; b < B; ++b)
+        if (!lsap_uses_lds(problems[b].nc)) bytes += lsap_state_bytes(problems[b].nr, problems[b].nc);
+    return bytes;
+}
+
+int splatraster_debug_set_lsap_lds(int mode)
+{
+    g_lsap_lds = mode ? 1 : 0;
+    return SPLATRASTER_OK;
+}
+
+int splatraster_lsap(int32_t B, const splatraster_lsap_problem* problems, const double* costs, int32_t maximize,
+                     int64_t* row_ind, int64_t* col_ind, int32_t* status, int32_t* steps, void* workspace, void* stream_)
+{
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    int chk = lsap_check(B, problems);
+    if (chk != SPLATRASTER_OK) return chk;
+    if (B == 0) return SPLATRASTER_OK;
+    if (!costs || !row_ind || !col_ind || !status || !steps) return SPLATRASTER_ERR_BAD_ARG;
+    if (splatraster_lsap_workspace_bytes(B, problems) > 0 && !workspace) return SPLATRASTER_ERR_BAD_ARG;
+    // three groups, one kernel variant each, launched in chunks of LSAP_BATCH problems
+    std::vector<LsapEntry> groups[3];
+    int64_t out = 0, ws = 0;
+    for (int32_t b = 0; b < B; ++b) {
+        const splatraster_lsap_problem& p = problems[b];
+        LsapEntry e;
+        e.cost_off = p.offset;
+        e.out_off = out;
+        e.ws_off = 0;
+        e.nr = p.nr;
+        e.nc = p.nc;
+        e.transposed = p.transposed ? 1 : 0;
+        e.index = b;
+        out += p.nr;
+        int g;
+        if (!lsap_uses_lds(p.nc)) {
+            g = 2;
+            e.ws_off = ws;
+            ws += (int64_t)lsap_state_bytes(p.nr, p.nc);
+        } else {
+            g = p.nc <= LSAP_LDS_SMALL ? 0 : 1;
+        }
+        groups[g].push_back(e);
+    }
+    char* wsp = reinterpret_cast<char*>(workspace);
+    for (int g = 0; g < 3; ++g) {
+        for (size_t c0 = 0; c0 < groups[g].size(); c0 += LSAP_BATCH) {
+            const size_t n = std::min((size_t)LSAP_BATCH, groups[g].size() - c0);
+            LsapBatch batch;
+            memset(&batch, 0, sizeof(batch));
+            for (size_t k = 0; k < n; ++k) batch.e[k] = groups[g][c0 + k];
+            if (g == 0)
+                hipLaunchKernelGGL(lsap_kernel<LSAP_LDS_SMALL>, dim3((unsigned)n), dim3(LSAP_THREADS), 0, stream, batch, costs,
+                                   maximize, row_ind, col_ind, status, steps, wsp);
+            else if (g == 1)
+                hipLaunchKernelGGL(lsap_kernel<LSAP_LDS_LARGE>, dim3((unsigned)n), dim3(LSAP_THREADS), 0, stream, batch, costs,
+                                   maximize, row_ind, col_ind, status, steps, wsp);
+            else
+                hipLaunchKernelGGL(lsap_kernel<0>, dim3((unsigned)n), dim3(LSAP_THREADS), 0, stream, batch, costs, maximize,
+                                   row_ind, col_ind, status, steps, wsp);
+            SR_LAUNCH_CHECK();
+        }
+    }
+    return SPLATRASTER_OK;
+}
+
+int splatraster_match_cost(int32_t D, int32_t N1, int32_t N2, const float* d1, const float* d2, float threshold, float* norms,
+                           double* cost, void* stream_)
+{
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    if (D < 1 || N1 < 1 || N2 < 1 || !d1 || !d2 || !norms || !cost) return SPLATRASTER_ERR_BAD_ARG;
+    hipLaunchKernelGGL(match_norm_kernel, dim3((N1 + 255) / 256), dim3(256), 0, stream, D, N1, d1, norms);
+    SR_LAUNCH_CHECK();
+    hipLaunchKernelGGL(match_norm_kernel, dim3((N2 + 255) / 256), dim3(256), 0, stream, D, N2, d2, norms + N1);
+    SR_LAUNCH_CHECK();
+    const bool tr = N2 < N1;   // the solver's orientation: rows = the smaller set
+    const int NR = tr ? N2 : N1, NC = tr ? N1 : N2;
+    const float* R = tr ? d2 : d1;
+    const float* Cm = tr ? d1 : d2;
+    const float* nR = tr ? norms + N1 : norms;
+    const float* nC = tr ? norms : norms + N1;
+    const dim3 grid((unsigned)((NC + MC_TILE - 1) / MC_TILE), (unsigned)((NR + MC_TILE - 1) / MC_TILE));
+    hipLaunchKernelGGL(match_cost_kernel, grid, dim3(MC_THREADS), 0, stream, D, NR, NC, R, nR, Cm, nC, threshold, cost);
+    SR_LAUNCH_CHECK();
+    return SPLATRASTER_OK;
+}
+
+int splatraster_match_sims(int32_t D, int32_t N1, int32_t N2, const float* d1, const float* d2, const float* norms,
+                           float threshold, int64_t K, const int64_t* i1, const int64_t* i2, float* sims, void* stream_)
+{
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    if (D < 1 || N1 < 1 || N2 < 1 || K < 0 || !d1 || !d2 || !norms) return SPLATRASTER_ERR_BAD_ARG;
+    if (K == 0) return SPLATRASTER_OK;
+    if (!i1 || !i2 || !sims) return SPLATRASTER_ERR_BAD_ARG;
+    hipLaunchKernelGGL(match_sims_kernel, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, stream, D, N1, N2, d1, d2, norms,
+                       threshold, K, i1, i2, sims);
+    SR_LAUNCH_CHECK();
+    return SPLATRASTER_OK;
+}
+
+size_t splatraster_frustum_workspace_bytes(int64_t N, int32_t width, int32_t height)
 {
     return fr_layout(nullptr, N, (int64_t)(width > 0 ? width : 0) * (height > 0 ? height : 0)).bytes;
 }
 
-static inline unsigned fr_blocks(int64_t n) { return (unsigned)((n + FR_THREADS - 1) / FR_THREADS); }
-
-int frustum_candidates(int64_t N, const float* points, const float* marker, float marker_threshold, const double* w2c,
-                       const double* K, int32_t width, int32_t height, const uint8_t* kp_mask, const float* depth,
-                       const double* c2w, const double* kp_K, int32_t* out_idx, float* out_xyz, double* out_uv,
-                       int64_t* out_count, void* workspace, hipStream_t stream)
+int splatraster_frustum_candidates(int64_t N, const float* points, const float* marker, float marker_threshold, const double* w2c,
+                                   const double* K, int32_t width, int32_t height, const uint8_t* kp_mask, const float* depth,
+                                   const double* c2w, const double* kp_K, int32_t* out_idx, float* out_xyz, double* out_uv,
+                                   int64_t* out_count, void* workspace, void* stream_)
 {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     if (N < 0 || width < 1 || height < 1 || !w2c || !K || !out_count || !workspace) return SPLATRASTER_ERR_BAD_ARG;
     if (N > 0 && (!points || !out_idx || !out_xyz || !out_uv)) return SPLATRASTER_ERR_BAD_ARG;
     const bool key = marker != nullptr;
@@ -770,4 +780,4 @@ int frustum_candidates(int64_t N, const float* points, const float* marker, floa
     return SPLATRASTER_OK;
 }
 
-}  // namespace sr
+}  // extern "C"

@@ -792,18 +792,25 @@ static int pnp_check(int32_t B, const splatraster_pnp_problem* p, const splatras
     return SPLATRASTER_OK;
 }
 
-size_t pnp_workspace_bytes(int32_t B, const splatraster_pnp_problem* problems, const splatraster_pnp_options* options)
+static inline unsigned pnp_blocks(int64_t threads, int per) { return (unsigned)((threads + per - 1) / per); }
+
+}  // namespace sr
+
+using namespace sr;
+
+extern "C" {
+
+size_t splatraster_pnp_workspace_bytes(int32_t B, const splatraster_pnp_problem* problems, const splatraster_pnp_options* options)
 {
     if (pnp_check(B, problems, options) != SPLATRASTER_OK || B == 0) return 0;
     return pnp_layout(B).total;
 }
 
-static inline unsigned pnp_blocks(int64_t threads, int per) { return (unsigned)((threads + per - 1) / per); }
-
-int pnp_hypotheses(int32_t B, const splatraster_pnp_problem* problems, const splatraster_pnp_options* options, int64_t trial0,
-                   int32_t ntrials, const double* points2d, const double* points3d, int32_t* samples, double* models,
-                   int32_t* nmodels, void* workspace, hipStream_t stream)
+int splatraster_pnp_hypotheses(int32_t B, const splatraster_pnp_problem* problems, const splatraster_pnp_options* options,
+                               int64_t trial0, int32_t ntrials, const double* points2d, const double* points3d, int32_t* samples,
+                               double* models, int32_t* nmodels, void* workspace, void* stream_)
 {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     const int st = pnp_check(B, problems, options);
     if (st != SPLATRASTER_OK || B == 0) return st;
     if (ntrials < 1 || ntrials > PNP_BATCH || trial0 < 0 || !points2d || !points3d || !samples || !models || !nmodels ||
@@ -821,10 +828,11 @@ int pnp_hypotheses(int32_t B, const splatraster_pnp_problem* problems, const spl
     return SPLATRASTER_OK;
 }
 
-int pnp_score(int32_t B, const splatraster_pnp_problem* problems, const splatraster_pnp_options* options, int32_t M,
-              const double* models, const double* points2d, const double* points3d, int32_t* count, double* sum,
-              void* workspace, hipStream_t stream)
+int splatraster_pnp_score(int32_t B, const splatraster_pnp_problem* problems, const splatraster_pnp_options* options, int32_t M,
+                          const double* models, const double* points2d, const double* points3d, int32_t* count, double* sum,
+                          void* workspace, void* stream_)
 {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     const int st = pnp_check(B, problems, options);
     if (st != SPLATRASTER_OK || B == 0) return st;
     if (M < 0 || (int64_t)B * M > (int64_t)PNP_BATCH * PNP_SOL * B) return SPLATRASTER_ERR_BAD_ARG;
@@ -841,10 +849,11 @@ int pnp_score(int32_t B, const splatraster_pnp_problem* problems, const splatras
     return SPLATRASTER_OK;
 }
 
-int pnp_solve(int32_t B, const splatraster_pnp_problem* problems, const splatraster_pnp_options* options, const double* points2d,
-              const double* points3d, double* R_out, double* t_out, int32_t* num_inliers, uint8_t* inlier_mask,
-              int32_t* status, int32_t* trials, void* workspace, hipStream_t stream)
+int splatraster_pnp(int32_t B, const splatraster_pnp_problem* problems, const splatraster_pnp_options* options,
+                    const double* points2d, const double* points3d, double* R_out, double* t_out, int32_t* num_inliers,
+                    uint8_t* inlier_mask, int32_t* status, int32_t* trials, void* workspace, void* stream_)
 {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     const int st = pnp_check(B, problems, options);
     if (st != SPLATRASTER_OK || B == 0) return st;
     int64_t total = 0;
@@ -900,4 +909,4 @@ int pnp_solve(int32_t B, const splatraster_pnp_problem* problems, const splatras
     return SPLATRASTER_OK;
 }
 
-}  // namespace sr
+}  // extern "C"

@@ -335,16 +335,23 @@ RetrievalPlan retrieval_plan(int64_t Q, int64_t N, int32_t k)
 
 }  // namespace
 
-size_t retrieval_workspace_bytes(int64_t Q, int64_t N, int32_t D, int32_t k)
+}  // namespace sr
+
+using namespace sr;
+
+extern "C" {
+
+size_t splatraster_retrieval_workspace_bytes(int64_t Q, int64_t N, int32_t D, int32_t k)
 {
     if (!retrieval_args_ok(Q, N, D, k) || Q == 0) return 0;
     const RetrievalPlan p = retrieval_plan(Q, N, k);
     return p.slices > 1 ? align_up((size_t)Q * p.slices * k * sizeof(unsigned long long), 256) : 0;
 }
 
-int retrieval_topk(int64_t Q, int64_t N, int32_t D, int32_t k, const float* query, const float* db, int64_t* idx, float* sims,
-                   int32_t* status, void* workspace, hipStream_t stream)
+int splatraster_retrieval_topk(int64_t Q, int64_t N, int32_t D, int32_t k, const float* query, const float* db, int64_t* idx,
+                               float* sims, int32_t* status, void* workspace, void* stream_)
 {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     if (!retrieval_args_ok(Q, N, D, k) || !status || !db) return SPLATRASTER_ERR_BAD_ARG;
     if (Q > 0 && (!query || !idx || !sims)) return SPLATRASTER_ERR_BAD_ARG;
     const RetrievalPlan p = retrieval_plan(Q, N, k);
@@ -375,9 +382,10 @@ int retrieval_topk(int64_t Q, int64_t N, int32_t D, int32_t k, const float* quer
     return SPLATRASTER_OK;
 }
 
-int pose_errors(int64_t B, const double* R_est, const double* t_est, const double* R_gt, const double* t_gt, const uint8_t* valid,
-                float* theta_deg, double* dist, hipStream_t stream)
+int splatraster_pose_errors(int64_t B, const double* R_est, const double* t_est, const double* R_gt, const double* t_gt,
+                            const uint8_t* valid, float* theta_deg, double* dist, void* stream_)
 {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     if (B < 0 || B >= (1ll << 31) * 256) return SPLATRASTER_ERR_BAD_ARG;
     if (B == 0) return SPLATRASTER_OK;
     if (!R_est || !t_est || !R_gt || !t_gt || !theta_deg || !dist) return SPLATRASTER_ERR_BAD_ARG;
@@ -387,8 +395,9 @@ int pose_errors(int64_t B, const double* R_est, const double* t_est, const doubl
     return SPLATRASTER_OK;
 }
 
-int pose_invert(int64_t B, const double* R, const double* t, double* R_out, double* t_out, hipStream_t stream)
+int splatraster_pose_invert(int64_t B, const double* R, const double* t, double* R_out, double* t_out, void* stream_)
 {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     if (B < 0 || B >= (1ll << 31) * 256) return SPLATRASTER_ERR_BAD_ARG;
     if (B == 0) return SPLATRASTER_OK;
     if (!R || !t || !R_out || !t_out) return SPLATRASTER_ERR_BAD_ARG;
@@ -397,4 +406,4 @@ int pose_invert(int64_t B, const double* R, const double* t, double* R_out, doub
     return SPLATRASTER_OK;
 }
 
-}  // namespace sr
+}  // extern "C"

@@ -313,23 +313,6 @@ sel_resolve_kernel(const uint32_t* __restrict__ surv, const uint64_t* __restrict
 // ---- host ---------------------------------------------------------------------------------------------------------------
 static inline unsigned sel_blocks(int64_t n) { return (unsigned)((n + SEL_THREADS - 1) / SEL_THREADS); }
 
-int landmark_scores(int64_t N, int32_t M, const float* points, const float* w2c, const double* K, const float* depths,
-                    int32_t width, int32_t height, int32_t* n_visible, int32_t* n_depth, double* depth_mean,
-                    double* depth_std, double* span, double* score, hipStream_t stream)
-{
-    if (N < 0 || M < 0 || width <= 0 || height <= 0 || !K) return SPLATRASTER_ERR_BAD_ARG;
-    if (N == 0) return SPLATRASTER_OK;
-    if (!points || !n_visible || !n_depth || !depth_mean || !depth_std || !span || !score) return SPLATRASTER_ERR_BAD_ARG;
-    if (M > 0 && (!w2c || !depths)) return SPLATRASTER_ERR_BAD_ARG;
-    if (N > ((int64_t)1 << 31) * SEL_THREADS) return SPLATRASTER_ERR_OVERFLOW;
-    SelK k;
-    for (int e = 0; e < 9; ++e) k.k[e] = K[e];
-    hipLaunchKernelGGL(landmark_scores_kernel, dim3(sel_blocks(N)), dim3(SEL_THREADS), 0, stream, N, M, points, w2c, k,
-                       depths, width, height, n_visible, n_depth, depth_mean, depth_std, span, score);
-    SR_LAUNCH_CHECK();
-    return SPLATRASTER_OK;
-}
-
 struct SelWs {
     uint32_t *keys, *vals, *keys_alt, *vals_alt, *flags, *surv, *count;
     uint64_t* total;
@@ -362,11 +345,36 @@ static SelWs sel_layout(char* base, int64_t N, int32_t num)
     return w;
 }
 
-size_t landmark_workspace_bytes(int64_t N, int32_t num) { return sel_layout(nullptr, N, num).bytes; }
+}  // namespace sr
 
-int landmark_select(int64_t N, const float* points, const double* score, int32_t num, double radius, int32_t* out_idx,
-                    int32_t* n_passes, void* workspace, hipStream_t stream)
+using namespace sr;
+
+extern "C" {
+
+int splatraster_landmark_scores(int64_t N, int32_t M, const float* points, const float* w2c, const double* K,
+                                const float* depths, int32_t width, int32_t height, int32_t* n_visible, int32_t* n_depth,
+                                double* depth_mean, double* depth_std, double* span, double* score, void* stream_)
 {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    if (N < 0 || M < 0 || width <= 0 || height <= 0 || !K) return SPLATRASTER_ERR_BAD_ARG;
+    if (N == 0) return SPLATRASTER_OK;
+    if (!points || !n_visible || !n_depth || !depth_mean || !depth_std || !span || !score) return SPLATRASTER_ERR_BAD_ARG;
+    if (M > 0 && (!w2c || !depths)) return SPLATRASTER_ERR_BAD_ARG;
+    if (N > ((int64_t)1 << 31) * SEL_THREADS) return SPLATRASTER_ERR_OVERFLOW;
+    SelK k;
+    for (int e = 0; e < 9; ++e) k.k[e] = K[e];
+    hipLaunchKernelGGL(landmark_scores_kernel, dim3(sel_blocks(N)), dim3(SEL_THREADS), 0, stream, N, M, points, w2c, k,
+                       depths, width, height, n_visible, n_depth, depth_mean, depth_std, span, score);
+    SR_LAUNCH_CHECK();
+    return SPLATRASTER_OK;
+}
+
+size_t splatraster_landmark_workspace_bytes(int64_t N, int32_t num) { return sel_layout(nullptr, N, num).bytes; }
+
+int splatraster_landmark_select(int64_t N, const float* points, const double* score, int32_t num, double radius,
+                                int32_t* out_idx, int32_t* n_passes, void* workspace, void* stream_)
+{
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     if (n_passes) *n_passes = 0;
     if (N < 1 || num < 1 || num > N || !points || !score || !out_idx || !workspace) return SPLATRASTER_ERR_BAD_ARG;
     if (!(radius > 0.0) || radius != radius || radius > 1e300) return SPLATRASTER_ERR_BAD_ARG;
@@ -418,4 +426,4 @@ int landmark_select(int64_t N, const float* points, const double* score, int32_t
     return SPLATRASTER_OK;
 }
 
-}  // namespace sr
+}  // extern "C"

@@ -17,7 +17,7 @@ import torch
 
 from . import _native
 from .grid_encoding import GridLayout
-from .rasterizer import _on_device, _prep, _stream
+from ._host import _on_device, _prep, _stream
 
 _SUPPORTED = ('supported: decoder.enc containing "hash", "tiled" or "dense" (a grid encoding) whose n_levels * n_features_per_level '
               'is a multiple of 16 up to 64, 2 <= decoder.num_layers <= 8, decoder.hidden_dim 32, 64 or 128, decoder.final_dim a '

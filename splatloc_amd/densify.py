@@ -4,7 +4,7 @@ from __future__ import annotations
 import torch
 
 from . import _native
-from .rasterizer import _ptr, _require_gpu, _stream, _on_device
+from ._host import _ptr, _require_gpu, _stream, _on_device
 
 
 def add_densification_stats(viewspace_grad: torch.Tensor, radii: torch.Tensor, xyz_gradient_accum: torch.Tensor,

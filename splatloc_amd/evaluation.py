@@ -16,7 +16,7 @@ import torch
 
 from . import _native
 from .fused import render_window
-from .rasterizer import _on_device, _prep, _ptr, _require_gpu, _stream
+from ._host import _on_device, _prep, _ptr, _require_gpu, _stream
 
 
 def eval_metrics(render: torch.Tensor, gt: torch.Tensor) -> torch.Tensor:

@@ -25,8 +25,8 @@ from typing import Optional
 import torch
 
 from . import _native
-from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, _on_device, _prep, _ptr, _require_gpu, _save,
-                         _saved, _stream, _window_compatible, rasterize_window)
+from ._host import _on_device, _prep, _ptr, _require_gpu, _stream
+from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, _save, _saved, _window_compatible, rasterize_window
 
 
 def activate_forward(xyz, f_dc, f_rest, scaling, rotation, opacity, extra, campos, active_sh_degree: int):

@@ -16,7 +16,7 @@ import torch
 
 from . import _native
 from .ply import header_bytes
-from .rasterizer import _stream
+from ._host import _ptr, _stream
 
 MAX_FRAMES = _native.FUSION_MAX_FRAMES
 MAX_FEAT_DIM = _native.FUSION_MAX_FEAT_DIM
@@ -106,10 +106,6 @@ def _free_bytes(dev) -> int:
     volume freed a moment ago sits there, and mem_get_info does not count it)"""
     free, _ = torch.cuda.mem_get_info(dev)
     return int(free) + int(torch.cuda.memory_reserved(dev)) - int(torch.cuda.memory_allocated(dev))
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
 
 
 class TSDFVolume:

@@ -13,7 +13,7 @@ from typing import Optional
 import torch
 
 from . import _native
-from .rasterizer import _on_device, _prep, _stream
+from ._host import _on_device, _prep, _stream
 
 _GRID_OTYPES = {"hashgrid": _native.GRID_HASH, "densegrid": _native.GRID_DENSE, "tiledgrid": _native.GRID_TILED}
 _GRID_TYPES = {"hash": _native.GRID_HASH, "dense": _native.GRID_DENSE, "tiled": _native.GRID_TILED}

@@ -21,7 +21,7 @@ from __future__ import annotations
 import torch
 
 from .knn import distCUDA2
-from .rasterizer import _require_gpu
+from ._host import _require_gpu
 
 C0 = 0.28209479177387814   # sh_utils.py: RGB2SH(rgb) = (rgb - 0.5) / C0
 

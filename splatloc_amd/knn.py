@@ -6,7 +6,7 @@ import ctypes as C
 import torch
 
 from . import _native
-from .rasterizer import _on_device
+from ._host import _on_device
 
 
 def distCUDA2(points: torch.Tensor) -> torch.Tensor:

@@ -8,13 +8,11 @@ fallback: without the device the calls raise.  Argument checks that need no data
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 import torch
 
 from . import _native, matching, pnp
-from .rasterizer import _stream
+from ._host import _stream, device, float_tensor, ptr, workspace
 
 MAX_K = 128                 # SPLATRASTER_RETRIEVAL_MAX_K
 RETRIEVAL_OK, RETRIEVAL_NONFINITE = 0, 1
@@ -24,21 +22,10 @@ Z_FLOOR = -10000.0          # test.py:344 kp_3d_mask
 _FLOATS = (torch.float16, torch.float32, torch.float64)
 
 
-def _device():
-    if not torch.cuda.is_available():
-        raise RuntimeError("localisation runs on the GPU: no HIP device is available")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
-
-
 def _descriptors(a, what):
     """numpy / torch f16, f32 or f64 [rows, D] (checked, not yet moved or converted)"""
-    t = torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else torch.as_tensor(a)
-    if t.dtype not in _FLOATS:
-        raise ValueError(f"{what} must be float16, float32 or float64, got {t.dtype}")
+    # converted first, so that a refused numpy array is named by its torch dtype like any other input
+    t = float_tensor(torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a, what, _FLOATS)
     if t.dim() != 2:
         raise ValueError(f"{what} must be [rows, D], got {tuple(t.shape)}")
     return t
@@ -60,15 +47,15 @@ def retrieve(query_desc, db_desc, k=10):
     k = int(k)
     if not 1 <= k <= min(N, MAX_K):
         raise ValueError(f"k = {k} must lie in [1, min(N, {MAX_K})] (N = {N})")
-    dev = _device()
+    dev = device("localisation")
     q = q.detach().to(device=dev, dtype=torch.float32).contiguous()
     d = d.detach().to(device=dev, dtype=torch.float32).contiguous()
     idx = torch.empty((Q, k), dtype=torch.int64, device=dev)
     sims = torch.empty((Q, k), dtype=torch.float32, device=dev)
     status = torch.empty(1, dtype=torch.int32, device=dev)
     lib = _native.load()
-    ws = torch.empty(max(int(lib.splatraster_retrieval_workspace_bytes(Q, N, D, k)), 1), dtype=torch.uint8, device=dev)
-    _native.check(lib.splatraster_retrieval_topk(Q, N, D, k, _ptr(q), _ptr(d), _ptr(idx), _ptr(sims), _ptr(status), _ptr(ws),
+    ws = workspace(lib.splatraster_retrieval_workspace_bytes(Q, N, D, k), dev)
+    _native.check(lib.splatraster_retrieval_topk(Q, N, D, k, ptr(q), ptr(d), ptr(idx), ptr(sims), ptr(status), ptr(ws),
                                                  _stream(dev)), "splatraster_retrieval_topk")
     if int(status.cpu()[0]) != RETRIEVAL_OK:   # the one host read of the call
         raise ValueError("descriptors contain non-finite entries")
@@ -137,14 +124,14 @@ def pose_errors(R_est, t_est, R_gt, t_gt, valid=None):
         valid = torch.as_tensor(valid).reshape(-1)
         if valid.shape[0] != B:
             raise ValueError(f"valid must hold {B} values, got {valid.shape[0]}")
-    dev = _device()
+    dev = device("localisation")
     f64 = lambda x: x.detach().to(device=dev, dtype=torch.float64).contiguous()  # noqa: E731
     Re, te, Rg, tg = f64(Re), f64(te), f64(Rg), f64(tg)
     v = None if valid is None else (valid.to(dev) != 0).to(torch.uint8).contiguous()
     theta = torch.empty(B, dtype=torch.float32, device=dev)
     dist = torch.empty(B, dtype=torch.float64, device=dev)
-    _native.check(_native.load().splatraster_pose_errors(B, _ptr(Re), _ptr(te), _ptr(Rg), _ptr(tg), _ptr(v), _ptr(theta),
-                                                         _ptr(dist), _stream(dev)), "splatraster_pose_errors")
+    _native.check(_native.load().splatraster_pose_errors(B, ptr(Re), ptr(te), ptr(Rg), ptr(tg), ptr(v), ptr(theta),
+                                                         ptr(dist), _stream(dev)), "splatraster_pose_errors")
     return theta, dist
 
 
@@ -242,8 +229,8 @@ class Localizer:
             raise ValueError(f"db_index refers to frames outside [0, {len(db_frames)})")
         kps, descs = [], []
         for qi, q in enumerate(queries):
-            kp = pnp._as_tensor(q["keypoints"], "keypoints")
-            ds = matching._float_tensor(q["descriptors"], "descriptors")
+            kp = float_tensor(q["keypoints"], "keypoints")
+            ds = float_tensor(q["descriptors"], "descriptors")
             if kp.dim() != 2 or kp.shape[1] != 2 or ds.dim() != 2 or ds.shape[1] != kp.shape[0]:
                 raise ValueError(f"query {qi}: keypoints must be [n, 2] and descriptors [C, n], got {tuple(kp.shape)} and "
                                  f"{tuple(ds.shape)}")
@@ -252,7 +239,7 @@ class Localizer:
             kps.append(kp)
             descs.append(ds)
         opt = pnp.options(**pnp.DEFAULTS)
-        dev = _device()
+        dev = device("localisation")
         lib = _native.load()
         stream = _stream(dev)
         if Q == 0:
@@ -301,28 +288,16 @@ class Localizer:
                 a = descs[qi].detach().to(device=dev, dtype=torch.float32).contiguous()
                 b = cand[index[qi]][1]
                 norms = torch.empty(n1 + n2, dtype=torch.float32, device=dev)
-                _native.check(lib.splatraster_match_cost(int(a.shape[0]), n1, n2, _ptr(a), _ptr(b), float(matching.THRESHOLD),
-                                                         _ptr(norms), C.c_void_p(cost.data_ptr() + 8 * off), stream),
-                              "splatraster_match_cost")
+                matching._cost_launch(a, b, matching.THRESHOLD, norms, cost, off, dev)
                 problems.append(matching.LsapProblem(off, min(n1, n2), max(n1, n2), int(n2 < n1), 0))
                 off += n1 * n2
                 total += min(n1, n2)
             B = len(problems)
-            table = (matching.LsapProblem * B)(*problems)
-            rows = torch.empty(total, dtype=torch.int64, device=dev)
-            cols = torch.empty(total, dtype=torch.int64, device=dev)
-            status = torch.empty(B, dtype=torch.int32, device=dev)
-            steps = torch.empty(B, dtype=torch.int32, device=dev)
-            ws = torch.empty(max(int(lib.splatraster_lsap_workspace_bytes(B, table)), 1), dtype=torch.uint8, device=dev)
-            _native.check(lib.splatraster_lsap(B, table, _ptr(cost), 0, _ptr(rows), _ptr(cols), _ptr(status), _ptr(steps),
-                                               _ptr(ws), stream), "splatraster_lsap")
+            rows, cols, status, _ = matching._lsap_launch(cost, problems, B, False, dev, total)
             # test.py:344 drops matched points with z <= -10000: decided for the chunk's frames at once
             z_ok = torch.stack([(cand[f][0][:, 2] > Z_FLOOR).all() for f in dict.fromkeys(index[qi] for qi in chunk)]).all()
             host = torch.cat([status, z_ok.to(torch.int32).reshape(1)]).cpu()   # the one host read of the chunk
-            if bool((host[:B] == matching.LSAP_INVALID).any()):
-                raise ValueError("matrix contains invalid numeric entries")
-            if bool((host[:B] == matching.LSAP_INFEASIBLE).any()):
-                raise ValueError("cost matrix is infeasible")
+            matching._lsap_raise(host[:B])
             o = 0
             for qi, (n1, n2) in zip(chunk, sizes):
                 k = min(n1, n2)
@@ -350,7 +325,7 @@ class Localizer:
             ninl[sel] = torch.stack([r["num_inliers"] for r in solved])
         R_c2w = torch.empty_like(R)
         t_c2w = torch.empty_like(t)
-        _native.check(lib.splatraster_pose_invert(Q, _ptr(R), _ptr(t), _ptr(R_c2w), _ptr(t_c2w), stream),
+        _native.check(lib.splatraster_pose_invert(Q, ptr(R), ptr(t), ptr(R_c2w), ptr(t_c2w), stream),
                       "splatraster_pose_invert")
         ok = success.reshape(-1, 1)
         return {"R_c2w": torch.where(ok.reshape(-1, 1, 1), R_c2w, retrieval_R), "t_c2w": torch.where(ok, t_c2w, retrieval_t),
@@ -364,7 +339,7 @@ class Localizer:
         Q = int(result["success"].shape[0])
         if tuple(gt.shape) != (Q, 4, 4) or gt.dtype not in _FLOATS:
             raise ValueError(f"gt_c2w must be a float [{Q}, 4, 4], got {gt.dtype} {tuple(gt.shape)}")
-        dev = _device()
+        dev = device("localisation")
         gt = gt.detach().to(device=dev, dtype=torch.float64)
         Rg, tg = gt[:, :3, :3].contiguous(), gt[:, :3, 3].contiguous()
         ok = result["success"]

@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _native
-from .rasterizer import _prep, _ptr, _require_gpu, _stream, _on_device
+from ._host import _prep, _ptr, _require_gpu, _stream, _on_device
 
 
 def _mapping_loss_launch(image, depth, marker, gt_image, gt_depth, kp, threshold: float, exposure, out=None):

@@ -14,7 +14,8 @@ import numpy as np
 import torch
 
 from . import _native
-from .rasterizer import _stream
+from ._host import _stream, device, float_tensor, workspace
+from ._host import ptr as _ptr   # tests and tools call matching._ptr
 
 MAX_NC = 65535          # SPLATRASTER_LSAP_MAX_NC: the solver's 16-bit column indices
 MAX_ELEMENTS = 1 << 31  # nr * nc must stay below
@@ -30,28 +31,6 @@ class LsapProblem(C.Structure):
                 ("reserved", C.c_int32)]
 
 
-def _device():
-    if not torch.cuda.is_available():
-        raise RuntimeError("2D-3D matching runs on the GPU: no HIP device is available")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
-
-
-def _float_tensor(a, what):
-    """numpy / torch f32 or f64 -> torch tensor (no device move)"""
-    if isinstance(a, np.ndarray):
-        if a.dtype not in (np.float32, np.float64):
-            raise ValueError(f"{what} must be float32 or float64, got {a.dtype}")
-        return torch.from_numpy(np.ascontiguousarray(a))
-    t = torch.as_tensor(a)
-    if t.dtype not in (torch.float32, torch.float64):
-        raise ValueError(f"{what} must be float32 or float64, got {t.dtype}")
-    return t
-
-
 def _check_cost(cost):
     shape = tuple(cost.shape) if hasattr(cost, "shape") else np.shape(cost)
     if len(shape) != 2:
@@ -63,27 +42,46 @@ def _check_cost(cost):
                          "(the larger dimension)")
     if lo * hi >= MAX_ELEMENTS:
         raise ValueError(f"cost matrix is {nr} x {nc}: the device solver takes fewer than 2^31 entries")
-    return _float_tensor(cost, "cost matrix")
+    return float_tensor(cost, "cost matrix")
 
 
-def _solve(costs, problems, B, maximize, dev, total):
-    """one splatraster_lsap call; returns (rows, cols, steps) device tensors, raises scipy's ValueError messages"""
+def _lsap_launch(costs, problems, B, maximize, dev, total):
+    """one splatraster_lsap call, no host read: (rows, cols, status, steps) device tensors"""
     lib = _native.load()
     table = (LsapProblem * max(B, 1))(*problems)
     rows = torch.empty(total, dtype=torch.int64, device=dev)
     cols = torch.empty(total, dtype=torch.int64, device=dev)
     status = torch.empty(B, dtype=torch.int32, device=dev)
     steps = torch.empty(B, dtype=torch.int32, device=dev)
-    ws = torch.empty(max(int(lib.splatraster_lsap_workspace_bytes(B, table)), 1), dtype=torch.uint8, device=dev)
+    ws = workspace(lib.splatraster_lsap_workspace_bytes(B, table), dev)
     st = lib.splatraster_lsap(B, table, _ptr(costs), 1 if maximize else 0, _ptr(rows), _ptr(cols), _ptr(status), _ptr(steps),
                               _ptr(ws), _stream(dev))
     _native.check(st, "splatraster_lsap")
-    sh = status.cpu()   # the one host read of the call
-    if bool((sh == LSAP_INVALID).any()):
+    return rows, cols, status, steps
+
+
+def _lsap_raise(status_host):
+    """scipy's ValueError messages for a host copy of the solver's status words"""
+    if bool((status_host == LSAP_INVALID).any()):
         raise ValueError("matrix contains invalid numeric entries")
-    if bool((sh == LSAP_INFEASIBLE).any()):
+    if bool((status_host == LSAP_INFEASIBLE).any()):
         raise ValueError("cost matrix is infeasible")
+
+
+def _solve(costs, problems, B, maximize, dev, total):
+    """one splatraster_lsap call; returns (rows, cols, steps) device tensors, raises scipy's ValueError messages"""
+    rows, cols, status, steps = _lsap_launch(costs, problems, B, maximize, dev, total)
+    _lsap_raise(status.cpu())   # the one host read of the call
     return rows, cols, steps
+
+
+def _cost_launch(a, b, threshold, norms, cost, offset, dev):
+    """splatraster_match_cost of a [D, N1], b [D, N2] (f32, device) into the N1 * N2 entries of `cost` (f64) from element
+    `offset`; norms [N1 + N2] is written too"""
+    st = _native.load().splatraster_match_cost(int(a.shape[0]), int(a.shape[1]), int(b.shape[1]), _ptr(a), _ptr(b),
+                                               float(threshold), _ptr(norms), C.c_void_p(cost.data_ptr() + 8 * offset),
+                                               _stream(dev))
+    _native.check(st, "splatraster_match_cost")
 
 
 def _orient(t, dev):
@@ -98,7 +96,7 @@ def linear_sum_assignment(cost, maximize=False, return_steps=False):
     cost: numpy or torch float32 / float64 [nr, nc] (float32 is widened exactly, as scipy does).  Raises scipy's ValueError
     for NaN / -inf entries ("matrix contains invalid numeric entries") and for "cost matrix is infeasible"."""
     t = _check_cost(cost)
-    dev = _device()
+    dev = device("2D-3D matching")
     nr, nc = int(t.shape[0]), int(t.shape[1])
     if nr == 0 or nc == 0:
         e = torch.empty(0, dtype=torch.int64, device=dev)
@@ -113,7 +111,7 @@ def linear_sum_assignment_batch(costs, maximize=False, return_steps=False):
     """linear_sum_assignment of every matrix of `costs` (a sequence of differently shaped matrices) in one launch: a list of
     (row_ind, col_ind).  One host read for the whole batch; an invalid or infeasible member raises for the batch."""
     ts = [_check_cost(c) for c in costs]
-    dev = _device()
+    dev = device("2D-3D matching")
     pieces, problems, shapes, off, total = [], [], [], 0, 0
     for t in ts:
         nr, nc = int(t.shape[0]), int(t.shape[1])
@@ -140,8 +138,8 @@ def linear_sum_assignment_batch(costs, maximize=False, return_steps=False):
 
 
 def _check_descriptors(d1, d2):
-    a = _float_tensor(d1, "descriptors1")
-    b = _float_tensor(d2, "descriptors2")
+    a = float_tensor(d1, "descriptors1")
+    b = float_tensor(d2, "descriptors2")
     if a.dim() != 2 or b.dim() != 2:
         raise ValueError(f"descriptors must be [D, N], got {tuple(a.shape)} and {tuple(b.shape)}")
     if a.shape[0] != b.shape[0]:
@@ -160,7 +158,7 @@ def match_descriptors(d1, d2, threshold=THRESHOLD, return_steps=False):
     matches [2, min(N1, N2)] (int64: d1 index, d2 index, ascending by d1 index) and sims [min(N1, N2)] (f32, the thresholded
     similarity of each pair, 0 for the pairs below threshold the assignment still makes)."""
     a, b = _check_descriptors(d1, d2)
-    dev = _device()
+    dev = device("2D-3D matching")
     D, N1, N2 = int(a.shape[0]), int(a.shape[1]), int(b.shape[1])
     if N1 == 0 or N2 == 0:
         m = torch.empty((2, 0), dtype=torch.int64, device=dev)
@@ -168,18 +166,15 @@ def match_descriptors(d1, d2, threshold=THRESHOLD, return_steps=False):
         return (m, s, 0) if return_steps else (m, s)
     a = a.detach().to(device=dev, dtype=torch.float32).contiguous()
     b = b.detach().to(device=dev, dtype=torch.float32).contiguous()
-    lib = _native.load()
     norms = torch.empty(N1 + N2, dtype=torch.float32, device=dev)
     cost = torch.empty(N1 * N2, dtype=torch.float64, device=dev)
-    stream = _stream(dev)
-    _native.check(lib.splatraster_match_cost(D, N1, N2, _ptr(a), _ptr(b), float(threshold), _ptr(norms), _ptr(cost), stream),
-                  "splatraster_match_cost")
+    _cost_launch(a, b, threshold, norms, cost, 0, dev)
     K = min(N1, N2)
     p = LsapProblem(0, K, max(N1, N2), int(N2 < N1), 0)
     rows, cols, steps = _solve(cost, [p], 1, False, dev, K)
     sims = torch.empty(K, dtype=torch.float32, device=dev)
-    _native.check(lib.splatraster_match_sims(D, N1, N2, _ptr(a), _ptr(b), _ptr(norms), float(threshold), K, _ptr(rows),
-                                             _ptr(cols), _ptr(sims), stream), "splatraster_match_sims")
+    _native.check(_native.load().splatraster_match_sims(D, N1, N2, _ptr(a), _ptr(b), _ptr(norms), float(threshold), K, _ptr(rows),
+                                                        _ptr(cols), _ptr(sims), _stream(dev)), "splatraster_match_sims")
     m = torch.stack([rows, cols], dim=0)
     return (m, sims, int(steps.cpu()[0])) if return_steps else (m, sims)
 
@@ -219,7 +214,7 @@ def frustum_candidates(points, w2c, K, width, height, marker=None, kp_mask=None,
     Key-Gaussian mode: also marker > marker_threshold; then every pixel of kp_mask == 1 ([height, width], row-major order) is
     back-projected with depth [height, width], c2w [4,4] and kp_K [3,3] and paired with its nearest kept point when closer
     than 0.1 (ties: the smaller index).  Returns device tensors (idx int64 [n], xyz f32 [n,3], uv f64 [n,2])."""
-    pts = _float_tensor(points, "points")
+    pts = float_tensor(points, "points")
     if pts.dim() != 2 or pts.shape[1] != 3:
         raise ValueError(f"points must be [N, 3], got {tuple(pts.shape)}")
     width, height = int(width), int(height)
@@ -244,7 +239,7 @@ def frustum_candidates(points, w2c, K, width, height, marker=None, kp_mask=None,
         c2w_h = _host_f64(c2w, (4, 4), "c2w")
         kK = _host_f64(kp_K, (3, 3), "kp_K")
         kp4 = torch.tensor([kK[0, 0], kK[1, 1], kK[0, 2], kK[1, 2]], dtype=torch.float64)
-    dev = _device()
+    dev = device("2D-3D matching")
     p = pts.detach().to(device=dev, dtype=torch.float32).contiguous()
     cap = width * height if key else N
     idx = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
@@ -252,7 +247,7 @@ def frustum_candidates(points, w2c, K, width, height, marker=None, kp_mask=None,
     uv = torch.empty((max(cap, 1), 2), dtype=torch.float64, device=dev)
     count = torch.zeros(1, dtype=torch.int64, device=dev)
     lib = _native.load()
-    ws = torch.empty(int(lib.splatraster_frustum_workspace_bytes(N, width, height)), dtype=torch.uint8, device=dev)
+    ws = workspace(lib.splatraster_frustum_workspace_bytes(N, width, height), dev)
     hp = lambda t: C.cast(t.numpy().ctypes.data, C.c_void_p)  # noqa: E731
     if key:
         m = mk.detach().to(device=dev, dtype=torch.float32).contiguous()

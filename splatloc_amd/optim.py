@@ -17,7 +17,7 @@ import ctypes as C
 import torch
 
 from . import _native
-from .rasterizer import _require_gpu, _stream, _on_device
+from ._host import _require_gpu, _stream, _on_device
 
 
 class Adam(torch.optim.Adam):

@@ -15,7 +15,8 @@ import numpy as np
 import torch
 
 from . import _native
-from .rasterizer import _stream
+from ._host import _stream, device, float_tensor, workspace
+from ._host import ptr as _ptr   # tests call pnp._ptr
 
 MAX_N = 1 << 20          # SPLATRASTER_PNP_MAX_N
 BATCH = 1024             # SPLATRASTER_PNP_BATCH: trials per round trip
@@ -35,16 +36,6 @@ class PnpOptions(C.Structure):
     """struct splatraster_pnp_options"""
     _fields_ = [("max_error_px", C.c_double), ("min_inlier_ratio", C.c_double), ("confidence", C.c_double),
                 ("seed", C.c_uint64), ("min_num_trials", C.c_int32), ("max_num_trials", C.c_int32)]
-
-
-def _device():
-    if not torch.cuda.is_available():
-        raise RuntimeError("absolute pose estimation runs on the GPU: no HIP device is available")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
 
 
 def options(max_error_px=12.0, min_inlier_ratio=0.01, min_num_trials=1000, max_num_trials=100000, confidence=0.9999, seed=0):
@@ -102,20 +93,9 @@ def _K_intrinsics(K):
     return fx, fy, cx, cy
 
 
-def _as_tensor(a, what):
-    if isinstance(a, np.ndarray):
-        if a.dtype not in (np.float32, np.float64):
-            raise ValueError(f"{what} must be float32 or float64, got {a.dtype}")
-        return torch.from_numpy(np.ascontiguousarray(a))
-    t = torch.as_tensor(a)
-    if t.dtype not in (torch.float32, torch.float64):
-        raise ValueError(f"{what} must be float32 or float64, got {t.dtype}")
-    return t
-
-
 def _points(p2d, p3d):
     """checked (points2D [N, 2], points3D [N, 3]) tensors, not yet moved or widened"""
-    a, b = _as_tensor(p2d, "points2D"), _as_tensor(p3d, "points3D")
+    a, b = float_tensor(p2d, "points2D"), float_tensor(p3d, "points3D")
     if a.dim() != 2 or a.shape[1] != 2:
         raise ValueError(f"points2D must be [N, 2], got {tuple(a.shape)}")
     if b.dim() != 2 or b.shape[1] != 3:
@@ -146,7 +126,7 @@ def _solve(items, opt, dev):
     mask = torch.empty(max(off, 1), dtype=torch.uint8, device=dev)
     status = torch.empty(B, dtype=torch.int32, device=dev)
     trials = torch.empty(B, dtype=torch.int32, device=dev)
-    ws = torch.empty(max(int(lib.splatraster_pnp_workspace_bytes(B, tab, C.byref(opt))), 1), dtype=torch.uint8, device=dev)
+    ws = workspace(lib.splatraster_pnp_workspace_bytes(B, tab, C.byref(opt)), dev)
     st = lib.splatraster_pnp(B, tab, C.byref(opt), _ptr(p2), _ptr(p3), _ptr(R), _ptr(t), _ptr(ninl), _ptr(mask), _ptr(status),
                              _ptr(trials), _ptr(ws), _stream(dev))
     _native.check(st, "splatraster_pnp")
@@ -179,7 +159,7 @@ def estimate_absolute_pose_batch(problems, max_error_px=12.0, min_inlier_ratio=0
         items.append((a, b, _K_intrinsics(p[2])))
     if len(items) > 65535:
         raise ValueError("at most 65535 problems per batch")
-    dev = _device()
+    dev = device("absolute pose estimation")
     run = [i for i, (a, _, _) in enumerate(items) if a.shape[0] >= 4]
     solved = _solve([items[i] for i in run], opt, dev) if run else []
     out = [None] * len(items)
@@ -232,7 +212,7 @@ def _absolute_pose(points2D, points3D, camera, **kw):
     intr = camera_intrinsics(camera)
     if a.shape[0] < 4:
         return {"success": False}, None
-    r = _solve([(a, b, intr)], options(**opt_kw), _device())[0]
+    r = _solve([(a, b, intr)], options(**opt_kw), device("absolute pose estimation"))[0]
     if not bool(r["success"].cpu()):
         return {"success": False}, None
     R = r["R"].cpu().numpy()

@@ -147,7 +147,8 @@ def refine_pose(render_target, gaussians: dict, camera, W2C_init: torch.Tensor, 
                                      background, on_step)
     import ctypes as C
     from . import _native
-    from .rasterizer import GaussianRasterizationSettings, _stream, view_backward, view_forward
+    from ._host import _stream
+    from .rasterizer import GaussianRasterizationSettings, view_backward, view_forward
     lib = _native.load()
     dev = gaussians["means3D"].device
     tgt_c, tgt_d = render_target

@@ -23,6 +23,7 @@ import torch
 from torch import nn
 
 from . import _native
+from ._host import _empty, _on_device, _prep, _ptr, _require_gpu, _stream  # noqa: F401 (re-exported)
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -38,70 +39,6 @@ class GaussianRasterizationSettings(NamedTuple):
     campos: torch.Tensor
     prefiltered: bool
     debug: bool
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _prep(t: Optional[torch.Tensor], device) -> Optional[torch.Tensor]:
-    """contiguous fp32 on `device`, 16-byte aligned (kernels use 128-bit loads).  The common case — the
-    tensor already is all that — costs three attribute checks (host time is what bounds small frames)."""
-    if t is None or t.numel() == 0:
-        return None
-    if t.dtype is torch.float32 and t.device == device and t.is_contiguous() and not (t.data_ptr() & 15):
-        return t.detach() if t.requires_grad else t
-    t = t.detach()
-    if t.dtype != torch.float32 or t.device != device or not t.is_contiguous():
-        t = t.to(device=device, dtype=torch.float32).contiguous()
-    if t.data_ptr() % 16:
-        t = t.clone()
-    return t
-
-
-_EMPTY: dict = {}
-
-
-def _empty(device) -> torch.Tensor:
-    """one shared zero-element placeholder per device for the `None` slots of save_for_backward"""
-    e = _EMPTY.get(device)
-    if e is None:
-        e = _EMPTY[device] = torch.empty(0, device=device)
-    return e
-
-
-class _on_device:
-    """`with torch.cuda.device(dev)` only when `dev` is not already current (the context manager costs ~10 us)."""
-
-    def __init__(self, device):
-        self.ctx = None if torch.cuda.current_device() == device.index else torch.cuda.device(device)
-
-    def __enter__(self):
-        if self.ctx is not None:
-            self.ctx.__enter__()
-
-    def __exit__(self, *a):
-        if self.ctx is not None:
-            self.ctx.__exit__(*a)
-
-
-_RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-
-
-def _stream(device) -> C.c_void_p:
-    """the hipStream_t torch would launch on right now (device's current stream).  The raw getter costs ~0.3 us; building a
-    torch.cuda.Stream object ~8 us — five of those per refinement iteration were 10 % of its host time."""
-    if _RAW_STREAM is not None:
-        idx = device.index
-        return C.c_void_p(_RAW_STREAM(torch.cuda.current_device() if idx is None else idx))
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _require_gpu(t: torch.Tensor, name: str) -> None:
-    if not t.is_cuda:
-        raise RuntimeError(
-            f"splatloc_amd rasterizer: `{name}` is on {t.device}; tensors must be on a ROCm device "
-            "(the HIP kernels are the only implementation, there is no CPU fallback)")
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,

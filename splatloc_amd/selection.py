@@ -13,16 +13,10 @@ import numpy as np
 import torch
 
 from . import _native
-from .rasterizer import _stream
+from ._host import _stream, device, ptr, workspace
 
 WIDTH, HEIGHT = 640, 480   # the reference's inside_check hard-codes 640 x 480
 RADIUS = 18.0
-
-
-def _device():
-    if not torch.cuda.is_available():
-        raise RuntimeError("landmark selection runs on the GPU: no HIP device is available")
-    return torch.device("cuda", torch.cuda.current_device())
 
 
 def _as(t, dtype, device) -> torch.Tensor:
@@ -57,7 +51,7 @@ def landmark_scores(points, w2cs, K, depths, width: int = WIDTH, height: int = H
     Kh = torch.as_tensor(K).detach().to("cpu", torch.float64).contiguous()
     if tuple(Kh.shape) != (3, 3):
         raise ValueError(f"K must be [3, 3], got {tuple(Kh.shape)}")
-    dev = _device()
+    dev = device("landmark selection")
     N, M = int(points.shape[0]), int(w2cs.shape[0])
     p = _as(points, torch.float32, dev)
     w = _as(w2cs, torch.float32, dev)
@@ -70,7 +64,6 @@ def landmark_scores(points, w2cs, K, depths, width: int = WIDTH, height: int = H
         out[k] = torch.empty(N, dtype=torch.float64, device=dev)
     if N == 0:
         return out
-    ptr = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None  # noqa: E731
     st = _native.load().splatraster_landmark_scores(
         N, M, ptr(p), ptr(w), C.cast(Kh.numpy().ctypes.data, C.c_void_p), ptr(d), width, height,
         ptr(out["n_visible"]), ptr(out["n_depth"]), ptr(out["depth_mean"]), ptr(out["depth_std"]), ptr(out["span"]),
@@ -95,7 +88,7 @@ def select_landmarks(points, scores, num: int, radius: float = RADIUS, return_pa
     radius = float(radius)
     if not (radius > 0.0 and np.isfinite(radius)):
         raise ValueError(f"radius must be positive and finite, got {radius}")
-    dev = _device()
+    dev = device("landmark selection")
     p = _as(points, torch.float32, dev)
     s = _as(scores, torch.float64, dev)
     if not bool(torch.isfinite(p).all()):
@@ -105,7 +98,7 @@ def select_landmarks(points, scores, num: int, radius: float = RADIUS, return_pa
         raise ValueError(f"only {distinct} distinct positions for {num} landmarks: the reference would halve the radius to 0 "
                          "and repeat points")
     lib = _native.load()
-    ws = torch.empty(int(lib.splatraster_landmark_workspace_bytes(N, num)), dtype=torch.uint8, device=dev)
+    ws = workspace(lib.splatraster_landmark_workspace_bytes(N, num), dev)
     out = torch.empty(num, dtype=torch.int32, device=dev)
     passes = C.c_int32(0)
     st = lib.splatraster_landmark_select(N, C.c_void_p(p.data_ptr()), C.c_void_p(s.data_ptr()), num, radius,
