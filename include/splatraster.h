@@ -183,8 +183,10 @@ int splatraster_backward(const splatraster_settings* s, int32_t P, int64_t R,
  * stable: every (view, tile) list is in (depth, index) order); only the float-atomic summation order of the
  * gradients differs, as it does from run to run anyway.  All views share the settings' image size, channel
  * count, scale modifier and background; tanfovx / tanfovy are per view (settings->tanfovx/y are ignored here).
- * Colours must be precomputed (`colors_precomp`, SplatLoc's configuration): view-dependent SH colours and the
- * pose-gradient extension stay on the per-view call (SPLATRASTER_ERR_UNSUPPORTED here).
+ * Colours must be precomputed (`colors_precomp`, SplatLoc's configuration): view-dependent SH colours stay on the
+ * per-view call (SPLATRASTER_ERR_UNSUPPORTED here).  The pose-gradient extension has a window entry point of its own,
+ * splatraster_backward_window_cameras below: the camera gradients of every view and NO parameter gradients (pose refinement
+ * freezes the map); splatraster_backward_window itself returns parameter gradients only.
  */
 #define SPLATRASTER_MAX_WINDOW_VIEWS 8
 
@@ -246,6 +248,26 @@ int splatraster_backward_window(const splatraster_settings* s, int32_t n_views, 
                                 float* dL_drotations, /* [P,4] or NULL */
                                 float* dL_dcov3D,     /* [P,6] or NULL */
                                 void* stream);
+
+/* Camera gradients of the n_views <= 8 views of a window, and nothing per Gaussian (pose refinement of a window of query frames
+ * against a frozen map): the accumulator fill and the compositing backward of splatraster_backward_window (the
+ * deterministic debug mode included), then ONE kernel with a thread per (view, Gaussian) that reduces the 27 partial sums of
+ * every view — per wave, per block, one atomic per value and block into one of the view's replicated sets, the view's last block
+ * (a ticket; no block waits for another) writes the view's outputs.  dL_dviewmatrix / dL_dprojmatrix [n_views,4,4] and
+ * dL_dcampos [n_views,3] (may be NULL; zeros: a window has precomputed colours only) are written in full, zeros for a view that
+ * sees nothing and when P == 0.  views[v].dL_dmeans2D is not written and may be NULL.  `workspace`: device memory of
+ * splatraster_window_camera_workspace_bytes(n_views) bytes (0 for n_views outside 1 .. 8), zeroed by this call on `stream`.
+ * n_views outside 1 .. 8 or a NULL required pointer: SPLATRASTER_ERR_BAD_ARG before any launch.  No host synchronisation. */
+size_t splatraster_window_camera_workspace_bytes(int32_t n_views);
+int splatraster_backward_window_cameras(const splatraster_settings* s, int32_t n_views, const splatraster_window_view* views,
+                                        int32_t P, const int64_t* num_rendered, const float* bg, const float* means3D,
+                                        const float* colors_precomp, const float* scales, const float* rotations,
+                                        const float* cov3D_precomp, void* geometry, const void* binning, const void* image,
+                                        void* workspace,
+                                        float* dL_dviewmatrix, /* [n_views,4,4] */
+                                        float* dL_dprojmatrix, /* [n_views,4,4] */
+                                        float* dL_dcampos,     /* [n_views,3] or NULL */
+                                        void* stream);
 
 /* The same backward, writing the gradients of SplatLoc's RAW parameters directly (SH degree 0, scales + rotations; what
  * gaussian_model.py:78-105 and gaussian_renderer/__init__.py:84-102 put between the optimiser tensors and the rasterizer call):
@@ -885,6 +907,28 @@ int splatraster_l1_rgbd_loss(int64_t n_color, const float* color, const float* t
 int splatraster_pose_step(const float* dL_dviewmatrix, const float* dL_dprojmatrix, const float* dL_dcampos, const float* W2C_init,
                           const float* projection_matrix, float lr_rot, float lr_trans, float beta1, float beta2, float eps,
                           int advance, float* state, float* viewmatrix, float* projmatrix, float* campos, void* stream);
+
+/* The two calls above for the 1 <= n_views <= 8 frames of a window, ONE launch each (splatloc_amd.pose.refine_poses).
+ * splatraster_l1_rgbd_loss_window: every view has n_color colour and n_depth depth elements; loss_out[v] += L of view v; the
+ * gradient planes are bit-identical to n_views single calls (a sign times a constant per element).  target_depth NULL in a
+ * view: no depth term there, its g_depth (when given) is zeroed. */
+typedef struct splatraster_l1_view {
+    const float* color;        /* [n_color] */
+    const float* target_color; /* [n_color] */
+    const float* depth;        /* [n_depth]; may be NULL when target_depth is */
+    const float* target_depth; /* [n_depth] or NULL */
+    float* g_color;            /* [n_color] out */
+    float* g_depth;            /* [n_depth] out, or NULL */
+} splatraster_l1_view;
+int splatraster_l1_rgbd_loss_window(int32_t n_views, const splatraster_l1_view* views /* host array */, int64_t n_color,
+                                    int64_t n_depth, float depth_weight, float* loss_out /* [n_views] device */, void* stream);
+/* splatraster_pose_step for n cameras, one thread per camera, the single call's arithmetic: state [n,20], dL_dviewmatrix /
+ * dL_dprojmatrix [n,16], dL_dcampos [n,3] or NULL, W2C_init [n,4,4], ONE projection_matrix [4,4] shared by the cameras; outputs
+ * viewmatrix / projmatrix [n,4,4], campos [n,3] or NULL.  A camera's result does not depend on its slot or on n. */
+int splatraster_pose_step_window(int32_t n, const float* dL_dviewmatrix, const float* dL_dprojmatrix, const float* dL_dcampos,
+                                 const float* W2C_init, const float* projection_matrix, float lr_rot, float lr_trans, float beta1,
+                                 float beta2, float eps, int advance, float* state, float* viewmatrix, float* projmatrix,
+                                 float* campos, void* stream);
 
 /* ---- per-stage timing (HIP events on the launch stream) ----------------------------- */
 

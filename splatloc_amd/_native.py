@@ -48,6 +48,11 @@ class WindowView(C.Structure):
                 ("dL_dmeans2D", C.c_void_p), ("dL_dout_last", C.c_void_p), ("color_grad_channels", C.c_int32)]
 
 
+class L1View(C.Structure):
+    """struct splatraster_l1_view"""
+    _fields_ = [(n, C.c_void_p) for n in ("color", "target_color", "depth", "target_depth", "g_color", "g_depth")]
+
+
 class LossView(C.Structure):
     """struct splatraster_loss_view"""
     _fields_ = [(n, C.c_void_p) for n in ("image", "depth", "marker", "gt_image", "gt_depth", "kp", "exposure", "g_image", "g_depth",
@@ -145,6 +150,9 @@ SYMBOLS = {
                                           + [_vp] * 6),
     "splatraster_backward_window": (C.c_int, [C.POINTER(Settings), _i32, C.POINTER(WindowView), _i32, C.POINTER(_i64)]
                                     + [_vp] * 16),
+    "splatraster_window_camera_workspace_bytes": (_sz, [_i32]),
+    "splatraster_backward_window_cameras": (C.c_int, [C.POINTER(Settings), _i32, C.POINTER(WindowView), _i32, C.POINTER(_i64)]
+                                            + [_vp] * 14),
     "splatraster_forward_window_geometry_raw": (C.c_int, [C.POINTER(Settings), _i32, C.POINTER(WindowView), _i32, _vp, C.POINTER(RawForward),
                                                           _vp, C.POINTER(_i64), _vp]),
     "splatraster_backward_window_raw": (C.c_int, [C.POINTER(Settings), _i32, C.POINTER(WindowView), _i32, C.POINTER(_i64)]
@@ -224,6 +232,8 @@ SYMBOLS = {
     "splatraster_eval_metrics": (C.c_int, [_i32, _i32, _i32] + [_vp] * 5),
     "splatraster_l1_rgbd_loss": (C.c_int, [_i64, _vp, _vp, _i64, _vp, _vp, C.c_float, _vp, _vp, _vp, _vp]),
     "splatraster_pose_step": (C.c_int, [_vp] * 5 + [C.c_float] * 5 + [C.c_int] + [_vp] * 5),
+    "splatraster_l1_rgbd_loss_window": (C.c_int, [_i32, C.POINTER(L1View), _i64, _i64, C.c_float, _vp, _vp]),
+    "splatraster_pose_step_window": (C.c_int, [_i32] + [_vp] * 5 + [C.c_float] * 5 + [C.c_int] + [_vp] * 5),
     "splatraster_error_string": (C.c_char_p, [C.c_int]),
     "splatraster_last_hip_error": (C.c_char_p, []),
     "splatraster_abi_version": (C.c_int, []),

@@ -586,6 +586,76 @@ static int window_render(const splatraster_settings* s, int32_t V, const splatra
     return launch_composite_fwd(*s, P, V, R, g, b, im, featp, bg, outs, stream);
 }
 
+// What every backward of a window starts with (after its own argument checks): the per-view gradient planes, the fill of the
+// accumulator rows (`pose`: and of the camera-gradient sets right behind them) and the compositing backward into them, the
+// deterministic debug mode included.  `out`: the buffer views, cameras and gradient planes the per-Gaussian pass then reads.
+struct BwdRows { GeomView g; BinView b; WinCams cams; WinGrad grads; };
+static int window_accumulate(const splatraster_settings* s, int32_t V, const splatraster_window_view* views, int32_t P, int64_t R,
+                             const float* bg, const float* colors_precomp, bool sh_colours, void* geometry, const void* binning,
+                             const void* image, bool pose, hipStream_t stream, BwdRows* out)
+{
+    int st = check_row_index_range(P, V, s->channels);
+    if (st) return st;
+    const int W = s->image_width, H = s->image_height;
+    GeomView& g = out->g;
+    BinView& b = out->b;
+    g = geom_view(geometry, P, V);
+    b = bin_view(const_cast<void*>(binning), P, V, R, W, H, s->channels);
+    ImgView im = img_view(const_cast<void*>(image), W, H, V);
+    const int C = s->channels;
+    const float* feat = sh_colours ? g.rgb : colors_precomp;
+    WinCams& cams = out->cams;
+    WinGrad& grads = out->grads;
+    cams = make_cams(V, views);
+    grads = WinGrad{};
+    grads.gc = C;
+    for (int v = 0; v < V; ++v) {
+        const int gcv = views[v].color_grad_channels;
+        if (gcv < 0 || gcv > C) return SPLATRASTER_ERR_BAD_ARG;
+        if (gcv != 0 && gcv < C) grads.gc = gcv;
+    }
+    for (int v = 0; v < V; ++v) {   // one convention per launch: all views split the last channel off, or none does
+        const int gcv = views[v].color_grad_channels ? views[v].color_grad_channels : C;
+        if (gcv != grads.gc) return SPLATRASTER_ERR_BAD_ARG;
+        grads.dL_dlast[v] = grads.gc < C ? views[v].dL_dout_last : nullptr;
+    }
+    for (int v = 0; v < V; ++v) {
+        grads.out_color[v] = views[v].out_color;
+        grads.out_depth[v] = views[v].out_depth;
+        grads.dL_dcolor[v] = views[v].dL_dout_color;
+        grads.dL_ddepth[v] = views[v].dL_dout_depth;
+        grads.dL_dalpha[v] = views[v].dL_dout_alpha;
+        grads.dL_dmeans2D[v] = views[v].dL_dmeans2D;
+    }
+    // zero the accumulator rows (outside the stage bracket: the stage is the kernel alone, so its
+    // figure can be held against the per-kernel rocprofv3 average)
+    const size_t gacc_n = gacc_total_floats(C, (size_t)P, (size_t)V);   // shared colour rows + per-(view, Gaussian) rows
+    const bool det = g_deterministic != 0;
+    long long* gacc64 = nullptr;   // debug mode only: stream-ordered scratch, freed below (never part of `binning`)
+    if (det) {
+        SR_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&gacc64), sizeof(long long) * gacc_n, stream));
+        SR_HIP_CHECK(hipMemsetAsync(gacc64, 0, sizeof(long long) * gacc_n, stream));
+    }
+    // (one fill: the camera-gradient accumulator sets lie directly behind the rows)
+    const size_t fill = pose ? (size_t)(reinterpret_cast<char*>(b.pose_acc) - reinterpret_cast<char*>(b.gacc)) + POSE_ACC_BYTES
+                             : sizeof(float) * gacc_n;
+    SR_HIP_CHECK(hipMemsetAsync(b.gacc, 0, fill, stream));
+    grads.bg = bg;
+    grads.bg_channels = bg ? s->bg_channels : 0;
+    {
+        StageTimer t(SPLATRASTER_STAGE_COMPOSITE_BWD, stream);
+        // deterministic mode: the kernel runs twice — per-element max of |partial| (into the zeroed float rows), then the
+        // fixed-point sums scaled by that maximum (composite_bwd.hip acc_add)
+        if (det) st = launch_composite_bwd(*s, P, V, R, g, b, im, (C % 4) ? b.featp : feat, C, grads, b.gacc, gacc64, 0, stream);
+        if (!st) st = launch_composite_bwd(*s, P, V, R, g, b, im, (C % 4) ? b.featp : feat, C, grads, b.gacc, gacc64, 1, stream);
+    }
+    if (det) {
+        if (!st) st = launch_fixed_to_float((int64_t)gacc_n, gacc64, b.gacc, gacc_det_headroom_drop(C, V), stream);
+        (void)hipFreeAsync(gacc64, stream);
+    }
+    return st;
+}
+
 // Backward of the window: one compositing grid over the V views into per-(view, Gaussian) accumulator rows, then
 // ONE per-Gaussian pass that sums the views into a single set of parameter gradients.
 static int window_backward(const splatraster_settings* s, int32_t V, const splatraster_window_view* views, int32_t P,
@@ -619,63 +689,15 @@ static int window_backward(const splatraster_settings* s, int32_t V, const splat
     if (!shs && (!colors_precomp || (!dL_dcolors && !raw))) return SPLATRASTER_ERR_BAD_ARG;
     if (cov3D_precomp ? !dL_dcov3D : (!scales || !rotations || ((!dL_dscales || !dL_drotations) && !raw)))
         return SPLATRASTER_ERR_BAD_ARG;
-    st = check_row_index_range(P, V, s->channels);
+    BwdRows rows;
+    st = window_accumulate(s, V, views, P, R, bg, colors_precomp, shs != nullptr, geometry, binning, image,
+                           dL_dviewmatrix && dL_dprojmatrix, stream, &rows);
     if (st) return st;
-    const int W = s->image_width, H = s->image_height;
-    GeomView g = geom_view(geometry, P, V);
-    BinView b = bin_view(const_cast<void*>(binning), P, V, R, W, H, s->channels);
-    ImgView im = img_view(const_cast<void*>(image), W, H, V);
+    const GeomView& g = rows.g;
+    const BinView& b = rows.b;
+    const WinCams& cams = rows.cams;
+    const WinGrad& grads = rows.grads;
     const int C = s->channels;
-    const float* feat = shs ? g.rgb : colors_precomp;
-    const WinCams cams = make_cams(V, views);
-    WinGrad grads{};
-    grads.gc = C;
-    for (int v = 0; v < V; ++v) {
-        const int gcv = views[v].color_grad_channels;
-        if (gcv < 0 || gcv > C) return SPLATRASTER_ERR_BAD_ARG;
-        if (gcv != 0 && gcv < C) grads.gc = gcv;
-    }
-    for (int v = 0; v < V; ++v) {   // one convention per launch: all views split the last channel off, or none does
-        const int gcv = views[v].color_grad_channels ? views[v].color_grad_channels : C;
-        if (gcv != grads.gc) return SPLATRASTER_ERR_BAD_ARG;
-        grads.dL_dlast[v] = grads.gc < C ? views[v].dL_dout_last : nullptr;
-    }
-    for (int v = 0; v < V; ++v) {
-        grads.out_color[v] = views[v].out_color;
-        grads.out_depth[v] = views[v].out_depth;
-        grads.dL_dcolor[v] = views[v].dL_dout_color;
-        grads.dL_ddepth[v] = views[v].dL_dout_depth;
-        grads.dL_dalpha[v] = views[v].dL_dout_alpha;
-        grads.dL_dmeans2D[v] = views[v].dL_dmeans2D;
-    }
-    // zero the accumulator rows (outside the stage bracket: the stage is the kernel alone, so its
-    // figure can be held against the per-kernel rocprofv3 average)
-    const size_t gacc_n = gacc_total_floats(C, (size_t)P, (size_t)V);   // shared colour rows + per-(view, Gaussian) rows
-    const bool det = g_deterministic != 0;
-    long long* gacc64 = nullptr;   // debug mode only: stream-ordered scratch, freed below (never part of `binning`)
-    if (det) {
-        SR_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&gacc64), sizeof(long long) * gacc_n, stream));
-        SR_HIP_CHECK(hipMemsetAsync(gacc64, 0, sizeof(long long) * gacc_n, stream));
-    }
-    const bool pose = dL_dviewmatrix && dL_dprojmatrix;
-    // (one fill: the camera-gradient accumulator sets lie directly behind the rows)
-    const size_t fill = pose ? (size_t)(reinterpret_cast<char*>(b.pose_acc) - reinterpret_cast<char*>(b.gacc)) + POSE_ACC_BYTES
-                             : sizeof(float) * gacc_n;
-    SR_HIP_CHECK(hipMemsetAsync(b.gacc, 0, fill, stream));
-    grads.bg = bg;
-    grads.bg_channels = bg ? s->bg_channels : 0;
-    {
-        StageTimer t(SPLATRASTER_STAGE_COMPOSITE_BWD, stream);
-        // deterministic mode: the kernel runs twice — per-element max of |partial| (into the zeroed float rows), then the
-        // fixed-point sums scaled by that maximum (composite_bwd.hip acc_add)
-        if (det) st = launch_composite_bwd(*s, P, V, R, g, b, im, (C % 4) ? b.featp : feat, C, grads, b.gacc, gacc64, 0, stream);
-        if (!st) st = launch_composite_bwd(*s, P, V, R, g, b, im, (C % 4) ? b.featp : feat, C, grads, b.gacc, gacc64, 1, stream);
-    }
-    if (det) {
-        if (!st) st = launch_fixed_to_float((int64_t)gacc_n, gacc64, b.gacc, gacc_det_headroom_drop(C, V), stream);
-        (void)hipFreeAsync(gacc64, stream);
-    }
-    if (st) return st;
     StageTimer t(SPLATRASTER_STAGE_PREPROCESS_BWD, stream);
     return launch_preprocess_bwd(*s, P, V, cams, grads, means3D, shs, scales, rotations, cov3D_precomp, g.clamped, g.rec,
                                  b.gacc, C, shs ? nullptr : dL_dcolors, dL_dmeans3D, dL_dopacities,
@@ -778,6 +800,50 @@ int splatraster_backward_window(const splatraster_settings* s, int32_t n_views, 
     return window_backward(s, n_views, views, P, R, bg, means3D, nullptr, colors_precomp, scales, rotations, cov3D_precomp,
                            geometry, binning, image, dL_dmeans3D, dL_dcolors, dL_dopacities, dL_dscales, dL_drotations,
                            dL_dcov3D, nullptr, nullptr, nullptr, nullptr, reinterpret_cast<hipStream_t>(stream));
+}
+
+size_t splatraster_window_camera_workspace_bytes(int32_t n_views)
+{
+    return (n_views < 1 || n_views > MAX_VIEWS) ? 0 : (size_t)n_views * POSE_ACC_BYTES;
+}
+
+int splatraster_backward_window_cameras(const splatraster_settings* s, int32_t n_views, const splatraster_window_view* views,
+                                        int32_t P, const int64_t* num_rendered, const float* bg, const float* means3D,
+                                        const float* colors_precomp, const float* scales, const float* rotations,
+                                        const float* cov3D_precomp, void* geometry, const void* binning, const void* image,
+                                        void* workspace, float* dL_dviewmatrix, float* dL_dprojmatrix, float* dL_dcampos,
+                                        void* stream_)
+{
+    const int32_t V = n_views;
+    int st = check_window(s, V, views);
+    if (st) return st;
+    if (P < 0 || !num_rendered || !workspace || !dL_dviewmatrix || !dL_dprojmatrix) return SPLATRASTER_ERR_BAD_ARG;
+    int64_t R = 0;
+    for (int v = 0; v < V; ++v) {
+        if (num_rendered[v] < 0) return SPLATRASTER_ERR_BAD_ARG;
+        R += num_rendered[v];
+    }
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    if (P == 0) {   // nothing to differentiate: the camera gradients are still defined (zero)
+        SR_HIP_CHECK(hipMemsetAsync(dL_dviewmatrix, 0, 16 * sizeof(float) * (size_t)V, stream));
+        SR_HIP_CHECK(hipMemsetAsync(dL_dprojmatrix, 0, 16 * sizeof(float) * (size_t)V, stream));
+        if (dL_dcampos) SR_HIP_CHECK(hipMemsetAsync(dL_dcampos, 0, 3 * sizeof(float) * (size_t)V, stream));
+        return SPLATRASTER_OK;
+    }
+    if (!means3D || !colors_precomp || !geometry || !binning || !image) return SPLATRASTER_ERR_BAD_ARG;
+    if (cov3D_precomp ? (scales || rotations) : (!scales || !rotations)) return SPLATRASTER_ERR_BAD_ARG;
+    for (int v = 0; v < V; ++v)     // (dL_dmeans2D is not written here and may be NULL)
+        if (!views[v].viewmatrix || !views[v].projmatrix || !views[v].radii || !views[v].out_color || !views[v].out_depth ||
+            !views[v].dL_dout_color)
+            return SPLATRASTER_ERR_BAD_ARG;
+    BwdRows rows;
+    st = window_accumulate(s, V, views, P, R, bg, colors_precomp, false, geometry, binning, image, false, stream, &rows);
+    if (st) return st;
+    // the sets and tickets of the V views: the caller's memory, zeroed on the stream in front of the kernel that adds to them
+    SR_HIP_CHECK(hipMemsetAsync(workspace, 0, splatraster_window_camera_workspace_bytes(V), stream));
+    StageTimer t(SPLATRASTER_STAGE_PREPROCESS_BWD, stream);
+    return launch_camera_bwd(*s, P, V, rows.cams, means3D, scales, rotations, cov3D_precomp, rows.g.rec, rows.b.gacc, s->channels,
+                             reinterpret_cast<float*>(workspace), dL_dviewmatrix, dL_dprojmatrix, dL_dcampos, stream);
 }
 
 int splatraster_forward_window_geometry_raw(const splatraster_settings* s, int32_t n_views, const splatraster_window_view* views,

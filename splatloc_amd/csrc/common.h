@@ -181,6 +181,12 @@ int launch_preprocess_bwd(const splatraster_settings& s, int32_t P, int32_t V, c
                           float* dL_dview /*[16] or null; V == 1 only*/, float* dL_dproj, float* dL_dcampos,
                           float* pose_acc /*BinView::pose_acc, zeroed by the caller; needed with dL_dview*/, hipStream_t stream,
                           const RawBwd* raw = nullptr);
+// camera gradients of the V views of a window and nothing per Gaussian (camera_bwd.hip): reads what preprocess_bwd_kernel<true>
+// reads of every (view, Gaussian) row; `ws`: V times (POSE_SETS sets + the ticket line), zeroed by the caller on the stream;
+// dL_dview / dL_dproj [V,16] and dL_dcampos [V,3] (or null) are written in full by the last block of every view
+int launch_camera_bwd(const splatraster_settings& s, int32_t P, int32_t V, const WinCams& cams, const float* means3D,
+                      const float* scales, const float* rotations, const float* cov3D_precomp, const float4* rec,
+                      const float* gacc, int C, float* ws, float* dL_dview, float* dL_dproj, float* dL_dcampos, hipStream_t stream);
 int launch_mark_visible(int32_t P, const float* means3D, const float* view, uint8_t* present,
                         hipStream_t stream);
 

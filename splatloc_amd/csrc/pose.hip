@@ -1,4 +1,5 @@
-// pose.hip — the two small kernels that close the pose-refinement loop on the device (splatloc_amd/pose.py refine_pose):
+// pose.hip — the two small kernels that close the pose-refinement loop on the device (splatloc_amd/pose.py refine_pose), and
+// their forms for the frames of a window (refine_poses: blockIdx.y = view of the loss, one thread per camera of the step):
 //   l1_rgbd_loss_kernel  L = mean |colour - target| + w_d mean |depth - target_d| and its gradient planes, one pass;
 //   pose_step_kernel     ONE thread: chains dL/dviewmatrix, dL/dprojmatrix, dL/dcampos (what the rasterizer's backward
 //                        returns, preprocess_bwd.hip) through  view = (T(w, t) W2C0)^T,  proj = view P,  campos = -R^T t  to the
@@ -69,15 +70,63 @@ l1_rgbd_loss_kernel(int64_t n_color, const float* __restrict__ color, const floa
     }
 }
 
+// the same for the V views of a window, blockIdx.y = view: a view's blocks do what l1_rgbd_loss_kernel's do on its planes
+struct L1Views {
+    const float* color[MAX_VIEWS];
+    const float* tgt_c[MAX_VIEWS];
+    const float* depth[MAX_VIEWS];
+    const float* tgt_d[MAX_VIEWS];
+    float* g_color[MAX_VIEWS];
+    float* g_depth[MAX_VIEWS];
+};
+__global__ void __launch_bounds__(L1_THREADS)
+l1_rgbd_loss_window_kernel(int64_t n_color, int64_t n_depth, L1Views views, float depth_weight, float* __restrict__ loss_out)
+{
+    __shared__ float s_sum[L1_THREADS / WAVE];
+    const int v = blockIdx.y;
+    const float* __restrict__ tgt_d = views.tgt_d[v];
+    float* __restrict__ g_depth = views.g_depth[v];
+    const float wc = 1.0f / (float)n_color, wd = (tgt_d && n_depth) ? depth_weight / (float)n_depth : 0.0f;
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthreads = (int64_t)gridDim.x * blockDim.x;
+    float acc = l1_region(n_color, views.color[v], views.tgt_c[v], wc, views.g_color[v], tid, nthreads);
+    if (tgt_d) {
+        acc += l1_region(n_depth, views.depth[v], tgt_d, wd, g_depth, tid, nthreads);
+    } else if (g_depth) {
+        for (int64_t e = tid; e < n_depth; e += nthreads) g_depth[e] = 0.0f;
+    }
+#pragma unroll
+    for (int o = WAVE / 2; o > 0; o >>= 1) acc += __shfl_xor(acc, o, WAVE);
+    if ((threadIdx.x & (WAVE - 1)) == 0) s_sum[threadIdx.x / WAVE] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float t = 0.0f;
+#pragma unroll
+        for (int k = 0; k < L1_THREADS / WAVE; ++k) t += s_sum[k];
+        atomicAdd(loss_out + v, t);
+    }
+}
+
+static int l1_blocks(int64_t n)
+{
+    const int blocks = (int)((n + L1_THREADS * 16 - 1) / (L1_THREADS * 16));
+    return blocks < 1 ? 1 : (blocks > 256 ? 256 : blocks);
+}
+
+static int launch_l1_rgbd_loss_window(int V, const L1Views& views, int64_t n_color, int64_t n_depth, float depth_weight,
+                                      float* loss_out, hipStream_t stream)
+{
+    hipLaunchKernelGGL(l1_rgbd_loss_window_kernel, dim3(l1_blocks(n_color + n_depth), V), dim3(L1_THREADS), 0, stream, n_color,
+                       n_depth, views, depth_weight, loss_out);
+    SR_LAUNCH_CHECK();
+    return SPLATRASTER_OK;
+}
+
 static int launch_l1_rgbd_loss(int64_t n_color, const float* color, const float* tgt_c, int64_t n_depth, const float* depth,
                         const float* tgt_d, float depth_weight, float* g_color, float* g_depth, float* loss_out,
                         hipStream_t stream)
 {
-    const int64_t n = n_color + n_depth;
-    int blocks = (int)((n + L1_THREADS * 16 - 1) / (L1_THREADS * 16));
-    blocks = blocks < 1 ? 1 : (blocks > 256 ? 256 : blocks);
-    hipLaunchKernelGGL(l1_rgbd_loss_kernel, dim3(blocks), dim3(L1_THREADS), 0, stream, n_color, color, tgt_c, n_depth, depth,
-                       tgt_d, depth_weight, g_color, g_depth, loss_out);
+    hipLaunchKernelGGL(l1_rgbd_loss_kernel, dim3(l1_blocks(n_color + n_depth)), dim3(L1_THREADS), 0, stream, n_color, color, tgt_c,
+                       n_depth, depth, tgt_d, depth_weight, g_color, g_depth, loss_out);
     SR_LAUNCH_CHECK();
     return SPLATRASTER_OK;
 }
@@ -126,13 +175,26 @@ __device__ void rodrigues(const double w[3], D3 R[3][3])
 }
 
 // state: w[3], t[3], exp_avg[6], exp_avg_sq[6], step, (pad)
+// WINDOW: one thread per camera of a window (launched with as many threads as cameras) — camera c reads and writes element c of
+// every array but the shared projection; the arithmetic is the single kernel's, statement for statement
+template <bool WINDOW = false>
 __global__ void pose_step_kernel(const float* __restrict__ dL_dview, const float* __restrict__ dL_dproj,
                                  const float* __restrict__ dL_dcampos, const float* __restrict__ W2C0,
                                  const float* __restrict__ Pm, float lr_rot, float lr_trans, float beta1, float beta2, float eps,
                                  int advance, float* __restrict__ state, float* __restrict__ view_out,
                                  float* __restrict__ proj_out, float* __restrict__ campos_out)
 {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    if constexpr (WINDOW) {
+        if (blockIdx.x != 0) return;
+        const int c = threadIdx.x;
+        if (dL_dview) dL_dview += 16 * c;
+        if (dL_dproj) dL_dproj += 16 * c;
+        if (dL_dcampos) dL_dcampos += 3 * c;
+        if (campos_out) campos_out += 3 * c;
+        W2C0 += 16 * c; state += 20 * c; view_out += 16 * c; proj_out += 16 * c;
+    } else {
+        if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    }
     double w[3], t[3];
     for (int k = 0; k < 3; ++k) { w[k] = state[k]; t[k] = state[3 + k]; }
     double A[4][4], P4[4][4];
@@ -212,7 +274,7 @@ static int launch_pose_step(const float* dL_dview, const float* dL_dproj, const 
                      float lr_rot, float lr_trans, float beta1, float beta2, float eps, int advance, float* state, float* view_out,
                      float* proj_out, float* campos_out, hipStream_t stream)
 {
-    hipLaunchKernelGGL(pose_step_kernel, dim3(1), dim3(64), 0, stream, dL_dview, dL_dproj, dL_dcampos, W2C0, Pm, lr_rot, lr_trans,
+    hipLaunchKernelGGL(pose_step_kernel<false>, dim3(1), dim3(64), 0, stream, dL_dview, dL_dproj, dL_dcampos, W2C0, Pm, lr_rot, lr_trans,
                        beta1, beta2, eps, advance, state, view_out, proj_out, campos_out);
     SR_LAUNCH_CHECK();
     return SPLATRASTER_OK;
@@ -243,6 +305,36 @@ int splatraster_pose_step(const float* dL_dviewmatrix, const float* dL_dprojmatr
     if (advance && (!dL_dviewmatrix || !dL_dprojmatrix)) return SPLATRASTER_ERR_BAD_ARG;
     return launch_pose_step(dL_dviewmatrix, dL_dprojmatrix, dL_dcampos, W2C_init, projection_matrix, lr_rot, lr_trans, beta1, beta2,
                             eps, advance, state, viewmatrix, projmatrix, campos, reinterpret_cast<hipStream_t>(stream));
+}
+
+int splatraster_l1_rgbd_loss_window(int32_t n_views, const splatraster_l1_view* views, int64_t n_color, int64_t n_depth,
+                                    float depth_weight, float* loss_out, void* stream)
+{
+    if (n_views < 1 || n_views > MAX_VIEWS || !views || n_color <= 0 || n_depth < 0 || !loss_out) return SPLATRASTER_ERR_BAD_ARG;
+    L1Views lv{};
+    for (int v = 0; v < n_views; ++v) {
+        const splatraster_l1_view& w = views[v];
+        if (!w.color || !w.target_color || !w.g_color) return SPLATRASTER_ERR_BAD_ARG;
+        if (n_depth > 0 && w.target_depth && !w.depth) return SPLATRASTER_ERR_BAD_ARG;
+        lv.color[v] = w.color; lv.tgt_c[v] = w.target_color; lv.depth[v] = w.depth; lv.tgt_d[v] = w.target_depth;
+        lv.g_color[v] = w.g_color; lv.g_depth[v] = w.g_depth;
+    }
+    return launch_l1_rgbd_loss_window(n_views, lv, n_color, n_depth, depth_weight, loss_out, reinterpret_cast<hipStream_t>(stream));
+}
+
+int splatraster_pose_step_window(int32_t n, const float* dL_dviewmatrix, const float* dL_dprojmatrix, const float* dL_dcampos,
+                                 const float* W2C_init, const float* projection_matrix, float lr_rot, float lr_trans, float beta1,
+                                 float beta2, float eps, int advance, float* state, float* viewmatrix, float* projmatrix,
+                                 float* campos, void* stream)
+{
+    if (n < 1 || n > MAX_VIEWS) return SPLATRASTER_ERR_BAD_ARG;
+    if (!W2C_init || !projection_matrix || !state || !viewmatrix || !projmatrix) return SPLATRASTER_ERR_BAD_ARG;
+    if (advance && (!dL_dviewmatrix || !dL_dprojmatrix)) return SPLATRASTER_ERR_BAD_ARG;
+    hipLaunchKernelGGL(pose_step_kernel<true>, dim3(1), dim3(n), 0, reinterpret_cast<hipStream_t>(stream), dL_dviewmatrix,
+                       dL_dprojmatrix, dL_dcampos, W2C_init, projection_matrix, lr_rot, lr_trans, beta1, beta2, eps, advance, state,
+                       viewmatrix, projmatrix, campos);
+    SR_LAUNCH_CHECK();
+    return SPLATRASTER_OK;
 }
 
 }  // extern "C"

@@ -190,6 +190,117 @@ def refine_pose(render_target, gaussians: dict, camera, W2C_init: torch.Tensor, 
         return (at_to_transform_matrix(w, t)[0] @ W2C0).detach(), hist
 
 
+def window_chunk(P: int, window: int = 8) -> int:
+    """Frames per launch sequence of `refine_poses`: min(window, 8, 2**24 // P) and at least 1 — `rasterize_window`'s rule (the
+    kernels address the (view, Gaussian) rows of a window with 24-bit multiplies)."""
+    from . import _native
+    return max(1, min(int(window), _native.MAX_WINDOW_VIEWS, (1 << 24) // max(int(P), 1)))
+
+
+def _check_refine_poses(render_targets, gaussians, camera, W2C_init, iterations, window):
+    """Argument errors of `refine_poses` (shapes only: nothing here reads a tensor's data or touches a device).  Returns
+    (N, colour, depth or None)."""
+    try:
+        tgt_c, tgt_d = render_targets
+    except (TypeError, ValueError):
+        raise ValueError("refine_poses: render_targets is (colour [N,C,H,W], depth [N,1,H,W] or None)") from None
+    if not isinstance(tgt_c, torch.Tensor) or tgt_c.dim() != 4:
+        raise ValueError("refine_poses: the colour target is one [N,C,H,W] tensor")
+    N, Cn, H, W = (int(x) for x in tgt_c.shape)
+    if N == 0:
+        raise ValueError("refine_poses: no frames (N == 0)")
+    if (H, W) != (int(camera.image_height), int(camera.image_width)):
+        raise ValueError(f"refine_poses: targets are {H}x{W}, the camera {int(camera.image_height)}x{int(camera.image_width)}")
+    if Cn != int(gaussians["colors"].shape[1]):
+        raise ValueError(f"refine_poses: {Cn} target channels, {int(gaussians['colors'].shape[1])} colour columns")
+    if isinstance(tgt_d, (list, tuple)):     # per-frame depth targets: all of them or none
+        if len(tgt_d) != N or any(d is None for d in tgt_d) != all(d is None for d in tgt_d):
+            raise ValueError("refine_poses: a depth target for some frames only (give one for every frame, or None)")
+        if tgt_d[0] is not None and any(int(d.numel()) != H * W for d in tgt_d):
+            raise ValueError(f"refine_poses: every depth target is [1,{H},{W}]")
+        tgt_d = None if tgt_d[0] is None else torch.stack([d.reshape(1, H, W) for d in tgt_d])
+    if tgt_d is not None:
+        if tgt_d.dim() != 4 or int(tgt_d.shape[0]) != N:
+            raise ValueError(f"refine_poses: depth targets for {int(tgt_d.shape[0]) if tgt_d.dim() else 0} of {N} frames "
+                             "(give one for every frame, or None)")
+        if tuple(tgt_d.shape[1:]) != (1, H, W):
+            raise ValueError(f"refine_poses: the depth target is [N,1,{H},{W}], not {tuple(tgt_d.shape)}")
+    if not isinstance(W2C_init, torch.Tensor) or tuple(W2C_init.shape) != (N, 4, 4):
+        raise ValueError(f"refine_poses: W2C_init is [{N},4,4], one start pose per frame")
+    if int(iterations) < 0 or int(window) < 1:
+        raise ValueError("refine_poses: iterations >= 0 and window >= 1")
+    return N, tgt_c, tgt_d
+
+
+def refine_poses(render_targets, gaussians: dict, camera, W2C_init: torch.Tensor, iterations: int = 100, lr_rot: float = 2e-3,
+                 lr_trans: float = 3e-3, depth_weight: float = 0.2, background: torch.Tensor | None = None, window: int = 8):
+    """`refine_pose` (graph-free) for N query frames of one camera model against one frozen map, `window` frames per launch
+    sequence: render_targets = (colour [N,C,H,W], depth [N,1,H,W] or None), W2C_init [N,4,4].  The frames are taken in chunks
+    of K = `window_chunk(P, window)`; a chunk runs its own `iterations` iterations, each ONE launch sequence whose length
+    does not depend on K: rasterizer.window_forward -> splatraster_l1_rgbd_loss_window -> rasterizer.window_backward_cameras
+    (camera gradients of the K views, nothing per Gaussian: the map is frozen) -> splatraster_pose_step_window (one thread per
+    frame; every frame keeps its own Adam state).  No torch operator, no autograd graph, no host read of a gradient inside an
+    iteration.  Returns (W2C [N,4,4], loss history [iterations, N] on the device).  Argument errors — shape mismatches, N == 0, a
+    depth target for some frames only — raise ValueError before any device access."""
+    N, tgt_c, tgt_d = _check_refine_poses(render_targets, gaussians, camera, W2C_init, iterations, window)
+    import ctypes as C
+    from . import _native
+    from ._host import _stream
+    from .rasterizer import GaussianRasterizationSettings, window_backward_cameras, window_forward
+    lib = _native.load()
+    dev = gaussians["means3D"].device
+    tgt_c = tgt_c.to(dev).float().contiguous()
+    tgt_d = None if (tgt_d is None or not depth_weight) else tgt_d.to(dev).float().contiguous()
+    W2C0 = W2C_init.to(dev).float().contiguous()
+    Pm = camera.projection_matrix.to(dev).float().contiguous()
+    H, W, Cn = int(camera.image_height), int(camera.image_width), int(tgt_c.shape[1])
+    bg = background if background is not None else torch.zeros(Cn if Cn <= 3 else 0, device=dev)
+    f32 = dict(dtype=torch.float32, device=dev)
+    hist = torch.zeros((iterations, N), **f32)
+    out = torch.empty((N, 4, 4), **f32)
+    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+    b1, b2, eps = 0.9, 0.999, 1e-8          # torch.optim.Adam's defaults, as refine_pose
+    n_c, n_d = Cn * H * W, H * W
+    K = window_chunk(int(gaussians["means3D"].shape[0]), window)
+    with torch.no_grad():
+        for a in range(0, N, K):
+            k = min(K, N - a)
+            state = torch.zeros((k, 20), **f32)     # per frame: w, t, Adam moments, step (splatraster_pose_step)
+            view, proj = torch.empty((k, 4, 4), **f32), torch.empty((k, 4, 4), **f32)
+            d = {"view": torch.empty((k, 4, 4), **f32), "proj": torch.empty((k, 4, 4), **f32), "campos": torch.empty((k, 3), **f32)}
+            ws = torch.empty((lib.splatraster_window_camera_workspace_bytes(k),), dtype=torch.uint8, device=dev)
+            g_color, g_depth = torch.empty((k, Cn, H, W), **f32), torch.empty((k, 1, H, W), **f32)
+
+            def step(advance):      # (no campos: precomputed colours do not read the camera centre)
+                _native.check(lib.splatraster_pose_step_window(
+                    k, ptr(d["view"]), ptr(d["proj"]), None, ptr(W2C0[a:a + k]), ptr(Pm), lr_rot, lr_trans, b1, b2, eps, advance,
+                    ptr(state), ptr(view), ptr(proj), None, _stream(dev)), "pose_step_window")
+
+            step(0)
+            # the camera tensors of frame j are rows of `view` / `proj`, rewritten in place by every step
+            settings = [GaussianRasterizationSettings(H, W, camera.tanfovx, camera.tanfovy, bg, 1.0, view[j], proj[j], 0, None,
+                                                      False, False) for j in range(k)]
+            grads = [(g_color[j], g_depth[j] if tgt_d is not None else None, None) for j in range(k)]
+            lv = (_native.L1View * k)()
+            for j in range(k):
+                lv[j].target_color = tgt_c[a + j].data_ptr()
+                lv[j].target_depth = None if tgt_d is None else tgt_d[a + j].data_ptr()
+                lv[j].g_color, lv[j].g_depth = g_color[j].data_ptr(), g_depth[j].data_ptr()
+            for it in range(iterations):
+                f = window_forward(gaussians["means3D"], gaussians["colors"], gaussians["opacities"], gaussians["scales"],
+                                   gaussians["rotations"], None, settings)
+                for j in range(k):
+                    lv[j].color, lv[j].depth = f.color[j].data_ptr(), f.depth[j].data_ptr()
+                _native.check(lib.splatraster_l1_rgbd_loss_window(k, lv, n_c, n_d, float(depth_weight),
+                                                                  C.c_void_p(hist.data_ptr() + 4 * (it * N + a)), _stream(dev)),
+                              "l1_rgbd_loss_window")
+                window_backward_cameras(f, grads, ws, d)
+                del f       # (the window's buffers go back to the allocator before the next forward takes its own)
+                step(1)
+            out[a:a + k] = at_to_transform_matrix(state[:, :3], state[:, 3:6]) @ W2C0[a:a + k]
+        return out, hist
+
+
 def _refine_pose_autograd(render_target, gaussians: dict, camera, W2C_init: torch.Tensor, iterations: int = 100,
                           lr_rot: float = 2e-3, lr_trans: float = 3e-3, depth_weight: float = 0.2,
                           background: torch.Tensor | None = None, on_step=None):

@@ -7,7 +7,7 @@ Python wrapper is un-vendored): `GaussianRasterizationSetti
 `(color[C,H,W], depth[1,H,W], alpha[1,H,W], radii[P] int32)`, `rasterize_gaussians` and the
 `_RasterizeGaussians` autograd.Function; `rasterize_window` / `_RasterizeWindow` for the views of a window as one launch
 sequence.  The launches themselves are plain functions (`view_forward` / `view_backward`, `window_forward` /
-`window_backward`), which the autograd Functions adapt and the graph-free loops call directly.
+`window_backward` / `window_backward_cameras`), which the autograd Functions adapt and the graph-free loops call directly.
 
 All compute is in the HIP library behind include/splatraster.h; tensors must live on a
 ROCm device.  No CPU fallback: CPU tensors raise.
@@ -407,6 +407,49 @@ def window_backward(f, grads, head: int = 0, grad_span: Optional[list] = None, r
         _native.check(lib.splatraster_backward_window_raw(
             C.byref(st), V, views, P, R, _ptr(f.bg), _ptr(f.m3), _ptr(f.col), _ptr(f.sca), _ptr(f.rot), _ptr(f.geom),
             _ptr(f.binning), _ptr(f.img), C.byref(rp), _ptr(d["m3"]), _stream(dev)), "backward_window_raw")
+    return d
+
+
+def window_backward_cameras(f, grads, workspace: Optional[torch.Tensor] = None, out: Optional[dict] = None) -> dict:
+    """The camera gradients of every view of `window_forward`'s frame `f`, and no parameter gradient
+    (splatraster_backward_window_cameras: the compositing backward of `window_backward`, then one kernel over the (view,
+    Gaussian) rows that writes nothing per Gaussian).  `grads`: per view (g_color [C,H,W], g_depth [1,H,W], g_alpha [1,H,W]);
+    None: that output did not reach the loss.  Returns {"view": [V,4,4], "proj": [V,4,4], "campos": [V,3]} (campos: zeros, a
+    window has precomputed colours only).  A loop passes `workspace` (uint8, splatraster_window_camera_workspace_bytes(V);
+    zeroed by the call) and `out` (the dict of an earlier call, overwritten) to reuse them."""
+    lib = _native.load()
+    dev, V, P, st = f.dev, f.V, f.P, f.st
+    if len(grads) != V:
+        raise ValueError(f"window_backward_cameras: {len(grads)} gradient tuples for {V} views")
+    f32 = dict(dtype=torch.float32, device=dev)
+    d = out if out is not None else {"view": torch.empty((V, 4, 4), **f32), "proj": torch.empty((V, 4, 4), **f32),
+                                     "campos": torch.empty((V, 3), **f32)}
+    nws = lib.splatraster_window_camera_workspace_bytes(V)
+    if workspace is None:
+        workspace = torch.empty((nws,), dtype=torch.uint8, device=dev)
+    assert workspace.numel() >= nws and all(tuple(d[k].shape) == shp for k, shp in (("view", (V, 4, 4)), ("proj", (V, 4, 4)),
+                                                                                   ("campos", (V, 3))))
+    views = _window_views(f)
+    keep = []
+    zeros_color = None
+    for v, (g_color, g_depth, g_alpha) in enumerate(grads):
+        g_color = _prep(g_color, dev)
+        if g_color is None:     # this view's colour buffer did not reach the loss
+            if zeros_color is None:
+                zeros_color = torch.zeros((st.channels, st.image_height, st.image_width), **f32)
+            g_color = zeros_color
+        g_depth, g_alpha = _prep(g_depth, dev), _prep(g_alpha, dev)
+        keep += [g_color, g_depth, g_alpha]
+        w = views[v]
+        w.dL_dout_color = g_color.data_ptr()
+        w.dL_dout_depth = None if g_depth is None else g_depth.data_ptr()
+        w.dL_dout_alpha = None if g_alpha is None else g_alpha.data_ptr()
+    R = (C.c_int64 * V)(*f.R)
+    with _on_device(dev):
+        _native.check(lib.splatraster_backward_window_cameras(
+            C.byref(st), V, views, P, R, _ptr(f.bg), _ptr(f.m3), _ptr(f.col), _ptr(f.sca), _ptr(f.rot), _ptr(f.cov),
+            _ptr(f.geom), _ptr(f.binning), _ptr(f.img), _ptr(workspace), _ptr(d["view"]), _ptr(d["proj"]), _ptr(d["campos"]),
+            _stream(dev)), "backward_window_cameras")
     return d
 
 

@@ -33,6 +33,7 @@ WHAT = [   # (file name regex, description; {placeholders} are filled by the ext
     (r"^fusion_time\.json$", "feature-TSDF fusion at office_0's size (21.9 M voxels x 256 channels, 640 x 480 frames) against the same update composed from torch operators, HIP events, interleaved regions (`tools/fusion_timing.py`): {fusion}"),
     (r"^pnp_time\.json$", "absolute pose (`solve_pose`: P3P LO-RANSAC + Cauchy refinement) on planted scenes, HIP events (`tools/pnp_time.py`): {pnp}"),
     (r"^localize_time\.json$", "localisation (`tools/localize_time.py`), HIP events, interleaved medians: fused retrieval against `torch.einsum(...).topk` and the batched `Localizer.localize` against the per-query loop: {localize}"),
+    (r"^pose_window_time\.json$", "pose refinement of 8 query frames at 640x480, `pose.refine_poses` per `window` against the loop of 8 `pose.refine_pose` calls, ms per frame-iteration, host clock around a device synchronise, alternating regions (`tools/pose_window_time.py`): {posewindow}"),
     (r"^matching_time\.json$", "2D-3D matching (`hungarian_solve` cost + exact assignment, batched solver, frustum candidates) against torch-CPU + scipy on the same host, HIP events (`tools/matching_time.py`): {matching}"),
     (r"^landmark_selection_time\.json$", "landmark selection (`gaussian_selectition`) at Replica scale on a synthetic room, HIP events per stage (`tools/landmark_selection_time.py`): {landmark}"),
     (r"r\d+_scene_lists.*\.json$", "one `color_refinement` iteration on a RECONSTRUCTED room (list-length distribution, per-kernel table; `tools/scene_lists.py`; suffix = the forced variant): {scenelists}"),
@@ -237,6 +238,20 @@ def localize(path):
             f"{d['per_query_loop_ms']:.0f} ms ({d['ratio_loop_over_localize']:.2f} x), bit-identical {d['bit_identical_to_loop']}")
 
 
+def posewindow(path):
+    j = _load(path) or {}
+    if not j.get("results"):
+        return str(j.get("status", "(no rows)"))
+    parts = []
+    for r in j["results"]:
+        v = r["variants"]
+        wins = ", ".join(f"window {k.split('_')[1]} {v[k]['ms_per_frame_iteration']:.4f}" for k in v if k != "loop")
+        parts.append(f"{r['workload']} (P = {r['P']}): loop {v['loop']['ms_per_frame_iteration']:.4f} ({v['loop']['min']:.4f} - {v['loop']['max']:.4f}), "
+                     f"{wins}; best window {r['best_window']} ({v['window_%d' % r['best_window']]['loop_over_this']:.3f} x the loop's speed), "
+                     f"poses within 2e-4 of the loop's: {r['poses_agree_within_2e-4']}")
+    return "; ".join(parts)
+
+
 def decoder(path):
     j = _load(path) or {}
     names = (("train_step_batch_256", "training step at batch 256"), ("inference_5000", "inference at N = 5 000"),
@@ -276,7 +291,7 @@ def setup_ab(path):
             f"{c['bwd_ms']['parent']:.4f} -> {c['bwd_ms']['change']:.4f} ms, ms x MHz {k['parent']['mean']:.0f} -> {k['change']['mean']:.0f}")
 
 
-EXTRACT = {"setup_pmc": setup_pmc, "kstats2": kstats2, "setup_ab": setup_ab, "scenelists": scenelists, "scene": scene, "ab": ab, "perview": perview, "mapidle": mapidle, "rccl": rccl, "kstats": kstats, "hbm": hbm, "sq": sq, "timeline": timeline, "bench": bench, "clocks": clocks, "gradbars": gradbars, "idle": idle, "landmark": landmark, "matching": matching, "pnp": pnp, "decoder": decoder, "fusion": fusion, "localize": localize}
+EXTRACT = {"setup_pmc": setup_pmc, "kstats2": kstats2, "setup_ab": setup_ab, "scenelists": scenelists, "scene": scene, "ab": ab, "perview": perview, "mapidle": mapidle, "rccl": rccl, "kstats": kstats, "hbm": hbm, "sq": sq, "timeline": timeline, "bench": bench, "clocks": clocks, "gradbars": gradbars, "idle": idle, "landmark": landmark, "matching": matching, "pnp": pnp, "decoder": decoder, "fusion": fusion, "localize": localize, "posewindow": posewindow}
 
 
 def describe(name, path):
