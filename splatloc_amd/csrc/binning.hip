@@ -34,11 +34,14 @@ static_assert(EMIT_SPAN == EMIT_BLOCK * EMIT_IPT, "common.h: EMIT_SPAN");
 // A window of V views: the n = V * P rows of all views are in ONE depth order; row g = v * P + i emits the
 // global tile ids v * tiles + t of its rect, so the single stable tile sort that follows leaves every
 // (view, tile) list in (depth, index) order — exactly what V separate calls produce.
+// KeyT: uint16_t when the global tile ids fit 16 bits and the tile sort takes its histogram / scan / scatter passes
+// (sort_keys16, scan_sort.hip): the keys are then 2 of the 8 bytes written per instance instead of 4.
+template <typename KeyT>
 __global__ void __launch_bounds__(EMIT_BLOCK)
 emit_kernel(int64_t R, int P /*rows: V * P*/, int Pv /*Gaussians per view*/, int tiles_per_view, int W, int H,
             const uint32_t* __restrict__ offsets,
             const uint32_t* __restrict__ depth_order, const float4* __restrict__ rec,
-            uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
+            KeyT* __restrict__ keys, uint32_t* __restrict__ vals,
             const uint32_t* __restrict__ span_owner /* first rank of span k, or NULL */,
             uint32_t* __restrict__ ranges, uint32_t nranges /* words to clear for payload_kernel */)
 {
@@ -114,22 +117,27 @@ emit_kernel(int64_t R, int P /*rows: V * P*/, int Pv /*Gaussians per view*/, int
             const uint32_t k = ju - s_off[a - 1];
             const uint32_t w = s_w[a - 1];
             const uint32_t row = k / w;
-            keys[j] = s_org[a - 1] + row * (uint32_t)gx + (k - row * w);
+            keys[j] = (KeyT)(s_org[a - 1] + row * (uint32_t)gx + (k - row * w));
             vals[j] = s_gid[a - 1];
         }
     }
 }
 
 int launch_emit(const splatraster_settings& s, int32_t P, int32_t V, int64_t R, const GeomView& g, uint32_t* keys,
-                uint32_t* vals, uint32_t* ranges, uint32_t nranges, hipStream_t stream)
+                uint32_t* vals, uint32_t* ranges, uint32_t nranges, hipStream_t stream, bool keys16)
 {
     if (R == 0) return SPLATRASTER_OK;
     const int64_t blocks = (R + EMIT_SPAN - 1) / EMIT_SPAN;
     const int n = P * V;
     const int tiles = ((s.image_width + TILE - 1) / TILE) * ((s.image_height + TILE - 1) / TILE);
-    hipLaunchKernelGGL(emit_kernel, dim3((unsigned)blocks), dim3(EMIT_BLOCK), 0, stream, R, n, P, tiles, s.image_width,
-                       s.image_height, g.offsets, g.depth_order, g.rec, keys, vals,
-                       scan_state_bytes(n) ? g.span_owner : nullptr, ranges, nranges);
+    const uint32_t* owner = scan_state_bytes(n) ? g.span_owner : nullptr;
+    if (keys16)   // [R] uint16_t in the first half of the [R] uint32_t array
+        hipLaunchKernelGGL(emit_kernel<uint16_t>, dim3((unsigned)blocks), dim3(EMIT_BLOCK), 0, stream, R, n, P, tiles, s.image_width,
+                           s.image_height, g.offsets, g.depth_order, g.rec, reinterpret_cast<uint16_t*>(keys), vals, owner, ranges,
+                           nranges);
+    else
+        hipLaunchKernelGGL(emit_kernel<uint32_t>, dim3((unsigned)blocks), dim3(EMIT_BLOCK), 0, stream, R, n, P, tiles, s.image_width,
+                           s.image_height, g.offsets, g.depth_order, g.rec, keys, vals, owner, ranges, nranges);
     SR_LAUNCH_CHECK();
     return SPLATRASTER_OK;
 }

@@ -101,6 +101,9 @@ static int host_slot(size_t n, HostSlot** out)
     return SPLATRASTER_OK;
 }
 
+#ifndef SR_TILE_KEYS16
+#define SR_TILE_KEYS16 1   // 0: 32-bit keys through the tile sort whatever their width (A/B baseline)
+#endif
 static inline int tile_bits(int tiles)
 {
     int b = 1;
@@ -528,7 +531,9 @@ static int window_render(const splatraster_settings* s, int32_t V, const splatra
     if (R > 0 && !feat) return SPLATRASTER_ERR_BAD_ARG;
     const int bits = tile_bits((int)gtiles);
     const int passes = (bits + 7) / 8;
-    // emit into the buffer pair from which `passes` ping-pongs end in (tile_list, point_list)
+    // emit into the buffer pair from which `passes` ping-pongs end in (tile_list, point_list); with 16-bit keys (sort_keys16) the
+    // same pair: the uint16_t keys fill the first half of k0 (and of k1 after the first of two passes), and the last pass
+    // reads them from the buffer that is NOT tile_list (1 pass: keys_tmp -> tile_list; 2: tile_list -> keys_tmp -> tile_list)
     uint32_t* k0 = (passes & 1) ? b.keys_tmp : b.tile_list;
     uint32_t* v0 = (passes & 1) ? b.vals_tmp : b.point_list;
     uint32_t* k1 = (passes & 1) ? b.tile_list : b.keys_tmp;
@@ -542,15 +547,17 @@ static int window_render(const splatraster_settings* s, int32_t V, const splatra
         if (st) return st;
     }
     if (R > 0 && !bins.on) {
+        const bool keys16 = SR_TILE_KEYS16 && sort_keys16(R, bits);
         {
             StageTimer t(SPLATRASTER_STAGE_EMIT, stream);
-            st = launch_emit(*s, P, V, R, g, k0, v0, b.ranges, 2u * (uint32_t)gtiles, stream);  // also clears the range table
+            st = launch_emit(*s, P, V, R, g, k0, v0, b.ranges, 2u * (uint32_t)gtiles, stream, keys16);  // also clears the range table
         }
         if (st) return st;
         bool in_alt = false;
         {
             StageTimer t(SPLATRASTER_STAGE_TILE_SORT, stream);
-            st = sort_pairs_u32(R, k0, v0, k1, v1, bits, b.sort_tmp, stream, &in_alt);
+            st = keys16 ? sort_pairs_k16(R, k0, v0, k1, v1, bits, b.sort_tmp, stream, &in_alt)
+                        : sort_pairs_u32(R, k0, v0, k1, v1, bits, b.sort_tmp, stream, &in_alt);
         }
         if (st) return st;
     }

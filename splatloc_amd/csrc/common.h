@@ -194,6 +194,11 @@ size_t sort_tmp_bytes(int64_t n);
 size_t sort_zero_bytes(int64_t n, int key_bits);
 int sort_pairs_u32(int64_t n, uint32_t* keys, uint32_t* vals, uint32_t* keys_alt, uint32_t* vals_alt,
                    int key_bits, void* tmp, hipStream_t stream, bool* result_in_alt, bool tmp_zeroed = false);
+// the tile sort's narrow form: true when a sort of n keys of key_bits bits moves them as uint16_t (then emit_kernel writes
+// uint16_t into the first half of `keys` and sort_pairs_k16 replaces sort_pairs_u32; same buffers, same result, uint32_t keys out)
+bool sort_keys16(int64_t n, int key_bits);
+int sort_pairs_k16(int64_t n, uint32_t* keys, uint32_t* vals, uint32_t* keys_alt, uint32_t* vals_alt, int key_bits, void* tmp,
+                   hipStream_t stream, bool* result_in_alt);
 // inclusive scan of in[perm[i] & 0xFFFFFF] (perm may be null; its words carry min(in[row], 255) in bits 24..31:
 // scan_sort.hip perm_value) into out[i]; total (u64 as 2 words) optional
 size_t scan_tmp_bytes(int64_t n);
@@ -248,7 +253,7 @@ int launch_bin_scatter_sort(const splatraster_settings& s, int32_t P, int32_t V,
                             const uint32_t* table, const BinView& b, uint64_t* keys, hipStream_t stream);
 
 int launch_emit(const splatraster_settings& s, int32_t P, int32_t V, int64_t R, const GeomView& g, uint32_t* keys,
-                uint32_t* vals, uint32_t* ranges, uint32_t nranges, hipStream_t stream);
+                uint32_t* vals, uint32_t* ranges, uint32_t nranges, hipStream_t stream, bool keys16 = false /*keys: [R] uint16_t*/);
 int launch_ranges_clear(int32_t tiles, uint32_t* ranges, hipStream_t stream);
 int launch_payload(const splatraster_settings& s, int32_t V, int64_t R, const GeomView& g, const BinView& b, hipStream_t stream);
 // 16-byte aligned copy of the [P, C] feature rows (returns feat itself when C % 4 == 0)

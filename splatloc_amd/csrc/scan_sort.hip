@@ -389,8 +389,11 @@ int exclusive_scan_u32(int64_t n, uint32_t* inout, uint32_t* total, void* tmp, h
 // ---------------------------------------------------------------------------------------
 // radix sort
 // ---------------------------------------------------------------------------------------
+// KIn / KOut: the key type a pass reads / writes.  uint32_t everywhere but in the tile sort of a window whose (view, tile)
+// ids fit 16 bits (sort_pairs_k16 below): there every pass reads uint16_t keys and only the last one widens them.
+template <typename KIn>
 __global__ void __launch_bounds__(SORT_THREADS)
-sort_hist_kernel(int64_t n, const uint32_t* __restrict__ keys, int shift, uint32_t nblocks,
+sort_hist_kernel(int64_t n, const KIn* __restrict__ keys, int shift, uint32_t nblocks,
                  uint32_t* __restrict__ table, uint32_t* __restrict__ zero, uint32_t nzero)
 {
     __shared__ uint32_t hist[RADIX];
@@ -402,15 +405,16 @@ sort_hist_kernel(int64_t n, const uint32_t* __restrict__ keys, int shift, uint32
 #pragma unroll
     for (int k = 0; k < SORT_ITEMS; ++k) {
         const int64_t i = base + (int64_t)k * SORT_THREADS + threadIdx.x;
-        if (i < n) atomicAdd(&hist[(keys[i] >> shift) & (RADIX - 1)], 1u);
+        if (i < n) atomicAdd(&hist[((uint32_t)keys[i] >> shift) & (RADIX - 1)], 1u);
     }
     __syncthreads();
     table[(size_t)threadIdx.x * nblocks + blockIdx.x] = hist[threadIdx.x];
 }
 
+template <typename KIn, typename KOut>
 __global__ void __launch_bounds__(SORT_THREADS)
-sort_scatter_kernel(int64_t n, const uint32_t* __restrict__ keys_in, const uint32_t* __restrict__ vals_in,
-                    uint32_t* __restrict__ keys_out, uint32_t* __restrict__ vals_out, int shift,
+sort_scatter_kernel(int64_t n, const KIn* __restrict__ keys_in, const uint32_t* __restrict__ vals_in,
+                    KOut* __restrict__ keys_out, uint32_t* __restrict__ vals_out, int shift,
                     uint32_t nblocks, const uint32_t* __restrict__ table)
 {
     __shared__ uint32_t wave_hist[SORT_WAVES][RADIX];
@@ -427,7 +431,7 @@ sort_scatter_kernel(int64_t n, const uint32_t* __restrict__ keys_in, const uint3
     for (int k = 0; k < SORT_ITEMS; ++k) {
         const int64_t i = wbase + (int64_t)k * WAVE + lane;
         const bool valid = i < n;
-        key[k] = valid ? keys_in[i] : 0u;
+        key[k] = valid ? (uint32_t)keys_in[i] : 0u;
         val[k] = valid ? vals_in[i] : 0u;
     }
 #pragma unroll
@@ -452,7 +456,8 @@ sort_scatter_kernel(int64_t n, const uint32_t* __restrict__ keys_in, const uint3
     // Block-local reorder through LDS before the global scatter: elements of one digit become
     // consecutive, so consecutive threads write consecutive addresses (runs of ~16 elements at
     // 256 bins) instead of 64 scattered 4-byte stores per instruction.
-    __shared__ uint32_t s_keys[SORT_TILE], s_vals[SORT_TILE];
+    __shared__ KIn s_keys[SORT_TILE];
+    __shared__ uint32_t s_vals[SORT_TILE];
     __shared__ uint32_t s_gbase[RADIX];   // global address of local slot 0 of the digit's run
     __shared__ uint32_t s_wsum[SORT_WAVES];
     {
@@ -489,7 +494,7 @@ sort_scatter_kernel(int64_t n, const uint32_t* __restrict__ keys_in, const uint3
         if (i < n) {
             const uint32_t digit = (key[k] >> shift) & (RADIX - 1);
             const uint32_t pos = wave_hist[w][digit] + rank[k];
-            s_keys[pos] = key[k];
+            s_keys[pos] = (KIn)key[k];
             s_vals[pos] = val[k];
         }
     }
@@ -502,7 +507,7 @@ sort_scatter_kernel(int64_t n, const uint32_t* __restrict__ keys_in, const uint3
         if (sl < cnt) {
             const uint32_t kk = s_keys[sl];
             const uint32_t dst = s_gbase[(kk >> shift) & (RADIX - 1)] + sl;
-            keys_out[dst] = kk;
+            keys_out[dst] = (KOut)kk;
             vals_out[dst] = s_vals[sl];
         }
     }
@@ -717,6 +722,46 @@ size_t sort_zero_bytes(int64_t n, int key_bits)
     return align_up(sizeof(SweepState), 256) + (size_t)passes * align_up((size_t)nb * RADIX * sizeof(uint32_t), 256);
 }
 
+// histogram / scan / scatter passes over 8-bit digits, ping-ponging between (kin, vin) and (kout, vout).  KIn = uint16_t:
+// the key arrays hold uint16_t (in the first half of their uint32_t storage) up to the input of the last pass, which
+// writes uint32_t keys — a pass never reads and writes the same buffer, so the two widths cannot overlap.
+template <typename KIn>
+static int sort_passes(int64_t n, int64_t nb, int passes, uint32_t* kin, uint32_t* vin, uint32_t* kout, uint32_t* vout, void* tmp,
+                       hipStream_t stream, bool* result_in_alt)
+{
+    uint32_t* table = reinterpret_cast<uint32_t*>(tmp);
+    void* scan_tmp = reinterpret_cast<char*>(tmp) + align_up((size_t)nb * RADIX * sizeof(uint32_t), 256);
+    for (int p = 0; p < passes; ++p) {
+        const int shift = p * 8;
+        const int64_t cnt = nb * RADIX;
+        const size_t sstate = scan_state_bytes(cnt);
+        hipLaunchKernelGGL(sort_hist_kernel<KIn>, dim3((unsigned)nb), dim3(SORT_THREADS), 0, stream, n,
+                           reinterpret_cast<const KIn*>(kin), shift, (uint32_t)nb, table, reinterpret_cast<uint32_t*>(scan_tmp),
+                           (uint32_t)(sstate / 4));
+        SR_LAUNCH_CHECK();
+        if (sstate) {
+            const int64_t snb = (cnt + SCAN_TILE - 1) / SCAN_TILE;
+            hipLaunchKernelGGL(scan_onepass_kernel<true>, dim3((unsigned)snb), dim3(SCAN_THREADS), 0, stream, cnt, table,
+                               nullptr, table, nullptr, reinterpret_cast<ScanState*>(scan_tmp), nullptr, 0u, 0u);
+            SR_LAUNCH_CHECK();
+        } else {
+            int st = scan_u32<true>(cnt, table, nullptr, table, nullptr, scan_tmp, stream);
+            if (st != SPLATRASTER_OK) return st;
+        }
+        if (p + 1 < passes)
+            hipLaunchKernelGGL((sort_scatter_kernel<KIn, KIn>), dim3((unsigned)nb), dim3(SORT_THREADS), 0, stream, n,
+                               reinterpret_cast<const KIn*>(kin), vin, reinterpret_cast<KIn*>(kout), vout, shift, (uint32_t)nb, table);
+        else
+            hipLaunchKernelGGL((sort_scatter_kernel<KIn, uint32_t>), dim3((unsigned)nb), dim3(SORT_THREADS), 0, stream, n,
+                               reinterpret_cast<const KIn*>(kin), vin, kout, vout, shift, (uint32_t)nb, table);
+        SR_LAUNCH_CHECK();
+        uint32_t* t = kin; kin = kout; kout = t;
+        t = vin; vin = vout; vout = t;
+    }
+    *result_in_alt = (passes & 1) != 0;
+    return SPLATRASTER_OK;
+}
+
 int sort_pairs_u32(int64_t n, uint32_t* keys, uint32_t* vals, uint32_t* keys_alt, uint32_t* vals_alt,
                    int key_bits, void* tmp, hipStream_t stream, bool* result_in_alt, bool tmp_zeroed)
 {
@@ -757,32 +802,23 @@ int sort_pairs_u32(int64_t n, uint32_t* keys, uint32_t* vals, uint32_t* keys_alt
         *result_in_alt = (passes & 1) != 0;
         return SPLATRASTER_OK;
     }
-    uint32_t* table = reinterpret_cast<uint32_t*>(tmp);
-    void* scan_tmp = reinterpret_cast<char*>(tmp) + align_up((size_t)nb * RADIX * sizeof(uint32_t), 256);
-    for (int p = 0; p < passes; ++p) {
-        const int shift = p * 8;
-        const int64_t cnt = nb * RADIX;
-        const size_t sstate = scan_state_bytes(cnt);
-        hipLaunchKernelGGL(sort_hist_kernel, dim3((unsigned)nb), dim3(SORT_THREADS), 0, stream, n, kin, shift,
-                           (uint32_t)nb, table, reinterpret_cast<uint32_t*>(scan_tmp), (uint32_t)(sstate / 4));
-        SR_LAUNCH_CHECK();
-        if (sstate) {
-            const int64_t snb = (cnt + SCAN_TILE - 1) / SCAN_TILE;
-            hipLaunchKernelGGL(scan_onepass_kernel<true>, dim3((unsigned)snb), dim3(SCAN_THREADS), 0, stream, cnt, table,
-                               nullptr, table, nullptr, reinterpret_cast<ScanState*>(scan_tmp), nullptr, 0u, 0u);
-            SR_LAUNCH_CHECK();
-        } else {
-            int st = scan_u32<true>(cnt, table, nullptr, table, nullptr, scan_tmp, stream);
-            if (st != SPLATRASTER_OK) return st;
-        }
-        hipLaunchKernelGGL(sort_scatter_kernel, dim3((unsigned)nb), dim3(SORT_THREADS), 0, stream, n, kin, vin,
-                           kout, vout, shift, (uint32_t)nb, table);
-        SR_LAUNCH_CHECK();
-        uint32_t* t = kin; kin = kout; kout = t;
-        t = vin; vin = vout; vout = t;
-    }
-    *result_in_alt = (passes & 1) != 0;
-    return SPLATRASTER_OK;
+    return sort_passes<uint32_t>(n, nb, passes, kin, vin, kout, vout, tmp, stream, result_in_alt);
+}
+
+// The tile sort of a window: global tile ids of at most 16 bits, written as uint16_t by emit_kernel, when the sort takes
+// the histogram / scan / scatter passes (the one-sweep form of small sorts is latency-bound: narrower keys buy nothing there).
+bool sort_keys16(int64_t n, int key_bits) { return n > 0 && key_bits > 0 && key_bits <= 16 && !sweep_items(n); }
+
+// sort_pairs_u32 for such keys: keys / keys_alt are the [n] uint32_t arrays of the 32-bit path, an array of uint16_t keys
+// lives in the first half of one; the result (the buffer that sort_pairs_u32 would leave it in) holds uint32_t keys.
+int sort_pairs_k16(int64_t n, uint32_t* keys, uint32_t* vals, uint32_t* keys_alt, uint32_t* vals_alt, int key_bits, void* tmp,
+                   hipStream_t stream, bool* result_in_alt)
+{
+    *result_in_alt = false;
+    if (!sort_keys16(n, key_bits)) return SPLATRASTER_ERR_BAD_ARG;
+    if (n >= (int64_t)1 << 32) return SPLATRASTER_ERR_OVERFLOW;
+    const int64_t nb = (n + SORT_TILE - 1) / SORT_TILE;
+    return sort_passes<uint16_t>(n, nb, (key_bits + 7) / 8, keys, vals, keys_alt, vals_alt, tmp, stream, result_in_alt);
 }
 
 }  // namespace sr

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Decision-grade A/B of variant libraries (tools/ablate.py) on ONE box: INTERLEAVED runs of the default bench.
 
-    tools/ab.py [--runs 12] [--workload S2] [--parity] [--out FILE.json] [--bench-args "..."] base NAME1 NAME2 ...
+    tools/ab.py [--runs 12] [--workload S2] [--parity] [--out FILE.json] [--bench-args "..."] [--stages emit,tile_sort,payload] base NAME1 NAME2 ...
 
 "base" = the in-tree library; NAME = splatloc_amd/_lib/variants/libsplatraster_NAME.so.  Round r runs every variant once, in
 an order rotated by r (base is not always the first to meet a cold or a warm device), each run being `python bench.py
@@ -12,7 +12,7 @@ two-sided p-value of the paired t-test — a gain is real when the interval excl
 runs on different boxes; box-to-box spread is +-2 %, run-to-run on one box +-0.3 %: only same-box, interleaved, paired
 comparisons resolve a 1 % effect (VERDICT r4 #4).  --parity runs the quick parity subset once per variant first.
 Every bench run carries its own telemetry (bench.py starts tools/gpu_sampler.py: amdsmi samples inside the timed regions), so
-each variant also gets mean shader clock, socket power, PPT-limit residency and busy %, and the per-run scatter of (clock,
+each variant also gets (--stages: the avg_ms of further bench stages, paired like the two compositing stages,) mean shader clock, socket power, PPT-limit residency and busy %, and the per-run scatter of (clock,
 power) against (fwd ms, bwd ms) is kept: a forward / backward coupling that is a POWER effect shows up as a clock / power
 difference between the variants (VERDICT r5 #3)."""
 import json
@@ -77,6 +77,7 @@ def main():
     workload = opt("--workload", "S2")
     out_path = opt("--out", None)
     extra = opt("--bench-args", "").split()
+    stages = [x for x in opt("--stages", "").split(",") if x]
     parity = "--parity" in args
     names = [a for a in args if not a.startswith("--")]
     if len(names) < 2 or names[0] != "base":
@@ -93,6 +94,8 @@ def main():
 
     res = {n: {"fps": [], "fwd_ms": [], "bwd_ms": [], "ms_per_step": [], "sclk_mhz": [], "power_w": [], "ppt_residency": [], "busy_pct": []}
            for n in names}
+    for n in names:
+        res[n].update({f"{x}_ms": [] for x in stages})
     par = {}
     if parity:
         for n in names:
@@ -113,6 +116,8 @@ def main():
             res[n]["ms_per_step"].append(d["ms_per_step"])
             res[n]["fwd_ms"].append(d["stages"]["composite_fwd"]["avg_ms"])
             res[n]["bwd_ms"].append(d["stages"]["composite_bwd"]["avg_ms"])
+            for x in stages:
+                res[n][f"{x}_ms"].append(d["stages"][x]["avg_ms"])
             tel = d.get("gpu_telemetry_in_timed_regions") or {}
             if tel.get("available"):
                 res[n]["sclk_mhz"].append((tel.get("sclk_mhz") or {}).get("mean"))
@@ -135,6 +140,8 @@ def main():
         out["vs_base"][n] = {"fps_diff": paired(res["base"]["fps"], res[n]["fps"]),
                              "fwd_ms_diff": paired(res["base"]["fwd_ms"], res[n]["fwd_ms"]),
                              "bwd_ms_diff": paired(res["base"]["bwd_ms"], res[n]["bwd_ms"])}
+        for x in stages:
+            out["vs_base"][n][f"{x}_ms_diff"] = paired(res["base"][f"{x}_ms"], res[n][f"{x}_ms"])
         for k in ("sclk_mhz", "power_w", "ppt_residency"):
             a = [x for x in res["base"][k] if isinstance(x, (int, float))]
             b = [x for x in res[n][k] if isinstance(x, (int, float))]

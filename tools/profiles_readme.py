@@ -49,6 +49,9 @@ WHAT = [   # (file name regex, description; {placeholders} are filled by the ext
     (r"^bwd_setup_pmc\.json$", "`rocprofv3 --pmc SQ_INSTS_SALU SQ_INSTS_VALU SQ_WAVES` of the headline backward per launch, parent against the change, one run each: {setup_pmc}"),
     (r"^bwd_setup_kernel_stats\.txt$", "`rocprofv3 --kernel-trace --stats` of the default bench, parent (first listing) and change (second): {kstats2}"),
     (r"^bwd_setup_ab\.json$", "`tools/ab.py`, base = the change, variant `parent` = the parent commit's library (differences are parent minus change): {ab}; {setup_ab}"),
+    (r"^front_end_kernel_stats\.txt$", "`rocprofv3 --kernel-trace --stats` of the default bench, parent (first listing) and the 16-bit tile-sort keys (second; DESIGN §3.1), us per launch: {fe_kstats}"),
+    (r"^front_end_pmc_hbm\.json$", "separate `--pmc FETCH_SIZE` / `--pmc WRITE_SIZE` passes of the same command for the radix front end's kernels, parent and change, and FETCH_SIZE of `payload_kernel` under the XCD-band mappings of `tools/patches/payload_xcd_band.patch`: {fe_pmc}"),
+    (r"^front_end_ab\.json$", "`tools/ab.py`, base = the change (16-bit tile-sort keys), variants = the parent commit's library and the rejected XCD-band mappings of `payload_kernel` with and without the 16-bit keys (differences are variant minus change): {ab}; {fe_ab}"),
     (r"traffic\.json$", "per-stage HBM bytes per launch that `bench.py` replays as `roofline.traffic` (recorded workload / launch mode inside)"),
     (r"valu\.json$", "VALU / MFMA / SALU wave-instructions, busy fractions of the two compositing kernels per launch (replayed by `bench.py` as `frame_valu` / `roofline_valu`)"),
     (r"r01_v1_first_.*", "round 1: the first correct pipeline (per-value DPP reductions, no reach masks)"),
@@ -291,7 +294,33 @@ def setup_ab(path):
             f"{c['bwd_ms']['parent']:.4f} -> {c['bwd_ms']['change']:.4f} ms, ms x MHz {k['parent']['mean']:.0f} -> {k['change']['mean']:.0f}")
 
 
-EXTRACT = {"setup_pmc": setup_pmc, "kstats2": kstats2, "setup_ab": setup_ab, "scenelists": scenelists, "scene": scene, "ab": ab, "perview": perview, "mapidle": mapidle, "rccl": rccl, "kstats": kstats, "hbm": hbm, "sq": sq, "timeline": timeline, "bench": bench, "clocks": clocks, "gradbars": gradbars, "idle": idle, "landmark": landmark, "matching": matching, "pnp": pnp, "decoder": decoder, "fusion": fusion, "localize": localize, "posewindow": posewindow}
+def fe_kstats(path):
+    """the two listings' large launches of the front-end kernels (the tile sort's; the depth sort's small ones share the names)"""
+    halves, out = open(path).read().split("# rocprofv3")[1:], []
+    for name in ("payload_kernel", "emit_kernel", "sort_hist_kernel", "sort_scatter_kernel"):
+        per = []
+        for h in halves:
+            rows = [ln.split() for ln in h.splitlines() if ln.startswith(name)]
+            per.append(" + ".join(f"{float(r[-6]):.1f}" for r in rows) or "-")
+        out.append(f"`{name}` " + " -> ".join(per))
+    return "; ".join(out)
+
+
+def fe_pmc(path):
+    j = _load(path) or {}
+    f = j.get("payload_kernel_fetched_MB_per_launch") or {}
+    return "`payload_kernel` fetched MB per launch (FETCH_SIZE as reported, not doubled): " + ", ".join(f"{k} {v:.0f}" for k, v in f.items())
+
+
+def fe_ab(path):
+    c = (_load(path) or {})["change_vs_parent"]
+    return (f"change minus parent {c['fps_diff_pct_of_parent_mean']['mean']:+.2f} % of the parent's frames/s (CI "
+            f"{c['fps_diff_pct_of_parent_mean']['ci95'][0]:+.2f} .. {c['fps_diff_pct_of_parent_mean']['ci95'][1]:+.2f} %, margin {c['margin_pct']} %), "
+            f"tile-sort stage {c['tile_sort_ms']['parent']:.4f} -> {c['tile_sort_ms']['change']:.4f} ms, payload stage {c['payload_ms']['parent']:.4f} -> "
+            f"{c['payload_ms']['change']:.4f} ms ({', '.join(f'{k} {v:.4f}' for k, v in c['payload_ms_of_band_variants'].items())})")
+
+
+EXTRACT = {"fe_kstats": fe_kstats, "fe_pmc": fe_pmc, "fe_ab": fe_ab, "setup_pmc": setup_pmc, "kstats2": kstats2, "setup_ab": setup_ab, "scenelists": scenelists, "scene": scene, "ab": ab, "perview": perview, "mapidle": mapidle, "rccl": rccl, "kstats": kstats, "hbm": hbm, "sq": sq, "timeline": timeline, "bench": bench, "clocks": clocks, "gradbars": gradbars, "idle": idle, "landmark": landmark, "matching": matching, "pnp": pnp, "decoder": decoder, "fusion": fusion, "localize": localize, "posewindow": posewindow}
 
 
 def describe(name, path):
