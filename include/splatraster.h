@@ -86,7 +86,9 @@ size_t splatraster_geometry_bytes(int32_t P);
  * sort's ping-pong buffers, the [tiles] range table, the per-instance payload (32-byte record
  * + quadrant reach mask) and, when channels % 4 != 0, the 16-byte-aligned feature table. */
 size_t splatraster_binning_bytes(int32_t P, int64_t R, int32_t width, int32_t height, int32_t channels);
-/* per-pixel forward state needed by backward: final transmittance, last contributor. */
+/* per-pixel forward state needed by backward: final transmittance, last contributor (its position in the tile's list), and behind
+ * them what the compact payload adds: the last contributor's position in the list's compact stream (a third 4-byte plane: 12 bytes
+ * per pixel) and the [2 * tiles] table of the compact ranges. */
 size_t splatraster_image_bytes(int32_t width, int32_t height);
 
 /* ---- forward ------------------------------------------------------------------------- */
@@ -348,7 +350,8 @@ typedef struct splatraster_binning_layout {
 typedef struct splatraster_image_layout {
     size_t final_T;   /* float[H*W] */
     size_t n_contrib; /* uint32[H*W] */
-    size_t total;
+    size_t total;     /* (behind the two planes, at 2 * n_contrib and 3 * n_contrib: uint32[H*W] n_contrib_c and uint32[2*tiles] cranges,
+                       *  written by forwards that stream the compact payload; splatraster_debug_set_payload_compact) */
 } splatraster_image_layout;
 int splatraster_get_geometry_layout(int32_t P, splatraster_geometry_layout* out);
 int splatraster_get_binning_layout(int32_t P, int64_t R, int32_t width, int32_t height, int32_t channels,
@@ -945,7 +948,7 @@ int splatraster_pose_step_window(int32_t n, const float* dL_dviewmatrix, const f
 #define SPLATRASTER_STAGE_COMPOSITE_FWD 6  /* composite_fwd_kernel */
 #define SPLATRASTER_STAGE_COMPOSITE_BWD 7  /* composite_bwd_kernel (the accumulator memset before it is not bracketed) */
 #define SPLATRASTER_STAGE_PREPROCESS_BWD 8 /* preprocess_bwd_kernel */
-#define SPLATRASTER_STAGE_PAYLOAD 9        /* payload_kernel: per-instance records, reach masks, tile ranges */
+#define SPLATRASTER_STAGE_PAYLOAD 9        /* payload_kernel / ranges_kernel + payload_tile_kernel: per-instance records, reach masks, tile ranges */
 #define SPLATRASTER_STAGE_COUNT 10
 
 int splatraster_timing_enable(int on);            /* all stages on / off */
@@ -995,6 +998,13 @@ int splatraster_debug_set_fwd_team(int mode);
 /* A/B / test hook: instance count from which the per-instance payload is written with streaming (non-temporal) stores
  * (HISTORY.md §11); < 0 restores the built-in default (8 Mi instances), 0 = always.  Results never depend on it. */
 int splatraster_debug_set_payload_stream_min(int64_t instances);
+/* A/B / test hook: the per-instance payload the compositing kernels stream (irec, ipack) holds only the instances that reach a
+ * quadrant of their tile, each list compacted in place.  -1 (default): on behind the radix front end for launches
+ * of one wave per quadrant over whole lists (not the team forward, not the split launches); 0: off — the full stream, one entry per
+ * instance.  radii, num_rendered, point_list, tile_list, ranges, n_contrib and final_T never depend on it; colours, depth and
+ * alpha are bit-identical for C <= 4 and C = 32..35 (C >= 36: which candidates share a pair-sum changes the last bit).  The
+ * backward reads a binning buffer the way its render stage wrote it, whatever the switch says by then. */
+int splatraster_debug_set_payload_compact(int mode);
 /* A/B / test hook: which front end orders the tile instances.  -1 (default): the binned front end (counting sort by
  * (view, tile) + one LDS sort per tile) for windows of at most 6144 (view, tile) lists — SplatLoc's own
  * 640x480 frames, singly or five at a time — and the two global radix sorts otherwise; 0: the radix sorts always; 1: the

@@ -167,6 +167,7 @@ SYMBOLS = {
     "splatraster_debug_set_tile_sort_cap": (C.c_int, [C.c_int]),
     "splatraster_debug_set_sort_fork": (C.c_int, [C.c_int]),
     "splatraster_debug_set_payload_stream_min": (C.c_int, [C.c_int64]),
+    "splatraster_debug_set_payload_compact": (C.c_int, [C.c_int]),
     "splatraster_mark_visible": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp]),
     "splatraster_get_geometry_layout": (C.c_int, [_i32, C.POINTER(GeometryLayout)]),
     "splatraster_get_binning_layout": (C.c_int, [_i32, _i64, _i32, _i32, _i32, C.POINTER(BinningLayout)]),
@@ -285,6 +286,8 @@ def load(build_if_missing: bool = True):
         lib.splatraster_debug_set_fwd_team(int(os.environ["SPLATRASTER_FWD_TEAM"]))
     if os.environ.get("SPLATRASTER_FRONT_END"):   # -1 auto, 0 radix sorts, 1 binned whenever the shape allows
         lib.splatraster_debug_set_front_end(int(os.environ["SPLATRASTER_FRONT_END"]))
+    if os.environ.get("SPLATRASTER_PAYLOAD_COMPACT"):   # -1 default (compact stream behind the radix front end), 0 the full stream
+        lib.splatraster_debug_set_payload_compact(int(os.environ["SPLATRASTER_PAYLOAD_COMPACT"]))
     if os.environ.get("SPLATRASTER_TILE_SORT_CAP"):
         lib.splatraster_debug_set_tile_sort_cap(int(os.environ["SPLATRASTER_TILE_SORT_CAP"]))
     if os.environ.get("SPLATRASTER_SORT_FORK"):
@@ -335,6 +338,12 @@ def set_front_end(mode: int) -> None:
     """-1: default choice; 0: the two global radix sorts always; 1: the binned front end whenever the shape allows
     (splatraster_debug_set_front_end; bit-identical results either way)."""
     check(load().splatraster_debug_set_front_end(int(mode)), "set_front_end")
+
+
+def set_payload_compact(mode: int) -> None:
+    """-1: default (the compositing kernels stream only the instances that reach a quadrant, behind the radix front end);
+    0: the full stream (splatraster_debug_set_payload_compact)."""
+    check(load().splatraster_debug_set_payload_compact(int(mode)), "set_payload_compact")
 
 
 def poll_stall() -> bool:

@@ -211,6 +211,109 @@ int launch_payload(const splatraster_settings& s, int32_t V, int64_t R, const Ge
     return SPLATRASTER_OK;
 }
 
+// ---- the payload compacted to the LIVE instances of every list ----------------------------------------------
+// An instance whose reach mask is 0 is never a candidate of any quadrant-wave (S2: 41 % of them), yet payload_kernel writes its
+// 36 bytes and the four waves of its tile stream them, forward and backward, and give it a slot of their 64-entry chunks.  Here
+// the stream the compositing kernels read — irec, ipack, nothing else — holds the live instances only: list t = [ranges[2t],
+// ranges[2t+1]) keeps its place and its order, its live entries move to the front, [cranges[2t], cranges[2t+1]).  point_list,
+// tile_list and ranges are what they were.  The kernels count contributors in compact positions (the plane n_contrib_c); the
+// forward translates a pixel's last one back to its full list position through the word this kernel puts where the stream
+// used to carry the radius (irec[2 pos].w, which no compositing kernel reads): the bits of j - ranges[2t] + 1.
+//
+// ranges first: one block per list needs the boundaries before it starts (payload_kernel found them on its way).
+__global__ void __launch_bounds__(256)
+ranges_kernel(int64_t R, const uint32_t* __restrict__ tile_list, uint32_t* __restrict__ ranges)
+{
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= R) return;
+    const uint32_t t = tile_list[j];
+    // per-tile [start, end) of the sorted list (the table was zeroed for the empty tiles)
+    if (j == 0 || tile_list[j - 1] != t) ranges[2 * t] = (uint32_t)j;
+    if (j == R - 1 || tile_list[j + 1] != t) ranges[2 * t + 1] = (uint32_t)(j + 1);
+}
+
+// One 256-thread block per (view, tile) list, 256 entries per step (a 64-entry chunk per wave).  The tile's origin is uniform:
+// no per-thread view / tile division.  Compaction is in place per list — a live entry's position is the list's start + the live
+// entries of the earlier steps + its rank in this step (wave ballots + four per-wave counts in LDS) — so no block waits for
+// another one and nothing is scanned globally.
+template <bool NT>
+__global__ void __launch_bounds__(256)
+payload_tile_kernel(int gx, int tiles_per_view, const uint32_t* __restrict__ ranges, const uint32_t* __restrict__ point_list,
+                    const float4* __restrict__ rec, float4* __restrict__ irec, uint32_t* __restrict__ ipack,
+                    uint32_t* __restrict__ cranges)
+{
+    __shared__ uint32_t s_live[4];
+    const uint32_t gt = blockIdx.x;   // global tile = view * tiles + tile
+    const uint32_t beg = ranges[2 * gt], end = ranges[2 * gt + 1];
+    const uint32_t tl = gt % (uint32_t)tiles_per_view;
+    const uint32_t ty = tl / (uint32_t)gx, tx = tl - ty * (uint32_t)gx;
+    const float ox = (float)(tx * TILE), oy = (float)(ty * TILE);
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (WAVE - lane));
+    uint32_t running = 0;   // live entries of the earlier steps
+#pragma unroll 1
+    for (uint32_t base = beg; base < end; base += 256u) {
+        const uint32_t j = base + threadIdx.x;
+        uint32_t g = 0u, mask = 0u;
+        float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0;
+        if (j < end) {
+            g = point_list[j];
+            a0 = rec[2 * (size_t)g];
+            a1 = rec[2 * (size_t)g + 1];   // one 32-byte gather
+            mask = quadrant_reach_mask(a0, a1, ox, oy);
+        }
+        const bool live = mask != 0u;
+        const uint64_t ballot = __builtin_amdgcn_ballot_w64(live);
+        if (lane == 0) s_live[wave] = (uint32_t)__popcll(ballot);
+        __syncthreads();
+        const uint32_t n0 = s_live[0], n1 = s_live[1], n2 = s_live[2], n3 = s_live[3];
+        __syncthreads();   // (the next step overwrites the counts)
+        const uint32_t before = (wave > 0 ? n0 : 0u) + (wave > 1 ? n1 : 0u) + (wave > 2 ? n2 : 0u);
+        if (live) {
+            const size_t pos = (size_t)beg + running + before + (uint32_t)__popcll(ballot & lt_mask);   // <= j
+            const float4 c1 = payload_conic(a1);   // pre-scaled for gauss_log2 (composite_common.h)
+            const float back = __uint_as_float(j - beg + 1u);   // full list position + 1: moved, never computed on
+            const uint32_t m = g | (mask << 24);
+            if (NT) {   // (payload_kernel: lists larger than the memory-side cache)
+                typedef float f32x4_t __attribute__((ext_vector_type(4)));
+                f32x4_t* out = reinterpret_cast<f32x4_t*>(irec) + 2 * pos;
+                __builtin_nontemporal_store((f32x4_t){a0.x, a0.y, a0.z, back}, out);
+                __builtin_nontemporal_store((f32x4_t){c1.x, c1.y, c1.z, c1.w}, out + 1);
+                __builtin_nontemporal_store(m, ipack + pos);
+            } else {
+                irec[2 * pos] = make_float4(a0.x, a0.y, a0.z, back);
+                irec[2 * pos + 1] = c1;
+                ipack[pos] = m;
+            }
+        }
+        running += n0 + n1 + n2 + n3;
+    }
+    if (threadIdx.x == 0) {
+        cranges[2 * gt] = beg;
+        cranges[2 * gt + 1] = beg + running;
+    }
+}
+
+int launch_payload_compact(const splatraster_settings& s, int32_t V, int64_t R, const GeomView& g, const BinView& b,
+                           uint32_t* cranges, hipStream_t stream)
+{
+    const int gx = (s.image_width + TILE - 1) / TILE, gy = (s.image_height + TILE - 1) / TILE;
+    const unsigned lists = (unsigned)(V * gx * gy);
+    if (R > 0) {   // (R == 0: the table was cleared, every compact range is [0, 0) too)
+        hipLaunchKernelGGL(ranges_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, stream, R, b.tile_list, b.ranges);
+        SR_LAUNCH_CHECK();
+    }
+    if (R >= g_payload_stream_min)
+        hipLaunchKernelGGL(payload_tile_kernel<true>, dim3(lists), dim3(256), 0, stream, gx, gx * gy, b.ranges, b.point_list, g.rec,
+                           b.irec, b.ipack, cranges);
+    else
+        hipLaunchKernelGGL(payload_tile_kernel<false>, dim3(lists), dim3(256), 0, stream, gx, gx * gy, b.ranges, b.point_list, g.rec,
+                           b.irec, b.ipack, cranges);
+    SR_LAUNCH_CHECK();
+    return SPLATRASTER_OK;
+}
+
 // Launch order of the compositing grids.  A window of SplatLoc's own 640x480 frames is 24 000 quadrant-waves on a machine
 // with ~8 000 wave slots: three rounds, and in tile order the last round starts waves of every length — the kernel then
 // waits for the longest of them (measured life times, list-scheduling model: 412 us in tile order, 363 us longest first,

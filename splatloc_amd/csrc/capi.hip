@@ -224,12 +224,23 @@ static size_t img_plane_bytes(int32_t W, int32_t H, int32_t V)
     return align_up((size_t)W * H * 4 * (size_t)(V > 0 ? V : 1), 256);
 }
 
+// final_T, n_contrib (where they always were), then what the compact payload adds: the plane n_contrib_c and the table cranges.
+// (The table belongs to the instance stream, but the binning buffer's size is pinned section by section
+//  — tests/test_accumulator_layout_sizes.py — while this buffer travels with it from the forward to the backward anyway.)
+static size_t img_cranges_bytes(int32_t W, int32_t H, int32_t V)
+{
+    return align_up(8 * (size_t)((W + TILE - 1) / TILE) * (size_t)((H + TILE - 1) / TILE) * (size_t)(V > 0 ? V : 1), 256);
+}
+static size_t img_bytes(int32_t W, int32_t H, int32_t V) { return 3 * img_plane_bytes(W, H, V) + img_cranges_bytes(W, H, V); }
+
 ImgView img_view(void* base, int32_t W, int32_t H, int32_t V)
 {
     char* b = reinterpret_cast<char*>(base);
     ImgView v;
     v.final_T = reinterpret_cast<float*>(b);
     v.n_contrib = reinterpret_cast<uint32_t*>(b + img_plane_bytes(W, H, V));
+    v.n_contrib_c = reinterpret_cast<uint32_t*>(b + 2 * img_plane_bytes(W, H, V));
+    v.cranges = reinterpret_cast<uint32_t*>(b + 3 * img_plane_bytes(W, H, V));
     return v;
 }
 
@@ -282,7 +293,7 @@ size_t splatraster_binning_bytes(int32_t P, int64_t R, int32_t width, int32_t he
 {
     return bin_layout(P, 1, R, width, height, channels).bytes;
 }
-size_t splatraster_image_bytes(int32_t width, int32_t height) { return 2 * img_plane_bytes(width, height, 1); }
+size_t splatraster_image_bytes(int32_t width, int32_t height) { return img_bytes(width, height, 1); }
 
 size_t splatraster_window_geometry_bytes(int32_t P, int32_t n_views) { return geom_layout(P, n_views).bytes; }
 size_t splatraster_window_binning_bytes(int32_t P, int32_t n_views, int64_t R_total, int32_t width, int32_t height,
@@ -292,7 +303,7 @@ size_t splatraster_window_binning_bytes(int32_t P, int32_t n_views, int64_t R_to
 }
 size_t splatraster_window_image_bytes(int32_t width, int32_t height, int32_t n_views)
 {
-    return 2 * img_plane_bytes(width, height, n_views);
+    return img_bytes(width, height, n_views);
 }
 
 int splatraster_get_geometry_layout(int32_t P, splatraster_geometry_layout* out)
@@ -330,7 +341,7 @@ int splatraster_get_window_image_layout(int32_t width, int32_t height, int32_t n
     if (!out || n_views < 1 || n_views > MAX_VIEWS) return SPLATRASTER_ERR_BAD_ARG;
     out->final_T = 0;
     out->n_contrib = img_plane_bytes(width, height, n_views);
-    out->total = 2 * img_plane_bytes(width, height, n_views);
+    out->total = img_bytes(width, height, n_views);
     return SPLATRASTER_OK;
 }
 
@@ -381,6 +392,30 @@ static int front_end_recorded(const void* geometry)   // -1 unknown, 0 radix, 1 
     std::lock_guard<std::mutex> lk(g_front_end_mu);
     auto it = g_front_end.find(geometry);
     return it == g_front_end.end() ? -1 : (it->second ? 1 : 0);
+}
+
+// Compact payload (binning.hip payload_tile_kernel): on behind the radix front end, for launches of one wave per quadrant over
+// whole lists — the binned front end writes its own payload, a team or a split launch walks full list positions.
+static int g_payload_compact = -1;   // splatraster_debug_set_payload_compact: -1 default (on), 0 off (payload_kernel, the full stream)
+static bool payload_compact(const splatraster_settings& s, int32_t V, int64_t R, bool binned)
+{
+    const int tiles = ((s.image_width + TILE - 1) / TILE) * ((s.image_height + TILE - 1) / TILE);
+    return g_payload_compact != 0 && R > 0 && !binned && !split_lists(s.channels, V, tiles) && !fwd_team_launch(s.channels, V, tiles);
+}
+// What the RENDER stage wrote into a binning buffer: the backward is a separate public call and must read the stream the way it was
+// written, whatever the debug switches say by then (the front end's record above, keyed by the binning buffer's address).
+static std::unordered_map<const void*, bool> g_compact;
+static void compact_record(const void* binning, bool on)
+{
+    std::lock_guard<std::mutex> lk(g_front_end_mu);
+    if (g_compact.size() > (1u << 14)) g_compact.clear();
+    g_compact[binning] = on;
+}
+static int compact_recorded(const void* binning)   // -1 unknown, 0 full stream, 1 compact
+{
+    std::lock_guard<std::mutex> lk(g_front_end_mu);
+    auto it = g_compact.find(binning);
+    return it == g_compact.end() ? -1 : (it->second ? 1 : 0);
 }
 
 static BinScratch bin_scratch(const splatraster_settings& s, int32_t P, int32_t V, void* geometry, bool geometry_stage)
@@ -567,9 +602,12 @@ static int window_render(const splatraster_settings* s, int32_t V, const splatra
     }
     if (st) return st;
     const float* featp = feat;  // 16-byte aligned rows for the compositing kernels
+    const bool compact = payload_compact(*s, V, R, bins.on);
+    compact_record(binning, compact);
     if (R > 0) {
         StageTimer t(SPLATRASTER_STAGE_PAYLOAD, stream);
-        if (!bins.on) st = launch_payload(*s, V, R, g, b, stream);
+        if (compact) st = launch_payload_compact(*s, V, R, g, b, im.cranges, stream);
+        else if (!bins.on) st = launch_payload(*s, V, R, g, b, stream);
         if (st) return st;
         if (s->channels % 4) {
             st = launch_pad_features(P, s->channels, feat, b.featp, stream);
@@ -589,6 +627,9 @@ static int window_render(const splatraster_settings* s, int32_t V, const splatra
         outs.depth[v] = views[v].out_depth;
         outs.alpha[v] = views[v].out_alpha;
     }
+    // compact: the kernels walk [cranges) of irec / ipack and count in its positions (n_contrib_c); the forward fills both planes
+    if (compact) b.ranges = im.cranges;
+    else im.n_contrib_c = nullptr;
     StageTimer t(SPLATRASTER_STAGE_COMPOSITE_FWD, stream);
     return launch_composite_fwd(*s, P, V, R, g, b, im, featp, bg, outs, stream);
 }
@@ -637,6 +678,12 @@ static int window_accumulate(const splatraster_settings* s, int32_t V, const spl
     // zero the accumulator rows (outside the stage bracket: the stage is the kernel alone, so its
     // figure can be held against the per-kernel rocprofv3 average)
     const size_t gacc_n = gacc_total_floats(C, (size_t)P, (size_t)V);   // shared colour rows + per-(view, Gaussian) rows
+    // the stream as the render stage wrote it: compact -> the kernels (unchanged) receive cranges for ranges and n_contrib_c for
+    // n_contrib; their `idx < last` test and the bound list0 + wave_last then hold in compact positions
+    const int rec_c = compact_recorded(binning);
+    const bool compact = rec_c >= 0 ? rec_c == 1 : payload_compact(*s, V, R, bin_scratch(*s, P, V, geometry, false).on);
+    BinView bw = b;      // what the compositing launch sees (`out` keeps the plain views)
+    if (compact) { bw.ranges = im.cranges; im.n_contrib = im.n_contrib_c; }
     const bool det = g_deterministic != 0;
     long long* gacc64 = nullptr;   // debug mode only: stream-ordered scratch, freed below (never part of `binning`)
     if (det) {
@@ -653,8 +700,8 @@ static int window_accumulate(const splatraster_settings* s, int32_t V, const spl
         StageTimer t(SPLATRASTER_STAGE_COMPOSITE_BWD, stream);
         // deterministic mode: the kernel runs twice — per-element max of |partial| (into the zeroed float rows), then the
         // fixed-point sums scaled by that maximum (composite_bwd.hip acc_add)
-        if (det) st = launch_composite_bwd(*s, P, V, R, g, b, im, (C % 4) ? b.featp : feat, C, grads, b.gacc, gacc64, 0, stream);
-        if (!st) st = launch_composite_bwd(*s, P, V, R, g, b, im, (C % 4) ? b.featp : feat, C, grads, b.gacc, gacc64, 1, stream);
+        if (det) st = launch_composite_bwd(*s, P, V, R, g, bw, im, (C % 4) ? b.featp : feat, C, grads, b.gacc, gacc64, 0, stream);
+        if (!st) st = launch_composite_bwd(*s, P, V, R, g, bw, im, (C % 4) ? b.featp : feat, C, grads, b.gacc, gacc64, 1, stream);
     }
     if (det) {
         if (!st) st = launch_fixed_to_float((int64_t)gacc_n, gacc64, b.gacc, gacc_det_headroom_drop(C, V), stream);
@@ -893,6 +940,12 @@ int splatraster_debug_set_small_panel_max_waves(int waves)
 int splatraster_debug_set_payload_stream_min(int64_t instances)
 {
     sr::set_payload_stream_min(instances);
+    return SPLATRASTER_OK;
+}
+
+int splatraster_debug_set_payload_compact(int mode)
+{
+    g_payload_compact = mode < 0 ? -1 : (mode ? 1 : 0);
     return SPLATRASTER_OK;
 }
 

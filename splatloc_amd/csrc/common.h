@@ -120,8 +120,12 @@ struct BinView {
     uint32_t* tile_order; // [V * tiles] global tile ids, longest list first: the launch order of the compositing kernels
 };
 struct ImgView {
-    float* final_T;       // [V][H * W]
-    uint32_t* n_contrib;  // [V][H * W]
+    float* final_T;         // [V][H * W]
+    uint32_t* n_contrib;    // [V][H * W] a pixel's last contributor: its position in the tile's list + 1 (0: none)
+    // compact payload (binning.hip payload_tile_kernel; behind the plain planes, whose offsets are what they always were):
+    uint32_t* n_contrib_c;  // [V][H * W] the same contributor's position + 1 in the list's COMPACT stream: what the backward bounds its walk by.
+                            //     A launch's own copy of this struct holds null here when the launch streams the full lists.
+    uint32_t* cranges;      // [2 * V * tiles] [start, end) of every list's live entries inside irec / ipack (start = ranges[2t])
 };
 
 GeomView geom_view(void* base, int32_t P, int32_t V);
@@ -256,6 +260,9 @@ int launch_emit(const splatraster_settings& s, int32_t P, int32_t V, int64_t R, 
                 uint32_t* vals, uint32_t* ranges, uint32_t nranges, hipStream_t stream, bool keys16 = false /*keys: [R] uint16_t*/);
 int launch_ranges_clear(int32_t tiles, uint32_t* ranges, hipStream_t stream);
 int launch_payload(const splatraster_settings& s, int32_t V, int64_t R, const GeomView& g, const BinView& b, hipStream_t stream);
+// ranges, then irec / ipack compacted to the live instances of every list and their table `cranges` (R > 0; radix front end)
+int launch_payload_compact(const splatraster_settings& s, int32_t V, int64_t R, const GeomView& g, const BinView& b,
+                           uint32_t* cranges, hipStream_t stream);
 // 16-byte aligned copy of the [P, C] feature rows (returns feat itself when C % 4 == 0)
 int launch_pad_features(int32_t P, int C, const float* feat, float* featp, hipStream_t stream);
 static inline int padded_channels(int C) { return (C + 3) & ~3; }
@@ -355,6 +362,7 @@ static_assert(SPLIT_EXTRA_TILES % 8 == 0, "the extra workgroups use the quadrant
 void set_split_max_waves(int waves);   // A/B hook (< 0: default)
 void set_fwd_team(int mode);           // A/B hook: teams of four waves for the longest lists of a narrow launch (-1 automatic, 0 never, 1 whenever possible)
 void set_payload_stream_min(int64_t instances);   // test hook (< 0: default)
+bool fwd_team_launch(int C, int V, int tiles);    // the forward of this shape would run composite_fwd_mixed_kernel (composite_fwd.hip)
 int split_max_waves();
 static inline bool split_lists(int C, int V, int tiles) { return C <= 4 && 4 * V * tiles <= split_max_waves(); }
 // parts of a list of `len` entries at position `rank` of the launch order

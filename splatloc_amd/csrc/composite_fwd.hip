@@ -113,7 +113,8 @@ composite_fwd_kernel(int W, int H, int CP4, int c0, int bg_channels, int write_a
                      const float4* __restrict__ irec, const float4* __restrict__ featp4,
                      const float* __restrict__ bg, WinOut outs,
                      float* __restrict__ final_T_all, uint32_t* __restrict__ n_contrib_all,
-                     const uint32_t* __restrict__ tile_order /*launch order (binning.hip), or null*/)
+                     const uint32_t* __restrict__ tile_order /*launch order (binning.hip), or null*/,
+                     uint32_t* __restrict__ n_contrib_c_all /*non-null: `ranges` / ipack / irec are the COMPACT stream (binning.hip payload_tile_kernel)*/)
 {
     static_assert(NC > 4, "narrow layouts have their own kernels");
     using Cfg = FwdCfg<NC>;
@@ -297,6 +298,12 @@ composite_fwd_kernel(int W, int H, int CP4, int c0, int bg_channels, int write_a
         for (int ch = 0; ch < NV; ++ch) acc[ch] = acc4[ch];
         D = acc4[3];
     }
+    // compact stream (launch-uniform): `last` is a position among the list's LIVE entries, which is what the backward walks; the
+    // list position n_contrib promises travels as bits in that entry's record (.w: moved, never computed on) — one gather per pixel
+    if (n_contrib_c_all != nullptr && write_aux && inside) {
+        (n_contrib_c_all + (size_t)view * H * W)[(size_t)py * W + px] = last;
+        if (last) last = __float_as_uint(irec[2 * (size_t)(beg + last - 1u)].w);
+    }
     if (MFMA) {
         mfma_drain(accA, accB);
         // D[ch][pix]: lane l, register r holds channel (r&3) + 8 (r>>2) + 4 (l>>5) of wave pixel
@@ -343,8 +350,9 @@ composite_fwd_kernel(int W, int H, int CP4, int c0, int bg_channels, int write_a
         const float4 *__restrict__ irec, const float4 *__restrict__ featp4, const float *__restrict__ bg, WinOut outs,      \
         float *__restrict__ final_T_all, uint32_t *__restrict__ n_contrib_all,                                              \
         float *__restrict__ ckpt_all /*split launches (common.h): [V][SPLIT_PARTS_MAX][NC + 2][H * W] segment records, else null*/, \
-        const uint32_t *__restrict__ nparts /*split launches: parts of every (view, tile) list (written with the launch order), or null: SPLIT_PARTS*/
-#define SR_FWD_ARGS W, H, CP4, c0, bg_channels, write_aux, tiles, V, P, ranges, ipack, irec, featp4, bg, outs, final_T_all, n_contrib_all, ckpt_all, nparts
+        const uint32_t *__restrict__ nparts /*split launches: parts of every (view, tile) list (written with the launch order), or null: SPLIT_PARTS*/, \
+        uint32_t *__restrict__ n_contrib_c_all /*non-null: `ranges` / ipack / irec are the COMPACT stream (one-wave kernel only; never with ckpt_all)*/
+#define SR_FWD_ARGS W, H, CP4, c0, bg_channels, write_aux, tiles, V, P, ranges, ipack, irec, featp4, bg, outs, final_T_all, n_contrib_all, ckpt_all, nparts, n_contrib_c_all
 
 // one quadrant of global tile `gtile` (= view * tiles + tile) by ONE wave; s_rec0 / s_rec1 / s_fq: WAVE + 1 float4 each, the wave's own
 template <int NC>
@@ -498,6 +506,11 @@ __device__ __forceinline__ void narrow_quadrant(SR_FWD_PARAMS, int gtile, int qu
         for (int ch = 0; ch < NC; ++ch) sacc[ch] = 0.0f;
         sD = 0.0f;
         for (int k = ck_k + 1; k < np; ++k) store_segment(k, false);   // segments the wave never reached contribute nothing
+    }
+    // compact stream (composite_fwd_kernel): compact position -> n_contrib_c, the list position behind it -> n_contrib
+    if (n_contrib_c_all != nullptr && write_aux && inside) {
+        (n_contrib_c_all + (size_t)view * H * W)[(size_t)py * W + px] = last;
+        if (last) last = __float_as_uint(irec[2 * (size_t)(beg + last - 1u)].w);
     }
     if (inside) {
         const size_t plane = (size_t)H * W;
@@ -939,6 +952,7 @@ struct FwdLaunch {
 
 static int g_fwd_team = -1;   // -1: automatic (the split launches' condition), 0: never, 1: every narrow launch that has a launch order, 2: and a team for each of its first TEAM_MAX lists
 void set_fwd_team(int mode) { g_fwd_team = mode; }
+bool fwd_team_launch(int C, int V, int tiles) { return g_fwd_team < 0 ? split_lists(C, V, tiles) : (g_fwd_team != 0 && C <= 4); }
 
 template <int NC>
 static int launch_one(const splatraster_settings& s, int c0, int write_aux, const GeomView& g,
@@ -954,19 +968,20 @@ static int launch_one(const splatraster_settings& s, int c0, int write_aux, cons
             hipLaunchKernelGGL(composite_fwd_mixed_kernel<NC>, dim3((unsigned)(L.V * tiles + 4 * TEAM_MAX)), dim3(4 * WAVE), 0, stream,
                                s.image_width, s.image_height, padded_channels(feat_stride) / 4, c0, s.bg_channels, write_aux, tiles, L.V, L.P,
                                b.ranges, b.ipack, b.irec, reinterpret_cast<const float4*>(featp), bg, *L.outs, im.final_T, im.n_contrib,
-                               (c0 == 0 && write_aux) ? L.ckpt : nullptr, b.nparts, b.tile_order, g_fwd_team == 2 ? 1 : 0);
+                               (c0 == 0 && write_aux) ? L.ckpt : nullptr, b.nparts, (uint32_t*)nullptr /*teams stream the full lists*/,
+                               b.tile_order, g_fwd_team == 2 ? 1 : 0);
         } else {
             hipLaunchKernelGGL(composite_fwd_narrow_kernel<NC>, dim3(blocks), dim3(WAVE), 0, stream, s.image_width,
                                s.image_height, padded_channels(feat_stride) / 4, c0, s.bg_channels, write_aux, tiles, L.V, L.P, b.ranges,
                                b.ipack, b.irec, reinterpret_cast<const float4*>(featp), bg, *L.outs, im.final_T,
                                im.n_contrib, (c0 == 0 && write_aux) ? L.ckpt : nullptr, use_tile_order(L.V, tiles) ? b.nparts : nullptr,
-                               use_tile_order(L.V, tiles) ? b.tile_order : nullptr);
+                               im.n_contrib_c, use_tile_order(L.V, tiles) ? b.tile_order : nullptr);
         }
     } else {
         hipLaunchKernelGGL(composite_fwd_kernel<NC>, dim3(blocks), dim3(WAVE), 0, stream, s.image_width,
                            s.image_height, padded_channels(feat_stride) / 4, c0, s.bg_channels, write_aux, tiles, L.V, L.P, b.ranges,
                            b.ipack, b.irec, reinterpret_cast<const float4*>(featp), bg, *L.outs, im.final_T,
-                           im.n_contrib, use_tile_order(L.V, tiles) ? b.tile_order : nullptr);
+                           im.n_contrib, use_tile_order(L.V, tiles) ? b.tile_order : nullptr, im.n_contrib_c);
     }
     SR_LAUNCH_CHECK();
     return SPLATRASTER_OK;
@@ -978,7 +993,9 @@ int launch_composite_fwd(const splatraster_settings& s, int32_t P, int32_t V, in
     (void)R;
     const int C = s.channels;
     const int tiles_v = ((s.image_width + TILE - 1) / TILE) * ((s.image_height + TILE - 1) / TILE);
-    const bool team = g_fwd_team < 0 ? split_lists(C, V, tiles_v) : (g_fwd_team != 0 && C <= 4);
+    const bool team = fwd_team_launch(C, V, tiles_v);
+    // (a compact stream never meets a team or a split launch: capi.hip payload_compact)
+    if (im.n_contrib_c != nullptr && (team || split_lists(C, V, tiles_v))) return SPLATRASTER_ERR_BAD_ARG;
     const FwdLaunch L{P, V, &outs, split_lists(C, V, tiles_v) ? b.ckpt : nullptr, team};
     int c0 = 0, aux = 1, st = SPLATRASTER_OK;
 #define SR_FWD_CASE(N)                                                                              \

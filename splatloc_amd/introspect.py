@@ -55,6 +55,39 @@ def image_views(img: torch.Tensor, W: int, H: int) -> dict:
     )
 
 
+def payload_state(fn_ctx_tensors, R: int, W: int, H: int, V: int = 1, compact: bool = True) -> dict:
+    """The per-instance stream the compositing kernels read, of a per-view (V = 1) or window forward (R: all its instances):
+    `irec` [n, 8] (pixel x, y, depth, a moved word | pre-scaled conic, opacity), `ids` [n] rows and `imask` [n] reach bits, entry by
+    entry.  compact = False: the full stream, n = R, one entry per instance of point_list.  compact = True (a forward that wrote
+    the compact payload — splatraster_debug_set_payload_compact): only the LIVE entries of every list, in list order — what lies
+    behind them in a list's span was never written and is not exposed —, with `cranges` [V * tiles, 2], `n_contrib_c` [V, H, W]
+    and `back` [n]: every entry's position + 1 in its full list (the word irec[:, 3] carries).  The offsets mirror
+    csrc/capi.hip: bin_layout / img_view."""
+    lib = _native.load()
+    _geom, binning, img = fn_ctx_tensors
+    BL, IL = _native.BinningLayout(), _native.ImageLayout()
+    _native.check(lib.splatraster_get_window_binning_layout(1, V, R, W, H, 4, C.byref(BL)), "window_binning_layout")
+    _native.check(lib.splatraster_get_window_image_layout(W, H, V, C.byref(IL)), "window_image_layout")
+    al = lambda b: (b + 255) // 256 * 256  # noqa: E731
+    tiles = V * ((W + 15) // 16) * ((H + 15) // 16)
+    n = max(int(R), 1)
+    irec_off = BL.ranges + al(8 * tiles) + al(lib.splatraster_sort_tmp_bytes(n) - 2 * al(4 * n))
+    irec = _view(binning, irec_off, 8 * int(R), torch.float32).view(int(R), 8)
+    ipack = _view(binning, irec_off + al(32 * n), int(R), torch.int32)
+    out = {}
+    if compact:
+        plane = IL.n_contrib                     # the planes are equally large: final_T, n_contrib, n_contrib_c, then the table
+        cr = _view(img, 3 * plane, 2 * tiles, torch.int32).view(tiles, 2).long()
+        lens = cr[:, 1] - cr[:, 0]
+        first = torch.cumsum(lens, 0) - lens     # every live entry's index: its list's start + its rank inside the list
+        idx = torch.repeat_interleave(cr[:, 0] - first, lens) + torch.arange(int(lens.sum()), device=lens.device)
+        irec, ipack = irec[idx], ipack[idx]
+        out.update(cranges=cr.int(), n_contrib_c=_view(img, 2 * plane, V * W * H, torch.int32).view(V, H, W),
+                   back=irec[:, 3].contiguous().view(torch.int32))
+    out.update(irec=irec, ids=ipack & 0xFFFFFF, imask=(ipack >> 24) & 0xF)
+    return out
+
+
 def forward_buffers(grad_fn):
     """(geom, binning, img) of the per-view or window forward behind an output's grad_fn."""
     from .rasterizer import _saved

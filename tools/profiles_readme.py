@@ -52,6 +52,9 @@ WHAT = [   # (file name regex, description; {placeholders} are filled by the ext
     (r"^front_end_kernel_stats\.txt$", "`rocprofv3 --kernel-trace --stats` of the default bench, parent (first listing) and the 16-bit tile-sort keys (second; DESIGN §3.1), us per launch: {fe_kstats}"),
     (r"^front_end_pmc_hbm\.json$", "separate `--pmc FETCH_SIZE` / `--pmc WRITE_SIZE` passes of the same command for the radix front end's kernels, parent and change, and FETCH_SIZE of `payload_kernel` under the XCD-band mappings of `tools/patches/payload_xcd_band.patch`: {fe_pmc}"),
     (r"^front_end_ab\.json$", "`tools/ab.py`, base = the change (16-bit tile-sort keys), variants = the parent commit's library and the rejected XCD-band mappings of `payload_kernel` with and without the 16-bit keys (differences are variant minus change): {ab}; {fe_ab}"),
+    (r"^payload_compact_kernel_stats\.txt$", "`rocprofv3 --kernel-trace --stats` of the default bench, parent (first listing) and the compact payload (second; DESIGN §3.1), us per launch: {pc_kstats}"),
+    (r"^payload_compact_pmc_hbm\.json$", "separate `--pmc FETCH_SIZE` / `--pmc WRITE_SIZE` runs of the default bench, parent and change, for the payload and the two compositing kernels, and the live fraction of the window's tile instances read through `introspect.payload_state`: {pc_pmc}"),
+    (r"^payload_compact_ab.*\.json$", "`tools/ab.py`, base = the change (compact payload), variant `parent` = the parent commit's library (differences are parent minus change): {ab}; {pc_ab}"),
     (r"traffic\.json$", "per-stage HBM bytes per launch that `bench.py` replays as `roofline.traffic` (recorded workload / launch mode inside)"),
     (r"valu\.json$", "VALU / MFMA / SALU wave-instructions, busy fractions of the two compositing kernels per launch (replayed by `bench.py` as `frame_valu` / `roofline_valu`)"),
     (r"r01_v1_first_.*", "round 1: the first correct pipeline (per-value DPP reductions, no reach masks)"),
@@ -294,6 +297,34 @@ def setup_ab(path):
             f"{c['bwd_ms']['parent']:.4f} -> {c['bwd_ms']['change']:.4f} ms, ms x MHz {k['parent']['mean']:.0f} -> {k['change']['mean']:.0f}")
 
 
+def pc_kstats(path):
+    halves, out = open(path).read().split("# rocprofv3")[1:], []
+    for name in ("payload_kernel", "ranges_kernel", "payload_tile_kernel", "composite_fwd_kernel<35>", "composite_bwd_kernel<35"):
+        per = []
+        for h in halves:
+            rows = [ln.split() for ln in h.splitlines() if ln.startswith(name)]
+            per.append(" + ".join(f"{float(r[-6]):.1f}" for r in rows) or "-")
+        out.append(f"`{name}` " + " -> ".join(per))
+    return "; ".join(out)
+
+
+def pc_pmc(path):
+    j = _load(path) or {}
+    w = j.get("written_MB_per_launch") or {}
+    return (f"live fraction {j.get('live_fraction', {}).get('live_fraction')}; MB written per launch (WRITE_SIZE as reported): "
+            + ", ".join(f"{k} {v:.0f}" for k, v in w.items()))
+
+
+def pc_ab(path):
+    c = (_load(path) or {}).get("change_vs_parent")
+    if not c:
+        return "(other workload: frames/s only)"
+    return (f"change minus parent {c['fps_diff_pct_of_parent_mean']['mean']:+.2f} % of the parent's frames/s (CI "
+            f"{c['fps_diff_pct_of_parent_mean']['ci95'][0]:+.2f} .. {c['fps_diff_pct_of_parent_mean']['ci95'][1]:+.2f} %, margin {c['margin_pct']} %); "
+            + "; ".join(f"{k} {v['parent_ms']:.4f} -> {v['change_ms']:.4f} ms, ms x MHz {v['parent_kcycles']:.0f} -> {v['change_kcycles']:.0f}"
+                        for k, v in c["stages"].items()))
+
+
 def fe_kstats(path):
     """the two listings' large launches of the front-end kernels (the tile sort's; the depth sort's small ones share the names)"""
     halves, out = open(path).read().split("# rocprofv3")[1:], []
@@ -320,7 +351,7 @@ def fe_ab(path):
             f"{c['payload_ms']['change']:.4f} ms ({', '.join(f'{k} {v:.4f}' for k, v in c['payload_ms_of_band_variants'].items())})")
 
 
-EXTRACT = {"fe_kstats": fe_kstats, "fe_pmc": fe_pmc, "fe_ab": fe_ab, "setup_pmc": setup_pmc, "kstats2": kstats2, "setup_ab": setup_ab, "scenelists": scenelists, "scene": scene, "ab": ab, "perview": perview, "mapidle": mapidle, "rccl": rccl, "kstats": kstats, "hbm": hbm, "sq": sq, "timeline": timeline, "bench": bench, "clocks": clocks, "gradbars": gradbars, "idle": idle, "landmark": landmark, "matching": matching, "pnp": pnp, "decoder": decoder, "fusion": fusion, "localize": localize, "posewindow": posewindow}
+EXTRACT = {"pc_kstats": pc_kstats, "pc_pmc": pc_pmc, "pc_ab": pc_ab, "fe_kstats": fe_kstats, "fe_pmc": fe_pmc, "fe_ab": fe_ab, "setup_pmc": setup_pmc, "kstats2": kstats2, "setup_ab": setup_ab, "scenelists": scenelists, "scene": scene, "ab": ab, "perview": perview, "mapidle": mapidle, "rccl": rccl, "kstats": kstats, "hbm": hbm, "sq": sq, "timeline": timeline, "bench": bench, "clocks": clocks, "gradbars": gradbars, "idle": idle, "landmark": landmark, "matching": matching, "pnp": pnp, "decoder": decoder, "fusion": fusion, "localize": localize, "posewindow": posewindow}
 
 
 def describe(name, path):
