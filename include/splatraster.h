@@ -188,7 +188,8 @@ int splatraster_backward(const splatraster_settings* s, int32_t P, int64_t R,
  * Colours must be precomputed (`colors_precomp`, SplatLoc's configuration): view-dependent SH colours stay on the
  * per-view call (SPLATRASTER_ERR_UNSUPPORTED here).  The pose-gradient extension has a window entry point of its own,
  * splatraster_backward_window_cameras below: the camera gradients of every view and NO parameter gradients (pose refinement
- * freezes the map); splatraster_backward_window itself returns parameter gradients only.
+ * freezes the map); splatraster_backward_window itself returns parameter gradients only, and
+ * splatraster_backward_window_joint returns both from one compositing backward.
  */
 #define SPLATRASTER_MAX_WINDOW_VIEWS 8
 
@@ -270,6 +271,33 @@ int splatraster_backward_window_cameras(const splatraster_settings* s, int32_t n
                                         float* dL_dprojmatrix, /* [n_views,4,4] */
                                         float* dL_dcampos,     /* [n_views,3] or NULL */
                                         void* stream);
+
+/* Parameter gradients AND camera gradients of the n_views <= 8 views of a window in one launch sequence (key-frame poses
+ * optimised together with the map over a window): ONE accumulator fill and ONE compositing backward (the
+ * deterministic debug mode and the compact payload stream included), the colour gather / copy of splatraster_backward_window,
+ * then ONE per-Gaussian kernel that reads every (view, Gaussian) row once, sums the views' parameter gradients in view order —
+ * the outputs of splatraster_backward_window, views[v].dL_dmeans2D included — and reduces the 27 camera partial sums of every view
+ * the way splatraster_backward_window_cameras does (replicated sets, one ticket per view; no block waits for another).  The
+ * argument rules are those of the two calls together; `workspace` and the camera outputs are that call's: [n_views,4,4],
+ * [n_views,4,4] and [n_views,3] (may be NULL; zeros), written in full, zeros for a view that sees nothing and when P == 0.
+ * n_views outside 1 .. 8 or a NULL required pointer: SPLATRASTER_ERR_BAD_ARG before any launch.  No host synchronisation.  For
+ * n_views == 1 the results are those of splatraster_backward with its three camera outputs, up to float summation order.
+ * Precomputed colours only, and no raw-parameter variant: splatraster_backward_window_raw returns no camera gradient. */
+int splatraster_backward_window_joint(const splatraster_settings* s, int32_t n_views, const splatraster_window_view* views,
+                                      int32_t P, const int64_t* num_rendered, const float* bg, const float* means3D,
+                                      const float* colors_precomp, const float* scales, const float* rotations,
+                                      const float* cov3D_precomp, void* geometry, const void* binning, const void* image,
+                                      float* dL_dmeans3D,   /* [P,3] */
+                                      float* dL_dcolors,    /* [P,C] */
+                                      float* dL_dopacities, /* [P,1] */
+                                      float* dL_dscales,    /* [P,3] or NULL */
+                                      float* dL_drotations, /* [P,4] or NULL */
+                                      float* dL_dcov3D,     /* [P,6] or NULL */
+                                      void* workspace,      /* splatraster_window_camera_workspace_bytes(n_views), zeroed by the call */
+                                      float* dL_dviewmatrix, /* [n_views,4,4] */
+                                      float* dL_dprojmatrix, /* [n_views,4,4] */
+                                      float* dL_dcampos,     /* [n_views,3] or NULL; zeros */
+                                      void* stream);
 
 /* The same backward, writing the gradients of SplatLoc's RAW parameters directly (SH degree 0, scales + rotations; what
  * gaussian_model.py:78-105 and gaussian_renderer/__init__.py:84-102 put between the optimiser tensors and the rasterizer call):

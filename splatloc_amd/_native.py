@@ -153,6 +153,8 @@ SYMBOLS = {
     "splatraster_window_camera_workspace_bytes": (_sz, [_i32]),
     "splatraster_backward_window_cameras": (C.c_int, [C.POINTER(Settings), _i32, C.POINTER(WindowView), _i32, C.POINTER(_i64)]
                                             + [_vp] * 14),
+    "splatraster_backward_window_joint": (C.c_int, [C.POINTER(Settings), _i32, C.POINTER(WindowView), _i32, C.POINTER(_i64)]
+                                          + [_vp] * 20),
     "splatraster_forward_window_geometry_raw": (C.c_int, [C.POINTER(Settings), _i32, C.POINTER(WindowView), _i32, _vp, C.POINTER(RawForward),
                                                           _vp, C.POINTER(_i64), _vp]),
     "splatraster_backward_window_raw": (C.c_int, [C.POINTER(Settings), _i32, C.POINTER(WindowView), _i32, C.POINTER(_i64)]

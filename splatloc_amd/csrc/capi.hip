@@ -900,6 +900,52 @@ int splatraster_backward_window_cameras(const splatraster_settings* s, int32_t n
                              reinterpret_cast<float*>(workspace), dL_dviewmatrix, dL_dprojmatrix, dL_dcampos, stream);
 }
 
+int splatraster_backward_window_joint(const splatraster_settings* s, int32_t n_views, const splatraster_window_view* views,
+                                      int32_t P, const int64_t* num_rendered, const float* bg, const float* means3D,
+                                      const float* colors_precomp, const float* scales, const float* rotations,
+                                      const float* cov3D_precomp, void* geometry, const void* binning, const void* image,
+                                      float* dL_dmeans3D, float* dL_dcolors, float* dL_dopacities, float* dL_dscales,
+                                      float* dL_drotations, float* dL_dcov3D, void* workspace, float* dL_dviewmatrix,
+                                      float* dL_dprojmatrix, float* dL_dcampos, void* stream_)
+{
+    const int32_t V = n_views;
+    int st = check_window(s, V, views);
+    if (st) return st;
+    if (P < 0 || !num_rendered || !workspace || !dL_dviewmatrix || !dL_dprojmatrix) return SPLATRASTER_ERR_BAD_ARG;
+    int64_t R = 0;
+    for (int v = 0; v < V; ++v) {
+        if (num_rendered[v] < 0) return SPLATRASTER_ERR_BAD_ARG;
+        R += num_rendered[v];
+    }
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    if (P == 0) {   // nothing to differentiate: the camera gradients are still defined (zero)
+        SR_HIP_CHECK(hipMemsetAsync(dL_dviewmatrix, 0, 16 * sizeof(float) * (size_t)V, stream));
+        SR_HIP_CHECK(hipMemsetAsync(dL_dprojmatrix, 0, 16 * sizeof(float) * (size_t)V, stream));
+        if (dL_dcampos) SR_HIP_CHECK(hipMemsetAsync(dL_dcampos, 0, 3 * sizeof(float) * (size_t)V, stream));
+        return SPLATRASTER_OK;
+    }
+    if (!means3D || !colors_precomp || !geometry || !binning || !image || !dL_dmeans3D || !dL_dcolors || !dL_dopacities)
+        return SPLATRASTER_ERR_BAD_ARG;
+    if (cov3D_precomp ? (scales || rotations || !dL_dcov3D) : (!scales || !rotations || !dL_dscales || !dL_drotations))
+        return SPLATRASTER_ERR_BAD_ARG;
+    for (int v = 0; v < V; ++v)
+        if (!views[v].viewmatrix || !views[v].projmatrix || !views[v].radii || !views[v].out_color || !views[v].out_depth ||
+            !views[v].dL_dout_color || !views[v].dL_dmeans2D)
+            return SPLATRASTER_ERR_BAD_ARG;
+    // ONE accumulator fill and ONE compositing backward for both gradient sets
+    BwdRows rows;
+    st = window_accumulate(s, V, views, P, R, bg, colors_precomp, false, geometry, binning, image, false, stream, &rows);
+    if (st) return st;
+    // the sets and tickets of the V views: the caller's memory, zeroed on the stream in front of the kernel that adds to them
+    SR_HIP_CHECK(hipMemsetAsync(workspace, 0, splatraster_window_camera_workspace_bytes(V), stream));
+    StageTimer t(SPLATRASTER_STAGE_PREPROCESS_BWD, stream);
+    return launch_window_joint_bwd(*s, P, V, rows.cams, rows.grads, means3D, scales, rotations, cov3D_precomp, rows.g.rec,
+                                   rows.b.gacc, s->channels, dL_dcolors, dL_dmeans3D, dL_dopacities,
+                                   cov3D_precomp ? nullptr : dL_dscales, cov3D_precomp ? nullptr : dL_drotations,
+                                   cov3D_precomp ? dL_dcov3D : nullptr, reinterpret_cast<float*>(workspace), dL_dviewmatrix,
+                                   dL_dprojmatrix, dL_dcampos, stream);
+}
+
 int splatraster_forward_window_geometry_raw(const splatraster_settings* s, int32_t n_views, const splatraster_window_view* views,
                                             int32_t P, const float* means3D, const splatraster_raw_forward* rf, void* geometry,
                                             int64_t* num_rendered, void* stream)

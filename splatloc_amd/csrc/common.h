@@ -191,6 +191,15 @@ int launch_preprocess_bwd(const splatraster_settings& s, int32_t P, int32_t V, c
 int launch_camera_bwd(const splatraster_settings& s, int32_t P, int32_t V, const WinCams& cams, const float* means3D,
                       const float* scales, const float* rotations, const float* cov3D_precomp, const float4* rec,
                       const float* gacc, int C, float* ws, float* dL_dview, float* dL_dproj, float* dL_dcampos, hipStream_t stream);
+// the colour gather / copy in front of a window's per-Gaussian pass (preprocess_bwd.hip)
+int launch_window_dcolors(int32_t P, int32_t V, int C, const float* gacc, float* dL_dcolors, hipStream_t stream);
+// parameter gradients summed over the V views (as launch_preprocess_bwd, precomputed colours) AND the camera gradients of every
+// view (as launch_camera_bwd; `ws` likewise) from one read of every (view, Gaussian) row (window_joint_bwd.hip)
+int launch_window_joint_bwd(const splatraster_settings& s, int32_t P, int32_t V, const WinCams& cams, const WinGrad& grads,
+                            const float* means3D, const float* scales, const float* rotations, const float* cov3D_precomp,
+                            const float4* rec, const float* gacc, int C, float* dL_dcolors, float* dL_dmeans3D,
+                            float* dL_dopacities, float* dL_dscales, float* dL_drotations, float* dL_dcov3D, float* ws,
+                            float* dL_dview, float* dL_dproj, float* dL_dcampos, hipStream_t stream);
 int launch_mark_visible(int32_t P, const float* means3D, const float* view, uint8_t* present,
                         hipStream_t stream);
 

@@ -493,6 +493,22 @@ copy_shared_dcolors_kernel(int64_t n /*P * SH*/, int C, GaccLayout GL, const flo
     dL_dcolors[i * C + ch] = gacc[GL.index((size_t)i, (size_t)i, ch)];
 }
 
+// dL_dcolors [P, C] of precomputed colours out of the accumulator rows: the copy of the shared table (C >= 32; its tail columns
+// are the per-Gaussian kernel's) or the gather over the V per-view rows
+int launch_window_dcolors(int32_t P, int32_t V, int C, const float* gacc, float* dL_dcolors, hipStream_t stream)
+{
+    const GaccLayout GL = gacc_layout(C, P);
+    const int64_t n = (int64_t)P * (GL.SH ? (int)GL.SH : C);
+    if (GL.SH)
+        hipLaunchKernelGGL(copy_shared_dcolors_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, C, GL, gacc,
+                           dL_dcolors);
+    else
+        hipLaunchKernelGGL(gather_dcolors_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, C, GL, V, gacc,
+                           dL_dcolors);
+    SR_LAUNCH_CHECK();
+    return SPLATRASTER_OK;
+}
+
 int launch_preprocess_bwd(const splatraster_settings& s, int32_t P, int32_t V, const WinCams& cams, const WinGrad& grads,
                           const float* means3D, const float* shs, const float* scales, const float* rotations,
                           const float* cov3D_precomp, const uint8_t* clamped, const float4* rec, const float* gacc, int C,
@@ -504,14 +520,8 @@ int launch_preprocess_bwd(const splatraster_settings& s, int32_t P, int32_t V, c
     const GaccLayout GL = gacc_layout(C, P);
     const int ntail = (dL_dcolors && !raw && GL.SH > 0) ? C - (int)GL.SH : 0;   // colour columns of the per-view rows: summed by the kernel below
     if (dL_dcolors && !raw) {
-        const int64_t n = (int64_t)P * (GL.SH ? (int)GL.SH : C);
-        if (GL.SH)
-            hipLaunchKernelGGL(copy_shared_dcolors_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, C, GL, gacc,
-                               dL_dcolors);
-        else
-            hipLaunchKernelGGL(gather_dcolors_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, C, GL, V, gacc,
-                               dL_dcolors);
-        SR_LAUNCH_CHECK();
+        const int st = launch_window_dcolors(P, V, C, gacc, dL_dcolors, stream);
+        if (st) return st;
     }
     const bool pose = dL_dview && dL_dproj;      // (the accumulator sets behind gacc were zeroed with the rows: capi.hip)
     if (pose && !pose_acc) return SPLATRASTER_ERR_BAD_ARG;

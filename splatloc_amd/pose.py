@@ -301,6 +301,102 @@ def refine_poses(render_targets, gaussians: dict, camera, W2C_init: torch.Tensor
         return out, hist
 
 
+class WindowPoses:
+    """Key-frame poses optimised TOGETHER with the map over a window (the trainer SplatLoc's `map()` descends from does this;
+    SplatLoc dropped it because its data sets come with poses): the device-side optimiser of N world-to-camera matrices on top of
+    `splatraster_pose_step_window` — frame j is W2C_j = T(w_j, t_j) @ W2C_init[j] with an axis-angle w_j and a translation t_j
+    (both start at zero) and its own Adam moments, `refine_poses`' parametrisation and defaults.
+
+    `view` [N,4,4], `proj` [N,4,4] and `campos` [N,3] hold the camera tensors of all frames as three LEAF tensors that require
+    grad; `cameras(ids)` hands out their rows (views: put them into a viewpoint's world_view_transform / full_proj_transform /
+    camera_center, or into GaussianRasterizationSettings), so a backward through `rasterize_window` — the joint window backward,
+    `rasterizer.window_backward(cameras=True)` — leaves every frame's gradient in the rows of `.grad`.  `step(ids)` advances the
+    listed frames from those rows (one launch per <= 8 frames: chain rule to (w, t), Adam, the next camera tensors written in
+    place — the 6 numbers of a frame never visit the host) and zeroes the rows; a frame's result does not depend on its slot or
+    on the frames stepped with it.  `fixed`: frames that no step moves — the gauge of a joint optimisation is free unless one
+    pose (or the map's positions) is held.  `W2C()`: the current poses [N,4,4]."""
+
+    def __init__(self, W2C_init: torch.Tensor, projection_matrix: torch.Tensor, lr_rot: float = 2e-3, lr_trans: float = 3e-3,
+                 betas=(0.9, 0.999), eps: float = 1e-8, fixed=()):
+        if not isinstance(W2C_init, torch.Tensor) or W2C_init.dim() != 3 or tuple(W2C_init.shape[1:]) != (4, 4) or not W2C_init.shape[0]:
+            raise ValueError("WindowPoses: W2C_init is [N,4,4] with N >= 1, one start pose per frame")
+        if tuple(projection_matrix.shape) != (4, 4):
+            raise ValueError("WindowPoses: projection_matrix is [4,4]")
+        N = int(W2C_init.shape[0])
+        self.fixed = frozenset(int(i) for i in fixed)
+        if any(i < 0 or i >= N for i in self.fixed):
+            raise ValueError(f"WindowPoses: fixed frames outside 0 .. {N - 1}")
+        if not W2C_init.is_cuda:
+            raise RuntimeError("WindowPoses runs on the GPU: W2C_init is on " + str(W2C_init.device))
+        dev = W2C_init.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.N, self.dev = N, dev
+        self.lr_rot, self.lr_trans, self.betas, self.eps = float(lr_rot), float(lr_trans), (float(betas[0]), float(betas[1])), float(eps)
+        self.W2C0 = W2C_init.detach().to(**f32).contiguous()
+        self.Pm = projection_matrix.detach().to(**f32).contiguous()
+        self.state = torch.zeros((N, 20), **f32)        # per frame: w, t, Adam moments, step (splatraster_pose_step)
+        self.view = torch.empty((N, 4, 4), **f32).requires_grad_(True)
+        self.proj = torch.empty((N, 4, 4), **f32).requires_grad_(True)
+        self.campos = torch.empty((N, 3), **f32).requires_grad_(True)
+        for a in range(0, N, 8):
+            self._launch(a, min(8, N - a), 0, None, self.state, self.view, self.proj, self.campos, self.W2C0)
+
+    def _launch(self, a, k, advance, grads, state, view, proj, campos, W2C0):
+        """splatraster_pose_step_window on rows [a, a + k) of the given tensors (`grads`: (dview, dproj, dcampos or None), the
+        same rows)"""
+        import ctypes as C
+        from . import _native
+        from ._host import _stream
+        row = lambda t: None if t is None else C.c_void_p(t.data_ptr() + a * t.stride(0) * 4)  # noqa: E731
+        gv, gp, gc = grads if grads is not None else (None, None, None)
+        _native.check(_native.load().splatraster_pose_step_window(
+            k, row(gv), row(gp), row(gc), row(W2C0), C.c_void_p(self.Pm.data_ptr()), self.lr_rot, self.lr_trans, self.betas[0],
+            self.betas[1], self.eps, advance, row(state), row(view), row(proj), row(campos), _stream(self.dev)), "pose_step_window")
+
+    def cameras(self, ids):
+        """(viewmatrix, projmatrix, campos) of frame `ids` (an int), or a list of such triples: rows of the three leaves"""
+        if isinstance(ids, int):
+            return self.view[ids], self.proj[ids], self.campos[ids]
+        return [(self.view[int(i)], self.proj[int(i)], self.campos[int(i)]) for i in ids]
+
+    def W2C(self) -> torch.Tensor:
+        with torch.no_grad():
+            return at_to_transform_matrix(self.state[:, :3], self.state[:, 3:6]) @ self.W2C0
+
+    def zero_grad(self, ids=None) -> None:
+        for t in (self.view, self.proj, self.campos):
+            if t.grad is not None:
+                if ids is None:
+                    t.grad.zero_()
+                else:
+                    t.grad[ids] = 0.0
+
+    def step(self, ids) -> None:
+        """One Adam step of the frames `ids` (any order, no repeats) from the rows of view.grad / proj.grad / campos.grad, which
+        are then zeroed; `fixed` frames are skipped.  A tensor without .grad contributes zeros."""
+        ids = [int(i) for i in ids]
+        if len(set(ids)) != len(ids) or any(i < 0 or i >= self.N for i in ids):
+            raise ValueError(f"WindowPoses.step: ids are distinct frames in 0 .. {self.N - 1}")
+        move = [i for i in ids if i not in self.fixed]
+        with torch.no_grad():
+            gv = self.view.grad if self.view.grad is not None else torch.zeros_like(self.view)
+            gp = self.proj.grad if self.proj.grad is not None else torch.zeros_like(self.proj)
+            gc = self.campos.grad
+            for a in range(0, len(move), 8):
+                chunk = move[a:a + 8]
+                k = len(chunk)
+                if chunk == list(range(chunk[0], chunk[0] + k)):     # neighbouring rows: the kernel works on them where they are
+                    self._launch(chunk[0], k, 1, (gv, gp, gc), self.state, self.view, self.proj, self.campos, self.W2C0)
+                    continue
+                sel = torch.tensor(chunk, device=self.dev)
+                state, view, proj, campos = self.state[sel], self.view[sel], self.proj[sel], self.campos[sel]
+                self._launch(0, k, 1, (gv[sel], gp[sel], None if gc is None else gc[sel]), state, view, proj, campos, self.W2C0[sel])
+                self.state[sel] = state
+                self.view.data[sel], self.proj.data[sel], self.campos.data[sel] = view, proj, campos
+            if ids:
+                self.zero_grad(torch.tensor(ids, device=self.dev))
+
+
 def _refine_pose_autograd(render_target, gaussians: dict, camera, W2C_init: torch.Tensor, iterations: int = 100,
                           lr_rot: float = 2e-3, lr_trans: float = 3e-3, depth_weight: float = 0.2,
                           background: torch.Tensor | None = None, on_step=None):

@@ -343,13 +343,19 @@ def window_outputs(f, head: int = 0) -> list:
     return [(f.color[v], f.depth[v], f.alpha[v], f.radii[v]) for v in range(f.V)]
 
 
-def window_backward(f, grads, head: int = 0, grad_span: Optional[list] = None, raw=None, reg=None) -> dict:
+def window_backward(f, grads, head: int = 0, grad_span: Optional[list] = None, raw=None, reg=None, cameras: bool = False,
+                    workspace: Optional[torch.Tensor] = None) -> dict:
     """ONE backward for the views of `window_forward`'s frame `f`.  `grads`: per view (g_color, g_last, g_depth, g_alpha) of
     `window_outputs(f, head)`; None: that output did not reach the loss.  Returns the gradients summed over the views, by
     name: m3, op, col, sca, rot, cov (`window_grad_span` pieces) and m2 [V,P,3] (dL/dmeans2D per view).  `grad_span`: a
     list the allocation is appended to.  `raw` (window_forward's): splatraster_backward_window_raw chains through the
     activations inside the per-Gaussian kernel and returns scaling, rotation, opacity, f_dc, extra instead of col / op /
-    sca / rot; `reg` = (row_grad [P], out [2], weight) joins the isotropic regulariser's term to dL/dscales there."""
+    sca / rot; `reg` = (row_grad [P], out [2], weight) joins the isotropic regulariser's term to dL/dscales there.
+    `cameras`: splatraster_backward_window_joint — the same compositing backward, then ONE per-Gaussian kernel that also
+    reduces the camera gradients of every view; the dict gains view [V,4,4], proj [V,4,4] and campos [V,3] (zeros: a window
+    has precomputed colours only).  `workspace` as in `window_backward_cameras`.  Not with `raw` (ValueError)."""
+    if cameras and raw is not None:
+        raise ValueError("window_backward: cameras=True has no raw-parameter variant (pass the activated tensors to window_forward)")
     lib = _native.load()
     dev, V, P, st = f.dev, f.V, f.P, f.st
     Cn = st.channels
@@ -383,6 +389,19 @@ def window_backward(f, grads, head: int = 0, grad_span: Optional[list] = None, r
         w.dL_dout_last = None if g_last is None else g_last.data_ptr()
         w.color_grad_channels = head
     R = (C.c_int64 * V)(*f.R)
+    if cameras:
+        d["view"], d["proj"], d["campos"] = (torch.empty(shp, **f32) for shp in ((V, 4, 4), (V, 4, 4), (V, 3)))
+        nws = lib.splatraster_window_camera_workspace_bytes(V)
+        if workspace is None:
+            workspace = torch.empty((nws,), dtype=torch.uint8, device=dev)
+        assert workspace.numel() >= nws
+        with _on_device(dev):
+            _native.check(lib.splatraster_backward_window_joint(
+                C.byref(st), V, views, P, R, _ptr(f.bg), _ptr(f.m3), _ptr(f.col), _ptr(f.sca), _ptr(f.rot), _ptr(f.cov),
+                _ptr(f.geom), _ptr(f.binning), _ptr(f.img), _ptr(d["m3"]), _ptr(d["col"]), _ptr(d["op"]), _ptr(d["sca"]),
+                _ptr(d["rot"]), _ptr(d["cov"]), _ptr(workspace), _ptr(d["view"]), _ptr(d["proj"]), _ptr(d["campos"]),
+                _stream(dev)), "backward_window_joint")
+        return d
     if raw is None:
         with _on_device(dev):
             _native.check(lib.splatraster_backward_window(
@@ -456,9 +475,11 @@ def window_backward_cameras(f, grads, workspace: Optional[torch.Tensor] = None, 
 class _RasterizeWindow(torch.autograd.Function):
     """The autograd adapter of `window_forward` / `window_backward`: the V views of one optimisation window
     (train_gaussians.py:195-229) as ONE launch sequence.  Inputs: the shared rasterizer arguments, the list of per-view
-    settings, then one `means2D` gradient carrier per view.  Outputs: (color_0, depth_0, alpha_0, radii_0, color_1, ...).
+    settings, then one `means2D` gradient carrier per view, then (viewmatrix, projmatrix, campos) of every view.
+    Outputs: (color_0, depth_0, alpha_0, radii_0, color_1, ...).
     The backward runs once, when autograd has the output gradients of every view, and returns parameter gradients already
-    summed over the views.  `grad_fn.R`: the instances per view.
+    summed over the views — and, when a camera tensor requires grad, that view's camera gradients from the same launch
+    sequence (`window_backward(cameras=True)`).  `grad_fn.R`: the instances per view.
 
     `split_last`: the colour buffer of every view is handed out as TWO autograd outputs, channels [0, C-1) and channel
     C-1 — SplatLoc's `render` = image[:3] and `kp_prob` = image[-1] (gaussian_renderer/__init__.py:133-135) — so the
@@ -470,8 +491,12 @@ class _RasterizeWindow(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means3D, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings, split_last, grad_span,
-                *means2D):
-        assert len(means2D) == len(settings)
+                *rest):
+        # rest: one means2D carrier per view, then (viewmatrix, projmatrix, campos) of every view — the settings' own tensors as
+        # explicit autograd inputs, the way _RasterizeGaussians takes them (inputs 9-11 there), so that a pose parametrisation
+        # upstream of them receives gradients
+        V = len(settings)
+        assert len(rest) in (V, 4 * V)
         f = window_forward(means3D, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings)
         ctx.dev, ctx.P, ctx.st, ctx.R, ctx.tanfov = f.dev, f.P, f.st, f.R, f.tanfov
         ctx.head, ctx.grad_span = _split_head(split_last, f.st.channels), grad_span
@@ -492,9 +517,13 @@ class _RasterizeWindow(torch.autograd.Function):
             grads = [gouts[5 * v:5 * v + 4] for v in range(V)]
         else:
             grads = [(gouts[4 * v], None, gouts[4 * v + 1], gouts[4 * v + 2]) for v in range(V)]
-        d = window_backward(f, grads, ctx.head, ctx.grad_span)
-        # (means3D, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings, split_last, grad_span, *means2D)
-        return (d["m3"], d["col"], d["op"], d["sca"], d["rot"], d["cov"], None, None, None) + tuple(d["m2"][v] for v in range(V))
+        # the joint call only when a camera tensor needs a gradient: otherwise the launch sequence is the plain one
+        need = ctx.needs_input_grad[9 + V:]
+        d = window_backward(f, grads, ctx.head, ctx.grad_span, cameras=any(need))
+        # (means3D, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings, split_last, grad_span, *means2D,
+        #  *(viewmatrix, projmatrix, campos per view))
+        cams = tuple(d[("view", "proj", "campos")[j % 3]][j // 3] if on else None for j, on in enumerate(need))
+        return (d["m3"], d["col"], d["op"], d["sca"], d["rot"], d["cov"], None, None, None) + tuple(d["m2"][v] for v in range(V)) + cams
 
 
 def rasterize_window(settings, means3D, means2D, colors_precomp, opacities, scales=None, rotations=None,
@@ -504,6 +533,8 @@ def rasterize_window(settings, means3D, means2D, colors_precomp, opacities, scal
     image size / scale modifier / background); `means2D`: one gradient carrier per view.  Returns a list of
     (color, depth, alpha, radii) per view — bit-identical to the per-view calls; the backward sums the views'
     parameter gradients in-kernel (one gradient set per window instead of V sets + V accumulation passes).
+    A view's `viewmatrix` / `projmatrix` / `campos` may require grad, as for the per-view call: the chunk's backward is then the
+    joint one (`window_backward(cameras=True)`) and they receive their gradients (`campos`: zeros).
     `split_last`: (rgb [C-1,H,W], last [H,W], depth, alpha, radii) per view instead (an integer g: (image[:g], image[-1],
     ...)) — see _RasterizeWindow.
     `grad_span`: a list; every chunk's backward appends its gradient allocation (`window_grad_span`: flat, the pieces and a
@@ -528,7 +559,8 @@ def rasterize_window(settings, means3D, means2D, colors_precomp, opacities, scal
     K = max(1, min(_native.MAX_WINDOW_VIEWS, (1 << 24) // max(int(means3D.shape[0]), 1)))
     for a in range(0, len(settings), K):
         flat = _RasterizeWindow.apply(means3D, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                                      tuple(settings[a:a + K]), split_last, grad_span, *means2D[a:a + K])
+                                      tuple(settings[a:a + K]), split_last, grad_span, *means2D[a:a + K],
+                                      *(t for rs in settings[a:a + K] for t in (rs.viewmatrix, rs.projmatrix, rs.campos)))
         n = 5 if _split_head(split_last, int(colors_precomp.shape[1])) else 4
         out += [tuple(flat[n * v:n * v + n]) for v in range(len(flat) // n)]
     return out

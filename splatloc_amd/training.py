@@ -205,6 +205,10 @@ def color_refinement_step(viewpoint_cam, gaussians, pipe, background, lambda_dss
     return loss
 
 
+def _cameras_require_grad(settings) -> bool:
+    return any(t is not None and t.requires_grad for rs in settings for t in (rs.viewmatrix, rs.projmatrix, rs.campos))
+
+
 def _map_grads_direct(mine, gaussians, pipe, background, config, with_reg: bool):
     """The gradient part of `map_step` without an autograd graph (`_grads_direct`; the per-view losses already carry their
     gradients).  Leaves the raw-parameter gradients in `.grad`.  Returns (pkgs, loss, [dL/dmeans2D per view]) or None when the
@@ -219,6 +223,8 @@ def _map_grads_direct(mine, gaussians, pipe, background, config, with_reg: bool)
         return None
     settings = [_view_settings(vp, gaussians, background, 1.0) for vp in mine]
     if not _window_compatible(settings):
+        return None
+    if _cameras_require_grad(settings):       # key-frame poses optimised with the map: the autograd window path (joint backward)
         return None
     pkgs = []
 
@@ -281,6 +287,9 @@ def map_step(viewpoints, gaussians, pipe, background, config, iteration_count: i
     mine = [viewpoints[i] for i in shard_views(list(range(len(viewpoints))), rank, world)]
     if render_path not in ("auto", "window", "per-view"):
         raise ValueError(f"map_step: unknown render_path {render_path!r}")
+    if multi and world > 1 and any(getattr(vp, a, None) is not None and getattr(vp, a).requires_grad for vp in viewpoints
+                                   for a in ("world_view_transform", "full_proj_transform", "camera_center")):
+        raise NotImplementedError("map_step: camera tensors that require grad on more than one rank (no pose exchange)")
     direct = None
     if mine and render_path == "auto":
         direct = _map_grads_direct(mine, gaussians, pipe, background, config, primitive_reg and rank == 0)

@@ -34,6 +34,7 @@ WHAT = [   # (file name regex, description; {placeholders} are filled by the ext
     (r"^pnp_time\.json$", "absolute pose (`solve_pose`: P3P LO-RANSAC + Cauchy refinement) on planted scenes, HIP events (`tools/pnp_time.py`): {pnp}"),
     (r"^localize_time\.json$", "localisation (`tools/localize_time.py`), HIP events, interleaved medians: fused retrieval against `torch.einsum(...).topk` and the batched `Localizer.localize` against the per-query loop: {localize}"),
     (r"^pose_window_time\.json$", "pose refinement of 8 query frames at 640x480, `pose.refine_poses` per `window` against the loop of 8 `pose.refine_pose` calls, ms per frame-iteration, host clock around a device synchronise, alternating regions (`tools/pose_window_time.py`): {posewindow}"),
+    (r"^joint_window_time\.json$", "one backward of a 5-view window that returns parameter AND camera gradients, ms per backward, host clock around a device synchronise, alternating regions (`tools/joint_window_time.py`): {jointwindow}"),
     (r"^matching_time\.json$", "2D-3D matching (`hungarian_solve` cost + exact assignment, batched solver, frustum candidates) against torch-CPU + scipy on the same host, HIP events (`tools/matching_time.py`): {matching}"),
     (r"^landmark_selection_time\.json$", "landmark selection (`gaussian_selectition`) at Replica scale on a synthetic room, HIP events per stage (`tools/landmark_selection_time.py`): {landmark}"),
     (r"r\d+_scene_lists.*\.json$", "one `color_refinement` iteration on a RECONSTRUCTED room (list-length distribution, per-kernel table; `tools/scene_lists.py`; suffix = the forced variant): {scenelists}"),
@@ -244,6 +245,20 @@ def localize(path):
             f"{d['per_query_loop_ms']:.0f} ms ({d['ratio_loop_over_localize']:.2f} x), bit-identical {d['bit_identical_to_loop']}")
 
 
+def jointwindow(path):
+    j = _load(path) or {}
+    if not j.get("results"):
+        return str(j.get("status", "(no rows)"))
+    parts = []
+    for r in j["results"]:
+        v = r["variants"]
+        parts.append(f"{r['workload']} ({r['width']}x{r['height']}, C = {r['channels']}, P = {r['P']}): joint call {v['joint']['ms_per_window_backward']:.4f} "
+                     f"({v['joint']['min']:.4f} - {v['joint']['max']:.4f}), `window_backward` + `window_backward_cameras` "
+                     f"{v['two_calls']['ms_per_window_backward']:.4f} ({v['two_calls']['this_over_joint']:.3f} x), five per-view calls "
+                     f"{v['per_view']['ms_per_window_backward']:.4f} ({v['per_view']['this_over_joint']:.3f} x)")
+    return "; ".join(parts)
+
+
 def posewindow(path):
     j = _load(path) or {}
     if not j.get("results"):
@@ -351,7 +366,7 @@ def fe_ab(path):
             f"{c['payload_ms']['change']:.4f} ms ({', '.join(f'{k} {v:.4f}' for k, v in c['payload_ms_of_band_variants'].items())})")
 
 
-EXTRACT = {"pc_kstats": pc_kstats, "pc_pmc": pc_pmc, "pc_ab": pc_ab, "fe_kstats": fe_kstats, "fe_pmc": fe_pmc, "fe_ab": fe_ab, "setup_pmc": setup_pmc, "kstats2": kstats2, "setup_ab": setup_ab, "scenelists": scenelists, "scene": scene, "ab": ab, "perview": perview, "mapidle": mapidle, "rccl": rccl, "kstats": kstats, "hbm": hbm, "sq": sq, "timeline": timeline, "bench": bench, "clocks": clocks, "gradbars": gradbars, "idle": idle, "landmark": landmark, "matching": matching, "pnp": pnp, "decoder": decoder, "fusion": fusion, "localize": localize, "posewindow": posewindow}
+EXTRACT = {"pc_kstats": pc_kstats, "pc_pmc": pc_pmc, "pc_ab": pc_ab, "fe_kstats": fe_kstats, "fe_pmc": fe_pmc, "fe_ab": fe_ab, "setup_pmc": setup_pmc, "kstats2": kstats2, "setup_ab": setup_ab, "scenelists": scenelists, "scene": scene, "ab": ab, "perview": perview, "mapidle": mapidle, "rccl": rccl, "kstats": kstats, "hbm": hbm, "sq": sq, "timeline": timeline, "bench": bench, "clocks": clocks, "gradbars": gradbars, "idle": idle, "landmark": landmark, "matching": matching, "pnp": pnp, "decoder": decoder, "fusion": fusion, "localize": localize, "jointwindow": jointwindow, "posewindow": posewindow}
 
 
 def describe(name, path):
