@@ -351,6 +351,59 @@ int splatraster_backward_window_raw(const splatraster_settings* s, int32_t n_vie
                                     const void* binning, const void* image, const splatraster_raw_params* raw,
                                     float* dL_dmeans3D /* [P,3] */, void* stream);
 
+/* ---- bounded window forward: no host wait for the instance count ------------------------------------------------------
+ * splatraster_forward_window_geometry stops the host until the instance count R is known, because the caller sizes `binning`
+ * by it.  The bounded calls take a `binning` of splatraster_window_binning_bytes(P, n_views, capacity, W, H, C) bytes instead, run
+ * geometry and render as ONE launch sequence, return no count, wait on no event and read nothing on the host that this frame
+ * writes (the front end's wide-list hint word is a hint from earlier frames).  R stays on the device.  A frame with
+ * R <= capacity is bit-identical to the two-stage forward (every output, point_list[:R], the range table, n_contrib, final_T).
+ * A frame that does not fit writes no key, no list, no payload word; its range table is all [0, 0), it renders the background,
+ * its backward yields zero gradients and nothing beyond `capacity` elements of any per-instance array is touched; the sequence
+ * records itself in the status block.
+ *
+ * Status block (64 bytes, owned by the library; one per optimisation loop).  `overflow` is STICKY: once set, every later bounded
+ * sequence with this status has an effective capacity of 0 (it renders background, whatever its own capacity) and every gated
+ * Adam launch (splatraster_adam_step_gated) returns without touching anything, until splatraster_bounded_status_clear.  A loop
+ * can therefore run ahead of the device: when it later reads `overflow`, nothing has changed since the parameters sequence
+ * `first_tag` started from; it synchronises once, grows `binning` to hold `first_total`, clears the status and replays from
+ * `first_tag`.  splatraster_bounded_status_read copies the host-mapped mirror and never synchronises: its fields are those of
+ * some recent moment each, copied in this order: last_tag, then overflow, then the rest.  Every sequence in front of `last_tag`
+ * has finished, so overflow == 0 in the same copy says that none of THEM overflowed (the sequence `last_tag` itself still
+ * may).  A set flag is a hint until it is read again behind a stream synchronisation, which gives the consistent record.
+ * splatraster_bounded_status_clear is a kernel in stream order and also zeroes the mirror from the host at once, so a caller
+ * that has synchronised the stream reads a clear block immediately.
+ *
+ * Binned front end only (small and medium frames — the host-bound ones; the radix front end sizes its sort grids by R on the
+ * host): where the two-stage forward would take the radix front end (and for P == 0) the bounded calls return
+ * SPLATRASTER_ERR_UNSUPPORTED before any launch.  0 <= capacity < 2^31.
+ *
+ * Backward of a bounded frame: splatraster_backward_window, _raw, _joint and _cameras use num_rendered only to lay out `binning`
+ * (and skip the compositing launch when it sums to 0); pass num_rendered = {capacity, 0, ...}. */
+typedef struct splatraster_bounded_status {
+    uint32_t total;       /* R of the last bounded sequence (saturated at 2^32 - 1) */
+    uint32_t overflow;    /* 0 or 1, sticky */
+    uint32_t first_tag;   /* tag of the first sequence that did not fit (valid while overflow == 1) */
+    uint32_t first_total; /* that sequence's R */
+    uint32_t last_tag;    /* tag of the last bounded sequence */
+    uint32_t reserved[11];
+} splatraster_bounded_status;
+int splatraster_bounded_status_create(void** handle);          /* on the current device; the block starts cleared */
+int splatraster_bounded_status_destroy(void* handle);          /* the caller has synchronised every stream that used it */
+int splatraster_bounded_status_read(const void* handle, splatraster_bounded_status* out);   /* host read of the mirror: no synchronisation */
+int splatraster_bounded_status_clear(void* handle, void* stream);                           /* stream-ordered */
+/* 1 when the bounded calls accept this shape under the present settings (the two-stage forward would take the binned front end), else 0 */
+int splatraster_forward_window_bounded_supported(int32_t P, int32_t n_views, int32_t width, int32_t height);
+int splatraster_forward_window_bounded(const splatraster_settings* s, int32_t n_views, const splatraster_window_view* views,
+                                       int32_t P, const float* means3D, const float* opacities, const float* scales,
+                                       const float* rotations, const float* cov3D_precomp, const float* bg,
+                                       const float* colors_precomp, void* geometry, void* binning, void* image,
+                                       int64_t capacity, uint32_t tag, void* status, void* stream);
+/* (raw-parameter mode: `raw->colors`, an output of this call, is the colour table the render stage reads) */
+int splatraster_forward_window_bounded_raw(const splatraster_settings* s, int32_t n_views, const splatraster_window_view* views,
+                                           int32_t P, const float* means3D, const splatraster_raw_forward* raw, const float* bg,
+                                           void* geometry, void* binning, void* image, int64_t capacity, uint32_t tag,
+                                           void* status, void* stream);
+
 /* ---- auxiliary entry points ---------------------------------------------------------- */
 
 /* present[i] = 1 when Gaussian i passes the near-plane test (view-space z > 0.2).
@@ -534,6 +587,15 @@ int splatraster_adam_step(int32_t n_groups, const splatraster_adam_group* groups
  * n_groups may be 0 (only the statistics). */
 int splatraster_adam_step_radii(int32_t n_groups, const splatraster_adam_group* groups, double beta1, double beta2, double eps,
                                 float row_gate_threshold, int32_t P, const int32_t* radii, float* max_radii2D, void* stream);
+
+/* The two launches above behind a bounded status block (splatraster_bounded_status_create): while its `overflow` word is set every
+ * block returns before it touches a parameter, a moment or max_radii2D; with the word clear the results are bit-identical to the
+ * ungated calls.  The word is read on the device, in stream order: no host synchronisation. */
+int splatraster_adam_step_gated(int32_t n_groups, const splatraster_adam_group* groups, double beta1, double beta2, double eps,
+                                float row_gate_threshold, const void* status, void* stream);
+int splatraster_adam_step_radii_gated(int32_t n_groups, const splatraster_adam_group* groups, double beta1, double beta2, double eps,
+                                      float row_gate_threshold, int32_t P, const int32_t* radii, float* max_radii2D,
+                                      const void* status, void* stream);
 
 /* Isotropic scale regulariser of SplatLoc.map (train_gaussians.py:222-228):
  *   mask = marker > 0.005;  loss = mean_{mask} | mean_k scaling[i,k] / (0.02 (1 - marker_i)) - 1 |

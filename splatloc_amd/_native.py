@@ -12,6 +12,7 @@ from . import build as _build
 
 _LIB = None
 ABI_VERSION = 20   # == SPLATRASTER_ABI_VERSION of include/splatraster.h
+ERR_UNSUPPORTED = 3
 
 OK = 0
 WARN_LOOKBACK_STALL = 5   # splatraster_poll_errors() only; not an error of any frame
@@ -102,6 +103,12 @@ class AdamGroup(C.Structure):
                 ("step", C.c_double)]
 
 
+class BoundedStatus(C.Structure):
+    """struct splatraster_bounded_status (64 bytes)"""
+    _fields_ = [("total", C.c_uint32), ("overflow", C.c_uint32), ("first_tag", C.c_uint32), ("first_total", C.c_uint32),
+                ("last_tag", C.c_uint32), ("reserved", C.c_uint32 * 11)]
+
+
 GRID_MAX_LEVELS = 32   # SPLATRASTER_GRID_MAX_LEVELS
 GRID_HASH, GRID_DENSE, GRID_TILED = 0, 1, 2   # SPLATRASTER_GRID_*
 
@@ -159,6 +166,15 @@ SYMBOLS = {
                                                           _vp, C.POINTER(_i64), _vp]),
     "splatraster_backward_window_raw": (C.c_int, [C.POINTER(Settings), _i32, C.POINTER(WindowView), _i32, C.POINTER(_i64)]
                                         + [_vp] * 8 + [C.POINTER(RawParams)] + [_vp] * 2),
+    "splatraster_bounded_status_create": (C.c_int, [C.POINTER(_vp)]),
+    "splatraster_bounded_status_destroy": (C.c_int, [_vp]),
+    "splatraster_bounded_status_read": (C.c_int, [_vp, C.POINTER(BoundedStatus)]),
+    "splatraster_bounded_status_clear": (C.c_int, [_vp, _vp]),
+    "splatraster_forward_window_bounded_supported": (C.c_int, [_i32, _i32, _i32, _i32]),
+    "splatraster_forward_window_bounded": (C.c_int, [C.POINTER(Settings), _i32, C.POINTER(WindowView), _i32] + [_vp] * 10
+                                           + [_i64, C.c_uint32, _vp, _vp]),
+    "splatraster_forward_window_bounded_raw": (C.c_int, [C.POINTER(Settings), _i32, C.POINTER(WindowView), _i32, _vp,
+                                                         C.POINTER(RawForward)] + [_vp] * 4 + [_i64, C.c_uint32, _vp, _vp]),
     "splatraster_get_window_geometry_layout": (C.c_int, [_i32, _i32, C.POINTER(GeometryLayout)]),
     "splatraster_get_window_binning_layout": (C.c_int, [_i32, _i32, _i64, _i32, _i32, _i32, C.POINTER(BinningLayout)]),
     "splatraster_get_window_image_layout": (C.c_int, [_i32, _i32, _i32, C.POINTER(ImageLayout)]),
@@ -224,6 +240,9 @@ SYMBOLS = {
     "splatraster_model_append": (C.c_int, [C.POINTER(Model)] * 7 + [_vp]),
     "splatraster_adam_step": (C.c_int, [_i32, C.POINTER(AdamGroup), C.c_double, C.c_double, C.c_double, C.c_float, _vp]),
     "splatraster_adam_step_radii": (C.c_int, [_i32, C.POINTER(AdamGroup), C.c_double, C.c_double, C.c_double, C.c_float, _i32, _vp, _vp, _vp]),
+    "splatraster_adam_step_gated": (C.c_int, [_i32, C.POINTER(AdamGroup), C.c_double, C.c_double, C.c_double, C.c_float, _vp, _vp]),
+    "splatraster_adam_step_radii_gated": (C.c_int, [_i32, C.POINTER(AdamGroup), C.c_double, C.c_double, C.c_double, C.c_float, _i32, _vp,
+                                                    _vp, _vp, _vp]),
     "splatraster_isotropic_loss_workspace_bytes": (_sz, [_i32]),
     "splatraster_isotropic_loss": (C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "splatraster_mapping_loss_workspace_bytes": (_sz, [_i32]),
@@ -340,6 +359,12 @@ def set_front_end(mode: int) -> None:
     """-1: default choice; 0: the two global radix sorts always; 1: the binned front end whenever the shape allows
     (splatraster_debug_set_front_end; bit-identical results either way)."""
     check(load().splatraster_debug_set_front_end(int(mode)), "set_front_end")
+
+
+def bounded_supported(P: int, V: int, W: int, H: int) -> bool:
+    """True where the bounded window forward applies: a window forward of this shape takes the binned front end under the
+    present settings (splatraster_forward_window_bounded_supported)."""
+    return bool(load().splatraster_forward_window_bounded_supported(int(P), int(V), int(W), int(H)))
 
 
 def set_payload_compact(mode: int) -> None:

@@ -38,7 +38,7 @@ EXTRA_FLAGS: list = []
 NO_CONTRACT = {"preprocess.hip", "binning.hip", "binsort.hip", "knn.hip", "selection.hip", "matching.hip", "pnp.hip", "fusion.hip"}
 SOURCES = ["preprocess.hip", "preprocess_bwd.hip", "camera_bwd.hip", "window_joint_bwd.hip", "scan_sort.hip", "binning.hip", "binsort.hip", "composite_fwd.hip",
            "composite_bwd.hip", "knn.hip", "activations.hip", "losses.hip", "densify.hip", "pose.hip", "grid_encoding.hip",
-           "decoder.hip", "selection.hip", "matching.hip", "pnp.hip", "fusion.hip", "retrieval.hip", "capi.hip"]
+           "decoder.hip", "selection.hip", "matching.hip", "pnp.hip", "fusion.hip", "retrieval.hip", "bounded.hip", "capi.hip"]
 
 
 def have_hipcc() -> bool:

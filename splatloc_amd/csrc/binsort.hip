@@ -80,12 +80,52 @@ __device__ __forceinline__ void wave_order()
 // Gaussians over hundreds of tiles — the thread-serial walk of such a rect was the block's critical path (33 / 48 us for
 // count / scatter on 196k rows where the uniform 500k-row cloud took 9 / 16 us).
 constexpr int BIN_INLINE_TILES = 8, BIN_QUEUE = 1024;
-template <int ROWS, bool SCATTER>
+
+// ---- bounded mode (splatraster_forward_window_bounded) --------------------------------------------------------------------
+// The caller sized the binning buffer for `capacity` instances without knowing R; R is total[0], on the device.  The three
+// launches of the render stage exist twice: as they always were (an empty `Bound` pack: the same signature and the same code),
+// and with a BoundedRun behind their arguments.  Every thread of a bounded launch evaluates the SAME predicate from the same
+// words — the scan's grand total and the status block's sticky overflow word — and a sequence that does not fit writes no key
+// and sees every list empty, so it touches no per-instance element at all.  The one thread that raises the flag
+// (bounded_publish: the last block of the last launch, which runs in every sequence) only ever turns a frame that did not fit
+// anyway into one whose effective capacity is 0: a reader on either side of that store reaches the same verdict (total >
+// capacity >= 0, so total > 0 as well).
+__device__ __forceinline__ bool bounded_fits(const uint32_t* __restrict__ total, const BoundedRun& bd)
+{
+    const uint32_t over = __hip_atomic_load(bd.status + BOUNDED_OVERFLOW, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint32_t cap = over ? 0u : bd.capacity;
+    return total[1] == 0u && total[0] <= cap;
+}
+// one thread per sequence: the device-resident block the kernels read, then its host-mapped mirror (read without a wait)
+__device__ __forceinline__ void bounded_publish(const uint32_t* __restrict__ total, const BoundedRun& bd)
+{
+    const uint32_t tot = total[1] ? 0xFFFFFFFFu : total[0];
+    uint32_t* st = bd.status;
+    uint32_t* mi = bd.mirror;
+    const bool first = st[BOUNDED_OVERFLOW] == 0u && tot > bd.capacity;
+    st[BOUNDED_TOTAL] = tot;
+    st[BOUNDED_LAST_TAG] = bd.tag;
+    __hip_atomic_store(mi + BOUNDED_TOTAL, tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(mi + BOUNDED_LAST_TAG, bd.tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (first) {   // sticky: later sequences leave the first one's record alone
+        st[BOUNDED_FIRST_TAG] = bd.tag;
+        st[BOUNDED_FIRST_TOTAL] = tot;
+        __hip_atomic_store(st + BOUNDED_OVERFLOW, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(mi + BOUNDED_FIRST_TAG, bd.tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(mi + BOUNDED_FIRST_TOTAL, tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(mi + BOUNDED_OVERFLOW, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
+// `Bound`: empty, or (const uint32_t* total, BoundedRun) — the scatter of a bounded sequence: keys holds bd.capacity entries
+template <int ROWS, bool SCATTER, typename... Bound>
 __global__ void __launch_bounds__(BIN_THREADS)
 bin_walk_kernel(int P, int tiles, int gx, int gy, int nchunk, const float4* __restrict__ rec,
                 uint32_t* __restrict__ table /*[(v * tiles + t) * nchunk + chunk]: COUNT out / exclusive prefix in*/,
-                uint64_t* __restrict__ keys /*SCATTER: [R]*/)
+                uint64_t* __restrict__ keys /*SCATTER: [R]*/, Bound... bd)
 {
+    if constexpr (sizeof...(Bound) > 0)
+        if (!bounded_fits(bd...)) return;   // (grid-uniform: no key is written)
     extern __shared__ uint32_t s_bin[];
     __shared__ uint64_t s_qkey[BIN_QUEUE];
     __shared__ uint32_t s_qrect[BIN_QUEUE];   // x0 | y0 << 8 | width << 16 | height << 24 (at most 255 tiles a side: BIN_MAX_TILES)
@@ -372,11 +412,12 @@ __device__ uint32_t* g_bin_wide_sink = nullptr;
 // First sort launch: one block of CAP / 16 threads per global tile, of which ceil(n / 1024) waves work on the list (the
 // others leave at once): a list of up to 1024 keys is one wave's alone.  Lists longer than CAP are the second launch's
 // (bin_sort_big_kernel finds them itself from the scanned table: the two launches share no state and may run side by side).
-template <int CAP>
+// `Bound`: empty, or (BoundedRun): every list of a sequence that does not fit is empty
+template <int CAP, typename... Bound>
 __global__ void __launch_bounds__(CAP / 16)
 bin_sort_tile_kernel(int gtiles, int tiles, int gx, int nchunk, const uint32_t* __restrict__ table /*exclusive prefix*/,
                      const uint32_t* __restrict__ total /*[0]: R*/, const uint64_t* __restrict__ keys,
-                     const float4* __restrict__ rec, BinView b)
+                     const float4* __restrict__ rec, BinView b, Bound... bd)
 {
     __shared__ double s_keys[CAP + CAP / 16];
     const uint32_t gt = blockIdx.x, t = threadIdx.x;
@@ -389,6 +430,8 @@ bin_sort_tile_kernel(int gtiles, int tiles, int gx, int nchunk, const uint32_t* 
     }
 #endif
     tile_span(gt, gtiles, nchunk, table, total, start, n);
+    if constexpr (sizeof...(Bound) > 0)
+        if (!bounded_fits(total, bd...)) { start = 0u; n = 0u; }
     if (t == 0) {   // empty tiles keep [0, 0), like the radix front end's zeroed table
         b.ranges[2 * gt] = n ? start : 0u;
         b.ranges[2 * gt + 1] = n ? start + n : 0u;
@@ -436,13 +479,22 @@ bin_sort_tile_kernel(int gtiles, int tiles, int gx, int nchunk, const uint32_t* 
 // registers of the block — 8 or 16 keys per thread, 64-bit integer compares, every distance beyond a wave exchanged through LDS
 // four registers at a time: ~70 us per list, 87 us of a refinement iteration at Replica scale where 15 - 40 lists of a frame
 // exceed 4 096 keys; profiles/r05_ab_probes.txt #11.)
+// `Bound`: empty, or (BoundedRun): always behind the tile launch on the same stream (ranges_final); thread 0 of the last block —
+// the block that also computes the launch order, present in every sequence — publishes the sequence's total and raises the flag
+template <typename... Bound>
 __global__ void __launch_bounds__(1024)
 bin_sort_big_kernel(int gtiles, int tiles, int gx, int nchunk, int cap /*the tile launch's CAP: longer lists are this launch's*/,
                     const uint32_t* __restrict__ table, const uint32_t* __restrict__ total, uint64_t* __restrict__ keys,
                     const float4* __restrict__ rec, BinView b,
                     uint32_t* __restrict__ order /*launch order of the compositing grids (tile_order.h), or null*/,
-                    int ranges_final /*the tile launch has finished (same stream): its range table may be read*/)
+                    int ranges_final /*the tile launch has finished (same stream): its range table may be read*/, Bound... bd)
 {
+    constexpr bool BOUNDED = sizeof...(Bound) > 0;
+    [[maybe_unused]] bool fits = true;
+    if constexpr (BOUNDED) {
+        fits = bounded_fits(total, bd...);
+        if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) bounded_publish(total, bd...);
+    }
     __shared__ double s_keys[BIN_SORT_BIG + BIN_SORT_BIG / 16];
     __shared__ uint32_t s_mine[BIN_BIG_MINE];   // this block's share of the long lists
     __shared__ uint32_t s_nmine;
@@ -455,7 +507,7 @@ bin_sort_big_kernel(int gtiles, int tiles, int gx, int nchunk, int cap /*the til
         if (ranges_final)   // (contiguous 8-byte entries)
             tile_order_block(gtiles, [&](int i) { return b.ranges[2 * i + 1] - b.ranges[2 * i]; }, order, s_cnt, s_wsum, b.nparts);
         else                // beside the tile launch: from the scanned table, like the lists below — nothing that launch writes is read here
-            tile_order_block(gtiles, [&](int i) { uint32_t st_, n_; tile_span((uint32_t)i, gtiles, nchunk, table, total, st_, n_); return n_; },
+            tile_order_block(gtiles, [&](int i) { uint32_t st_, n_; tile_span((uint32_t)i, gtiles, nchunk, table, total, st_, n_); if constexpr (BOUNDED) { if (!fits) n_ = 0u; } return n_; },
                              order, s_cnt, s_wsum, b.nparts);
         __syncthreads();
     }
@@ -468,6 +520,8 @@ bin_sort_big_kernel(int gtiles, int tiles, int gx, int nchunk, int cap /*the til
     for (uint32_t i = blockIdx.x + t * gridDim.x; i < (uint32_t)gtiles; i += gridDim.x * 1024u) {
         uint32_t st_, n_;
         tile_span(i, gtiles, nchunk, table, total, st_, n_);
+        if constexpr (BOUNDED)
+            if (!fits) n_ = 0u;
         if (n_ > (uint32_t)cap) {
             const uint32_t slot = atomicAdd(&s_nmine, 1u);
             if (slot < (uint32_t)BIN_BIG_MINE) s_mine[slot] = i;
@@ -600,18 +654,27 @@ static int side_stream(int dev, SideStream** out)
 
 // render stage: scatter the keys, sort every tile's list, write the payload
 int launch_bin_scatter_sort(const splatraster_settings& s, int32_t P, int32_t V, int64_t R, const GeomView& g,
-                            const uint32_t* table, const BinView& b, uint64_t* keys, hipStream_t stream)
+                            const uint32_t* table, const BinView& b, uint64_t* keys, hipStream_t stream, const BoundedRun* bd)
 {
     const int gx = (s.image_width + TILE - 1) / TILE, gy = (s.image_height + TILE - 1) / TILE;
     const int tiles = gx * gy, nchunk = bin_chunks(P, V, tiles);
     const int gtiles = V * tiles;
     (void)R;
-    switch (bin_rows_per_thread(P, V, tiles)) {
+#define SR_BIN_SCATTER_BOUNDED(ROWS) hipLaunchKernelGGL((bin_walk_kernel<ROWS, true, const uint32_t*, BoundedRun>), dim3((unsigned)nchunk, (unsigned)V), \
+                                                        dim3(BIN_THREADS), (size_t)tiles * sizeof(uint32_t), stream, P, tiles, gx, gy, nchunk, g.rec,    \
+                                                        const_cast<uint32_t*>(table), keys, (const uint32_t*)g.total, *bd)
+    if (bd) switch (bin_rows_per_thread(P, V, tiles)) {
+        case 1: SR_BIN_SCATTER_BOUNDED(1); break;
+        case 2: SR_BIN_SCATTER_BOUNDED(2); break;
+        default: SR_BIN_SCATTER_BOUNDED(8); break;
+    }
+    else switch (bin_rows_per_thread(P, V, tiles)) {
         case 1: SR_BIN_WALK(1, true, const_cast<uint32_t*>(table), keys); break;
         case 2: SR_BIN_WALK(2, true, const_cast<uint32_t*>(table), keys); break;
         default: SR_BIN_WALK(8, true, const_cast<uint32_t*>(table), keys); break;
     }
 #undef SR_BIN_WALK
+#undef SR_BIN_SCATTER_BOUNDED
     SR_LAUNCH_CHECK();
     int dev = 0;
     SR_HIP_CHECK(hipGetDevice(&dev));
@@ -631,6 +694,20 @@ int launch_bin_scatter_sort(const splatraster_settings& s, int32_t P, int32_t V,
     // and joined before the compositing grids (round 5: 40 us of a Replica-scale frame were one 8 192-key sort AFTER the tile
     // launch had finished).  Without long lists the second launch only computes the launch order: same stream, no events.
     const int tile_cap = wide ? BIN_SORT_TILE_WIDE : BIN_SORT_TILE_NARROW;
+    if (bd) {   // one stream, no events: tile launch, then the long lists + launch order + status
+        if (wide)
+            hipLaunchKernelGGL((bin_sort_tile_kernel<BIN_SORT_TILE_WIDE, BoundedRun>), dim3((unsigned)gtiles), dim3(BIN_SORT_TILE_WIDE / 16), 0,
+                               stream, gtiles, tiles, gx, nchunk, table, (const uint32_t*)g.total, (const uint64_t*)keys, (const float4*)g.rec, b, *bd);
+        else
+            hipLaunchKernelGGL((bin_sort_tile_kernel<BIN_SORT_TILE_NARROW, BoundedRun>), dim3((unsigned)gtiles), dim3(BIN_SORT_TILE_NARROW / 16), 0,
+                               stream, gtiles, tiles, gx, nchunk, table, (const uint32_t*)g.total, (const uint64_t*)keys, (const float4*)g.rec, b, *bd);
+        SR_LAUNCH_CHECK();
+        hipLaunchKernelGGL(bin_sort_big_kernel<BoundedRun>, dim3(BIN_BIG_BLOCKS), dim3(1024), 0, stream, gtiles, tiles, gx, nchunk, tile_cap,
+                           table, (const uint32_t*)g.total, keys, (const float4*)g.rec, b,
+                           use_tile_order(V, tiles) ? b.tile_order : (uint32_t*)nullptr, 1, *bd);
+        SR_LAUNCH_CHECK();
+        return SPLATRASTER_OK;
+    }
     const bool fork = g_bin_fork == 1 || (g_bin_fork < 0 && long_lists);
     hipStream_t side = stream;
     SideStream* ss = nullptr;
@@ -641,7 +718,7 @@ int launch_bin_scatter_sort(const splatraster_settings& s, int32_t P, int32_t V,
         SR_HIP_CHECK(hipEventRecord(ss->fork, stream));
         SR_HIP_CHECK(hipStreamWaitEvent(side, ss->fork, 0));
         // the long lists first: they are the launch sequence's longest blocks
-        hipLaunchKernelGGL(bin_sort_big_kernel, dim3(BIN_BIG_BLOCKS), dim3(1024), 0, side, gtiles, tiles, gx, nchunk,
+        hipLaunchKernelGGL(bin_sort_big_kernel<>, dim3(BIN_BIG_BLOCKS), dim3(1024), 0, side, gtiles, tiles, gx, nchunk,
                            tile_cap, table, g.total, keys, g.rec, b,
                            use_tile_order(V, tiles) ? b.tile_order : (uint32_t*)nullptr, 0);
         SR_LAUNCH_CHECK();
@@ -657,7 +734,7 @@ int launch_bin_scatter_sort(const splatraster_settings& s, int32_t P, int32_t V,
     if (fork) {
         SR_HIP_CHECK(hipStreamWaitEvent(stream, ss->join, 0));
     } else {
-        hipLaunchKernelGGL(bin_sort_big_kernel, dim3(BIN_BIG_BLOCKS), dim3(1024), 0, stream, gtiles, tiles, gx, nchunk,
+        hipLaunchKernelGGL(bin_sort_big_kernel<>, dim3(BIN_BIG_BLOCKS), dim3(1024), 0, stream, gtiles, tiles, gx, nchunk,
                            tile_cap, table, g.total, keys, g.rec, b,
                            use_tile_order(V, tiles) ? b.tile_order : (uint32_t*)nullptr, 1);
         SR_LAUNCH_CHECK();

@@ -440,13 +440,15 @@ static BinScratch bin_scratch(const splatraster_settings& s, int32_t P, int32_t 
 static int window_geometry(const splatraster_settings* s, int32_t V, const splatraster_window_view* views, int32_t P,
                            const float* means3D, const float* shs, const float* opacities, const float* scales,
                            const float* rotations, const float* cov3D_precomp, void* geometry, int64_t* num_rendered,
-                           hipStream_t stream, const RawFwd* raw = nullptr)
+                           hipStream_t stream, const RawFwd* raw = nullptr,
+                           bool bounded = false /*no count comes back (num_rendered is NULL) and the host waits for nothing: binned front end only*/)
 {
     int st = check_window(s, V, views);
     if (st) return st;
-    if (P < 0 || !num_rendered) return SPLATRASTER_ERR_BAD_ARG;
-    for (int v = 0; v < V; ++v) num_rendered[v] = 0;
-    if (P == 0) return SPLATRASTER_OK;
+    if (P < 0 || (!num_rendered && !bounded)) return SPLATRASTER_ERR_BAD_ARG;
+    if (!bounded)
+        for (int v = 0; v < V; ++v) num_rendered[v] = 0;
+    if (P == 0) return bounded ? SPLATRASTER_ERR_UNSUPPORTED : SPLATRASTER_OK;
     if (raw) {      // the raw tensors stand in for opacities / scales / rotations (which are this call's OUTPUTS: raw->scales ...)
         if (shs || cov3D_precomp || !raw->scaling || !raw->rotation || !raw->opacity || !raw->f_dc || !raw->scales || !raw->rotations ||
             !raw->opacities || !raw->colors || raw->E != s->channels - 3 || (raw->E > 0 && !raw->extra))
@@ -476,18 +478,21 @@ static int window_geometry(const splatraster_settings* s, int32_t V, const splat
     char* base = reinterpret_cast<char*>(geometry);
     const WinCams cams = make_cams(V, views);
     const BinScratch bins = bin_scratch(*s, P, V, geometry, true);
+    if (bounded && !bins.on) return SPLATRASTER_ERR_UNSUPPORTED;   // (nothing launched yet)
     HostSlot* slot = nullptr;
     const size_t nblk = (size_t)preprocess_blocks(P);
-    st = host_slot(nblk * (size_t)V, &slot);
-    if (st) return st;
-    g.block_tiles = slot->dp;     // the per-(view, block) instance sums land in host memory
+    if (!bounded) {
+        st = host_slot(nblk * (size_t)V, &slot);
+        if (st) return st;
+        g.block_tiles = slot->dp;     // the per-(view, block) instance sums land in host memory
+    }   // (bounded: nobody reads the sums; they stay in the geometry buffer's own scratch, and no kernel is left writing a pinned slot)
     // preprocess_kernel stores into the thread's pinned slot: an error return between its launch and the wait below must not
     // leave the kernel writing a slot the next call on this thread may free, reallocate or read (state 1: launched, wait for
     // the stream; 2: the event behind the kernel is recorded, wait for that; 0: nothing in flight)
     struct SlotGuard {
         HostSlot* slot; hipStream_t stream; int state;
         ~SlotGuard() { if (state == 2) (void)hipEventSynchronize(slot->ev); else if (state == 1) (void)hipStreamSynchronize(stream); }
-    } guard{slot, stream, 1};
+    } guard{slot, stream, bounded ? 0 : 1};
     {
         StageTimer t(SPLATRASTER_STAGE_PREPROCESS, stream);
         // the look-back state of the depth sort and of the scan is cleared by preprocess_kernel
@@ -501,8 +506,10 @@ static int window_geometry(const splatraster_settings* s, int32_t V, const splat
                                    reinterpret_cast<uint32_t*>(base + L.scan_tmp), (uint32_t)(scan_state_bytes(n) / 4), stream, true, raw);
     }
     if (st) return st;
-    SR_HIP_CHECK(hipEventRecord(slot->ev, stream));
-    guard.state = 2;
+    if (!bounded) {
+        SR_HIP_CHECK(hipEventRecord(slot->ev, stream));
+        guard.state = 2;
+    }
     if (bins.on) {
         // binned front end (binsort.hip): per-(tile, chunk) counts + their scan instead of the depth sort + offsets scan
         StageTimer t(SPLATRASTER_STAGE_DEPTH_SORT, stream);
@@ -525,6 +532,7 @@ static int window_geometry(const splatraster_settings* s, int32_t V, const splat
     }
     if (st) return st;
     }
+    if (bounded) return SPLATRASTER_OK;   // R stays on the device (g.total)
     SR_HIP_CHECK(hipEventSynchronize(slot->ev));  // preprocess only: sort and scan may still be running
     guard.state = 0;
     uint64_t total = 0;
@@ -541,7 +549,8 @@ static int window_geometry(const splatraster_settings* s, int32_t V, const splat
 // Stage 2: ONE emission, ONE tile sort keyed by (view, tile), one payload pass, one compositing grid over the V views.
 static int window_render(const splatraster_settings* s, int32_t V, const splatraster_window_view* views, int32_t P,
                          int64_t R, const float* bg, const float* colors_precomp, void* geometry, void* binning,
-                         void* image, hipStream_t stream)
+                         void* image, hipStream_t stream,
+                         const BoundedRun* bd = nullptr /*bounded sequence: R is the CAPACITY `binning` was laid out for*/)
 {
     int st = check_window(s, V, views);
     if (st) return st;
@@ -563,7 +572,7 @@ static int window_render(const splatraster_settings* s, int32_t V, const splatra
     if (geometry) g = geom_view(geometry, P, V);
     BinView b = bin_view(binning, P, V, R, W, H, s->channels);
     const float* feat = colors_precomp ? colors_precomp : g.rgb;
-    if (R > 0 && !feat) return SPLATRASTER_ERR_BAD_ARG;
+    if ((R > 0 || bd) && !feat) return SPLATRASTER_ERR_BAD_ARG;
     const int bits = tile_bits((int)gtiles);
     const int passes = (bits + 7) / 8;
     // emit into the buffer pair from which `passes` ping-pongs end in (tile_list, point_list); with 16-bit keys (sort_keys16) the
@@ -574,11 +583,15 @@ static int window_render(const splatraster_settings* s, int32_t V, const splatra
     uint32_t* k1 = (passes & 1) ? b.tile_list : b.keys_tmp;
     uint32_t* v1 = (passes & 1) ? b.point_list : b.vals_tmp;
     const BinScratch bins = bin_scratch(*s, P, V, geometry, false);
-    if (R > 0 && bins.on) {
+    if (bd && !bins.on) return SPLATRASTER_ERR_UNSUPPORTED;
+    // a bounded sequence always launches the binned front end: whether the frame is empty is known on the device only, and the
+    // front end itself leaves a cleared range table and a valid launch order when the total is 0
+    const bool binned = bins.on && (R > 0 || bd);
+    if (binned) {
         // binned front end: scatter the 64-bit keys into their (tile, chunk) pieces, sort every tile's list in LDS and write
         // the payload + lists + ranges (binsort.hip); the keys live where the radix path keeps its unsorted pairs
         StageTimer t(SPLATRASTER_STAGE_TILE_SORT, stream);
-        st = launch_bin_scatter_sort(*s, P, V, R, g, bins.table, b, reinterpret_cast<uint64_t*>(b.keys_tmp), stream);
+        st = launch_bin_scatter_sort(*s, P, V, R, g, bins.table, b, reinterpret_cast<uint64_t*>(b.keys_tmp), stream, bd);
         if (st) return st;
     }
     if (R > 0 && !bins.on) {
@@ -596,7 +609,7 @@ static int window_render(const splatraster_settings* s, int32_t V, const splatra
         }
         if (st) return st;
     }
-    if (R == 0) {   // nothing was emitted: the table is cleared here instead
+    if (R == 0 && !bd) {   // nothing was emitted: the table is cleared here instead
         StageTimer t(SPLATRASTER_STAGE_RANGES, stream);
         st = launch_ranges_clear((int32_t)gtiles, b.ranges, stream);
     }
@@ -604,7 +617,7 @@ static int window_render(const splatraster_settings* s, int32_t V, const splatra
     const float* featp = feat;  // 16-byte aligned rows for the compositing kernels
     const bool compact = payload_compact(*s, V, R, bins.on);
     compact_record(binning, compact);
-    if (R > 0) {
+    if (R > 0 || bd) {
         StageTimer t(SPLATRASTER_STAGE_PAYLOAD, stream);
         if (compact) st = launch_payload_compact(*s, V, R, g, b, im.cranges, stream);
         else if (!bins.on) st = launch_payload(*s, V, R, g, b, stream);
@@ -615,7 +628,7 @@ static int window_render(const splatraster_settings* s, int32_t V, const splatra
         }
     }
     if (st) return st;
-    if (!(R > 0 && bins.on)) {   // launch order of the compositing grids (the range table is final here, also when nothing was
+    if (!binned) {               // launch order of the compositing grids (the range table is final here, also when nothing was
                                  // emitted); the binned front end's last launch has computed it (binsort.hip)
         StageTimer t(SPLATRASTER_STAGE_RANGES, stream);
         st = launch_tile_order(*s, V, b, stream);
@@ -955,6 +968,57 @@ int splatraster_forward_window_geometry_raw(const splatraster_settings* s, int32
                      rf->opacities, rf->colors};
     return window_geometry(s, n_views, views, P, means3D, nullptr, nullptr, nullptr, nullptr, nullptr, geometry, num_rendered,
                            reinterpret_cast<hipStream_t>(stream), &raw);
+}
+
+// Geometry + render as one launch sequence into a binning buffer of `capacity` instances (include/splatraster.h, "bounded window
+// forward"): every check of both stages that can fail does so before the first launch.
+static int window_bounded(const splatraster_settings* s, int32_t V, const splatraster_window_view* views, int32_t P,
+                          const float* means3D, const float* opacities, const float* scales, const float* rotations,
+                          const float* cov3D_precomp, const RawFwd* raw, const float* bg, const float* colors_precomp, void* geometry,
+                          void* binning, void* image, int64_t capacity, uint32_t tag, void* status, hipStream_t stream)
+{
+    int st = check_window(s, V, views);
+    if (st) return st;
+    if (!status || capacity < 0 || P < 0 || !geometry || !binning || !image || !colors_precomp) return SPLATRASTER_ERR_BAD_ARG;
+    if (capacity >= ((int64_t)1 << 31)) return SPLATRASTER_ERR_OVERFLOW;
+    if (s->bg_channels > 0 && !bg) return SPLATRASTER_ERR_BAD_ARG;
+    for (int v = 0; v < V; ++v)
+        if (!views[v].out_color || !views[v].out_depth || !views[v].out_alpha) return SPLATRASTER_ERR_BAD_ARG;
+    const BoundedStatus* h = reinterpret_cast<const BoundedStatus*>(status);
+    const BoundedRun bd{(uint32_t)capacity, tag, h->dev, h->host_dev};
+    st = window_geometry(s, V, views, P, means3D, nullptr, opacities, scales, rotations, cov3D_precomp, geometry, nullptr, stream,
+                         raw, true);
+    if (st) return st;
+    return window_render(s, V, views, P, capacity, bg, colors_precomp, geometry, binning, image, stream, &bd);
+}
+
+int splatraster_forward_window_bounded_supported(int32_t P, int32_t n_views, int32_t width, int32_t height)
+{
+    if (P <= 0 || n_views < 1 || n_views > MAX_VIEWS || width <= 0 || height <= 0) return 0;
+    const GeomLayout L = geom_layout(P, n_views);
+    return use_bins(P, n_views, (width + TILE - 1) / TILE, (height + TILE - 1) / TILE, L.total - L.sort_keys) ? 1 : 0;
+}
+
+int splatraster_forward_window_bounded(const splatraster_settings* s, int32_t n_views, const splatraster_window_view* views,
+                                       int32_t P, const float* means3D, const float* opacities, const float* scales,
+                                       const float* rotations, const float* cov3D_precomp, const float* bg,
+                                       const float* colors_precomp, void* geometry, void* binning, void* image,
+                                       int64_t capacity, uint32_t tag, void* status, void* stream)
+{
+    return window_bounded(s, n_views, views, P, means3D, opacities, scales, rotations, cov3D_precomp, nullptr, bg, colors_precomp,
+                          geometry, binning, image, capacity, tag, status, reinterpret_cast<hipStream_t>(stream));
+}
+
+int splatraster_forward_window_bounded_raw(const splatraster_settings* s, int32_t n_views, const splatraster_window_view* views,
+                                           int32_t P, const float* means3D, const splatraster_raw_forward* rf, const float* bg,
+                                           void* geometry, void* binning, void* image, int64_t capacity, uint32_t tag,
+                                           void* status, void* stream)
+{
+    if (!rf) return SPLATRASTER_ERR_BAD_ARG;
+    const RawFwd raw{rf->scaling, rf->rotation, rf->opacity, rf->f_dc, rf->extra, rf->extra_channels, rf->scales, rf->rotations,
+                     rf->opacities, rf->colors};
+    return window_bounded(s, n_views, views, P, means3D, nullptr, nullptr, nullptr, nullptr, &raw, bg, rf->colors, geometry, binning,
+                          image, capacity, tag, status, reinterpret_cast<hipStream_t>(stream));
 }
 
 int splatraster_backward_window_raw(const splatraster_settings* s, int32_t n_views, const splatraster_window_view* views,

@@ -262,8 +262,27 @@ size_t bin_scratch_bytes(int32_t P, int32_t V, int tiles);
 bool use_bins(int32_t P, int32_t V, int gx, int gy /*tiles per row / column of a view*/, size_t scratch_bytes);
 int launch_bin_count(const splatraster_settings& s, int32_t P, int32_t V, const GeomView& g, uint32_t* table, void* scan_tmp,
                      hipStream_t stream);
+// Bounded mode (splatraster_forward_window_bounded): the render stage runs into a binning buffer laid out for `capacity`
+// instances while R stays on the device.  The status block (splatraster_bounded_status: 16 words) exists twice: a device-resident
+// copy the kernels read, and a host-mapped coherent mirror the host reads without waiting for the stream.
+enum { BOUNDED_TOTAL = 0, BOUNDED_OVERFLOW = 1, BOUNDED_FIRST_TAG = 2, BOUNDED_FIRST_TOTAL = 3, BOUNDED_LAST_TAG = 4, BOUNDED_WORDS = 16 };
+struct BoundedRun {
+    uint32_t capacity;   // instances the per-instance arrays of `binning` hold
+    uint32_t tag;        // the caller's name for this sequence
+    uint32_t* status;    // device-resident block
+    uint32_t* mirror;    // the host-mapped copy as the device addresses it
+};
+struct BoundedStatus {   // what a status handle points to (bounded.hip)
+    uint32_t* dev;       // hipMalloc
+    uint32_t* host;      // hipHostMalloc, mapped + coherent
+    uint32_t* host_dev;  // `host` as the device addresses it
+    int device;
+};
+int launch_bounded_status_clear(const BoundedStatus& st, hipStream_t stream);
+// `bd` non-null: the bounded sequence (scatter, tile launch, long lists + launch order + status on ONE stream; R is ignored)
 int launch_bin_scatter_sort(const splatraster_settings& s, int32_t P, int32_t V, int64_t R, const GeomView& g,
-                            const uint32_t* table, const BinView& b, uint64_t* keys, hipStream_t stream);
+                            const uint32_t* table, const BinView& b, uint64_t* keys, hipStream_t stream,
+                            const BoundedRun* bd = nullptr);
 
 int launch_emit(const splatraster_settings& s, int32_t P, int32_t V, int64_t R, const GeomView& g, uint32_t* keys,
                 uint32_t* vals, uint32_t* ranges, uint32_t nranges, hipStream_t stream, bool keys16 = false /*keys: [R] uint16_t*/);

@@ -299,9 +299,18 @@ __device__ __forceinline__ void adam_element(const AdamTable& T, int gq, float g
 }
 
 // scalar form: any alignment
-__global__ void __launch_bounds__(256)
-adam_kernel(AdamTable T, unsigned long long total)
+// `Gate`: empty, or (const uint32_t* status) — the device copy of a bounded status block (splatraster_adam_step_gated): while its
+// overflow word is set every block leaves before it touches a parameter, a moment or max_radii2D
+__device__ __forceinline__ bool adam_gate_closed(const uint32_t* status)
 {
+    return __hip_atomic_load(status + BOUNDED_OVERFLOW, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
+}
+template <typename... Gate>
+__global__ void __launch_bounds__(256)
+adam_kernel(AdamTable T, unsigned long long total, Gate... gate)
+{
+    if constexpr (sizeof...(Gate) > 0)
+        if (adam_gate_closed(gate...)) return;
     for (unsigned long long e = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; e < total + (unsigned long long)T.radii_n;
          e += (unsigned long long)gridDim.x * blockDim.x) {
         if (e >= total) { radii_update(T, e - total); continue; }
@@ -326,9 +335,12 @@ struct AdamQuads {
     unsigned long long qend[ADAM_MAX_GROUPS];   // exclusive end of the group's quad range
     long long numel[ADAM_MAX_GROUPS];
 };
+template <typename... Gate>
 __global__ void __launch_bounds__(256)
-adam_quad_kernel(AdamTable T, AdamQuads Q, unsigned long long total_quads)
+adam_quad_kernel(AdamTable T, AdamQuads Q, unsigned long long total_quads, Gate... gate)
 {
+    if constexpr (sizeof...(Gate) > 0)
+        if (adam_gate_closed(gate...)) return;
     const unsigned long long radii_quads = ((unsigned long long)T.radii_n + 3ull) / 4ull;
     for (unsigned long long q = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; q < total_quads + radii_quads;
          q += (unsigned long long)gridDim.x * blockDim.x) {
@@ -387,7 +399,8 @@ adam_quad_kernel(AdamTable T, AdamQuads Q, unsigned long long total_quads)
 }
 
 int adam_step(int n, const splatraster_adam_group* groups, double beta1, double beta2, double eps, float gate_thr,
-              int32_t radii_n, const int32_t* radii, float* max_radii, hipStream_t stream)
+              int32_t radii_n, const int32_t* radii, float* max_radii, hipStream_t stream,
+              const uint32_t* gate_status = nullptr /*device copy of a bounded status block: the gated instantiations*/)
 {
     AdamTable T{};
     AdamQuads Q{};
@@ -420,11 +433,13 @@ int adam_step(int n, const splatraster_adam_group* groups, double beta1, double 
     if (aligned) {
         unsigned long long blocks = (total_quads + ((unsigned long long)T.radii_n + 3ull) / 4ull + 255) / 256;
         if (blocks > 4096) blocks = 4096;   // grid-stride: 16 workgroups per CU
-        hipLaunchKernelGGL(adam_quad_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, T, Q, total_quads);
+        if (gate_status) hipLaunchKernelGGL(adam_quad_kernel<const uint32_t*>, dim3((unsigned)blocks), dim3(256), 0, stream, T, Q, total_quads, gate_status);
+        else hipLaunchKernelGGL(adam_quad_kernel<>, dim3((unsigned)blocks), dim3(256), 0, stream, T, Q, total_quads);
     } else {
         unsigned long long blocks = (total + (unsigned long long)T.radii_n + 255) / 256;
         if (blocks > 4096) blocks = 4096;
-        hipLaunchKernelGGL(adam_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, T, total);
+        if (gate_status) hipLaunchKernelGGL(adam_kernel<const uint32_t*>, dim3((unsigned)blocks), dim3(256), 0, stream, T, total, gate_status);
+        else hipLaunchKernelGGL(adam_kernel<>, dim3((unsigned)blocks), dim3(256), 0, stream, T, total);
     }
     SR_LAUNCH_CHECK();
     return SPLATRASTER_OK;
@@ -641,6 +656,25 @@ int splatraster_adam_step_radii(int32_t n_groups, const splatraster_adam_group* 
     if (n_groups < 0 || n_groups > ADAM_MAX_GROUPS || (n_groups > 0 && !groups) || P < 0 || (P > 0 && (!radii || !max_radii2D)))
         return SPLATRASTER_ERR_BAD_ARG;
     return adam_step(n_groups, groups, beta1, beta2, eps, row_gate_threshold, P, radii, max_radii2D, reinterpret_cast<hipStream_t>(stream));
+}
+
+int splatraster_adam_step_gated(int32_t n_groups, const splatraster_adam_group* groups, double beta1, double beta2, double eps,
+                                float row_gate_threshold, const void* status, void* stream)
+{
+    if (n_groups < 0 || n_groups > ADAM_MAX_GROUPS || (n_groups > 0 && !groups) || !status) return SPLATRASTER_ERR_BAD_ARG;
+    if (n_groups == 0) return SPLATRASTER_OK;
+    return adam_step(n_groups, groups, beta1, beta2, eps, row_gate_threshold, 0, nullptr, nullptr, reinterpret_cast<hipStream_t>(stream),
+                     reinterpret_cast<const BoundedStatus*>(status)->dev);
+}
+
+int splatraster_adam_step_radii_gated(int32_t n_groups, const splatraster_adam_group* groups, double beta1, double beta2, double eps,
+                                      float row_gate_threshold, int32_t P, const int32_t* radii, float* max_radii2D,
+                                      const void* status, void* stream)
+{
+    if (n_groups < 0 || n_groups > ADAM_MAX_GROUPS || (n_groups > 0 && !groups) || P < 0 || (P > 0 && (!radii || !max_radii2D)) || !status)
+        return SPLATRASTER_ERR_BAD_ARG;
+    return adam_step(n_groups, groups, beta1, beta2, eps, row_gate_threshold, P, radii, max_radii2D, reinterpret_cast<hipStream_t>(stream),
+                     reinterpret_cast<const BoundedStatus*>(status)->dev);
 }
 
 size_t splatraster_isotropic_loss_workspace_bytes(int32_t P) { return isotropic_workspace_bytes(P); }

@@ -55,6 +55,23 @@ def image_views(img: torch.Tensor, W: int, H: int) -> dict:
     )
 
 
+def binning_spans(V: int, R: int, W: int, H: int) -> dict:
+    """Byte offsets of the per-instance arrays of a binning buffer laid out for R instances of a per-view (V = 1) or window
+    forward: `point_list`, `tile_list` (the four list arrays fill [0, `ranges`)), the range table `ranges` ([V * tiles, 2]
+    words), the payload arrays `irec` (32 bytes per instance) and `ipack` (4), `payload_end`, and `total`.  None of them depends
+    on the Gaussian or channel count.  The offsets mirror csrc/capi.hip: bin_layout."""
+    lib = _native.load()
+    BL = _native.BinningLayout()
+    _native.check(lib.splatraster_get_window_binning_layout(1, V, R, W, H, 4, C.byref(BL)), "window_binning_layout")
+    al = lambda b: (b + 255) // 256 * 256  # noqa: E731
+    tiles = V * ((W + 15) // 16) * ((H + 15) // 16)
+    n = max(int(R), 1)
+    irec = BL.ranges + al(8 * tiles) + al(lib.splatraster_sort_tmp_bytes(n) - 2 * al(4 * n))
+    ipack = irec + al(32 * n)
+    return dict(point_list=BL.point_list, tile_list=BL.tile_list, ranges=BL.ranges, tiles=tiles, irec=irec, ipack=ipack,
+                payload_end=ipack + al(4 * n))
+
+
 def payload_state(fn_ctx_tensors, R: int, W: int, H: int, V: int = 1, compact: bool = True) -> dict:
     """The per-instance stream the compositing kernels read, of a per-view (V = 1) or window forward (R: all its instances):
     `irec` [n, 8] (pixel x, y, depth, a moved word | pre-scaled conic, opacity), `ids` [n] rows and `imask` [n] reach bits, entry by
@@ -65,15 +82,12 @@ def payload_state(fn_ctx_tensors, R: int, W: int, H: int, V: int = 1, compact: b
     csrc/capi.hip: bin_layout / img_view."""
     lib = _native.load()
     _geom, binning, img = fn_ctx_tensors
-    BL, IL = _native.BinningLayout(), _native.ImageLayout()
-    _native.check(lib.splatraster_get_window_binning_layout(1, V, R, W, H, 4, C.byref(BL)), "window_binning_layout")
+    IL = _native.ImageLayout()
     _native.check(lib.splatraster_get_window_image_layout(W, H, V, C.byref(IL)), "window_image_layout")
-    al = lambda b: (b + 255) // 256 * 256  # noqa: E731
-    tiles = V * ((W + 15) // 16) * ((H + 15) // 16)
-    n = max(int(R), 1)
-    irec_off = BL.ranges + al(8 * tiles) + al(lib.splatraster_sort_tmp_bytes(n) - 2 * al(4 * n))
-    irec = _view(binning, irec_off, 8 * int(R), torch.float32).view(int(R), 8)
-    ipack = _view(binning, irec_off + al(32 * n), int(R), torch.int32)
+    sp = binning_spans(V, R, W, H)
+    tiles = sp["tiles"]
+    irec = _view(binning, sp["irec"], 8 * int(R), torch.float32).view(int(R), 8)
+    ipack = _view(binning, sp["ipack"], int(R), torch.int32)
     out = {}
     if compact:
         plane = IL.n_contrib                     # the planes are equally large: final_T, n_contrib, n_contrib_c, then the table

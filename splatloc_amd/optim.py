@@ -25,10 +25,17 @@ class Adam(torch.optim.Adam):
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=0, amsgrad=False)
         self.key_gate = None        # (gate tensor with one value per xyz row, threshold, group name)
         self._radii_update = None   # (radii, max_radii2D) for the next step() — set_radii_update
+        self._gate = None           # a rasterizer.BoundedStatus: step() launches the gated kernels — set_gate
 
     def set_key_gate(self, gate: torch.Tensor, threshold: float = 0.005, group: str = "xyz") -> None:
         """Rows of `group` whose gate value exceeds `threshold` see a zero gradient in step()."""
         self.key_gate = None if gate is None else (gate, float(threshold), group)
+
+    def set_gate(self, status) -> None:
+        """`status` (a rasterizer.BoundedStatus, or None): step() becomes splatraster_adam_step[_radii]_gated — while the block's
+        sticky `overflow` word is set the launch returns without touching a parameter, a moment or max_radii2D (the host-side
+        step counters still advance: the loop that owns the block rewinds them).  With the word clear: bit-identical."""
+        self._gate = status
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -96,17 +103,30 @@ class Adam(torch.optim.Adam):
             thr = gate_spec[1] if gate_spec is not None else 0.0
             if betas is None:
                 betas, eps = (0.9, 0.999), 1e-8
+            gate = getattr(self, "_gate", None)
+            if gate is not None and dev is not None and dev.index is not None and gate.device != dev:
+                raise RuntimeError(f"splatloc_amd.optim.Adam: the gate's status block lives on {gate.device}, the parameters on {dev}")
             if radii_update is not None:      # the frame's max_radii2D line rides this launch (set_radii_update)
                 radii, max_radii = radii_update
                 dev = radii.device if dev is None else dev
                 with _on_device(dev):
-                    _native.check(lib.splatraster_adam_step_radii(len(entries), arr, C.c_double(betas[0]), C.c_double(betas[1]),
-                                                                  C.c_double(eps), C.c_float(thr), int(radii.numel()), radii.data_ptr(),
-                                                                  max_radii.data_ptr(), _stream(dev)), "adam_step_radii")
+                    if gate is not None:
+                        _native.check(lib.splatraster_adam_step_radii_gated(
+                            len(entries), arr, C.c_double(betas[0]), C.c_double(betas[1]), C.c_double(eps), C.c_float(thr),
+                            int(radii.numel()), radii.data_ptr(), max_radii.data_ptr(), gate.handle, _stream(dev)), "adam_step_radii_gated")
+                    else:
+                        _native.check(lib.splatraster_adam_step_radii(len(entries), arr, C.c_double(betas[0]), C.c_double(betas[1]),
+                                                                      C.c_double(eps), C.c_float(thr), int(radii.numel()), radii.data_ptr(),
+                                                                      max_radii.data_ptr(), _stream(dev)), "adam_step_radii")
             else:
                 with _on_device(dev):
-                    _native.check(lib.splatraster_adam_step(len(entries), arr, C.c_double(betas[0]), C.c_double(betas[1]),
-                                                            C.c_double(eps), C.c_float(thr), _stream(dev)), "adam_step")
+                    if gate is not None:
+                        _native.check(lib.splatraster_adam_step_gated(len(entries), arr, C.c_double(betas[0]), C.c_double(betas[1]),
+                                                                      C.c_double(eps), C.c_float(thr), gate.handle, _stream(dev)),
+                                      "adam_step_gated")
+                    else:
+                        _native.check(lib.splatraster_adam_step(len(entries), arr, C.c_double(betas[0]), C.c_double(betas[1]),
+                                                                C.c_double(eps), C.c_float(thr), _stream(dev)), "adam_step")
         del keep
         return loss
 

@@ -272,14 +272,88 @@ def _window_views(f):
     return views
 
 
-def window_forward(means3D, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings, raw=None):
+class BoundedStatus:
+    """A status block of the bounded window forward (splatraster_bounded_status_create) on `device`: R of the last sequence, the
+    sticky overflow flag and the record of the first sequence that did not fit.  `read()` copies the host-mapped mirror (last_tag,
+    then overflow, then the rest) and never synchronises; `clear()` is stream-ordered.  The owner calls `close()` once every
+    stream that used the block has been synchronised (or uses it as a context manager, which synchronises the device first)."""
+
+    def __init__(self, device):
+        self.lib = _native.load()
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("BoundedStatus needs a GPU device (no CPU fallback)")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        h = C.c_void_p()
+        with _on_device(self.device):
+            _native.check(self.lib.splatraster_bounded_status_create(C.byref(h)), "bounded_status_create")
+        self.handle = h
+
+    def read(self) -> _native.BoundedStatus:
+        out = _native.BoundedStatus()
+        _native.check(self.lib.splatraster_bounded_status_read(self.handle, C.byref(out)), "bounded_status_read")
+        return out
+
+    def clear(self) -> None:
+        with _on_device(self.device):
+            _native.check(self.lib.splatraster_bounded_status_clear(self.handle, _stream(self.device)), "bounded_status_clear")
+
+    def close(self) -> None:
+        if self.handle:
+            self.lib.splatraster_bounded_status_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        torch.cuda.synchronize(self.device)
+        self.close()
+
+
+class BoundedWindow:
+    """What `window_forward(bounded=...)` renders into: a status block, the capacity (instances) the reusable `binning` tensor
+    is laid out for, and the tag of the next sequence.  `reserve(capacity, ...)` (re)allocates `binning` for a frame shape —
+    the only allocation of the mode, made when the shape or the capacity changes, never per frame.  A frame of more than
+    `capacity` instances renders the background and sets the status block's sticky `overflow` (include/splatraster.h).
+    `close()` frees a status block the window created itself (after the caller has synchronised the device)."""
+
+    def __init__(self, device, capacity: int = 0, status: Optional[BoundedStatus] = None):
+        self._own_status = status is None
+        self.status = status if status is not None else BoundedStatus(device)
+        self.device = self.status.device
+        self.capacity = int(capacity)
+        self.binning = None
+        self.next_tag = 0
+        self._shape = None
+
+    def reserve(self, capacity: int, P: int, V: int, W: int, H: int, Cn: int) -> torch.Tensor:
+        shape = (int(capacity), P, V, W, H, Cn)
+        if self.binning is None or self._shape != shape:
+            n = _native.load().splatraster_window_binning_bytes(P, V, int(capacity), W, H, Cn)
+            self.binning = torch.empty((n,), dtype=torch.uint8, device=self.device)
+            self.capacity, self._shape = int(capacity), shape
+        return self.binning
+
+    def close(self) -> None:
+        if self._own_status:
+            self.status.close()
+
+
+def window_forward(means3D, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings, raw=None, bounded=None):
     """The views of `settings` (1 <= V <= MAX_WINDOW_VIEWS, `_window_compatible`) as ONE launch sequence:
     splatraster_forward_window_geometry (+ _render).  Returns the frame: dev, P, V, st, R (instances per view), tanfov,
     the prepared inputs (`_WINDOW_INPUTS` and bg, None when absent), cams [(view, proj, campos)] per view and the buffers
     radii [V,P], geom, binning, img, color [V,C,H,W], depth [V,1,H,W], alpha [V,1,H,W].
     `raw` = (scaling [P,3], rotation [P,4], opacity [P,1], f_dc [P,1,3], extra [P,E] or None): RAW-parameter mode, in place of
     colors_precomp / opacities / scales / rotations (None): splatraster_forward_window_geometry_raw activates them inside the
-    projection kernel and fills the frame's col [P,3+E], opa, sca, rot."""
+    projection kernel and fills the frame's col [P,3+E], opa, sca, rot.
+    `bounded` (a BoundedWindow): ONE call, splatraster_forward_window_bounded[_raw], into `bounded.binning` (laid out for
+    `bounded.capacity` instances; reserved here on first use or when the shape changed) with the tag `bounded.next_tag`, which
+    is then advanced: no host wait for the instance count and no allocation of `binning` per frame.  The frame's `R` is None
+    (the count stays on the device: `bounded.status`), `capacity` is set, and `binning` is the shared tensor — valid until the
+    next bounded forward.  Only where the binned front end runs: else RuntimeError ("unsupported configuration")."""
     lib = _native.load()
     _require_gpu(means3D, "means3D")
     dev = means3D.device
@@ -311,6 +385,7 @@ def window_forward(means3D, colors_precomp, opacities, scales, rotations, cov3Ds
     f.img = torch.empty((lib.splatraster_window_image_bytes(W, H, V),), dtype=torch.uint8, device=dev)
     stream = _stream(dev)
     R = (C.c_int64 * V)()
+    f.capacity = None
     with _on_device(dev):
         if raw is not None:
             sc_r, ro_r, op_r, fd_r, ex_r = raw
@@ -319,6 +394,24 @@ def window_forward(means3D, colors_precomp, opacities, scales, rotations, cov3Ds
             rf.extra = None if ex_r is None else ex_r.data_ptr()
             rf.extra_channels = E
             rf.scales, rf.rotations, rf.opacities, rf.colors = sca.data_ptr(), rot.data_ptr(), opa.data_ptr(), col.data_ptr()
+        if bounded is not None:
+            if bounded.device != (dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())):
+                raise ValueError(f"window_forward: the bounded window lives on {bounded.device}, the tensors on {dev}")
+            f.binning = bounded.reserve(bounded.capacity, P, V, W, H, Cn)
+            f.R, f.capacity = None, bounded.capacity
+            tag = bounded.next_tag & 0xFFFFFFFF
+            bounded.next_tag += 1
+            if raw is not None:
+                _native.check(lib.splatraster_forward_window_bounded_raw(
+                    C.byref(st), V, views, P, _ptr(m3), C.byref(rf), _ptr(bg), _ptr(f.geom), _ptr(f.binning), _ptr(f.img),
+                    f.capacity, tag, bounded.status.handle, stream), "forward_window_bounded_raw")
+            else:
+                _native.check(lib.splatraster_forward_window_bounded(
+                    C.byref(st), V, views, P, _ptr(m3), _ptr(opa), _ptr(sca), _ptr(rot), _ptr(cov), _ptr(bg), _ptr(col),
+                    _ptr(f.geom), _ptr(f.binning), _ptr(f.img), f.capacity, tag, bounded.status.handle, stream),
+                    "forward_window_bounded")
+            return f
+        if raw is not None:
             _native.check(lib.splatraster_forward_window_geometry_raw(
                 C.byref(st), V, views, P, _ptr(m3), C.byref(rf), _ptr(f.geom), R, stream), "forward_window_geometry_raw")
         else:
@@ -332,6 +425,14 @@ def window_forward(means3D, colors_precomp, opacities, scales, rotations, cov3Ds
             C.byref(st), V, views, P, R, _ptr(bg), _ptr(col), _ptr(f.geom), _ptr(f.binning), _ptr(f.img), stream),
             "forward_window_render")
     return f
+
+
+def _layout_counts(f):
+    """num_rendered of a window frame's backward: the counts `binning` was laid out for — the per-view R, or for a bounded
+    frame (R is None) {capacity, 0, ...}."""
+    if f.R is None:
+        return (C.c_int64 * f.V)(int(f.capacity), *([0] * (f.V - 1)))
+    return (C.c_int64 * f.V)(*f.R)
 
 
 def window_outputs(f, head: int = 0) -> list:
@@ -388,7 +489,7 @@ def window_backward(f, grads, head: int = 0, grad_span: Optional[list] = None, r
         w.dL_dmeans2D = d["m2"][v].data_ptr() if P else None
         w.dL_dout_last = None if g_last is None else g_last.data_ptr()
         w.color_grad_channels = head
-    R = (C.c_int64 * V)(*f.R)
+    R = _layout_counts(f)
     if cameras:
         d["view"], d["proj"], d["campos"] = (torch.empty(shp, **f32) for shp in ((V, 4, 4), (V, 4, 4), (V, 3)))
         nws = lib.splatraster_window_camera_workspace_bytes(V)
@@ -463,7 +564,7 @@ def window_backward_cameras(f, grads, workspace: Optional[torch.Tensor] = None, 
         w.dL_dout_color = g_color.data_ptr()
         w.dL_dout_depth = None if g_depth is None else g_depth.data_ptr()
         w.dL_dout_alpha = None if g_alpha is None else g_alpha.data_ptr()
-    R = (C.c_int64 * V)(*f.R)
+    R = _layout_counts(f)
     with _on_device(dev):
         _native.check(lib.splatraster_backward_window_cameras(
             C.byref(st), V, views, P, R, _ptr(f.bg), _ptr(f.m3), _ptr(f.col), _ptr(f.sca), _ptr(f.rot), _ptr(f.cov),

@@ -29,7 +29,7 @@ import torch
 from .camera import PinholeCamera
 from .densify import ATTR, GROUPS
 from .keyframe import extend_from_pcd_seq
-from .training import LAST_STEP_INFO, color_refinement_step, map_step
+from .training import LAST_STEP_INFO, color_refinement_step, map_step, refine_bounded
 
 # configs/replica_nerf/base_config.yaml (the values train_gaussians.py reads)
 DEFAULT_CONFIG = {
@@ -173,15 +173,17 @@ def load_depth(config, viewpoint):
 
 
 def do_recon(gaussians, keyframes, pipe=None, background=None, config=None, refine_iterations: int = 26000, seed: int = 0,
-             batched: bool = True, group=None, on_event=None, distributed: bool = True) -> dict:
+             batched: bool = True, group=None, on_event=None, distributed: bool = True, bounded_refine: bool = False) -> dict:
     """SplatLoc.do_recon (train_gaussians.py:310-355) on `keyframes` (the reference: every `kf_interval`-th dataset frame).
     `batched = False` renders every window — and every refinement iteration — as the reference does: one `render()` per view
     through the drop-in autograd.Function (`render_path="per-view"` of training.map_step / color_refinement_step) instead of
     one graph-free launch sequence per window; `stats["render_paths"]` records which paths the map steps took.  The random draws the reference takes from global RNGs (`torch.randperm` of the window,
     `random.randint` of the refinement view, `np.random.choice` of the key-frame down-sampling) come from generators seeded
     by `seed`, identical on every rank of a frame-parallel job.  `distributed = False`: no collective even when a process
-    group exists — every rank reconstructs a scene of its own (one scene per GPU: /root/reference/replica.sh).  Returns counters
-    and timings; the model is updated in place."""
+    group exists — every rank reconstructs a scene of its own (one scene per GPU: /root/reference/replica.sh).
+    `bounded_refine = True`: the refinement phase runs through training.refine_bounded (the same iterations and the same draws of
+    the view, without the host wait for every frame's instance count; 500 iterations per call, between the "refine" events);
+    stats["refine_rewinds"] counts its replays.  Returns counters and timings; the model is updated in place."""
     cfg = config or gaussians.config
     tr, opt = cfg["Training"], cfg["opt_params"]
     dev = gaussians._xyz.device
@@ -222,12 +224,25 @@ def do_recon(gaussians, keyframes, pipe=None, background=None, config=None, refi
     stats["map_seconds"] = time.perf_counter() - t0
     t1 = time.perf_counter()
     keys = list(viewpoints.keys())
-    for iteration in range(1, refine_iterations + 1):                                       # train_gaussians.py:269-297
-        cam = viewpoints[keys[rng_r.randint(0, len(keys) - 1)]]
-        color_refinement_step(cam, gaussians, pipe, background, opt["lambda_dssim"], iteration,
-                              primitive_reg=bool(tr.get("primitive_reg", True)), render_path=path)
-        if on_event and iteration % 500 == 0:
-            on_event("refine", iteration, gaussians)
+    stats["refine_rewinds"] = 0
+    if bounded_refine and batched:
+        capacity = None     # carried from call to call: one probing forward for the whole phase
+        for first in range(1, refine_iterations + 1, 500):
+            n = min(500, refine_iterations + 1 - first)
+            cams = [viewpoints[keys[rng_r.randint(0, len(keys) - 1)]] for _ in range(n)]
+            res = refine_bounded(cams, gaussians, pipe, background, opt["lambda_dssim"], first, n,
+                                 primitive_reg=bool(tr.get("primitive_reg", True)), initial_capacity=capacity)
+            capacity = res["capacity_history"][-1] if res["capacity_history"] else None
+            stats["refine_rewinds"] += res["rewinds"]
+            if on_event and (first + n - 1) % 500 == 0:
+                on_event("refine", first + n - 1, gaussians)
+    else:
+        for iteration in range(1, refine_iterations + 1):                                   # train_gaussians.py:269-297
+            cam = viewpoints[keys[rng_r.randint(0, len(keys) - 1)]]
+            color_refinement_step(cam, gaussians, pipe, background, opt["lambda_dssim"], iteration,
+                                  primitive_reg=bool(tr.get("primitive_reg", True)), render_path=path)
+            if on_event and iteration % 500 == 0:
+                on_event("refine", iteration, gaussians)
     if refine_iterations and distributed:
         # one view per step does not shard: every rank refined its own replica redundantly, and float-atomic
         # rounding lets redundant replicas drift in the last bits — rank 0's state becomes everybody's again (one broadcast)

@@ -7,6 +7,7 @@ may be torch.optim.Adam or splatloc_amd.optim.Adam (one launch over the 8 groups
 from __future__ import annotations
 
 import os
+import time
 
 import math
 
@@ -70,7 +71,7 @@ def _raw_backward_ok(gaussians) -> bool:
 _PARAMS = ("_xyz", "_features_dc", "_features_rest", "_scaling", "_rotation", "_opacity", "_kp_score")
 
 
-def _grads_direct(gaussians, settings, loss_grads, with_reg: bool):
+def _grads_direct(gaussians, settings, loss_grads, with_reg: bool, bounded=None):
     """The gradient part of a refinement iteration or a map step WITHOUT an autograd graph: the launch functions the graph
     path runs through its autograd Functions (fused.activate_forward / _backward, rasterizer.window_forward / _backward,
     losses.isotropic_forward), called directly.  At SplatLoc's frame size both steps are HOST-bound (tools/refine_idle.py,
@@ -85,7 +86,7 @@ def _grads_direct(gaussians, settings, loss_grads, with_reg: bool):
     tests/test_gpu_refine.py).  `outs`: (rgb, kp_prob, depth, opacity, radii) per view; `loss_grads` returns (loss,
     [(g_rgb, g_kp_prob, g_depth) per view]).  Gradients land in `.grad` exactly as autograd would leave them: `_xyz` <-
     dL/dmeans3D, `_features_rest` <- its empty gradient, `_kp_score` <- its gradient (a zero column when only RGB reaches
-    the loss), `_marker` <- nothing.
+    the loss), `_marker` <- nothing.  `bounded`: window_forward's (the forward waits for no instance count).
     Returns (outs, loss, dL/dmeans2D [V, P, 3])."""
     from .fused import activate_backward, activate_forward
     from .losses import isotropic_forward
@@ -95,11 +96,11 @@ def _grads_direct(gaussians, settings, loss_grads, with_reg: bool):
     raw = act = None
     if _raw_backward_ok(g):
         raw = (g._scaling.detach(), g._rotation.detach(), g._opacity.detach(), g._features_dc.detach(), g._kp_score.detach())
-        frame = window_forward(xyz, None, None, None, None, None, settings, raw=raw)
+        frame = window_forward(xyz, None, None, None, None, None, settings, raw=raw, bounded=bounded)
     else:
         (scales, rotations, opacity, colors), act = activate_forward(xyz, g._features_dc, g._features_rest, g._scaling,
                                                                      g._rotation, g._opacity, g._kp_score, None, 0)
-        frame = window_forward(xyz, colors, opacity, scales, rotations, None, settings)
+        frame = window_forward(xyz, colors, opacity, scales, rotations, None, settings, bounded=bounded)
     outs = window_outputs(frame, 3)
     loss, grads = loss_grads(outs)
     reg = None
@@ -138,8 +139,8 @@ def _key_gate(gaussians, on: bool) -> None:
         gaussians._xyz.grad[gaussians._marker.detach().squeeze() > 0.005] = 0
 
 
-def _color_refinement_step_direct(viewpoint_cam, gaussians, background, lambda_dssim, iteration, primitive_reg):
-    """The iteration of `color_refinement_step` without an autograd graph (`_grads_direct`)."""
+def _color_refinement_step_direct(viewpoint_cam, gaussians, background, lambda_dssim, iteration, primitive_reg, bounded=None):
+    """The iteration of `color_refinement_step` without an autograd graph (`_grads_direct`).  `bounded`: see `refine_bounded`."""
     from .fused import _view_settings
 
     def loss_grads(outs):
@@ -151,7 +152,8 @@ def _color_refinement_step_direct(viewpoint_cam, gaussians, background, lambda_d
         return loss, [(g_image, None, None)]
 
     with torch.no_grad():
-        outs, loss, _m2 = _grads_direct(gaussians, [_view_settings(viewpoint_cam, gaussians, background, 1.0)], loss_grads, False)
+        outs, loss, _m2 = _grads_direct(gaussians, [_view_settings(viewpoint_cam, gaussians, background, 1.0)], loss_grads, False,
+                                        bounded=bounded)
         radii = outs[0][4]
         opt = gaussians.optimizer
         _key_gate(gaussians, primitive_reg)
@@ -203,6 +205,133 @@ def color_refinement_step(viewpoint_cam, gaussians, pipe, background, lambda_dss
         opt.zero_grad(set_to_none=True)
         update_learning_rate(gaussians, iteration)
     return loss
+
+
+def _bounded_refine_ok(gaussians, pipe, viewpoints, background) -> bool:
+    """`refine_bounded` applies: the graph-free iteration (`_direct_refine_ok`), the fused Adam with its gate and its radii line,
+    and frames the binned front end renders (the bounded forward's scope: include/splatraster.h)."""
+    from . import _native
+    from .fused import _view_settings
+    from .rasterizer import _window_compatible
+    opt = gaussians.optimizer
+    if not viewpoints or not _direct_refine_ok(gaussians, pipe) or not (hasattr(opt, "set_gate") and hasattr(opt, "set_radii_update")):
+        return False
+    distinct = list({id(vp): vp for vp in viewpoints}.values())
+    if not _window_compatible([_view_settings(vp, gaussians, background, 1.0) for vp in distinct]):
+        return False
+    vp = viewpoints[0]
+    return _native.bounded_supported(int(gaussians._xyz.shape[0]), 1, int(vp.image_width), int(vp.image_height))
+
+
+def _host_optimizer_state(opt) -> list:
+    """What an Adam step changes on the HOST: every group's learning rate and every parameter's step count."""
+    return [(grp["lr"], [float(opt.state[p]["step"]) if opt.state.get(p) else None for p in grp["params"]])
+            for grp in opt.param_groups]
+
+
+def _restore_host_optimizer_state(opt, snap) -> None:
+    for grp, (lr, steps) in zip(opt.param_groups, snap):
+        grp["lr"] = lr
+        for p, stp in zip(grp["params"], steps):
+            st = opt.state.get(p)
+            if st:      # (a state created by a gated step holds zero moments — what the first real step creates)
+                st["step"].fill_(0.0 if stp is None else stp)
+
+
+def refine_bounded(viewpoints, gaussians, pipe, background, lambda_dssim: float, first_iteration: int, n_iterations: int,
+                   primitive_reg: bool = True, initial_capacity=None) -> dict:
+    """`n_iterations` iterations of `color_refinement_step` (iteration numbers first_iteration, first_iteration + 1, ...; iteration
+    i renders viewpoints[i % len(viewpoints)]) whose forwards do not stop the host for the instance count: every iteration's
+    launches — bounded forward, loss, backward, gated Adam — are enqueued without a wait, so the host runs ahead of the device.
+
+    The frame is rendered into ONE reusable binning buffer of `capacity` instances (rasterizer.BoundedWindow).  Capacity policy:
+    `initial_capacity`, or 1.25 x the R of one ordinary (synchronous) forward of viewpoints[0], at least 4096; after an overflow
+    1.5 x the R that did not fit.  After enqueuing an iteration the loop reads the status block's host mirror (no
+    synchronisation).  A frame that does not fit sets the block's STICKY overflow flag on the device: from that sequence on every
+    forward renders background and every Adam launch returns at once, so no parameter, moment or max_radii2D changes behind
+    it.  When the host sees the flag it synchronises once, grows the buffer, clears the block, restores the host-side step counts
+    and learning rates of iteration `first_tag`, and resumes there — the replay is exact, and the end state is that of the
+    plain loop (bit for bit in the library's deterministic mode).
+
+    Falls back to the loop of `color_refinement_step` calls where the mode does not apply (`_bounded_refine_ok`).
+    Returns {"losses": [loss tensor per iteration], "rewinds": int, "capacity_history": [capacities used], "bounded": bool,
+    "enqueue_seconds": host time until the last iteration was enqueued (replays included; the final wait is not)}."""
+    from .fused import _view_settings
+    from .rasterizer import BoundedWindow, window_forward
+    t_start = t_enqueued = time.perf_counter()
+    viewpoints = list(viewpoints)
+    n_iterations = int(n_iterations)
+    if n_iterations <= 0 or not _bounded_refine_ok(gaussians, pipe, viewpoints, background):
+        losses = [color_refinement_step(viewpoints[i % len(viewpoints)], gaussians, pipe, background, lambda_dssim,
+                                        first_iteration + i, primitive_reg=primitive_reg) for i in range(n_iterations)]
+        return {"losses": losses, "rewinds": 0, "capacity_history": [], "bounded": False, "enqueue_seconds": time.perf_counter() - t_start}
+    dev = gaussians._xyz.device
+    opt = gaussians.optimizer
+    if initial_capacity is None:
+        with torch.no_grad():     # one ordinary forward: its count is this loop's only host wait when every frame fits
+            g = gaussians
+            if _raw_backward_ok(g):
+                raw = (g._scaling.detach(), g._rotation.detach(), g._opacity.detach(), g._features_dc.detach(), g._kp_score.detach())
+                probe = window_forward(g._xyz, None, None, None, None, None, [_view_settings(viewpoints[0], g, background, 1.0)], raw=raw)
+            else:
+                from .fused import activate_forward
+                (sca, rot, opa, col), _act = activate_forward(g._xyz, g._features_dc, g._features_rest, g._scaling, g._rotation,
+                                                              g._opacity, g._kp_score, None, 0)
+                probe = window_forward(g._xyz, col, opa, sca, rot, None, [_view_settings(viewpoints[0], g, background, 1.0)])
+        capacity = max(4096, int(math.ceil(1.25 * sum(probe.R))))
+        del probe
+    else:
+        capacity = int(initial_capacity)
+    bw = BoundedWindow(dev, capacity)
+    history = [capacity]
+    losses, snaps, rewinds = [], {}, 0
+    opt.set_gate(bw.status)
+    try:
+        i = 0
+        while True:
+            if i < n_iterations:
+                snaps[i] = _host_optimizer_state(opt)
+                bw.next_tag = i
+                losses.append(_color_refinement_step_direct(viewpoints[i % len(viewpoints)], gaussians, background, lambda_dssim,
+                                                            first_iteration + i, primitive_reg, bounded=bw))
+                i += 1
+                # ONE read of the mirror, never a wait.  It copies last_tag BEFORE overflow: the sequences in front of
+                # `last_tag` have finished — their stores are all visible — so a clear flag read after it proves that none
+                # of them overflowed, and their snapshots can go.  (The sequence `last_tag` itself may still raise the flag.)
+                rec = bw.status.read()
+                if not rec.overflow:
+                    for k in [k for k in snaps if k < int(rec.last_tag)]:
+                        del snaps[k]
+                    continue
+            else:
+                t_enqueued = time.perf_counter()
+            # the flag was seen, or everything is enqueued: ONE wait, and only the record read BEHIND it is acted on — a flag
+            # seen in front of it is a hint (the mirror may lag the stream)
+            torch.cuda.synchronize(dev)
+            rec = bw.status.read()
+            if not rec.overflow:
+                if i >= n_iterations:
+                    break
+                continue
+            k, need = int(rec.first_tag), int(rec.first_total)
+            if k not in snaps or need <= capacity:
+                raise RuntimeError(f"refine_bounded: inconsistent overflow record (tag {k}, total {need}, capacity {capacity})")
+            capacity = max(int(math.ceil(1.5 * need)), capacity + 1)
+            bw.capacity = capacity
+            history.append(capacity)
+            rewinds += 1
+            bw.status.clear()      # (the stream is idle: the mirror reads clear from here on)
+            _restore_host_optimizer_state(opt, snaps[k])
+            del losses[k:]
+            for j in [j for j in snaps if j > k]:
+                del snaps[j]
+            i = k
+    finally:
+        opt.set_gate(None)
+        torch.cuda.synchronize(dev)
+        bw.close()
+    return {"losses": losses, "rewinds": rewinds, "capacity_history": history, "bounded": True,
+            "enqueue_seconds": t_enqueued - t_start}
 
 
 def _cameras_require_grad(settings) -> bool:

@@ -34,6 +34,7 @@ WHAT = [   # (file name regex, description; {placeholders} are filled by the ext
     (r"^pnp_time\.json$", "absolute pose (`solve_pose`: P3P LO-RANSAC + Cauchy refinement) on planted scenes, HIP events (`tools/pnp_time.py`): {pnp}"),
     (r"^localize_time\.json$", "localisation (`tools/localize_time.py`), HIP events, interleaved medians: fused retrieval against `torch.einsum(...).topk` and the batched `Localizer.localize` against the per-query loop: {localize}"),
     (r"^pose_window_time\.json$", "pose refinement of 8 query frames at 640x480, `pose.refine_poses` per `window` against the loop of 8 `pose.refine_pose` calls, ms per frame-iteration, host clock around a device synchronise, alternating regions (`tools/pose_window_time.py`): {posewindow}"),
+    (r"^refine_bounded_time\.json$", "`training.refine_bounded` (no host wait for the instance count) against this tree's plain loop of `color_refinement_step` calls (not a build of the parent commit), us per iteration, host clock around a device synchronise, interleaved regions in one process (`tools/refine_bounded_time.py`): {refinebounded}"),
     (r"^joint_window_time\.json$", "one backward of a 5-view window that returns parameter AND camera gradients, ms per backward, host clock around a device synchronise, alternating regions (`tools/joint_window_time.py`): {jointwindow}"),
     (r"^matching_time\.json$", "2D-3D matching (`hungarian_solve` cost + exact assignment, batched solver, frustum candidates) against torch-CPU + scipy on the same host, HIP events (`tools/matching_time.py`): {matching}"),
     (r"^landmark_selection_time\.json$", "landmark selection (`gaussian_selectition`) at Replica scale on a synthetic room, HIP events per stage (`tools/landmark_selection_time.py`): {landmark}"),
@@ -259,6 +260,21 @@ def jointwindow(path):
     return "; ".join(parts)
 
 
+def refinebounded(path):
+    j = _load(path) or {}
+    if not j.get("shapes"):
+        return str(j.get("status", "(no rows)"))
+    parts = []
+    for r in j["shapes"]:
+        d = r["paired_plain_minus_bounded_us"]
+        parts.append(f"{r['shape']} (P = {r['P']}): plain {r['plain']['wall_us_per_iteration']:.1f} wall / {r['plain']['host_enqueue_us_per_iteration']:.1f} host / "
+                     f"{r['plain']['kernel_us_per_iteration_torch_profiler']:.1f} kernels, bounded {r['bounded']['wall_us_per_iteration']:.1f} / "
+                     f"{r['bounded']['host_enqueue_us_per_iteration']:.1f} / {r['bounded']['kernel_us_per_iteration_torch_profiler']:.1f}; paired plain - bounded "
+                     f"{d['mean']:+.1f} us (2 s.e. {d['two_standard_errors']:.1f}), faster beyond the spread: {r['bounded_faster_beyond_paired_spread']}, "
+                     f"rewinds {r['rewinds_in_timed_regions']}")
+    return "; ".join(parts)
+
+
 def posewindow(path):
     j = _load(path) or {}
     if not j.get("results"):
@@ -366,7 +382,7 @@ def fe_ab(path):
             f"{c['payload_ms']['change']:.4f} ms ({', '.join(f'{k} {v:.4f}' for k, v in c['payload_ms_of_band_variants'].items())})")
 
 
-EXTRACT = {"pc_kstats": pc_kstats, "pc_pmc": pc_pmc, "pc_ab": pc_ab, "fe_kstats": fe_kstats, "fe_pmc": fe_pmc, "fe_ab": fe_ab, "setup_pmc": setup_pmc, "kstats2": kstats2, "setup_ab": setup_ab, "scenelists": scenelists, "scene": scene, "ab": ab, "perview": perview, "mapidle": mapidle, "rccl": rccl, "kstats": kstats, "hbm": hbm, "sq": sq, "timeline": timeline, "bench": bench, "clocks": clocks, "gradbars": gradbars, "idle": idle, "landmark": landmark, "matching": matching, "pnp": pnp, "decoder": decoder, "fusion": fusion, "localize": localize, "jointwindow": jointwindow, "posewindow": posewindow}
+EXTRACT = {"pc_kstats": pc_kstats, "pc_pmc": pc_pmc, "pc_ab": pc_ab, "fe_kstats": fe_kstats, "fe_pmc": fe_pmc, "fe_ab": fe_ab, "setup_pmc": setup_pmc, "kstats2": kstats2, "setup_ab": setup_ab, "scenelists": scenelists, "scene": scene, "ab": ab, "perview": perview, "mapidle": mapidle, "rccl": rccl, "kstats": kstats, "hbm": hbm, "sq": sq, "timeline": timeline, "bench": bench, "clocks": clocks, "gradbars": gradbars, "idle": idle, "landmark": landmark, "matching": matching, "pnp": pnp, "decoder": decoder, "fusion": fusion, "localize": localize, "jointwindow": jointwindow, "posewindow": posewindow, "refinebounded": refinebounded}
 
 
 def describe(name, path):
