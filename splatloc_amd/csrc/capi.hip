@@ -773,6 +773,35 @@ static int window_backward(const splatraster_settings* s, int32_t V, const splat
                                  b.pose_acc, stream, raw);
 }
 
+// R of a window: the sum of the per-view instance counts its geometry stage returned
+static int window_instances(int32_t V, const int64_t* num_rendered, int64_t* R)
+{
+    if (!num_rendered || V < 1 || V > MAX_VIEWS) return SPLATRASTER_ERR_BAD_ARG;
+    *R = 0;
+    for (int v = 0; v < V; ++v) {
+        if (num_rendered[v] < 0) return SPLATRASTER_ERR_BAD_ARG;
+        *R += num_rendered[v];
+    }
+    return SPLATRASTER_OK;
+}
+
+// What splatraster_backward_window_cameras and _joint check first: the window, then P, the workspace, the camera outputs and the
+// counts (summed into *R).  P == 0 leaves nothing to differentiate, but the camera gradients are still defined: zero, filled here.
+static int camera_window_begin(const splatraster_settings* s, int32_t V, const splatraster_window_view* views, int32_t P,
+                               const int64_t* num_rendered, const void* workspace, float* dL_dviewmatrix, float* dL_dprojmatrix,
+                               float* dL_dcampos, hipStream_t stream, int64_t* R)
+{
+    int st = check_window(s, V, views);
+    if (st) return st;
+    if (P < 0 || !workspace || !dL_dviewmatrix || !dL_dprojmatrix || window_instances(V, num_rendered, R)) return SPLATRASTER_ERR_BAD_ARG;
+    if (P == 0) {
+        SR_HIP_CHECK(hipMemsetAsync(dL_dviewmatrix, 0, 16 * sizeof(float) * (size_t)V, stream));
+        SR_HIP_CHECK(hipMemsetAsync(dL_dprojmatrix, 0, 16 * sizeof(float) * (size_t)V, stream));
+        if (dL_dcampos) SR_HIP_CHECK(hipMemsetAsync(dL_dcampos, 0, 3 * sizeof(float) * (size_t)V, stream));
+    }
+    return SPLATRASTER_OK;
+}
+
 }  // namespace sr
 
 extern "C" {
@@ -842,12 +871,8 @@ int splatraster_forward_window_render(const splatraster_settings* s, int32_t n_v
                                       int32_t P, const int64_t* num_rendered, const float* bg, const float* colors_precomp,
                                       void* geometry, void* binning, void* image, void* stream)
 {
-    if (!num_rendered || n_views < 1 || n_views > MAX_VIEWS) return SPLATRASTER_ERR_BAD_ARG;
-    int64_t R = 0;
-    for (int v = 0; v < n_views; ++v) {
-        if (num_rendered[v] < 0) return SPLATRASTER_ERR_BAD_ARG;
-        R += num_rendered[v];
-    }
+    int64_t R;
+    if (window_instances(n_views, num_rendered, &R)) return SPLATRASTER_ERR_BAD_ARG;
     return window_render(s, n_views, views, P, R, bg, colors_precomp, geometry, binning, image,
                          reinterpret_cast<hipStream_t>(stream));
 }
@@ -858,12 +883,8 @@ int splatraster_backward_window(const splatraster_settings* s, int32_t n_views, 
                                 const void* binning, const void* image, float* dL_dmeans3D, float* dL_dcolors,
                                 float* dL_dopacities, float* dL_dscales, float* dL_drotations, float* dL_dcov3D, void* stream)
 {
-    if (!num_rendered || n_views < 1 || n_views > MAX_VIEWS) return SPLATRASTER_ERR_BAD_ARG;
-    int64_t R = 0;
-    for (int v = 0; v < n_views; ++v) {
-        if (num_rendered[v] < 0) return SPLATRASTER_ERR_BAD_ARG;
-        R += num_rendered[v];
-    }
+    int64_t R;
+    if (window_instances(n_views, num_rendered, &R)) return SPLATRASTER_ERR_BAD_ARG;
     return window_backward(s, n_views, views, P, R, bg, means3D, nullptr, colors_precomp, scales, rotations, cov3D_precomp,
                            geometry, binning, image, dL_dmeans3D, dL_dcolors, dL_dopacities, dL_dscales, dL_drotations,
                            dL_dcov3D, nullptr, nullptr, nullptr, nullptr, reinterpret_cast<hipStream_t>(stream));
@@ -882,21 +903,10 @@ int splatraster_backward_window_cameras(const splatraster_settings* s, int32_t n
                                         void* stream_)
 {
     const int32_t V = n_views;
-    int st = check_window(s, V, views);
-    if (st) return st;
-    if (P < 0 || !num_rendered || !workspace || !dL_dviewmatrix || !dL_dprojmatrix) return SPLATRASTER_ERR_BAD_ARG;
-    int64_t R = 0;
-    for (int v = 0; v < V; ++v) {
-        if (num_rendered[v] < 0) return SPLATRASTER_ERR_BAD_ARG;
-        R += num_rendered[v];
-    }
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    if (P == 0) {   // nothing to differentiate: the camera gradients are still defined (zero)
-        SR_HIP_CHECK(hipMemsetAsync(dL_dviewmatrix, 0, 16 * sizeof(float) * (size_t)V, stream));
-        SR_HIP_CHECK(hipMemsetAsync(dL_dprojmatrix, 0, 16 * sizeof(float) * (size_t)V, stream));
-        if (dL_dcampos) SR_HIP_CHECK(hipMemsetAsync(dL_dcampos, 0, 3 * sizeof(float) * (size_t)V, stream));
-        return SPLATRASTER_OK;
-    }
+    int64_t R;
+    int st = camera_window_begin(s, V, views, P, num_rendered, workspace, dL_dviewmatrix, dL_dprojmatrix, dL_dcampos, stream, &R);
+    if (st || P == 0) return st;
     if (!means3D || !colors_precomp || !geometry || !binning || !image) return SPLATRASTER_ERR_BAD_ARG;
     if (cov3D_precomp ? (scales || rotations) : (!scales || !rotations)) return SPLATRASTER_ERR_BAD_ARG;
     for (int v = 0; v < V; ++v)     // (dL_dmeans2D is not written here and may be NULL)
@@ -922,21 +932,10 @@ int splatraster_backward_window_joint(const splatraster_settings* s, int32_t n_v
                                       float* dL_dprojmatrix, float* dL_dcampos, void* stream_)
 {
     const int32_t V = n_views;
-    int st = check_window(s, V, views);
-    if (st) return st;
-    if (P < 0 || !num_rendered || !workspace || !dL_dviewmatrix || !dL_dprojmatrix) return SPLATRASTER_ERR_BAD_ARG;
-    int64_t R = 0;
-    for (int v = 0; v < V; ++v) {
-        if (num_rendered[v] < 0) return SPLATRASTER_ERR_BAD_ARG;
-        R += num_rendered[v];
-    }
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    if (P == 0) {   // nothing to differentiate: the camera gradients are still defined (zero)
-        SR_HIP_CHECK(hipMemsetAsync(dL_dviewmatrix, 0, 16 * sizeof(float) * (size_t)V, stream));
-        SR_HIP_CHECK(hipMemsetAsync(dL_dprojmatrix, 0, 16 * sizeof(float) * (size_t)V, stream));
-        if (dL_dcampos) SR_HIP_CHECK(hipMemsetAsync(dL_dcampos, 0, 3 * sizeof(float) * (size_t)V, stream));
-        return SPLATRASTER_OK;
-    }
+    int64_t R;
+    int st = camera_window_begin(s, V, views, P, num_rendered, workspace, dL_dviewmatrix, dL_dprojmatrix, dL_dcampos, stream, &R);
+    if (st || P == 0) return st;
     if (!means3D || !colors_precomp || !geometry || !binning || !image || !dL_dmeans3D || !dL_dcolors || !dL_dopacities)
         return SPLATRASTER_ERR_BAD_ARG;
     if (cov3D_precomp ? (scales || rotations || !dL_dcov3D) : (!scales || !rotations || !dL_dscales || !dL_drotations))
@@ -1027,12 +1026,8 @@ int splatraster_backward_window_raw(const splatraster_settings* s, int32_t n_vie
                                     const void* binning, const void* image, const splatraster_raw_params* rp, float* dL_dmeans3D,
                                     void* stream)
 {
-    if (!num_rendered || n_views < 1 || n_views > MAX_VIEWS || !rp) return SPLATRASTER_ERR_BAD_ARG;
-    int64_t R = 0;
-    for (int v = 0; v < n_views; ++v) {
-        if (num_rendered[v] < 0) return SPLATRASTER_ERR_BAD_ARG;
-        R += num_rendered[v];
-    }
+    int64_t R;
+    if (window_instances(n_views, num_rendered, &R) || !rp) return SPLATRASTER_ERR_BAD_ARG;
     if (rp->reg_row_grad && !rp->reg_out) return SPLATRASTER_ERR_BAD_ARG;
     const RawBwd raw{rp->scaling, rp->rotation, rp->opacity, rp->f_dc, rp->extra_channels, rp->dL_dscaling, rp->dL_drotation,
                      rp->dL_dopacity, rp->dL_df_dc, rp->dL_dextra, rp->reg_row_grad, rp->reg_out, rp->reg_weight};

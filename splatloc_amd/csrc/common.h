@@ -185,8 +185,8 @@ int launch_preprocess_bwd(const splatraster_settings& s, int32_t P, int32_t V, c
                           float* dL_dview /*[16] or null; V == 1 only*/, float* dL_dproj, float* dL_dcampos,
                           float* pose_acc /*BinView::pose_acc, zeroed by the caller; needed with dL_dview*/, hipStream_t stream,
                           const RawBwd* raw = nullptr);
-// camera gradients of the V views of a window and nothing per Gaussian (camera_bwd.hip): reads what preprocess_bwd_kernel<true>
-// reads of every (view, Gaussian) row; `ws`: V times (POSE_SETS sets + the ticket line), zeroed by the caller on the stream;
+// camera gradients of the V views of a window and nothing per Gaussian (camera_bwd.hip; the arithmetic is projection_bwd.h's, as in
+// the two launches around it): reads what preprocess_bwd_kernel<true> reads of every (view, Gaussian) row; `ws`: V times (POSE_SETS sets + the ticket line), zeroed by the caller on the stream;
 // dL_dview / dL_dproj [V,16] and dL_dcampos [V,3] (or null) are written in full by the last block of every view
 int launch_camera_bwd(const splatraster_settings& s, int32_t P, int32_t V, const WinCams& cams, const float* means3D,
                       const float* scales, const float* rotations, const float* cov3D_precomp, const float4* rec,
@@ -302,6 +302,7 @@ static inline int padded_channels(int C) { return (C + 3) & ~3; }
 // sixteen 256-byte lines instead of 27 words every block hits), the LAST block to finish (ticket) sums the sets and writes the outputs
 constexpr int POSE_SETS = 16, POSE_SET_FLOATS = 64;
 constexpr size_t POSE_ACC_BYTES = (size_t)POSE_SETS * POSE_SET_FLOATS * sizeof(float) + 256;   // + the ticket's own line
+constexpr int POSE_ACC_FLOATS = (int)(POSE_ACC_BYTES / sizeof(float));      // a window's workspace: one such slice per view
 __host__ __device__ constexpr int gacc_moment_offset(int C) { return ((C & 15) + 7 <= 16) ? C : ((C + 15) & ~15); }
 __host__ __device__ constexpr int gacc_row_floats(int C) { return (gacc_moment_offset(C) + 7 + 15) & ~15; }
 // Where the columns [0, gacc_row_floats(C)) of such a row live.  The feature table is shared by the views of a window, so the only

@@ -444,6 +444,40 @@ def window_outputs(f, head: int = 0) -> list:
     return [(f.color[v], f.depth[v], f.alpha[v], f.radii[v]) for v in range(f.V)]
 
 
+def _window_grad_views(f, grads, head: int = 0, m2: Optional[torch.Tensor] = None):
+    """`_window_views(f)` with the gradient planes of a backward filled in.  `grads`: per view (g_color, g_last, g_depth,
+    g_alpha), None for an output that did not reach the loss — the colour plane is then ONE shared plane of zeros; `m2`
+    [V,P,3]: where dL/dmeans2D goes.  Returns the array and the tensors that must outlive the call."""
+    dev, st = f.dev, f.st
+    views = _window_views(f)
+    keep = []
+    zeros_color = None
+    for v, (g_color, g_last, g_depth, g_alpha) in enumerate(grads):
+        g_color, g_last, g_depth, g_alpha = (_prep(g, dev) for g in (g_color, g_last, g_depth, g_alpha))
+        if g_color is None:     # this view's colour buffer did not reach the loss
+            if zeros_color is None:
+                zeros_color = torch.zeros((st.channels, st.image_height, st.image_width), dtype=torch.float32, device=dev)
+            g_color = zeros_color
+        keep += [g_color, g_depth, g_alpha, g_last]
+        w = views[v]
+        w.dL_dout_color = g_color.data_ptr()
+        w.dL_dout_depth = None if g_depth is None else g_depth.data_ptr()
+        w.dL_dout_alpha = None if g_alpha is None else g_alpha.data_ptr()
+        w.dL_dmeans2D = m2[v].data_ptr() if m2 is not None and f.P else None
+        w.dL_dout_last = None if g_last is None else g_last.data_ptr()
+        w.color_grad_channels = head
+    return views, keep
+
+
+def _camera_workspace(lib, V: int, dev, workspace: Optional[torch.Tensor]) -> torch.Tensor:
+    """The sets and tickets of the camera reduction of V views: the caller's tensor, checked, or a new one."""
+    nws = lib.splatraster_window_camera_workspace_bytes(V)
+    if workspace is None:
+        workspace = torch.empty((nws,), dtype=torch.uint8, device=dev)
+    assert workspace.numel() >= nws
+    return workspace
+
+
 def window_backward(f, grads, head: int = 0, grad_span: Optional[list] = None, raw=None, reg=None, cameras: bool = False,
                     workspace: Optional[torch.Tensor] = None) -> dict:
     """ONE backward for the views of `window_forward`'s frame `f`.  `grads`: per view (g_color, g_last, g_depth, g_alpha) of
@@ -470,32 +504,11 @@ def window_backward(f, grads, head: int = 0, grad_span: Optional[list] = None, r
         # AccumulateGrad would then deep-copy them instead of keeping them as the parameters' .grad
         grad_span.append({"flat": d["flat"], "tail": d["tail"]})
     d["m2"] = torch.empty((V, P, 3), **f32)
-    views = _window_views(f)
-    keep = []
-    zeros_color = None
-    for v, (g_color, g_last, g_depth, g_alpha) in enumerate(grads):
-        g_last = _prep(g_last, dev)
-        g_color = _prep(g_color, dev)
-        if g_color is None:     # this view's colour buffer did not reach the loss
-            if zeros_color is None:
-                zeros_color = torch.zeros((Cn, st.image_height, st.image_width), **f32)
-            g_color = zeros_color
-        g_depth, g_alpha = _prep(g_depth, dev), _prep(g_alpha, dev)
-        keep += [g_color, g_depth, g_alpha, g_last]
-        w = views[v]
-        w.dL_dout_color = g_color.data_ptr()
-        w.dL_dout_depth = None if g_depth is None else g_depth.data_ptr()
-        w.dL_dout_alpha = None if g_alpha is None else g_alpha.data_ptr()
-        w.dL_dmeans2D = d["m2"][v].data_ptr() if P else None
-        w.dL_dout_last = None if g_last is None else g_last.data_ptr()
-        w.color_grad_channels = head
+    views, keep = _window_grad_views(f, grads, head, d["m2"])
     R = _layout_counts(f)
     if cameras:
         d["view"], d["proj"], d["campos"] = (torch.empty(shp, **f32) for shp in ((V, 4, 4), (V, 4, 4), (V, 3)))
-        nws = lib.splatraster_window_camera_workspace_bytes(V)
-        if workspace is None:
-            workspace = torch.empty((nws,), dtype=torch.uint8, device=dev)
-        assert workspace.numel() >= nws
+        workspace = _camera_workspace(lib, V, dev, workspace)
         with _on_device(dev):
             _native.check(lib.splatraster_backward_window_joint(
                 C.byref(st), V, views, P, R, _ptr(f.bg), _ptr(f.m3), _ptr(f.col), _ptr(f.sca), _ptr(f.rot), _ptr(f.cov),
@@ -544,26 +557,9 @@ def window_backward_cameras(f, grads, workspace: Optional[torch.Tensor] = None, 
     f32 = dict(dtype=torch.float32, device=dev)
     d = out if out is not None else {"view": torch.empty((V, 4, 4), **f32), "proj": torch.empty((V, 4, 4), **f32),
                                      "campos": torch.empty((V, 3), **f32)}
-    nws = lib.splatraster_window_camera_workspace_bytes(V)
-    if workspace is None:
-        workspace = torch.empty((nws,), dtype=torch.uint8, device=dev)
-    assert workspace.numel() >= nws and all(tuple(d[k].shape) == shp for k, shp in (("view", (V, 4, 4)), ("proj", (V, 4, 4)),
-                                                                                   ("campos", (V, 3))))
-    views = _window_views(f)
-    keep = []
-    zeros_color = None
-    for v, (g_color, g_depth, g_alpha) in enumerate(grads):
-        g_color = _prep(g_color, dev)
-        if g_color is None:     # this view's colour buffer did not reach the loss
-            if zeros_color is None:
-                zeros_color = torch.zeros((st.channels, st.image_height, st.image_width), **f32)
-            g_color = zeros_color
-        g_depth, g_alpha = _prep(g_depth, dev), _prep(g_alpha, dev)
-        keep += [g_color, g_depth, g_alpha]
-        w = views[v]
-        w.dL_dout_color = g_color.data_ptr()
-        w.dL_dout_depth = None if g_depth is None else g_depth.data_ptr()
-        w.dL_dout_alpha = None if g_alpha is None else g_alpha.data_ptr()
+    workspace = _camera_workspace(lib, V, dev, workspace)
+    assert all(tuple(d[k].shape) == shp for k, shp in (("view", (V, 4, 4)), ("proj", (V, 4, 4)), ("campos", (V, 3))))
+    views, keep = _window_grad_views(f, [(g_color, None, g_depth, g_alpha) for g_color, g_depth, g_alpha in grads])
     R = _layout_counts(f)
     with _on_device(dev):
         _native.check(lib.splatraster_backward_window_cameras(

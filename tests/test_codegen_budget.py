@@ -69,3 +69,24 @@ def test_backward_kernels_stay_within_their_register_budget():
     assert ref["ScratchSize"] == 0 and ref["Occupancy"] >= 5, ref
     refine = _kernel(u, "_ZN2sr20composite_bwd_kernelILi3ELb0ELb0ELb0E")       # color_refinement: 3 channels, no depth / alpha terms
     assert refine["ScratchSize"] == 0 and refine["Occupancy"] == 8, refine
+
+
+def test_per_gaussian_backward_kernels_keep_their_occupancy():
+    """The three kernels built from projection_bwd.h (HISTORY.md §19): nothing in scratch, the camera reduction's LDS allocated
+    once per kernel (s_pose[4][32] + s_last), and no instantiation below the waves per SIMD it had with its own copy of the
+    derivative.  window_joint_bwd_kernel<4> sits two registers under its boundary (166 of 168): the occupancy assertion is
+    what holds it there."""
+    pre, cam, joint = _usage("preprocess_bwd.hip"), _usage("camera_bwd.hip"), _usage("window_joint_bwd.hip")
+    for u in (pre, cam, joint):
+        for name, k in u.items():
+            assert k["ScratchSize"] == 0 and k["VGPRs Spill"] == 0, (name, k)
+    # preprocess_bwd_kernel<POSE, RAW, TQ>
+    occ = {(0, 1, 0): 3, (1, 0, 4): 2, (1, 0, 1): 2, (1, 0, 0): 3, (0, 0, 4): 2, (0, 0, 1): 3, (0, 0, 0): 3}
+    for (pose, raw, tq), waves in occ.items():
+        k = _kernel(pre, f"_ZN2sr21preprocess_bwd_kernelILb{pose}ELb{raw}ELi{tq}EE")
+        assert k["Occupancy"] >= waves and k["LDS Size"] == (516 if pose else 0), ((pose, raw, tq), k)
+    for tq in (4, 1, 0):
+        k = _kernel(joint, f"_ZN2sr23window_joint_bwd_kernelILi{tq}EE")
+        assert k["Occupancy"] >= 3 and k["LDS Size"] == 516, (tq, k)
+    k = _kernel(cam, "_ZN2sr17camera_bwd_kernelE")
+    assert k["Occupancy"] >= 8 and k["LDS Size"] == 516, k

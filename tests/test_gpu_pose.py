@@ -35,18 +35,31 @@ def _camera_tensors(cam, R, t):
     return view, proj, campos
 
 
-@pytest.mark.parametrize("use_sh", [False, True])
-def test_pose_gradients_match_oracle(use_sh):
+# the last three: instantiations of the per-view kernel with camera gradients that nothing else reaches — a colour tail of
+# three columns (C = 35) and of more than four (C = 40) behind the shared table, a precomputed covariance; their parameter
+# gradients are checked as well (the same kernel writes them behind the camera sums)
+@pytest.mark.parametrize("use_sh,C,seed,use_cov", [
+    pytest.param(False, 4, 70, False, id="False"), pytest.param(True, 3, 71, False, id="True"),
+    pytest.param(False, 35, 110, False, id="C35"), pytest.param(False, 40, 105, False, id="C40"),
+    pytest.param(False, 4, 74, True, id="cov3D")])
+def test_pose_gradients_match_oracle(use_sh, C, seed, use_cov):
     from splatloc_amd import GaussianRasterizationSettings, GaussianRasterizer
     dev = torch.device("cuda:0")
-    C = 3 if use_sh else 4
-    sc = make_scene(3000, 256, 192, C, 70 + int(use_sh), scale_median=0.03)
+    with_params = C > 4 or use_cov
+    sc = make_scene(3000, 256, 192, C, seed, scale_median=0.03)
     ang = 0.15
     R = torch.tensor([[np.cos(ang), 0, np.sin(ang)], [0, 1, 0], [-np.sin(ang), 0, np.cos(ang)]], dtype=torch.float32)
     sc.camera = PinholeCamera(256, 192, 128.0, 128.0, 127.5 + 0.4, 95.5 - 0.2, R, torch.tensor([0.05, -0.03, 0.2]))
     g = torch.Generator().manual_seed(3)
     shs = 0.5 * torch.randn(3000, 16, 3, generator=g) if use_sh else None
+    cov = None
+    if use_cov:     # a seeded L L^T, as tests/test_gpu_window_joint.py builds it
+        Lm = torch.randn(3000, 3, 3, generator=torch.Generator().manual_seed(5)) * 0.03
+        S = Lm @ Lm.transpose(1, 2)
+        cov = torch.stack([S[:, 0, 0], S[:, 0, 1], S[:, 0, 2], S[:, 1, 1], S[:, 1, 2], S[:, 2, 2]], 1).contiguous()
     kw = dict(sh_degree=2, colors_precomp=None, shs=shs.numpy()) if use_sh else {}
+    if use_cov:
+        kw = dict(scales=None, rotations=None, cov3D_precomp=cov.numpy())
     f = oracle_forward(sc, **kw)
     b = oracle_backward(f, sc)
     cam = sc.camera
@@ -56,11 +69,15 @@ def test_pose_gradients_match_oracle(use_sh):
     rs = GaussianRasterizationSettings(192, 256, cam.tanfovx, cam.tanfovy, sc.bg.to(dev), 1.0, view, proj,
                                        2 if use_sh else 0, campos, False, False)
     t = lambda x: x.to(dev)  # noqa: E731
-    color, depth, alpha, radii = GaussianRasterizer(raster_settings=rs)(
-        means3D=t(sc.means3D), means2D=torch.zeros(3000, 3, device=dev), shs=t(shs) if use_sh else None,
-        colors_precomp=None if use_sh else t(sc.features), opacities=t(sc.opacities), scales=t(sc.scales),
-        rotations=t(sc.rotations), cov3D_precomp=None)
+    leaf = lambda x: x.to(dev).clone().requires_grad_(with_params)  # noqa: E731
+    inp = dict(means3D=leaf(sc.means3D), means2D=leaf(torch.zeros(3000, 3)), opacities=leaf(sc.opacities),
+               colors_precomp=None if use_sh else leaf(sc.features), scales=None if use_cov else leaf(sc.scales),
+               rotations=None if use_cov else leaf(sc.rotations), cov3D_precomp=leaf(cov) if use_cov else None)
+    color, depth, alpha, radii = GaussianRasterizer(raster_settings=rs)(shs=t(shs) if use_sh else None, **inp)
     ((color * t(sc.dL_dcolor)).sum() + (depth * t(sc.dL_ddepth)).sum() + (alpha * t(sc.dL_dalpha)).sum()).backward()
+    if with_params:
+        assert int(color.grad_fn.num_rendered) == f["num_rendered"]
+        assert float(np.abs(b["dL_dviewmatrix"]).max()) > 0 and float(np.abs(b["dL_dprojmatrix"]).max()) > 0
     assert_grad_close("dL_dviewmatrix", view.grad.cpu().numpy(), b["dL_dviewmatrix"], rtol=3e-3, atol_scale=3e-4)
     assert_grad_close("dL_dprojmatrix", proj.grad.cpu().numpy(), b["dL_dprojmatrix"], rtol=3e-3, atol_scale=3e-4)
     if use_sh:
@@ -68,6 +85,15 @@ def test_pose_gradients_match_oracle(use_sh):
         assert float(np.abs(b["dL_dcampos"]).max()) > 0
     else:
         assert campos.grad is None or float(campos.grad.abs().max()) == 0.0
+    if with_params:
+        for name, ref in (("means3D", "dL_dmeans3D"), ("means2D", "dL_dmeans2D"), ("opacities", "dL_dopacities"),
+                          ("colors_precomp", "dL_dcolors"), ("scales", "dL_dscales"), ("rotations", "dL_drotations"),
+                          ("cov3D_precomp", "dL_dcov3D")):
+            if inp[name] is None:
+                assert b[ref] is None
+                continue
+            assert float(np.abs(b[ref]).max()) > 0, ref
+            assert_grad_close(ref, inp[name].grad.cpu().numpy(), b[ref])
 
 
 def test_pose_refinement_converges():
