@@ -123,21 +123,19 @@ emit_kernel(int64_t R, int P /*rows: V * P*/, int Pv /*Gaussians per view*/, int
     }
 }
 
-int launch_emit(const splatraster_settings& s, int32_t P, int32_t V, int64_t R, const GeomView& g, uint32_t* keys,
-                uint32_t* vals, uint32_t* ranges, uint32_t nranges, hipStream_t stream, bool keys16)
+int launch_emit(const FramePlan& p, int64_t R, const GeomView& g, uint32_t* keys, uint32_t* vals, uint32_t* ranges,
+                uint32_t nranges, hipStream_t stream, bool keys16)
 {
     if (R == 0) return SPLATRASTER_OK;
     const int64_t blocks = (R + EMIT_SPAN - 1) / EMIT_SPAN;
-    const int n = P * V;
-    const int tiles = ((s.image_width + TILE - 1) / TILE) * ((s.image_height + TILE - 1) / TILE);
+    const int n = p.P * p.V;
     const uint32_t* owner = scan_state_bytes(n) ? g.span_owner : nullptr;
     if (keys16)   // [R] uint16_t in the first half of the [R] uint32_t array
-        hipLaunchKernelGGL(emit_kernel<uint16_t>, dim3((unsigned)blocks), dim3(EMIT_BLOCK), 0, stream, R, n, P, tiles, s.image_width,
-                           s.image_height, g.offsets, g.depth_order, g.rec, reinterpret_cast<uint16_t*>(keys), vals, owner, ranges,
-                           nranges);
+        hipLaunchKernelGGL(emit_kernel<uint16_t>, dim3((unsigned)blocks), dim3(EMIT_BLOCK), 0, stream, R, n, p.P, p.tiles, p.W, p.H,
+                           g.offsets, g.depth_order, g.rec, reinterpret_cast<uint16_t*>(keys), vals, owner, ranges, nranges);
     else
-        hipLaunchKernelGGL(emit_kernel<uint32_t>, dim3((unsigned)blocks), dim3(EMIT_BLOCK), 0, stream, R, n, P, tiles, s.image_width,
-                           s.image_height, g.offsets, g.depth_order, g.rec, keys, vals, owner, ranges, nranges);
+        hipLaunchKernelGGL(emit_kernel<uint32_t>, dim3((unsigned)blocks), dim3(EMIT_BLOCK), 0, stream, R, n, p.P, p.tiles, p.W, p.H,
+                           g.offsets, g.depth_order, g.rec, keys, vals, owner, ranges, nranges);
     SR_LAUNCH_CHECK();
     return SPLATRASTER_OK;
 }
@@ -197,15 +195,14 @@ payload_kernel(int64_t R, int gx, int tiles_per_view, int V, const uint32_t* __r
     if (j == R - 1 || tile_list[j + 1] != t) ranges[2 * t + 1] = (uint32_t)(j + 1);
 }
 
-int launch_payload(const splatraster_settings& s, int32_t V, int64_t R, const GeomView& g, const BinView& b, hipStream_t stream)
+int launch_payload(const FramePlan& p, int64_t R, const GeomView& g, const BinView& b, hipStream_t stream)
 {
     if (R == 0) return SPLATRASTER_OK;
-    const int gx = (s.image_width + TILE - 1) / TILE, gy = (s.image_height + TILE - 1) / TILE;
     if (R >= g_payload_stream_min)
-        hipLaunchKernelGGL(payload_kernel<true>, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, stream, R, gx, gx * gy, V,
+        hipLaunchKernelGGL(payload_kernel<true>, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, stream, R, p.gx, p.tiles, p.V,
                            b.point_list, b.tile_list, g.rec, b.irec, b.ipack, b.ranges);
     else
-        hipLaunchKernelGGL(payload_kernel<false>, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, stream, R, gx, gx * gy, V,
+        hipLaunchKernelGGL(payload_kernel<false>, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, stream, R, p.gx, p.tiles, p.V,
                            b.point_list, b.tile_list, g.rec, b.irec, b.ipack, b.ranges);
     SR_LAUNCH_CHECK();
     return SPLATRASTER_OK;
@@ -295,20 +292,18 @@ payload_tile_kernel(int gx, int tiles_per_view, const uint32_t* __restrict__ ran
     }
 }
 
-int launch_payload_compact(const splatraster_settings& s, int32_t V, int64_t R, const GeomView& g, const BinView& b,
-                           uint32_t* cranges, hipStream_t stream)
+int launch_payload_compact(const FramePlan& p, int64_t R, const GeomView& g, const BinView& b, uint32_t* cranges, hipStream_t stream)
 {
-    const int gx = (s.image_width + TILE - 1) / TILE, gy = (s.image_height + TILE - 1) / TILE;
-    const unsigned lists = (unsigned)(V * gx * gy);
+    const unsigned lists = (unsigned)p.gtiles;
     if (R > 0) {   // (R == 0: the table was cleared, every compact range is [0, 0) too)
         hipLaunchKernelGGL(ranges_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, stream, R, b.tile_list, b.ranges);
         SR_LAUNCH_CHECK();
     }
     if (R >= g_payload_stream_min)
-        hipLaunchKernelGGL(payload_tile_kernel<true>, dim3(lists), dim3(256), 0, stream, gx, gx * gy, b.ranges, b.point_list, g.rec,
+        hipLaunchKernelGGL(payload_tile_kernel<true>, dim3(lists), dim3(256), 0, stream, p.gx, p.tiles, b.ranges, b.point_list, g.rec,
                            b.irec, b.ipack, cranges);
     else
-        hipLaunchKernelGGL(payload_tile_kernel<false>, dim3(lists), dim3(256), 0, stream, gx, gx * gy, b.ranges, b.point_list, g.rec,
+        hipLaunchKernelGGL(payload_tile_kernel<false>, dim3(lists), dim3(256), 0, stream, p.gx, p.tiles, b.ranges, b.point_list, g.rec,
                            b.irec, b.ipack, cranges);
     SR_LAUNCH_CHECK();
     return SPLATRASTER_OK;
@@ -319,7 +314,7 @@ int launch_payload_compact(const splatraster_settings& s, int32_t V, int64_t R, 
 // waits for the longest of them (measured life times, list-scheduling model: 412 us in tile order, 363 us longest first,
 // 338 us ideal).  One small block buckets the (view, tile) lists by length (16 entries per bucket, longest first); the
 // compositing kernels map block -> tile_order[block's tile slot].  Which tile a wave works on changes, never what it computes.
-// Only for launches of a few rounds (use_tile_order, common.h).
+// Only for launches of a few rounds (FramePlan::order).
 __global__ void __launch_bounds__(ORDER_THREADS)
 tile_order_kernel(int T, const uint32_t* __restrict__ ranges, uint32_t* __restrict__ order, uint32_t* __restrict__ nparts)
 {
@@ -328,11 +323,10 @@ tile_order_kernel(int T, const uint32_t* __restrict__ ranges, uint32_t* __restri
     tile_order_block(T, [&](int i) { return ranges[2 * i + 1] - ranges[2 * i]; }, order, s_cnt, s_wsum, nparts);
 }
 
-int launch_tile_order(const splatraster_settings& s, int32_t V, const BinView& b, hipStream_t stream)
+int launch_tile_order(const FramePlan& p, const BinView& b, hipStream_t stream)
 {
-    const int gx = (s.image_width + TILE - 1) / TILE, gy = (s.image_height + TILE - 1) / TILE;
-    if (!use_tile_order(V, gx * gy)) return SPLATRASTER_OK;
-    hipLaunchKernelGGL(tile_order_kernel, dim3(1), dim3(ORDER_THREADS), 0, stream, V * gx * gy, b.ranges, b.tile_order, b.nparts);
+    if (!p.order) return SPLATRASTER_OK;
+    hipLaunchKernelGGL(tile_order_kernel, dim3(1), dim3(ORDER_THREADS), 0, stream, (int)p.gtiles, b.ranges, b.tile_order, b.nparts);
     SR_LAUNCH_CHECK();
     return SPLATRASTER_OK;
 }

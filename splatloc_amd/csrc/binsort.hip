@@ -564,9 +564,6 @@ bin_sort_big_kernel(int gtiles, int tiles, int gx, int nchunk, int cap /*the til
 }
 
 // ---- host side -------------------------------------------------------------------------------
-static int g_bin_mode = -1;   // -1 auto, 0 never, 1 whenever the shape allows
-void set_bin_mode(int mode) { g_bin_mode = mode < 0 ? -1 : (mode > 1 ? 1 : mode); }
-
 size_t bin_table_entries(int32_t P, int32_t V, int tiles)
 {
     return (size_t)(V > 0 ? V : 1) * (size_t)tiles * (size_t)bin_chunks(P, V, tiles);
@@ -578,23 +575,11 @@ size_t bin_scratch_bytes(int32_t P, int32_t V, int tiles)
     return align_up(entries * sizeof(uint32_t), 256) + scan_tmp_bytes((int64_t)entries);
 }
 
-bool use_bins(int32_t P, int32_t V, int gx, int gy, size_t scratch_bytes)
-{
-    const int tiles = gx * gy;
-    if (g_bin_mode == 0 || P <= 0 || tiles <= 0 || tiles > BIN_MAX_TILES || gx > 255 || gy > 255) return false;
-    if (bin_table_entries(P, V, tiles) >= ((size_t)1 << 31)) return false;
-    if (bin_scratch_bytes(P, V, tiles) > scratch_bytes) return false;
-    if (g_bin_mode == 1) return true;
-    return (int64_t)V * tiles <= BIN_AUTO_MAX_TILES;
-}
-
 // geometry stage: per-(tile, chunk) counts and their exclusive scan (the state words of the scan at scan_tmp must be zero:
 // preprocess_kernel clears them)
-int launch_bin_count(const splatraster_settings& s, int32_t P, int32_t V, const GeomView& g, uint32_t* table, void* scan_tmp,
-                     hipStream_t stream)
+int launch_bin_count(const FramePlan& p, const GeomView& g, uint32_t* table, void* scan_tmp, hipStream_t stream)
 {
-    const int gx = (s.image_width + TILE - 1) / TILE, gy = (s.image_height + TILE - 1) / TILE;
-    const int tiles = gx * gy, nchunk = bin_chunks(P, V, tiles);
+    const int P = p.P, V = p.V, gx = p.gx, gy = p.gy, tiles = p.tiles, nchunk = bin_chunks(P, V, tiles);
 #define SR_BIN_WALK(ROWS, SC, ...) hipLaunchKernelGGL((bin_walk_kernel<ROWS, SC>), dim3((unsigned)nchunk, (unsigned)V), dim3(BIN_THREADS), \
                                                       (size_t)tiles * sizeof(uint32_t), stream, P, tiles, gx, gy, nchunk, g.rec, __VA_ARGS__)
     switch (bin_rows_per_thread(P, V, tiles)) {
@@ -653,13 +638,12 @@ static int side_stream(int dev, SideStream** out)
 }
 
 // render stage: scatter the keys, sort every tile's list, write the payload
-int launch_bin_scatter_sort(const splatraster_settings& s, int32_t P, int32_t V, int64_t R, const GeomView& g,
-                            const uint32_t* table, const BinView& b, uint64_t* keys, hipStream_t stream, const BoundedRun* bd)
+int launch_bin_scatter_sort(const FramePlan& p, const GeomView& g, const uint32_t* table, const BinView& b, uint64_t* keys,
+                            hipStream_t stream, const BoundedRun* bd)
 {
-    const int gx = (s.image_width + TILE - 1) / TILE, gy = (s.image_height + TILE - 1) / TILE;
-    const int tiles = gx * gy, nchunk = bin_chunks(P, V, tiles);
-    const int gtiles = V * tiles;
-    (void)R;
+    const int P = p.P, V = p.V, gx = p.gx, gy = p.gy, tiles = p.tiles, nchunk = bin_chunks(P, V, tiles);
+    const int gtiles = (int)p.gtiles;
+    uint32_t* const order = p.order ? b.tile_order : nullptr;
 #define SR_BIN_SCATTER_BOUNDED(ROWS) hipLaunchKernelGGL((bin_walk_kernel<ROWS, true, const uint32_t*, BoundedRun>), dim3((unsigned)nchunk, (unsigned)V), \
                                                         dim3(BIN_THREADS), (size_t)tiles * sizeof(uint32_t), stream, P, tiles, gx, gy, nchunk, g.rec,    \
                                                         const_cast<uint32_t*>(table), keys, (const uint32_t*)g.total, *bd)
@@ -703,8 +687,7 @@ int launch_bin_scatter_sort(const splatraster_settings& s, int32_t P, int32_t V,
                                stream, gtiles, tiles, gx, nchunk, table, (const uint32_t*)g.total, (const uint64_t*)keys, (const float4*)g.rec, b, *bd);
         SR_LAUNCH_CHECK();
         hipLaunchKernelGGL(bin_sort_big_kernel<BoundedRun>, dim3(BIN_BIG_BLOCKS), dim3(1024), 0, stream, gtiles, tiles, gx, nchunk, tile_cap,
-                           table, (const uint32_t*)g.total, keys, (const float4*)g.rec, b,
-                           use_tile_order(V, tiles) ? b.tile_order : (uint32_t*)nullptr, 1, *bd);
+                           table, (const uint32_t*)g.total, keys, (const float4*)g.rec, b, order, 1, *bd);
         SR_LAUNCH_CHECK();
         return SPLATRASTER_OK;
     }
@@ -719,8 +702,7 @@ int launch_bin_scatter_sort(const splatraster_settings& s, int32_t P, int32_t V,
         SR_HIP_CHECK(hipStreamWaitEvent(side, ss->fork, 0));
         // the long lists first: they are the launch sequence's longest blocks
         hipLaunchKernelGGL(bin_sort_big_kernel<>, dim3(BIN_BIG_BLOCKS), dim3(1024), 0, side, gtiles, tiles, gx, nchunk,
-                           tile_cap, table, g.total, keys, g.rec, b,
-                           use_tile_order(V, tiles) ? b.tile_order : (uint32_t*)nullptr, 0);
+                           tile_cap, table, g.total, keys, g.rec, b, order, 0);
         SR_LAUNCH_CHECK();
         SR_HIP_CHECK(hipEventRecord(ss->join, side));
     }
@@ -735,8 +717,7 @@ int launch_bin_scatter_sort(const splatraster_settings& s, int32_t P, int32_t V,
         SR_HIP_CHECK(hipStreamWaitEvent(stream, ss->join, 0));
     } else {
         hipLaunchKernelGGL(bin_sort_big_kernel<>, dim3(BIN_BIG_BLOCKS), dim3(1024), 0, stream, gtiles, tiles, gx, nchunk,
-                           tile_cap, table, g.total, keys, g.rec, b,
-                           use_tile_order(V, tiles) ? b.tile_order : (uint32_t*)nullptr, 1);
+                           tile_cap, table, g.total, keys, g.rec, b, order, 1);
         SR_LAUNCH_CHECK();
     }
     return SPLATRASTER_OK;

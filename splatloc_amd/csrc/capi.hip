@@ -2,6 +2,7 @@
 // raster pipeline (argument validation and stage sequencing), the sort and timing entry points, error strings and polling,
 // and the raster debug hooks.  Every other stage defines its splatraster_* / splatknn_* entry points in an extern "C" block
 // at the end of its own .hip (densify.hip, matching.hip, ...).  No torch types; everything is raw device pointers.
+#include <assert.h>
 #include <string.h>
 
 #include <mutex>
@@ -15,9 +16,11 @@ namespace sr {
 
 static thread_local std::string g_last_error;
 static int g_deterministic = 0;   // splatraster_debug_set_deterministic
-static int g_split_max_waves = SPLIT_MAX_WAVES;
-void set_split_max_waves(int waves) { g_split_max_waves = waves < 0 ? SPLIT_MAX_WAVES : (waves > SPLIT_MAX_WAVES ? SPLIT_MAX_WAVES : waves); }
-int split_max_waves() { return g_split_max_waves; }
+// the knobs behind a frame's launch plan (their setters at the end of this file): frame_plan() alone reads them
+static int g_split_max_waves = SPLIT_MAX_WAVES;   // quadrant-waves up to which a narrow launch is split
+static int g_fwd_team = -1;         // -1: automatic (the split launches' condition), 0: never, 1: every narrow launch that has a launch order, 2: and a team for each of its first TEAM_MAX lists
+static int g_payload_compact = -1;  // -1 default (on), 0 off (payload_kernel, the full stream)
+static int g_bin_mode = -1;         // front end: -1 auto, 0 radix always, 1 binned whenever the shape allows
 
 void set_hip_error(hipError_t e, const char* what)
 {
@@ -111,6 +114,10 @@ static inline int tile_bits(int tiles)
     return b;
 }
 
+// tiles per row / column of a view: the buffer layouts below take W, H before any plan exists
+struct TileGrid { int gx, gy; };
+static inline TileGrid tile_grid(int32_t W, int32_t H) { return TileGrid{(W + TILE - 1) / TILE, (H + TILE - 1) / TILE}; }
+
 struct GeomLayout {
     size_t rec0, rec1, tiles_touched, depth_order, offsets, rgb, clamped, sort_keys, keys_alt, vals_alt,
         sort_tmp, scan_tmp, total, block_tiles, span_owner, bytes;
@@ -168,7 +175,8 @@ static BinLayout bin_layout(int32_t P, int32_t V, int64_t R, int32_t W, int32_t 
 {
     const size_t n = (size_t)(R > 0 ? R : 1);
     const size_t nv = (size_t)(V > 0 ? V : 1);
-    const size_t tiles = (size_t)((W + TILE - 1) / TILE) * (size_t)((H + TILE - 1) / TILE) * nv;
+    const TileGrid tg = tile_grid(W, H);
+    const size_t tiles = (size_t)tg.gx * (size_t)tg.gy * nv;
     BinLayout L;
     size_t o = 0;
     auto take = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 256); return at; };
@@ -229,7 +237,8 @@ static size_t img_plane_bytes(int32_t W, int32_t H, int32_t V)
 //  — tests/test_accumulator_layout_sizes.py — while this buffer travels with it from the forward to the backward anyway.)
 static size_t img_cranges_bytes(int32_t W, int32_t H, int32_t V)
 {
-    return align_up(8 * (size_t)((W + TILE - 1) / TILE) * (size_t)((H + TILE - 1) / TILE) * (size_t)(V > 0 ? V : 1), 256);
+    const TileGrid tg = tile_grid(W, H);
+    return align_up(8 * (size_t)tg.gx * (size_t)tg.gy * (size_t)(V > 0 ? V : 1), 256);
 }
 static size_t img_bytes(int32_t W, int32_t H, int32_t V) { return 3 * img_plane_bytes(W, H, V) + img_cranges_bytes(W, H, V); }
 
@@ -373,63 +382,82 @@ static WinCams make_cams(int32_t V, const splatraster_window_view* views)
 
 // The binned front end (binsort.hip) keeps its (tile, chunk) table and the state of its scan where the radix front end
 // keeps the depth-sort buffers (sort_keys ... scan_tmp): the geometry buffer's size does not depend on the path.
-struct BinScratch { bool on; uint32_t* table; void* scan_tmp; int64_t entries; };
+struct BinScratch { uint32_t* table; void* scan_tmp; int64_t entries; };
 
-// Which front end the GEOMETRY stage chose for a geometry buffer: the render stage is a separate public call and must follow
-// that choice, not re-derive it from the process-wide debug switch (splatraster_debug_set_front_end between the two stages
-// would otherwise make the render read a (tile, chunk) table that was never built).  Host-side, keyed by the buffer's address;
-// an address the geometry stage has not seen (or that was dropped when the map was trimmed) falls back to use_bins().
-static std::mutex g_front_end_mu;
-static std::unordered_map<const void*, bool> g_front_end;
-static void front_end_record(const void* geometry, bool on)
+// What a stage WROTE at a buffer: the next stage is a separate public call and must follow that, not re-derive it from the
+// process-wide debug switches as they stand by then (a switch flipped between two calls would otherwise make the render read a
+// (tile, chunk) table that was never built, or the backward walk a stream or segment records nobody wrote).  The geometry stage
+// records its front end under the geometry buffer, the render stage {front end, stream, segment records} under the binning
+// buffer.  Host-side, keyed by the buffer's address; an address without a record (never seen, or dropped when the map was
+// trimmed) falls back to the switches.
+struct Written { bool binned, compact, split; };
+static std::mutex g_written_mu;
+static std::unordered_map<const void*, Written> g_written;
+static void written_record(const void* at, const Written& w)
 {
-    std::lock_guard<std::mutex> lk(g_front_end_mu);
-    if (g_front_end.size() > (1u << 14)) g_front_end.clear();
-    g_front_end[geometry] = on;
+    std::lock_guard<std::mutex> lk(g_written_mu);
+    if (g_written.size() > (1u << 15)) g_written.clear();   // (both kinds of buffer: twice the entries either kind used to be given)
+    g_written[at] = w;
 }
-static int front_end_recorded(const void* geometry)   // -1 unknown, 0 radix, 1 binned
+static bool written_find(const void* at, Written* w)
 {
-    std::lock_guard<std::mutex> lk(g_front_end_mu);
-    auto it = g_front_end.find(geometry);
-    return it == g_front_end.end() ? -1 : (it->second ? 1 : 0);
-}
-
-// Compact payload (binning.hip payload_tile_kernel): on behind the radix front end, for launches of one wave per quadrant over
-// whole lists — the binned front end writes its own payload, a team or a split launch walks full list positions.
-static int g_payload_compact = -1;   // splatraster_debug_set_payload_compact: -1 default (on), 0 off (payload_kernel, the full stream)
-static bool payload_compact(const splatraster_settings& s, int32_t V, int64_t R, bool binned)
-{
-    const int tiles = ((s.image_width + TILE - 1) / TILE) * ((s.image_height + TILE - 1) / TILE);
-    return g_payload_compact != 0 && R > 0 && !binned && !split_lists(s.channels, V, tiles) && !fwd_team_launch(s.channels, V, tiles);
-}
-// What the RENDER stage wrote into a binning buffer: the backward is a separate public call and must read the stream the way it was
-// written, whatever the debug switches say by then (the front end's record above, keyed by the binning buffer's address).
-static std::unordered_map<const void*, bool> g_compact;
-static void compact_record(const void* binning, bool on)
-{
-    std::lock_guard<std::mutex> lk(g_front_end_mu);
-    if (g_compact.size() > (1u << 14)) g_compact.clear();
-    g_compact[binning] = on;
-}
-static int compact_recorded(const void* binning)   // -1 unknown, 0 full stream, 1 compact
-{
-    std::lock_guard<std::mutex> lk(g_front_end_mu);
-    auto it = g_compact.find(binning);
-    return it == g_compact.end() ? -1 : (it->second ? 1 : 0);
+    std::lock_guard<std::mutex> lk(g_written_mu);
+    auto it = g_written.find(at);
+    if (it != g_written.end()) *w = it->second;
+    return it != g_written.end();
 }
 
-static BinScratch bin_scratch(const splatraster_settings& s, int32_t P, int32_t V, void* geometry, bool geometry_stage)
+// The launch plan of a frame (common.h).  `geometry`: follow the front end its geometry stage recorded (null: the geometry stage
+// itself, which decides); `binning`: follow what its render stage recorded (the backwards).  R: the instances `binning` is laid
+// out for (0 where no stream is decided).
+static FramePlan frame_plan(int32_t W, int32_t H, int C, int32_t P, int32_t V, int64_t R, const void* geometry, const void* binning)
 {
-    const int gx = (s.image_width + TILE - 1) / TILE, gy = (s.image_height + TILE - 1) / TILE, tiles = gx * gy;
-    const GeomLayout L = geom_layout(P, V);
+    FramePlan p{};
+    const TileGrid tg = tile_grid(W, H);
+    p.W = W; p.H = H; p.gx = tg.gx; p.gy = tg.gy; p.tiles = tg.gx * tg.gy; p.gtiles = (int64_t)p.tiles * V;
+    p.P = P; p.V = V; p.C = C;
+    p.order = SR_TILE_ORDER && 4 * p.gtiles <= TILE_ORDER_MAX_WAVES;
+    p.team_every = g_fwd_team == 2 ? 1 : 0;
+    Written w{};
+    const bool rendered = binning && written_find(binning, &w);   // (then no forward follows: no team)
+    if (!rendered && !(geometry && written_find(geometry, &w))) {
+        // binned front end (binsort.hip): where the shape allows and its table fits the depth-sort scratch of the geometry buffer
+        const GeomLayout L = geom_layout(P, V);
+        w.binned = g_bin_mode != 0 && P > 0 && p.tiles > 0 && p.tiles <= BIN_MAX_TILES && p.gx <= 255 && p.gy <= 255 &&
+                   bin_table_entries(P, V, p.tiles) < ((size_t)1 << 31) && bin_scratch_bytes(P, V, p.tiles) <= L.total - L.sort_keys &&
+                   (g_bin_mode == 1 || p.gtiles <= BIN_AUTO_MAX_TILES);
+    }
+    p.binned = w.binned;
+    p.split = rendered ? w.split : C <= 4 && 4 * p.gtiles <= g_split_max_waves;
+    p.team = !rendered && (g_fwd_team < 0 ? p.split : (g_fwd_team != 0 && C <= 4));
+    // compact payload (binning.hip payload_tile_kernel): behind the radix front end, for launches of one wave per quadrant over
+    // whole lists — the binned front end writes its own payload, a team or a split launch walks full list positions
+    p.compact = rendered ? w.compact : g_payload_compact != 0 && R > 0 && !p.binned && !p.split && !p.team;
+    assert(!p.compact || (!p.binned && !p.split && !p.team && R > 0));
+    return p;
+}
+
+// The (BinView, ImgView) pair a compositing launch sees.  Compact stream: the kernels (unchanged) walk [cranges) of irec / ipack
+// and count in its positions — the forward fills both planes (n_contrib, n_contrib_c), the backward receives n_contrib_c for
+// n_contrib: its `idx < last` test and the bound list0 + wave_last then hold in compact positions.  Full stream: no n_contrib_c.
+struct CompositeViews { BinView b; ImgView im; };
+static CompositeViews composite_views(const FramePlan& p, BinView b, ImgView im, bool backward)
+{
+    if (!p.compact) im.n_contrib_c = nullptr;
+    else {
+        b.ranges = im.cranges;
+        if (backward) im.n_contrib = im.n_contrib_c;
+    }
+    return CompositeViews{b, im};
+}
+
+static BinScratch bin_scratch(const FramePlan& p, void* geometry)
+{
     BinScratch b{};
-    if (!geometry || P <= 0) return b;
-    const int recorded = geometry_stage ? -1 : front_end_recorded(geometry);
-    b.on = recorded >= 0 ? recorded == 1 : use_bins(P, V, gx, gy, L.total - L.sort_keys);
-    if (geometry_stage) front_end_record(geometry, b.on);
-    if (!b.on) return b;
+    if (!p.binned) return b;
+    const GeomLayout L = geom_layout(p.P, p.V);
     char* base = reinterpret_cast<char*>(geometry);
-    b.entries = (int64_t)bin_table_entries(P, V, tiles);
+    b.entries = (int64_t)bin_table_entries(p.P, p.V, p.tiles);
     b.table = reinterpret_cast<uint32_t*>(base + L.sort_keys);
     b.scan_tmp = base + L.sort_keys + align_up((size_t)b.entries * sizeof(uint32_t), 256);
     return b;
@@ -477,8 +505,10 @@ static int window_geometry(const splatraster_settings* s, int32_t V, const splat
     GeomView g = geom_view(geometry, P, V);
     char* base = reinterpret_cast<char*>(geometry);
     const WinCams cams = make_cams(V, views);
-    const BinScratch bins = bin_scratch(*s, P, V, geometry, true);
-    if (bounded && !bins.on) return SPLATRASTER_ERR_UNSUPPORTED;   // (nothing launched yet)
+    const FramePlan plan = frame_plan(s->image_width, s->image_height, s->channels, P, V, 0, nullptr, nullptr);
+    if (bounded && !plan.binned) return SPLATRASTER_ERR_UNSUPPORTED;   // (nothing launched yet)
+    written_record(geometry, Written{plan.binned, false, false});
+    const BinScratch bins = bin_scratch(plan, geometry);
     HostSlot* slot = nullptr;
     const size_t nblk = (size_t)preprocess_blocks(P);
     if (!bounded) {
@@ -496,7 +526,7 @@ static int window_geometry(const splatraster_settings* s, int32_t V, const splat
     {
         StageTimer t(SPLATRASTER_STAGE_PREPROCESS, stream);
         // the look-back state of the depth sort and of the scan is cleared by preprocess_kernel
-        if (bins.on)
+        if (plan.binned)
             st = launch_preprocess(*s, P, V, cams, means3D, shs, opacities, scales, rotations, cov3D_precomp, g, nullptr, 0u,
                                    reinterpret_cast<uint32_t*>(bins.scan_tmp), (uint32_t)(scan_state_bytes(bins.entries) / 4),
                                    stream, false, raw);
@@ -510,10 +540,10 @@ static int window_geometry(const splatraster_settings* s, int32_t V, const splat
         SR_HIP_CHECK(hipEventRecord(slot->ev, stream));
         guard.state = 2;
     }
-    if (bins.on) {
+    if (plan.binned) {
         // binned front end (binsort.hip): per-(tile, chunk) counts + their scan instead of the depth sort + offsets scan
         StageTimer t(SPLATRASTER_STAGE_DEPTH_SORT, stream);
-        st = launch_bin_count(*s, P, V, g, bins.table, bins.scan_tmp, stream);
+        st = launch_bin_count(plan, g, bins.table, bins.scan_tmp, stream);
         if (st) return st;
     } else {
     {
@@ -563,14 +593,14 @@ static int window_render(const splatraster_settings* s, int32_t V, const splatra
     st = check_row_index_range(P, V, s->channels);
     if (st) return st;
     if (!binning) return SPLATRASTER_ERR_BAD_ARG;
-    const int W = s->image_width, H = s->image_height;
-    const int tiles = ((W + TILE - 1) / TILE) * ((H + TILE - 1) / TILE);
-    const int64_t gtiles = (int64_t)tiles * V;
+    const FramePlan plan = frame_plan(s->image_width, s->image_height, s->channels, P, V, R, geometry, nullptr);
+    const int W = plan.W, H = plan.H;
+    const int64_t gtiles = plan.gtiles;
     if (gtiles >= ((int64_t)1 << 31)) return SPLATRASTER_ERR_OVERFLOW;
-    ImgView im = img_view(image, W, H, V);
+    const ImgView im = img_view(image, W, H, V);
     GeomView g{};
     if (geometry) g = geom_view(geometry, P, V);
-    BinView b = bin_view(binning, P, V, R, W, H, s->channels);
+    const BinView b = bin_view(binning, P, V, R, W, H, s->channels);
     const float* feat = colors_precomp ? colors_precomp : g.rgb;
     if ((R > 0 || bd) && !feat) return SPLATRASTER_ERR_BAD_ARG;
     const int bits = tile_bits((int)gtiles);
@@ -582,23 +612,23 @@ static int window_render(const splatraster_settings* s, int32_t V, const splatra
     uint32_t* v0 = (passes & 1) ? b.vals_tmp : b.point_list;
     uint32_t* k1 = (passes & 1) ? b.tile_list : b.keys_tmp;
     uint32_t* v1 = (passes & 1) ? b.point_list : b.vals_tmp;
-    const BinScratch bins = bin_scratch(*s, P, V, geometry, false);
-    if (bd && !bins.on) return SPLATRASTER_ERR_UNSUPPORTED;
-    // a bounded sequence always launches the binned front end: whether the frame is empty is known on the device only, and the
+    // a bounded sequence always has the binned front end: whether the frame is empty is known on the device only, and the
     // front end itself leaves a cleared range table and a valid launch order when the total is 0
-    const bool binned = bins.on && (R > 0 || bd);
+    if (bd && !plan.binned) return SPLATRASTER_ERR_UNSUPPORTED;
+    const BinScratch bins = bin_scratch(plan, geometry);
+    const bool binned = plan.binned && (R > 0 || bd);   // (its launches run)
     if (binned) {
         // binned front end: scatter the 64-bit keys into their (tile, chunk) pieces, sort every tile's list in LDS and write
         // the payload + lists + ranges (binsort.hip); the keys live where the radix path keeps its unsorted pairs
         StageTimer t(SPLATRASTER_STAGE_TILE_SORT, stream);
-        st = launch_bin_scatter_sort(*s, P, V, R, g, bins.table, b, reinterpret_cast<uint64_t*>(b.keys_tmp), stream, bd);
+        st = launch_bin_scatter_sort(plan, g, bins.table, b, reinterpret_cast<uint64_t*>(b.keys_tmp), stream, bd);
         if (st) return st;
     }
-    if (R > 0 && !bins.on) {
+    if (R > 0 && !plan.binned) {
         const bool keys16 = SR_TILE_KEYS16 && sort_keys16(R, bits);
         {
             StageTimer t(SPLATRASTER_STAGE_EMIT, stream);
-            st = launch_emit(*s, P, V, R, g, k0, v0, b.ranges, 2u * (uint32_t)gtiles, stream, keys16);  // also clears the range table
+            st = launch_emit(plan, R, g, k0, v0, b.ranges, 2u * (uint32_t)gtiles, stream, keys16);  // also clears the range table
         }
         if (st) return st;
         bool in_alt = false;
@@ -615,12 +645,11 @@ static int window_render(const splatraster_settings* s, int32_t V, const splatra
     }
     if (st) return st;
     const float* featp = feat;  // 16-byte aligned rows for the compositing kernels
-    const bool compact = payload_compact(*s, V, R, bins.on);
-    compact_record(binning, compact);
+    written_record(binning, Written{plan.binned, plan.compact, plan.split});
     if (R > 0 || bd) {
         StageTimer t(SPLATRASTER_STAGE_PAYLOAD, stream);
-        if (compact) st = launch_payload_compact(*s, V, R, g, b, im.cranges, stream);
-        else if (!bins.on) st = launch_payload(*s, V, R, g, b, stream);
+        if (plan.compact) st = launch_payload_compact(plan, R, g, b, im.cranges, stream);
+        else if (!plan.binned) st = launch_payload(plan, R, g, b, stream);
         if (st) return st;
         if (s->channels % 4) {
             st = launch_pad_features(P, s->channels, feat, b.featp, stream);
@@ -631,7 +660,7 @@ static int window_render(const splatraster_settings* s, int32_t V, const splatra
     if (!binned) {               // launch order of the compositing grids (the range table is final here, also when nothing was
                                  // emitted); the binned front end's last launch has computed it (binsort.hip)
         StageTimer t(SPLATRASTER_STAGE_RANGES, stream);
-        st = launch_tile_order(*s, V, b, stream);
+        st = launch_tile_order(plan, b, stream);
     }
     if (st) return st;
     WinOut outs{};
@@ -640,11 +669,9 @@ static int window_render(const splatraster_settings* s, int32_t V, const splatra
         outs.depth[v] = views[v].out_depth;
         outs.alpha[v] = views[v].out_alpha;
     }
-    // compact: the kernels walk [cranges) of irec / ipack and count in its positions (n_contrib_c); the forward fills both planes
-    if (compact) b.ranges = im.cranges;
-    else im.n_contrib_c = nullptr;
+    const CompositeViews cv = composite_views(plan, b, im, false);
     StageTimer t(SPLATRASTER_STAGE_COMPOSITE_FWD, stream);
-    return launch_composite_fwd(*s, P, V, R, g, b, im, featp, bg, outs, stream);
+    return launch_composite_fwd(*s, plan, g, cv.b, cv.im, featp, bg, outs, stream);
 }
 
 // What every backward of a window starts with (after its own argument checks): the per-view gradient planes, the fill of the
@@ -662,7 +689,9 @@ static int window_accumulate(const splatraster_settings* s, int32_t V, const spl
     BinView& b = out->b;
     g = geom_view(geometry, P, V);
     b = bin_view(const_cast<void*>(binning), P, V, R, W, H, s->channels);
-    ImgView im = img_view(const_cast<void*>(image), W, H, V);
+    // the stream and the segment records as the render stage wrote them (`out` keeps the plain views)
+    const FramePlan plan = frame_plan(W, H, s->channels, P, V, R, geometry, binning);
+    const CompositeViews cv = composite_views(plan, b, img_view(const_cast<void*>(image), W, H, V), true);
     const int C = s->channels;
     const float* feat = sh_colours ? g.rgb : colors_precomp;
     WinCams& cams = out->cams;
@@ -691,12 +720,6 @@ static int window_accumulate(const splatraster_settings* s, int32_t V, const spl
     // zero the accumulator rows (outside the stage bracket: the stage is the kernel alone, so its
     // figure can be held against the per-kernel rocprofv3 average)
     const size_t gacc_n = gacc_total_floats(C, (size_t)P, (size_t)V);   // shared colour rows + per-(view, Gaussian) rows
-    // the stream as the render stage wrote it: compact -> the kernels (unchanged) receive cranges for ranges and n_contrib_c for
-    // n_contrib; their `idx < last` test and the bound list0 + wave_last then hold in compact positions
-    const int rec_c = compact_recorded(binning);
-    const bool compact = rec_c >= 0 ? rec_c == 1 : payload_compact(*s, V, R, bin_scratch(*s, P, V, geometry, false).on);
-    BinView bw = b;      // what the compositing launch sees (`out` keeps the plain views)
-    if (compact) { bw.ranges = im.cranges; im.n_contrib = im.n_contrib_c; }
     const bool det = g_deterministic != 0;
     long long* gacc64 = nullptr;   // debug mode only: stream-ordered scratch, freed below (never part of `binning`)
     if (det) {
@@ -713,8 +736,8 @@ static int window_accumulate(const splatraster_settings* s, int32_t V, const spl
         StageTimer t(SPLATRASTER_STAGE_COMPOSITE_BWD, stream);
         // deterministic mode: the kernel runs twice — per-element max of |partial| (into the zeroed float rows), then the
         // fixed-point sums scaled by that maximum (composite_bwd.hip acc_add)
-        if (det) st = launch_composite_bwd(*s, P, V, R, g, bw, im, (C % 4) ? b.featp : feat, C, grads, b.gacc, gacc64, 0, stream);
-        if (!st) st = launch_composite_bwd(*s, P, V, R, g, bw, im, (C % 4) ? b.featp : feat, C, grads, b.gacc, gacc64, 1, stream);
+        if (det) st = launch_composite_bwd(plan, R, g, cv.b, cv.im, (C % 4) ? b.featp : feat, C, grads, b.gacc, gacc64, 0, stream);
+        if (!st) st = launch_composite_bwd(plan, R, g, cv.b, cv.im, (C % 4) ? b.featp : feat, C, grads, b.gacc, gacc64, 1, stream);
     }
     if (det) {
         if (!st) st = launch_fixed_to_float((int64_t)gacc_n, gacc64, b.gacc, gacc_det_headroom_drop(C, V), stream);
@@ -771,6 +794,11 @@ static int window_backward(const splatraster_settings* s, int32_t V, const splat
                                  cov3D_precomp ? nullptr : dL_dscales, cov3D_precomp ? nullptr : dL_drotations,
                                  cov3D_precomp ? dL_dcov3D : nullptr, dL_dshs, dL_dviewmatrix, dL_dprojmatrix, dL_dcampos,
                                  b.pose_acc, stream, raw);
+}
+
+static RawFwd raw_forward(const splatraster_raw_forward& rf)
+{
+    return RawFwd{rf.scaling, rf.rotation, rf.opacity, rf.f_dc, rf.extra, rf.extra_channels, rf.scales, rf.rotations, rf.opacities, rf.colors};
 }
 
 // R of a window: the sum of the per-view instance counts its geometry stage returned
@@ -963,8 +991,7 @@ int splatraster_forward_window_geometry_raw(const splatraster_settings* s, int32
                                             int64_t* num_rendered, void* stream)
 {
     if (!rf) return SPLATRASTER_ERR_BAD_ARG;
-    const RawFwd raw{rf->scaling, rf->rotation, rf->opacity, rf->f_dc, rf->extra, rf->extra_channels, rf->scales, rf->rotations,
-                     rf->opacities, rf->colors};
+    const RawFwd raw = raw_forward(*rf);
     return window_geometry(s, n_views, views, P, means3D, nullptr, nullptr, nullptr, nullptr, nullptr, geometry, num_rendered,
                            reinterpret_cast<hipStream_t>(stream), &raw);
 }
@@ -994,8 +1021,7 @@ static int window_bounded(const splatraster_settings* s, int32_t V, const splatr
 int splatraster_forward_window_bounded_supported(int32_t P, int32_t n_views, int32_t width, int32_t height)
 {
     if (P <= 0 || n_views < 1 || n_views > MAX_VIEWS || width <= 0 || height <= 0) return 0;
-    const GeomLayout L = geom_layout(P, n_views);
-    return use_bins(P, n_views, (width + TILE - 1) / TILE, (height + TILE - 1) / TILE, L.total - L.sort_keys) ? 1 : 0;
+    return frame_plan(width, height, 1, P, n_views, 0, nullptr, nullptr).binned ? 1 : 0;
 }
 
 int splatraster_forward_window_bounded(const splatraster_settings* s, int32_t n_views, const splatraster_window_view* views,
@@ -1014,8 +1040,7 @@ int splatraster_forward_window_bounded_raw(const splatraster_settings* s, int32_
                                            void* status, void* stream)
 {
     if (!rf) return SPLATRASTER_ERR_BAD_ARG;
-    const RawFwd raw{rf->scaling, rf->rotation, rf->opacity, rf->f_dc, rf->extra, rf->extra_channels, rf->scales, rf->rotations,
-                     rf->opacities, rf->colors};
+    const RawFwd raw = raw_forward(*rf);
     return window_bounded(s, n_views, views, P, means3D, nullptr, nullptr, nullptr, nullptr, &raw, bg, rf->colors, geometry, binning,
                           image, capacity, tag, status, reinterpret_cast<hipStream_t>(stream));
 }
@@ -1056,7 +1081,7 @@ int splatraster_debug_set_payload_compact(int mode)
 
 int splatraster_debug_set_front_end(int mode)
 {
-    set_bin_mode(mode);
+    g_bin_mode = mode < 0 ? -1 : (mode > 1 ? 1 : mode);
     return SPLATRASTER_OK;
 }
 
@@ -1074,13 +1099,13 @@ int splatraster_debug_set_tile_sort_cap(int keys)
 
 int splatraster_debug_set_split_max_waves(int waves)
 {
-    set_split_max_waves(waves);
+    g_split_max_waves = waves < 0 ? SPLIT_MAX_WAVES : (waves > SPLIT_MAX_WAVES ? SPLIT_MAX_WAVES : waves);
     return SPLATRASTER_OK;
 }
 
 int splatraster_debug_set_fwd_team(int mode)
 {
-    set_fwd_team(mode < 0 ? -1 : (mode > 2 ? 2 : mode));
+    g_fwd_team = mode < 0 ? -1 : (mode > 2 ? 2 : mode);
     return SPLATRASTER_OK;
 }
 

@@ -128,6 +128,24 @@ struct ImgView {
     uint32_t* cranges;      // [2 * V * tiles] [start, end) of every list's live entries inside irec / ipack (start = ranges[2t])
 };
 
+// ---- a frame's launch plan ------------------------------------------------------------------
+// Everything the raster launchers need to know about a frame's shape and about the decisions more than one public call must
+// agree on.  Made once per call by frame_plan() (capi.hip), the only reader of the knobs behind the decisions; what a stage
+// wrote travels to the next public call as a host-side record keyed by the buffer (capi.hip), and the plan follows it.
+struct FramePlan {
+    int W, H, gx, gy;     // frame; tiles per row / column of a view
+    int tiles;            // per view
+    int64_t gtiles;       // V * tiles: the (view, tile) lists of the window
+    int32_t P, V;
+    int C;
+    bool binned;          // front end: binsort.hip (else the radix front end: emit, tile sort, payload)
+    bool compact;         // irec / ipack hold the live entries only: kernels get cranges / n_contrib_c (!binned, !split, !team, R > 0)
+    bool split;           // the forward writes segment records; a backward may run parts
+    bool team;            // forward: composite_fwd_mixed_kernel where the launch has an order (follows `split` unless forced)
+    int team_every;       // ... and a team for each of its first TEAM_MAX lists
+    bool order;           // the compositing grids run in launch order (tile_order, nparts)
+};
+
 GeomView geom_view(void* base, int32_t P, int32_t V);
 BinView bin_view(void* base, int32_t P, int32_t V, int64_t R, int32_t W, int32_t H, int32_t C);
 ImgView img_view(void* base, int32_t W, int32_t H, int32_t V);
@@ -256,12 +274,9 @@ void set_bin_tile_cap(int cap);             // test / A-B hook: 2048 or 4096 for
 constexpr int BIN_SORT_BIG = 16384, BIN_BIG_BLOCKS = 128; // the launch for longer lists (keys in 139 KB of LDS, 1024 threads; blocks)
 constexpr int BIN_BIG_MINE = 1024;          // long lists one block of that launch can be handed (list k is block k % BIN_BIG_BLOCKS's)
 static_assert((size_t)BIN_MAX_TILES * MAX_VIEWS <= (size_t)BIN_BIG_MINE * BIN_BIG_BLOCKS, "every (view, tile) list could be a long one");
-void set_bin_mode(int mode);   // -1 auto, 0 radix front end always, 1 binned whenever the shape allows
 size_t bin_table_entries(int32_t P, int32_t V, int tiles);
 size_t bin_scratch_bytes(int32_t P, int32_t V, int tiles);
-bool use_bins(int32_t P, int32_t V, int gx, int gy /*tiles per row / column of a view*/, size_t scratch_bytes);
-int launch_bin_count(const splatraster_settings& s, int32_t P, int32_t V, const GeomView& g, uint32_t* table, void* scan_tmp,
-                     hipStream_t stream);
+int launch_bin_count(const FramePlan& p, const GeomView& g, uint32_t* table, void* scan_tmp, hipStream_t stream);
 // Bounded mode (splatraster_forward_window_bounded): the render stage runs into a binning buffer laid out for `capacity`
 // instances while R stays on the device.  The status block (splatraster_bounded_status: 16 words) exists twice: a device-resident
 // copy the kernels read, and a host-mapped coherent mirror the host reads without waiting for the stream.
@@ -279,18 +294,16 @@ struct BoundedStatus {   // what a status handle points to (bounded.hip)
     int device;
 };
 int launch_bounded_status_clear(const BoundedStatus& st, hipStream_t stream);
-// `bd` non-null: the bounded sequence (scatter, tile launch, long lists + launch order + status on ONE stream; R is ignored)
-int launch_bin_scatter_sort(const splatraster_settings& s, int32_t P, int32_t V, int64_t R, const GeomView& g,
-                            const uint32_t* table, const BinView& b, uint64_t* keys, hipStream_t stream,
-                            const BoundedRun* bd = nullptr);
+// `bd` non-null: the bounded sequence (scatter, tile launch, long lists + launch order + status on ONE stream)
+int launch_bin_scatter_sort(const FramePlan& p, const GeomView& g, const uint32_t* table, const BinView& b, uint64_t* keys,
+                            hipStream_t stream, const BoundedRun* bd = nullptr);
 
-int launch_emit(const splatraster_settings& s, int32_t P, int32_t V, int64_t R, const GeomView& g, uint32_t* keys,
-                uint32_t* vals, uint32_t* ranges, uint32_t nranges, hipStream_t stream, bool keys16 = false /*keys: [R] uint16_t*/);
+int launch_emit(const FramePlan& p, int64_t R, const GeomView& g, uint32_t* keys, uint32_t* vals, uint32_t* ranges,
+                uint32_t nranges, hipStream_t stream, bool keys16 = false /*keys: [R] uint16_t*/);
 int launch_ranges_clear(int32_t tiles, uint32_t* ranges, hipStream_t stream);
-int launch_payload(const splatraster_settings& s, int32_t V, int64_t R, const GeomView& g, const BinView& b, hipStream_t stream);
+int launch_payload(const FramePlan& p, int64_t R, const GeomView& g, const BinView& b, hipStream_t stream);
 // ranges, then irec / ipack compacted to the live instances of every list and their table `cranges` (R > 0; radix front end)
-int launch_payload_compact(const splatraster_settings& s, int32_t V, int64_t R, const GeomView& g, const BinView& b,
-                           uint32_t* cranges, hipStream_t stream);
+int launch_payload_compact(const FramePlan& p, int64_t R, const GeomView& g, const BinView& b, uint32_t* cranges, hipStream_t stream);
 // 16-byte aligned copy of the [P, C] feature rows (returns feat itself when C % 4 == 0)
 int launch_pad_features(int32_t P, int C, const float* feat, float* featp, hipStream_t stream);
 static inline int padded_channels(int C) { return (C + 3) & ~3; }
@@ -388,12 +401,7 @@ constexpr int SPLIT_PARTS_MAX = 4 * SPLIT_PARTS;       // segment records per pi
 #endif
 constexpr int SPLIT_LONG = SR_SPLIT_LONG, SPLIT_EXTRA_TILES = SR_SPLIT_EXTRA_TILES;
 static_assert(SPLIT_EXTRA_TILES % 8 == 0, "the extra workgroups use the quadrant id scheme (8 tiles per 32 ids)");
-void set_split_max_waves(int waves);   // A/B hook (< 0: default)
-void set_fwd_team(int mode);           // A/B hook: teams of four waves for the longest lists of a narrow launch (-1 automatic, 0 never, 1 whenever possible)
 void set_payload_stream_min(int64_t instances);   // test hook (< 0: default)
-bool fwd_team_launch(int C, int V, int tiles);    // the forward of this shape would run composite_fwd_mixed_kernel (composite_fwd.hip)
-int split_max_waves();
-static inline bool split_lists(int C, int V, int tiles) { return C <= 4 && 4 * V * tiles <= split_max_waves(); }
 // parts of a list of `len` entries at position `rank` of the launch order
 __host__ __device__ static inline uint32_t split_count(uint32_t len, uint32_t rank)
 {
@@ -406,7 +414,7 @@ __host__ __device__ static inline uint32_t split_part(uint32_t len, uint32_t np 
     return len < (uint32_t)SPLIT_MIN_LIST ? len : ((len / np + 63u) & ~63u);
 }
 
-int launch_composite_fwd(const splatraster_settings& s, int32_t P, int32_t V, int64_t R, const GeomView& g, const BinView& b,
+int launch_composite_fwd(const splatraster_settings& s /*bg_channels*/, const FramePlan& p, const GeomView& g, const BinView& b,
                          const ImgView& im, const float* featp /*padded rows, shared by the views*/, const float* bg,
                          const WinOut& out, hipStream_t stream);
 // launch order of the compositing grids: global tile ids by descending list length (binning.hip) — for launches of a few
@@ -416,9 +424,8 @@ int launch_composite_fwd(const splatraster_settings& s, int32_t P, int32_t V, in
 #define SR_TILE_ORDER 1   // 0 = compositing grids always in tile order (A/B)
 #endif
 constexpr int TILE_ORDER_MAX_WAVES = 32768;
-static inline bool use_tile_order(int V, int tiles_per_view) { return SR_TILE_ORDER && 4ll * V * tiles_per_view <= TILE_ORDER_MAX_WAVES; }
-int launch_tile_order(const splatraster_settings& s, int32_t V, const BinView& b, hipStream_t stream);
-int launch_composite_bwd(const splatraster_settings& s, int32_t P, int32_t V, int64_t R, const GeomView& g,
+int launch_tile_order(const FramePlan& p, const BinView& b, hipStream_t stream);   // (nothing unless p.order)
+int launch_composite_bwd(const FramePlan& p, int64_t R, const GeomView& g,
                          const BinView& b, const ImgView& im, const float* feat, int feat_stride,
                          const WinGrad& grads,
                          float* gacc /*GaccLayout: dL/dfeature | moments sum E dx, E dy, E dx^2,

@@ -735,35 +735,31 @@ static int g_small_panel_max_waves = SR_BWD_SMALL_PANEL_MAX_WAVES;
 void set_small_panel_max_waves(int waves) { g_small_panel_max_waves = waves < 0 ? SR_BWD_SMALL_PANEL_MAX_WAVES : waves; }
 
 struct BwdLaunch {
-    int P, V;
     const WinGrad* grads;
     const float* ckpt;   // non-null: split launch — SPLIT_PARTS waves per quadrant, wave k > 0 from the forward's segment records (common.h)
     int det_pass;        // deterministic mode: 0 = per-element max pass, 1 = fixed-point sum pass (acc_add)
 };
 
 template <int NC, bool DET, bool AUX = true>
-static int launch_one_bwd(const splatraster_settings& s, int c0, int first, const GeomView& g,
-                          const BinView& b, const ImgView& im, const float* feat, int feat_stride,
-                          const BwdLaunch& L, float* gacc, long long* gacc64, hipStream_t stream)
+static int launch_one_bwd(const FramePlan& p, int c0, int first, const BinView& b, const ImgView& im, const float* feat,
+                          int feat_stride, const BwdLaunch& L, float* gacc, long long* gacc64, hipStream_t stream)
 {
-    (void)g;
-    const int gx = (s.image_width + TILE - 1) / TILE, gy = (s.image_height + TILE - 1) / TILE;
-    const int tiles = gx * gy;
-    const unsigned blocks = quadrant_blocks(L.V * tiles, gx);  // 4 quadrants per (view, tile) (+ padding of the id space)
+    const int gx = p.gx, tiles = p.tiles;
+    const unsigned blocks = quadrant_blocks((int)p.gtiles, gx);  // 4 quadrants per (view, tile) (+ padding of the id space)
     const float* ckpt = (NC <= 4 && c0 == 0 && first) ? L.ckpt : nullptr;
-    const GaccLayout GL = gacc_layout(s.channels, L.P);
+    const GaccLayout GL = gacc_layout(p.C, p.P);
     if (NC == 35 && (c0 != 0 || GL.SH != 32u || GL.PV != 16u)) return SPLATRASTER_ERR_UNSUPPORTED;   // (the headline kernel's constants)
     // split launches with a launch order: three groups of extra workgroups (parts 4 .. 15 of the SPLIT_EXTRA_TILES longest lists) lead the grid
-    const bool extras = ckpt != nullptr && use_tile_order(L.V, tiles);
+    const bool extras = ckpt != nullptr && p.order;
     const unsigned extra_blocks = extras ? (unsigned)(SPLIT_PARTS_MAX / SPLIT_PARTS - 1) * quadrant_blocks(SPLIT_EXTRA_TILES, gx) : 0u;
     const dim3 grid(blocks + extra_blocks, ckpt ? (unsigned)SPLIT_PARTS : 1u);
 #define SR_BWD_LAUNCH(SPV)                                                                                          \
-    hipLaunchKernelGGL((composite_bwd_kernel<NC, DET, SPV, AUX>), grid, dim3(WAVE), 0, stream, s.image_width,           \
-                       s.image_height, feat_stride, padded_channels(feat_stride) / 4, c0, first, tiles, L.V, L.P,      \
+    hipLaunchKernelGGL((composite_bwd_kernel<NC, DET, SPV, AUX>), grid, dim3(WAVE), 0, stream, p.W,                     \
+                       p.H, feat_stride, padded_channels(feat_stride) / 4, c0, first, tiles, p.V, p.P,                 \
                        b.ranges, b.ipack, b.irec, reinterpret_cast<const float4*>(feat), *L.grads,       \
                        im.final_T, im.n_contrib, gacc, GL,                                                             \
-                       gacc_moment_offset(s.channels), gacc64, ckpt, extras ? b.nparts : nullptr, (int)extra_blocks,               \
-                       use_tile_order(L.V, tiles) ? b.tile_order : nullptr, L.det_pass)
+                       gacc_moment_offset(p.C), gacc64, ckpt, extras ? b.nparts : nullptr, (int)extra_blocks,                      \
+                       p.order ? b.tile_order : nullptr, L.det_pass)
     if constexpr (NC >= 4 && NC <= 15 && AUX) {   // C = 3 and below: the flush costs what the 8 saved butterfly values gain (A/B: S0 0.036 vs 0.041 ms)
         // per VIEW: small frames (SplatLoc's 640x480) take the panel variant — also as a window of V views (A/B at the
         // reference layout, 5 views: 0.816 vs 0.869 ms); large frames the butterfly variant at full occupancy
@@ -779,15 +775,17 @@ static int launch_one_bwd(const splatraster_settings& s, int c0, int first, cons
     return SPLATRASTER_OK;
 }
 
-int launch_composite_bwd(const splatraster_settings& s, int32_t P, int32_t V, int64_t R, const GeomView& g,
+int launch_composite_bwd(const FramePlan& p, int64_t R, const GeomView& g,
                          const BinView& b, const ImgView& im, const float* feat, int feat_stride,
                          const WinGrad& grads, float* gacc, long long* gacc64, int det_pass, hipStream_t stream)
 {
+    (void)g;
     if (R == 0) return SPLATRASTER_OK;
     const bool det = gacc64 != nullptr;
-    int C = s.channels;
-    const int tiles_v = ((s.image_width + TILE - 1) / TILE) * ((s.image_height + TILE - 1) / TILE);
-    const BwdLaunch L{P, V, &grads, (!det && split_lists(s.channels, V, tiles_v)) ? b.ckpt : nullptr, det_pass};
+    int C = p.C;
+    const int V = p.V;
+    // (the deterministic mode never splits; without the forward's segment records — p.split — nobody may)
+    const BwdLaunch L{&grads, (!det && p.split) ? b.ckpt : nullptr, det_pass};
     // Channels and auxiliary planes that did not reach the loss are not computed: when the last channel's gradient
     // travels apart (grads.gc = C - 1) and NO view has one, the launch covers channels [0, C - 1) only — its dL/dfeature
     // column stays at the zero the accumulator rows were cleared to; without any depth / alpha gradient the RGB kernel
@@ -802,9 +800,9 @@ int launch_composite_bwd(const splatraster_settings& s, int32_t P, int32_t V, in
     //  given the same gradient as full planes: tests/test_gpu_bwd_sources.py)
     if (grads.gc < C && !any_last && !det) C = grads.gc;
     if (C == 3 && !any_aux && !det)   // (the panel variant of this kernel measured equal at 640x480: 0.752 vs 0.760 ms per refinement iteration)
-        return launch_one_bwd<3, false, false>(s, 0, 1, g, b, im, feat, feat_stride, L, gacc, gacc64, stream);
-#define SR_BWD_ARGS g, b, im, feat, feat_stride, L, gacc, gacc64, stream
-#define SR_BWD_ONE(N, c0_, first_) (det ? launch_one_bwd<N, true>(s, c0_, first_, SR_BWD_ARGS) : launch_one_bwd<N, false>(s, c0_, first_, SR_BWD_ARGS))
+        return launch_one_bwd<3, false, false>(p, 0, 1, b, im, feat, feat_stride, L, gacc, gacc64, stream);
+#define SR_BWD_ARGS b, im, feat, feat_stride, L, gacc, gacc64, stream
+#define SR_BWD_ONE(N, c0_, first_) (det ? launch_one_bwd<N, true>(p, c0_, first_, SR_BWD_ARGS) : launch_one_bwd<N, false>(p, c0_, first_, SR_BWD_ARGS))
 #define SR_BWD_CASE(N) \
     case N: return SR_BWD_ONE(N, 0, 1);
     switch (C) {

@@ -944,63 +944,52 @@ int launch_debug_exp2(int64_t n, const float* x, float* y, hipStream_t stream)
 }
 
 struct FwdLaunch {
-    int P, V;
     const WinOut* outs;
     float* ckpt;   // non-null: split launch (the backward runs SPLIT_PARTS waves per quadrant: the forward records every quarter's own sums)
     bool team;     // narrow layouts on a frame that does not fill the machine: composite_fwd_mixed_kernel (teams of four waves for the longest lists)
 };
 
-static int g_fwd_team = -1;   // -1: automatic (the split launches' condition), 0: never, 1: every narrow launch that has a launch order, 2: and a team for each of its first TEAM_MAX lists
-void set_fwd_team(int mode) { g_fwd_team = mode; }
-bool fwd_team_launch(int C, int V, int tiles) { return g_fwd_team < 0 ? split_lists(C, V, tiles) : (g_fwd_team != 0 && C <= 4); }
-
 template <int NC>
-static int launch_one(const splatraster_settings& s, int c0, int write_aux, const GeomView& g,
-                      const BinView& b, const ImgView& im, const float* featp, int feat_stride,
-                      const float* bg, const FwdLaunch& L, hipStream_t stream)
+static int launch_one(const splatraster_settings& s, const FramePlan& p, int c0, int write_aux, const BinView& b, const ImgView& im,
+                      const float* featp, int feat_stride, const float* bg, const FwdLaunch& L, hipStream_t stream)
 {
-    (void)g;
-    const int gx = (s.image_width + TILE - 1) / TILE, gy = (s.image_height + TILE - 1) / TILE;
-    const int tiles = gx * gy;
-    const unsigned blocks = quadrant_blocks(L.V * tiles, gx);  // 4 quadrants per (view, tile) (+ padding of the id space)
+    const int tiles = p.tiles;
+    const unsigned blocks = quadrant_blocks((int)p.gtiles, p.gx);  // 4 quadrants per (view, tile) (+ padding of the id space)
     if constexpr (NC <= 4) {
-        if (L.team && use_tile_order(L.V, tiles)) {
-            hipLaunchKernelGGL(composite_fwd_mixed_kernel<NC>, dim3((unsigned)(L.V * tiles + 4 * TEAM_MAX)), dim3(4 * WAVE), 0, stream,
-                               s.image_width, s.image_height, padded_channels(feat_stride) / 4, c0, s.bg_channels, write_aux, tiles, L.V, L.P,
+        if (L.team && p.order) {
+            hipLaunchKernelGGL(composite_fwd_mixed_kernel<NC>, dim3((unsigned)(p.gtiles + 4 * TEAM_MAX)), dim3(4 * WAVE), 0, stream,
+                               p.W, p.H, padded_channels(feat_stride) / 4, c0, s.bg_channels, write_aux, tiles, p.V, p.P,
                                b.ranges, b.ipack, b.irec, reinterpret_cast<const float4*>(featp), bg, *L.outs, im.final_T, im.n_contrib,
                                (c0 == 0 && write_aux) ? L.ckpt : nullptr, b.nparts, (uint32_t*)nullptr /*teams stream the full lists*/,
-                               b.tile_order, g_fwd_team == 2 ? 1 : 0);
+                               b.tile_order, p.team_every);
         } else {
-            hipLaunchKernelGGL(composite_fwd_narrow_kernel<NC>, dim3(blocks), dim3(WAVE), 0, stream, s.image_width,
-                               s.image_height, padded_channels(feat_stride) / 4, c0, s.bg_channels, write_aux, tiles, L.V, L.P, b.ranges,
+            hipLaunchKernelGGL(composite_fwd_narrow_kernel<NC>, dim3(blocks), dim3(WAVE), 0, stream, p.W,
+                               p.H, padded_channels(feat_stride) / 4, c0, s.bg_channels, write_aux, tiles, p.V, p.P, b.ranges,
                                b.ipack, b.irec, reinterpret_cast<const float4*>(featp), bg, *L.outs, im.final_T,
-                               im.n_contrib, (c0 == 0 && write_aux) ? L.ckpt : nullptr, use_tile_order(L.V, tiles) ? b.nparts : nullptr,
-                               im.n_contrib_c, use_tile_order(L.V, tiles) ? b.tile_order : nullptr);
+                               im.n_contrib, (c0 == 0 && write_aux) ? L.ckpt : nullptr, p.order ? b.nparts : nullptr,
+                               im.n_contrib_c, p.order ? b.tile_order : nullptr);
         }
     } else {
-        hipLaunchKernelGGL(composite_fwd_kernel<NC>, dim3(blocks), dim3(WAVE), 0, stream, s.image_width,
-                           s.image_height, padded_channels(feat_stride) / 4, c0, s.bg_channels, write_aux, tiles, L.V, L.P, b.ranges,
+        hipLaunchKernelGGL(composite_fwd_kernel<NC>, dim3(blocks), dim3(WAVE), 0, stream, p.W,
+                           p.H, padded_channels(feat_stride) / 4, c0, s.bg_channels, write_aux, tiles, p.V, p.P, b.ranges,
                            b.ipack, b.irec, reinterpret_cast<const float4*>(featp), bg, *L.outs, im.final_T,
-                           im.n_contrib, use_tile_order(L.V, tiles) ? b.tile_order : nullptr, im.n_contrib_c);
+                           im.n_contrib, p.order ? b.tile_order : nullptr, im.n_contrib_c);
     }
     SR_LAUNCH_CHECK();
     return SPLATRASTER_OK;
 }
 
-int launch_composite_fwd(const splatraster_settings& s, int32_t P, int32_t V, int64_t R, const GeomView& g, const BinView& b,
+int launch_composite_fwd(const splatraster_settings& s, const FramePlan& p, const GeomView& g, const BinView& b,
                          const ImgView& im, const float* featp, const float* bg, const WinOut& outs, hipStream_t stream)
 {
-    (void)R;
-    const int C = s.channels;
-    const int tiles_v = ((s.image_width + TILE - 1) / TILE) * ((s.image_height + TILE - 1) / TILE);
-    const bool team = fwd_team_launch(C, V, tiles_v);
-    // (a compact stream never meets a team or a split launch: capi.hip payload_compact)
-    if (im.n_contrib_c != nullptr && (team || split_lists(C, V, tiles_v))) return SPLATRASTER_ERR_BAD_ARG;
-    const FwdLaunch L{P, V, &outs, split_lists(C, V, tiles_v) ? b.ckpt : nullptr, team};
+    (void)g;
+    const int C = p.C;
+    // (a compact stream never meets a team or a split launch: frame_plan, capi.hip)
+    const FwdLaunch L{&outs, p.split ? b.ckpt : nullptr, p.team};
     int c0 = 0, aux = 1, st = SPLATRASTER_OK;
 #define SR_FWD_CASE(N)                                                                              \
     case N:                                                                                         \
-        return launch_one<N>(s, 0, 1, g, b, im, featp, C, bg, L, stream);
+        return launch_one<N>(s, p, 0, 1, b, im, featp, C, bg, L, stream);
     switch (C) {
         SR_FWD_CASE(1) SR_FWD_CASE(2) SR_FWD_CASE(3) SR_FWD_CASE(4) SR_FWD_CASE(8) SR_FWD_CASE(16)
         SR_FWD_CASE(32) SR_FWD_CASE(35)
@@ -1010,13 +999,13 @@ int launch_composite_fwd(const splatraster_settings& s, int32_t P, int32_t V, in
     // generic channel count: chunked passes (alpha is re-evaluated per chunk)
     while (c0 < C && st == SPLATRASTER_OK) {
         const int left = C - c0;
-        if (left >= 32) { st = launch_one<32>(s, c0, aux, g, b, im, featp, C, bg, L, stream); c0 += 32; }
-        else if (left >= 16) { st = launch_one<16>(s, c0, aux, g, b, im, featp, C, bg, L, stream); c0 += 16; }
-        else if (left >= 8) { st = launch_one<8>(s, c0, aux, g, b, im, featp, C, bg, L, stream); c0 += 8; }
-        else if (left >= 4) { st = launch_one<4>(s, c0, aux, g, b, im, featp, C, bg, L, stream); c0 += 4; }
-        else if (left == 3) { st = launch_one<3>(s, c0, aux, g, b, im, featp, C, bg, L, stream); c0 += 3; }
-        else if (left == 2) { st = launch_one<2>(s, c0, aux, g, b, im, featp, C, bg, L, stream); c0 += 2; }
-        else { st = launch_one<1>(s, c0, aux, g, b, im, featp, C, bg, L, stream); c0 += 1; }
+        if (left >= 32) { st = launch_one<32>(s, p, c0, aux, b, im, featp, C, bg, L, stream); c0 += 32; }
+        else if (left >= 16) { st = launch_one<16>(s, p, c0, aux, b, im, featp, C, bg, L, stream); c0 += 16; }
+        else if (left >= 8) { st = launch_one<8>(s, p, c0, aux, b, im, featp, C, bg, L, stream); c0 += 8; }
+        else if (left >= 4) { st = launch_one<4>(s, p, c0, aux, b, im, featp, C, bg, L, stream); c0 += 4; }
+        else if (left == 3) { st = launch_one<3>(s, p, c0, aux, b, im, featp, C, bg, L, stream); c0 += 3; }
+        else if (left == 2) { st = launch_one<2>(s, p, c0, aux, b, im, featp, C, bg, L, stream); c0 += 2; }
+        else { st = launch_one<1>(s, p, c0, aux, b, im, featp, C, bg, L, stream); c0 += 1; }
         aux = 0;
     }
     return st;

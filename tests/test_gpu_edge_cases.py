@@ -330,6 +330,92 @@ def test_split_backward_with_8_and_16_parts_matches_unsplit(C, aux, front_end):
     assert far.sum() <= 30 and (np.abs(sb[far] - go[far]) <= np.abs(ua[far] - go[far]) + 1e-3 * np.abs(go[far])).mean() >= 0.6 if far.any() else True
 
 
+GRAD_KEYS = ("m3", "m2", "op", "col", "sca", "rot")
+
+
+def _view_grads(sc, aux, before_forward, before_backward, dev="cuda:0"):
+    """view_forward + view_backward as two public calls with a debug switch set in front of each: the gradients by GRAD_KEYS"""
+    from splatloc_amd import rasterizer
+    from tests.helpers import hip_settings
+    d = torch.device(dev)
+    before_forward()
+    f = rasterizer.view_forward(sc.means3D.to(d), None, sc.features.to(d), sc.opacities.to(d), sc.scales.to(d), sc.rotations.to(d),
+                                None, hip_settings(sc, d))
+    before_backward()
+    g = rasterizer.view_backward(f, sc.dL_dcolor.to(d), sc.dL_ddepth.to(d) if aux else None, sc.dL_dalpha.to(d) if aux else None)
+    torch.cuda.synchronize()
+    return {k: g[k] for k in GRAD_KEYS}
+
+
+@pytest.mark.parametrize("C,aux", [(4, True), (3, False)])
+def test_backward_follows_the_split_decision_of_its_forward(C, aux):
+    """The forward writes the segment records of a split launch, the backward reads them, and the two are separate public calls:
+    what the render stage recorded under the binning buffer decides, not splatraster_debug_set_split_max_waves as it stands at
+    backward time.  Flipped between the calls in both directions (0 -> -1: a backward that split here would start its later
+    parts from records nobody wrote; -1 -> 0), one frame with lists of 16, 16, 8 and 4 parts and twelve that are never split:
+    the oracle's gradients, and per row those of the run with the forward's setting held throughout."""
+    from splatloc_amd import _native
+    lib = _native.load()
+    sc = _clustered(6000, 64, 64, C, seed=500 + C, clusters=[(2600, (20.3, 18.2)), (1300, (52.6, 40.1)), (400, (40.2, 56.7))])
+    f = oracle_forward(sc)
+    lens = (f["ranges"][:, 1].astype(np.int64) - f["ranges"][:, 0].astype(np.int64))
+    assert lens.size == 16 and int((lens >= 2048).sum()) == 2 and int(((lens >= 1024) & (lens < 2048)).sum()) == 1
+    assert int(((lens >= 256) & (lens < 1024)).sum()) == 1 and int((lens < 256).sum()) == 12
+    bo = oracle_backward(f, sc, use_depth=aux, use_alpha=aux)
+    knob = lambda w: (lambda: lib.splatraster_debug_set_split_max_waves(w))  # noqa: E731
+    try:
+        for first, then in ((0, -1), (-1, 0)):
+            held = _view_grads(sc, aux, knob(first), knob(first))
+            flipped = _view_grads(sc, aux, knob(first), knob(then))
+            for n in GRAD_KEYS:
+                ga, gb = held[n].cpu().numpy(), flipped[n].cpu().numpy()
+                assert_grad_close(f"{n} {first}->{then}", gb, ga, rtol=1e-4, atol_scale=2e-5)
+                assert_grad_rows_close(f"rows {n} {first}->{then}", gb, ga, rtol=1e-4, row_atol=1e-3, allow_frac=1e-3, outlier_factor=100.0)
+            assert_grad_close(f"dL_dmeans3D vs oracle {first}->{then}", flipped["m3"].cpu().numpy(), bo["dL_dmeans3D"])
+            assert_grad_close(f"dL_dcolors vs oracle {first}->{then}", flipped["col"].cpu().numpy(), bo["dL_dcolors"])
+    finally:
+        lib.splatraster_debug_set_split_max_waves(-1)
+
+
+@pytest.mark.parametrize("window", [False, True])
+def test_backward_follows_the_stream_its_forward_wrote(window):
+    """The render stage records which stream it wrote (compacted to the live instances, or full) under the binning buffer; the
+    backward follows the record whatever splatraster_debug_set_payload_compact says by then.  Radix front end, whole lists,
+    deterministic sums, the ragged frame of tests/test_gpu_payload_compact.py (>= 20 % of its instances dead: asserted there):
+    every gradient bit-identical to the run without a flip — one view, and a window of two."""
+    from splatloc_amd import _native, rasterizer
+    from tests.test_gpu_accumulator_layout import _views
+    lib = _native.load()
+    sc = make_scene(3000, 333, 201, 4, 32, scale_median=0.03)
+    dev = torch.device("cuda:0")
+    views = _views(sc, 2, dev)
+
+    def grads(at_forward, at_backward):
+        if not window:
+            return _view_grads(sc, True, lambda: _native.set_payload_compact(at_forward), lambda: _native.set_payload_compact(at_backward))
+        _native.set_payload_compact(at_forward)
+        f = rasterizer.window_forward(sc.means3D.to(dev), sc.features.to(dev), sc.opacities.to(dev), sc.scales.to(dev),
+                                      sc.rotations.to(dev), None, [rs for _, rs, _ in views])
+        _native.set_payload_compact(at_backward)
+        g = rasterizer.window_backward(f, [(gc, None, gd, ga) for _, _, (gc, gd, ga) in views])
+        torch.cuda.synchronize()
+        return {k: g[k] for k in GRAD_KEYS}
+
+    _native.set_front_end(0)
+    lib.splatraster_debug_set_split_max_waves(0)
+    _native.set_deterministic(True)
+    try:
+        for first, then in ((-1, 0), (0, -1)):
+            held, flipped = grads(first, first), grads(first, then)
+            for n in GRAD_KEYS:
+                assert torch.equal(held[n], flipped[n]), (n, first, then)
+    finally:
+        _native.set_deterministic(False)
+        _native.set_payload_compact(-1)
+        lib.splatraster_debug_set_split_max_waves(-1)
+        _native.set_front_end(-1)
+
+
 @pytest.mark.parametrize("C,W,H,P,scale", [(4, 256, 256, 40_000, 0.05), (3, 250, 130, 6_000, 0.12), (1, 64, 48, 3_000, 0.3), (2, 16, 16, 700, 0.25)])
 def test_team_forward_changes_nothing(C, W, H, P, scale):
     """Narrow layouts on a frame that does not fill the machine run the forward with a TEAM of four waves per quadrant (two
