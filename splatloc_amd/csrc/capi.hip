@@ -671,7 +671,7 @@ static int window_render(const splatraster_settings* s, int32_t V, const splatra
     }
     const CompositeViews cv = composite_views(plan, b, im, false);
     StageTimer t(SPLATRASTER_STAGE_COMPOSITE_FWD, stream);
-    return launch_composite_fwd(*s, plan, g, cv.b, cv.im, featp, bg, outs, stream);
+    return launch_composite_fwd(*s, plan, cv.b, cv.im, featp, bg, outs, stream);
 }
 
 // What every backward of a window starts with (after its own argument checks): the per-view gradient planes, the fill of the

@@ -414,9 +414,9 @@ __host__ __device__ static inline uint32_t split_part(uint32_t len, uint32_t np 
     return len < (uint32_t)SPLIT_MIN_LIST ? len : ((len / np + 63u) & ~63u);
 }
 
-int launch_composite_fwd(const splatraster_settings& s /*bg_channels*/, const FramePlan& p, const GeomView& g, const BinView& b,
-                         const ImgView& im, const float* featp /*padded rows, shared by the views*/, const float* bg,
-                         const WinOut& out, hipStream_t stream);
+int launch_composite_fwd(const splatraster_settings& s /*bg_channels*/, const FramePlan& p, const BinView& b, const ImgView& im,
+                         const float* featp /*padded rows, shared by the views*/, const float* bg, const WinOut& out,
+                         hipStream_t stream);
 // launch order of the compositing grids: global tile ids by descending list length (binning.hip) — for launches of a few
 // rounds of waves only (a window of 640x480 frames: fwd 0.409 -> 0.397, bwd 0.758 -> 0.744 ms); on large grids the order costs
 // more L2 locality between neighbouring tiles than the shorter tail gains (S2: fwd 1.93 -> 1.97, bwd 4.24 -> 4.31 ms)

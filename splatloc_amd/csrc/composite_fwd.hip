@@ -9,9 +9,10 @@
 // one 256-thread workgroup they met at three barriers per batch and spent > 50 % of their
 // cycles waiting.  Here every quadrant walks the tile's list on its own, wave-synchronously,
 // with no __syncthreads anywhere:
-//   * the list is streamed 64 entries at a time from the per-instance payload written by
-//     payload_kernel (binning.hip): packed word (id | reach mask) + 32-byte record, contiguous in sorted
-//     order -> independent coalesced loads per lane, issued one chunk ahead;
+//   * the list is streamed 64 entries at a time from the per-instance payload: packed word (id | reach mask)
+//     + 32-byte record, contiguous in sorted order -> independent coalesced loads per lane, issued one chunk
+//     ahead.  Its writers: payload_kernel, payload_tile_kernel (the COMPACT stream: live instances only; both
+//     binning.hip) and the sort kernels of the binned front end (binsort.hip);
 //   * only entries whose mask says they may reach THIS quadrant become candidates; their
 //     feature rows (4*C bytes) are gathered into LDS, at most FS rows per round;
 //   * candidates are composited two at a time (twice the ILP of the alpha evaluation, and
@@ -94,6 +95,175 @@ __device__ __forceinline__ int first_bit(uint64_t m)
     return j;
 }
 
+// ---- the steps every walker of a tile list shares -------------------------------------------------------------------------------
+// composite_fwd_kernel (wide layouts), narrow_quadrant (C <= 4, one wave) and team_quadrant (C <= 4, four waves) do the same
+// operations on the same operands in the same order because each of these steps is written once, here.
+
+__device__ __forceinline__ int tile_columns(int W) { return (W + TILE - 1) / TILE; }
+
+// what a wave knows about its 8x8 quadrant of global tile `gtile` (= view * tiles + tile) and about its lane's pixel in it
+struct QuadFrame {
+    int view;            // wave-uniform (scalar)
+    uint32_t row0;       // the view's first row: feature row of row g is g - row0
+    int qx, qy, px, py;  // the quadrant's and the lane's first / own pixel
+    bool inside;
+    uint32_t beg, end;   // the tile's list
+    size_t plane, pix;   // H * W; the pixel's offset in a plane
+};
+__device__ __forceinline__ QuadFrame quadrant_frame(int W, int H, int tiles, int V, int P, const uint32_t* __restrict__ ranges, int gtile,
+                                                    int quad, int lane)
+{
+    QuadFrame F;
+    const int gx = tile_columns(W);
+    F.view = (V == 1) ? 0 : gtile / tiles;
+    const int tile = gtile - F.view * tiles;
+    F.row0 = (uint32_t)F.view * (uint32_t)P;
+    F.qx = (tile % gx) * TILE + (quad & 1) * 8, F.qy = (tile / gx) * TILE + (quad >> 1) * 8;
+    F.px = F.qx + (lane & 7), F.py = F.qy + (lane >> 3);
+    F.inside = F.px < W && F.py < H;
+    F.beg = ranges[2 * gtile], F.end = ranges[2 * gtile + 1];
+    F.plane = (size_t)H * W;
+    F.pix = (size_t)F.py * W + F.px;
+    return F;
+}
+
+// the packed word (id | reach bits << 24) of list entry `at`; 0 (reaches nothing) behind the list's end
+__device__ __forceinline__ uint32_t list_word(const uint32_t* __restrict__ ipack, uint32_t at, uint32_t end) { return at < end ? ipack[at] : 0u; }
+
+// the next two candidates of a chunk, front to back; j1 = -1 when one was left: the ABSENT candidate (an empty mask stays empty)
+__device__ __forceinline__ void next_pair(uint64_t& cand, int& j0, int& j1)
+{
+    j0 = first_bit(cand);
+    cand &= cand - 1;
+    j1 = first_bit(cand);
+    cand &= cand - 1;
+}
+
+// alpha of two Gaussians (q: pre-scaled conic, opacity) at offsets d = centre - pixel, and whether each passes the tests.  Alpha is
+// tested BEFORE the min with 0.99, like the backward: a NaN from an overflowed power is a miss, which is the only thing the argument
+// clamp of exp2_shared was there for (composite_common.h).  The absent candidate (opacity 0) never passes.
+struct PairAlpha { float al0, al1; bool pass0, pass1; };
+__device__ __forceinline__ PairAlpha pair_alpha(const float4& q0, float dx0, float dy0, const float4& q1, float dx1, float dy1)
+{
+    const float pw0 = gauss_log2(q0, dx0, dy0), pw1 = gauss_log2(q1, dx1, dy1);  // log2 of the weight
+    const float ar0 = q0.w * exp2_core(pw0), ar1 = q1.w * exp2_core(pw1);
+    return {fminf(ALPHA_MAX, ar0), fminf(ALPHA_MAX, ar1), pw0 <= 0.0f && ar0 >= ALPHA_MIN, pw1 <= 0.0f && ar1 >= ALPHA_MIN};
+}
+
+// the transmittance chain over a pair: the blending weights w = alpha T (0: no hit), T and `active` (pixel still accumulating) moved on
+struct PairWeights { float w0, w1; bool hit0, hit1; };
+__device__ __forceinline__ PairWeights transmit_pair(bool& active, float& T, bool pass0, float al0, bool pass1, float al1)
+{
+    // Gaussian 0
+    const bool live0 = active && pass0;
+    const float tT0 = transmit(T, al0);
+    const bool hit0 = live0 && tT0 >= T_EPS;
+    const bool act1 = active && !(live0 && !hit0);  // transmittance exhausted: pixel finished
+    const float w0 = hit0 ? al0 * T : 0.0f;
+    const float T1 = hit0 ? tT0 : T;
+    // Gaussian 1
+    const bool live1 = act1 && pass1;
+    const float tT1 = transmit(T1, al1);
+    const bool hit1 = live1 && tT1 >= T_EPS;
+    active = act1 && !(live1 && !hit1);
+    const float w1 = hit1 ? al1 * T1 : 0.0f;
+    T = hit1 ? tT1 : T1;
+    return {w0, w1, hit0, hit1};
+}
+
+// two FMAs in list order per channel and for the depth (forward -2.7 % at C = 3 / 4 against the pair-sum form)
+template <int N>
+__device__ __forceinline__ void accumulate_pair(float (&acc)[N], float& D, const float* f0, float z0, float w0, const float* f1, float z1,
+                                                float w1)
+{
+#pragma unroll
+    for (int ch = 0; ch < N; ++ch) acc[ch] = fmaf(f1[ch], w1, fmaf(f0[ch], w0, acc[ch]));
+    D = fmaf(z1, w1, fmaf(z0, w0, D));
+}
+
+// ---- split launches (common.h): the backward runs several waves per quadrant, one per part of the list.  Segment record k
+// = { T in front of the segment's first entry, the colours and the depth the segment ALONE contributes } — segment sums are
+// accumulated from zero, so they are accurate relative to their own (transmittance-scaled) magnitude; the backward rebuilds "what
+// lies behind a boundary" from the sums of the later segments (a prefix C_k subtracted from the image would carry the image's
+// rounding, 1e-7 |C|, into a remainder of size T_k |C|).
+struct SplitCursor {
+    int np;         // parts of this list (wave-uniform)
+    uint32_t part;  // entries per part; 0: not a split launch
+    uint32_t at;    // the entry the current segment ends in front of
+    int k;          // the current segment
+};
+__device__ __forceinline__ SplitCursor split_cursor(const float* ckpt_all, const uint32_t* __restrict__ nparts, int gtile, uint32_t beg,
+                                                    uint32_t end)
+{
+    SplitCursor c;
+    c.np = (ckpt_all != nullptr && nparts != nullptr) ? (int)nparts[gtile] : SPLIT_PARTS;
+    c.part = ckpt_all != nullptr ? split_part(end - beg, (uint32_t)c.np) : 0u;
+    c.at = c.part ? beg + c.part : 0xFFFFFFFFu;
+    c.k = 0;
+    return c;
+}
+// a segment ends in front of entry `base`: the cursor moves on to the next one (the segment that ended is c.k - 1)
+__device__ __forceinline__ bool segment_ends(SplitCursor& c, uint32_t base)
+{
+    if (base != c.at) return false;
+    ++c.k;
+    c.at = c.k < c.np - 1 ? c.at + c.part : 0xFFFFFFFFu;
+    return true;
+}
+// plane `pl` of the pixel's segment record k: ckpt_all is [V][SPLIT_PARTS_MAX][NC + 2][H * W], plane 0 = T, 1 .. NC colours, NC + 1 depth
+template <int NC>
+__device__ __forceinline__ float* segment_record(float* __restrict__ ckpt_all, const QuadFrame& F, int k, int pl)
+{
+    return ckpt_all + (((size_t)F.view * SPLIT_PARTS_MAX + k) * (NC + 2) + pl) * F.plane + F.pix;
+}
+template <int NC>
+__device__ __forceinline__ void store_segment_sums(float* __restrict__ ckpt_all, const QuadFrame& F, int k, const float (&sacc)[NC], float sD)
+{
+    float* ck = segment_record<NC>(ckpt_all, F, k, 1);
+#pragma unroll
+    for (int ch = 0; ch < NC; ++ch) ck[(size_t)ch * F.plane] = sacc[ch];
+    ck[(size_t)NC * F.plane] = sD;
+}
+// the walk is over: the open segment's sums, and nothing for the segments it never reached
+template <int NC>
+__device__ __forceinline__ void store_last_segments(float* __restrict__ ckpt_all, const QuadFrame& F, const SplitCursor& c, float (&sacc)[NC],
+                                                    float sD)
+{
+    if (!F.inside) return;
+    store_segment_sums<NC>(ckpt_all, F, c.k, sacc, sD);
+#pragma unroll
+    for (int ch = 0; ch < NC; ++ch) sacc[ch] = 0.0f;
+    for (int k = c.k + 1; k < c.np; ++k) store_segment_sums<NC>(ckpt_all, F, k, sacc, 0.0f);
+}
+
+// ---- the pixel's results ----
+// compact stream (launch-uniform): `last` is a position among the list's LIVE entries, which is what the backward walks (-> n_contrib_c);
+// the list position n_contrib promises travels as bits in that entry's record (.w: moved, never computed on) — one gather per pixel
+__device__ __forceinline__ uint32_t compact_last(uint32_t* __restrict__ n_contrib_c_all, const float4* __restrict__ irec, const QuadFrame& F,
+                                                 uint32_t last)
+{
+    (n_contrib_c_all + (size_t)F.view * F.plane)[F.pix] = last;
+    return last ? __float_as_uint(irec[2 * (size_t)(F.beg + last - 1u)].w) : last;
+}
+// channels c_first .. c_first + N - 1 over the background
+template <int N>
+__device__ __forceinline__ void store_colors(float* __restrict__ out_color /*of the view*/, const QuadFrame& F, int c_first,
+                                             const float (&acc)[N], float T, const float* __restrict__ bg, int bg_channels)
+{
+#pragma unroll
+    for (int ch = 0; ch < N; ++ch) {
+        const int c = c_first + ch;
+        out_color[(size_t)c * F.plane + F.pix] = acc[ch] + T * (c < bg_channels ? bg[c] : 0.0f);
+    }
+}
+__device__ __forceinline__ void store_coverage(float* __restrict__ out_alpha /*of the view*/, float* __restrict__ final_T_all,
+                                               uint32_t* __restrict__ n_contrib_all, const QuadFrame& F, float T, uint32_t last)
+{
+    out_alpha[F.pix] = 1.0f - T;
+    (final_T_all + (size_t)F.view * F.plane)[F.pix] = T;
+    (n_contrib_all + (size_t)F.view * F.plane)[F.pix] = last;
+}
+
 template <int NC>
 struct FwdCfg {
     static constexpr bool MFMA = NC >= 32;
@@ -131,29 +301,21 @@ composite_fwd_kernel(int W, int H, int CP4, int c0, int bg_channels, int write_a
     __shared__ uint32_t s_cgid[FS];
 
     int gtile, quad;   // global tile = view * tiles + tile: the grid covers the V views of the window
-    const int gx = (W + TILE - 1) / TILE;
-    quadrant_of_block(blockIdx.x, V * tiles, gx, gtile, quad, tile_order);
+    quadrant_of_block(blockIdx.x, V * tiles, tile_columns(W), gtile, quad, tile_order);
     if (gtile >= V * tiles) return;
-    const int view = (V == 1) ? 0 : gtile / tiles;      // wave-uniform (scalar)
-    const int tile = gtile - view * tiles;
-    const uint32_t row0 = (uint32_t)view * (uint32_t)P;  // the view's first row: feature row of row g is g - row0
-    float* __restrict__ out_color = outs.color[view];
-    float* __restrict__ out_depth = outs.depth[view];
-    float* __restrict__ out_alpha = outs.alpha[view];
-    float* __restrict__ final_T = final_T_all + (size_t)view * H * W;
-    uint32_t* __restrict__ n_contrib = n_contrib_all + (size_t)view * H * W;
     const int lane = threadIdx.x;
-    const int qx = (tile % gx) * TILE + (quad & 1) * 8, qy = (tile / gx) * TILE + (quad >> 1) * 8;
-    const int px = qx + (lane & 7), py = qy + (lane >> 3);
-    const bool inside = px < W && py < H;
-    const float fx = (float)px, fy = (float)py;
-    const uint32_t beg = ranges[2 * gtile], end = ranges[2 * gtile + 1];
+    const QuadFrame F = quadrant_frame(W, H, tiles, V, P, ranges, gtile, quad, lane);
+    float* __restrict__ out_color = outs.color[F.view];
+    float* __restrict__ out_depth = outs.depth[F.view];
+    float* __restrict__ out_alpha = outs.alpha[F.view];
+    const float fx = (float)F.px, fy = (float)F.py;
+    const uint32_t beg = F.beg, end = F.end;
 
     if (lane == 0) {
         s_rec0[0] = make_float4(0.f, 0.f, 0.f, 0.f);
         s_rec1[0] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    bool active = inside;  // pixel still accumulating
+    bool active = F.inside;  // pixel still accumulating
     float T = 1.0f, D = 0.0f;
     float acc[NV > 0 ? NV : 1];
 #pragma unroll
@@ -202,7 +364,7 @@ composite_fwd_kernel(int W, int H, int CP4, int c0, int bg_channels, int write_a
             const int rank = __popcll(cand & lt_mask);
             const int ncand = min(FS, (int)__popcll(cand));
             __builtin_amdgcn_wave_barrier();
-            if (cur_reach && ((cand >> lane) & 1ull) && rank < FS) s_cgid[rank] = cur_gid - row0;   // feature row (shared by the views)
+            if (cur_reach && ((cand >> lane) & 1ull) && rank < FS) s_cgid[rank] = cur_gid - F.row0;   // feature row (shared by the views)
             __builtin_amdgcn_wave_barrier();
             // 16-byte pieces of the 16-byte-aligned padded rows
 #pragma unroll SR_FWD_STAGE_UNROLL
@@ -222,10 +384,8 @@ composite_fwd_kernel(int W, int H, int CP4, int c0, int bg_channels, int write_a
             // ---- composite them front to back, two at a time ----
 #pragma unroll 1
             for (int slot = 0; slot < ncand; slot += 2) {
-                const int j0 = first_bit(cand);
-                cand &= cand - 1;
-                const int j1 = first_bit(cand);   // -1 in the last pair of an odd round: the absent candidate
-                cand &= cand - 1;                 // (an empty mask stays empty)
+                int j0, j1;                       // j1 = -1 in the last pair of an odd round
+                next_pair(cand, j0, j1);
                 const float4 p0 = s_rec0[1 + j0], q0 = s_rec1[1 + j0];
                 const float4 p1 = s_rec0[1 + j1], q1 = s_rec1[1 + j1];
                 const int s1 = slot + 1;          // row ncand of an odd round was zeroed while staging
@@ -239,28 +399,11 @@ composite_fwd_kernel(int W, int H, int CP4, int c0, int bg_channels, int write_a
                     a41 = s_feat[s1 * NCP + l4];
                 }
                 if constexpr (MFMA) __builtin_amdgcn_sched_barrier(0);
-                const float dx0 = p0.x - fx, dy0 = p0.y - fy, dx1 = p1.x - fx, dy1 = p1.y - fy;
-                const float pw0 = gauss_log2(q0, dx0, dy0), pw1 = gauss_log2(q1, dx1, dy1);  // log2 of the weight
-                // (alpha is tested BEFORE the min with 0.99, like the backward: a NaN from an overflowed power is a miss, which is
-                //  the only thing the argument clamp of exp2_shared was there for — composite_common.h)
-                const float ar0 = q0.w * exp2_core(pw0), ar1 = q1.w * exp2_core(pw1);
-                const float al0 = fminf(ALPHA_MAX, ar0), al1 = fminf(ALPHA_MAX, ar1);
-                // Gaussian 0
-                const bool live0 = active && pw0 <= 0.0f && ar0 >= ALPHA_MIN;
-                const float tT0 = transmit(T, al0);
-                const bool hit0 = live0 && tT0 >= T_EPS;
-                const bool act1 = active && !(live0 && !hit0);  // transmittance exhausted: pixel finished
-                const float w0 = hit0 ? al0 * T : 0.0f;
-                const float T1 = hit0 ? tT0 : T;
-                // Gaussian 1 (the absent candidate has alpha = 0)
-                const bool live1 = act1 && pw1 <= 0.0f && ar1 >= ALPHA_MIN;
-                const float tT1 = transmit(T1, al1);
-                const bool hit1 = live1 && tT1 >= T_EPS;
-                active = act1 && !(live1 && !hit1);
-                const float w1 = hit1 ? al1 * T1 : 0.0f;
-                T = hit1 ? tT1 : T1;
+                const PairAlpha al = pair_alpha(q0, p0.x - fx, p0.y - fy, q1, p1.x - fx, p1.y - fy);
+                const PairWeights wt = transmit_pair(active, T, al.pass0, al.al0, al.pass1, al.al1);
+                const float w0 = wt.w0, w1 = wt.w1;
                 const uint32_t idx = base - beg;
-                last = hit1 ? idx + (uint32_t)j1 + 1u : (hit0 ? idx + (uint32_t)j0 + 1u : last);
+                last = wt.hit1 ? idx + (uint32_t)j1 + 1u : (wt.hit0 ? idx + (uint32_t)j0 + 1u : last);
                 // No "skip if nobody hit" branch here on purpose: with the reach masks ~95 % of the
                 // candidates hit, and a conditional around the accumulation makes hipcc merge the two
                 // paths by copying all 32 accumulator registers per pair (seen in the .s).
@@ -269,16 +412,14 @@ composite_fwd_kernel(int W, int H, int CP4, int c0, int bg_channels, int write_a
                 if constexpr (M4) {
                     mfma_acc_4x4x1(acc4, a40, w0);
                     mfma_acc_4x4x1(acc4, a41, w1);
-                } else {
+                } else if constexpr (MFMA) {
+                    // beside the MFMA accumulation the pair-sum form (mul + fma + add) measured FASTER than two FMAs in list order
+                    // (1.90 vs 1.99 ms per window)
 #pragma unroll
-                    for (int ch = 0; ch < NV; ++ch) {
-                        // narrow layouts: two FMAs in list order (forward -2.7 % at C = 3 / 4); beside the MFMA accumulation of
-                        // wide layouts the pair-sum form (mul + fma + add) measured FASTER (1.90 vs 1.99 ms per window)
-                        if (MFMA) acc[ch] += f0[ch] * w0 + f1[ch] * w1;
-                        else acc[ch] = fmaf(f1[ch], w1, fmaf(f0[ch], w0, acc[ch]));
-                    }
-                    if (MFMA) D += p0.z * w0 + p1.z * w1;
-                    else D = fmaf(p1.z, w1, fmaf(p0.z, w0, D));
+                    for (int ch = 0; ch < NV; ++ch) acc[ch] += f0[ch] * w0 + f1[ch] * w1;
+                    D += p0.z * w0 + p1.z * w1;
+                } else {
+                    accumulate_pair(acc, D, f0, p0.z, w0, f1, p1.z, w1);
                 }
                 if (MFMA) {
                     float b0 = w0, b1 = w1;
@@ -291,20 +432,16 @@ composite_fwd_kernel(int W, int H, int CP4, int c0, int bg_channels, int write_a
         }
     }
 
-    const size_t plane = (size_t)H * W;
     if constexpr (M4) {
         mfma_drain4(acc4);
 #pragma unroll
         for (int ch = 0; ch < NV; ++ch) acc[ch] = acc4[ch];
         D = acc4[3];
     }
-    // compact stream (launch-uniform): `last` is a position among the list's LIVE entries, which is what the backward walks; the
-    // list position n_contrib promises travels as bits in that entry's record (.w: moved, never computed on) — one gather per pixel
-    if (n_contrib_c_all != nullptr && write_aux && inside) {
-        (n_contrib_c_all + (size_t)view * H * W)[(size_t)py * W + px] = last;
-        if (last) last = __float_as_uint(irec[2 * (size_t)(beg + last - 1u)].w);
-    }
+    if (n_contrib_c_all != nullptr && write_aux && F.inside) last = compact_last(n_contrib_c_all, irec, F, last);
     if (MFMA) {
+        const size_t plane = F.plane;
+        const int qx = F.qx, qy = F.qy;
         mfma_drain(accA, accB);
         // D[ch][pix]: lane l, register r holds channel (r&3) + 8 (r>>2) + 4 (l>>5) of wave pixel
         // (l & 31) [accA] / 32 + (l & 31) [accB]; T of those pixels comes from lanes (l&31), 32+(l&31).
@@ -321,18 +458,11 @@ composite_fwd_kernel(int W, int H, int CP4, int c0, int bg_channels, int write_a
             if (inb) out_color[(size_t)c * plane + (size_t)yb * W + xb] = accB[r] + TB * bgc;
         }
     }
-    if (inside) {
-        const size_t pix = (size_t)py * W + px;
-#pragma unroll
-        for (int ch = 0; ch < NV; ++ch) {
-            const int c = c0 + NM + ch;
-            out_color[(size_t)c * plane + pix] = acc[ch] + T * (c < bg_channels ? bg[c] : 0.0f);
-        }
+    if (F.inside) {
+        if constexpr (NV > 0) store_colors(out_color, F, c0 + NM, acc, T, bg, bg_channels);
         if (write_aux) {
-            out_depth[pix] = D;
-            out_alpha[pix] = 1.0f - T;
-            final_T[pix] = T;
-            n_contrib[pix] = last;
+            out_depth[F.pix] = D;
+            store_coverage(out_alpha, final_T_all, n_contrib_all, F, T, last);
         }
     }
 }
@@ -349,7 +479,7 @@ composite_fwd_kernel(int W, int H, int CP4, int c0, int bg_channels, int write_a
         const uint32_t *__restrict__ ranges, const uint32_t *__restrict__ ipack /*id | reach bits << 24*/,                  \
         const float4 *__restrict__ irec, const float4 *__restrict__ featp4, const float *__restrict__ bg, WinOut outs,      \
         float *__restrict__ final_T_all, uint32_t *__restrict__ n_contrib_all,                                              \
-        float *__restrict__ ckpt_all /*split launches (common.h): [V][SPLIT_PARTS_MAX][NC + 2][H * W] segment records, else null*/, \
+        float *__restrict__ ckpt_all /*split launches (common.h): the segment records (segment_record), else null*/, \
         const uint32_t *__restrict__ nparts /*split launches: parts of every (view, tile) list (written with the launch order), or null: SPLIT_PARTS*/, \
         uint32_t *__restrict__ n_contrib_c_all /*non-null: `ranges` / ipack / irec are the COMPACT stream (one-wave kernel only; never with ckpt_all)*/
 #define SR_FWD_ARGS W, H, CP4, c0, bg_channels, write_aux, tiles, V, P, ranges, ipack, irec, featp4, bg, outs, final_T_all, n_contrib_all, ckpt_all, nparts, n_contrib_c_all
@@ -362,27 +492,19 @@ __device__ __forceinline__ void narrow_quadrant(SR_FWD_PARAMS, int gtile, int qu
     static_assert(NC >= 1 && NC <= 4, "one 16-byte piece per feature row");
     // chunk entry j at [1 + j]; entry 0 is the ABSENT candidate (opacity 0: alpha = 0, never live), read through j1 = -1 by the
     // last pair of an odd chunk
-    const int gx = (W + TILE - 1) / TILE;
-    const int view = (V == 1) ? 0 : gtile / tiles;      // wave-uniform (scalar)
-    const int tile = gtile - view * tiles;
-    const uint32_t row0 = (uint32_t)view * (uint32_t)P;  // the view's first row: feature row of row g is g - row0
-    float* __restrict__ out_color = outs.color[view];
-    float* __restrict__ out_depth = outs.depth[view];
-    float* __restrict__ out_alpha = outs.alpha[view];
-    float* __restrict__ final_T = final_T_all + (size_t)view * H * W;
-    uint32_t* __restrict__ n_contrib = n_contrib_all + (size_t)view * H * W;
-    const int qx = (tile % gx) * TILE + (quad & 1) * 8, qy = (tile / gx) * TILE + (quad >> 1) * 8;
-    const int px = qx + (lane & 7), py = qy + (lane >> 3);
-    const bool inside = px < W && py < H;
-    const float fx = (float)px, fy = (float)py;
-    const uint32_t beg = ranges[2 * gtile], end = ranges[2 * gtile + 1];
+    const QuadFrame F = quadrant_frame(W, H, tiles, V, P, ranges, gtile, quad, lane);
+    float* __restrict__ out_color = outs.color[F.view];
+    float* __restrict__ out_depth = outs.depth[F.view];
+    float* __restrict__ out_alpha = outs.alpha[F.view];
+    const float fx = (float)F.px, fy = (float)F.py;
+    const uint32_t beg = F.beg, end = F.end, row0 = F.row0;
 
     if (lane == 0) {
         s_rec0[0] = make_float4(0.f, 0.f, 0.f, 0.f);
         s_rec1[0] = make_float4(0.f, 0.f, 0.f, 0.f);
         s_fq[0] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    bool active = inside;  // pixel still accumulating
+    bool active = F.inside;  // pixel still accumulating
     float T = 1.0f, D = 0.0f;
     float acc[NC];
 #pragma unroll
@@ -394,10 +516,6 @@ __device__ __forceinline__ void narrow_quadrant(SR_FWD_PARAMS, int gtile, int qu
     const uint32_t fo = (uint32_t)(c0 >> 2);
     uint32_t pw = 0, pw2 = 0;
     float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0, af = a0;
-    auto fetch_word = [&](uint32_t base, uint32_t& w_) {
-        w_ = 0u;
-        if (base + (uint32_t)lane < end) w_ = ipack[base + (uint32_t)lane];
-    };
     auto fetch_entry = [&](uint32_t base, uint32_t w_) {
         if (base + (uint32_t)lane < end) {
             const uint32_t j = base + (uint32_t)lane;
@@ -407,42 +525,25 @@ __device__ __forceinline__ void narrow_quadrant(SR_FWD_PARAMS, int gtile, int qu
             if ((w_ >> (24 + quad)) & 1u) af = featp4[(size_t)(__umul24((w_ & 0xFFFFFFu) - row0, (uint32_t)CP4) + fo)];
         }
     };
-    fetch_word(beg, pw);
-    fetch_word(beg + WAVE, pw2);
+    pw = list_word(ipack, beg + (uint32_t)lane, end);
+    pw2 = list_word(ipack, beg + WAVE + (uint32_t)lane, end);
     fetch_entry(beg, pw);
 
     bool wave_done = __builtin_amdgcn_ballot_w64(active) == 0;
-    // split launches (common.h): the backward runs SPLIT_PARTS waves per quadrant, one per part of the list.  Segment record k
-    // = { T in front of the segment's first entry, the colours and the depth the segment ALONE contributes } — segment sums
-    // are accumulated from zero, so they are accurate relative to their own (transmittance-scaled) magnitude; the backward
-    // rebuilds "what lies behind a boundary" from the sums of the later segments (a prefix C_k subtracted from the image
-    // would carry the image's rounding, 1e-7 |C|, into a remainder of size T_k |C|).
-    const int np = (ckpt_all != nullptr && nparts != nullptr) ? (int)nparts[gtile] : SPLIT_PARTS;   // (wave-uniform)
-    const uint32_t part = ckpt_all != nullptr ? split_part(end - beg, (uint32_t)np) : 0u;
-    uint32_t ck_at = part ? beg + part : 0xFFFFFFFFu;
-    int ck_k = 0;
+    SplitCursor cur = split_cursor(ckpt_all, nparts, gtile, beg, end);
     float sacc[NC], sD = 0.0f;     // the current segment's own sums (split launches only)
 #pragma unroll
     for (int ch = 0; ch < NC; ++ch) sacc[ch] = 0.0f;
-    auto store_segment = [&](int k, bool with_next_T) {
-        if (inside) {
-            const size_t pl = (size_t)H * W;
-            float* ck = ckpt_all + ((size_t)view * SPLIT_PARTS_MAX + k) * (NC + 2) * pl + (size_t)py * W + px;
-#pragma unroll
-            for (int ch = 0; ch < NC; ++ch) ck[(size_t)(1 + ch) * pl] = sacc[ch];
-            ck[(size_t)(1 + NC) * pl] = sD;
-            if (with_next_T) ck[(size_t)(NC + 2) * pl] = T;     // plane 0 of record k + 1
-        }
-    };
 #pragma unroll 1
     for (uint32_t base = beg; base < end && !wave_done; base += WAVE) {
-        if (base == ck_at) {   // a segment ends in front of this entry
-            store_segment(ck_k, true);
+        if (segment_ends(cur, base)) {   // its sums, and T in front of the next one (plane 0 of that record)
+            if (F.inside) {
+                store_segment_sums<NC>(ckpt_all, F, cur.k - 1, sacc, sD);
+                *segment_record<NC>(ckpt_all, F, cur.k, 0) = T;
+            }
 #pragma unroll
             for (int ch = 0; ch < NC; ++ch) sacc[ch] = 0.0f;
             sD = 0.0f;
-            ++ck_k;
-            ck_at = ck_k < np - 1 ? ck_at + part : 0xFFFFFFFFu;
         }
         uint64_t cand = __builtin_amdgcn_ballot_w64((pw >> (24 + quad)) & 1u);
         if (cand != 0) {
@@ -455,76 +556,33 @@ __device__ __forceinline__ void narrow_quadrant(SR_FWD_PARAMS, int gtile, int qu
         // the next chunk's entries and the word of the one behind it: issued now, consumed after this chunk has been composited
         pw = pw2;
         fetch_entry(base + WAVE, pw);
-        fetch_word(base + 2 * WAVE, pw2);
+        pw2 = list_word(ipack, base + 2 * WAVE + (uint32_t)lane, end);
         const uint32_t idx = base - beg;
 #pragma unroll 1
         while (cand != 0) {
             // ---- front to back, two at a time ----
-            const int j0 = first_bit(cand);
-            cand &= cand - 1;
-            const int j1 = first_bit(cand);   // -1 in the last pair of an odd chunk: the absent candidate
-            cand &= cand - 1;                 // (an empty mask stays empty)
+            int j0, j1;                       // j1 = -1 in the last pair of an odd chunk
+            next_pair(cand, j0, j1);
             const float4 p0 = s_rec0[1 + j0], q0 = s_rec1[1 + j0], f0 = s_fq[1 + j0];
             const float4 p1 = s_rec0[1 + j1], q1 = s_rec1[1 + j1], f1 = s_fq[1 + j1];
-            const float dx0 = p0.x - fx, dy0 = p0.y - fy, dx1 = p1.x - fx, dy1 = p1.y - fy;
-            const float pw0 = gauss_log2(q0, dx0, dy0), pw1 = gauss_log2(q1, dx1, dy1);  // log2 of the weight
-            // (alpha is tested BEFORE the min with 0.99, like the backward: a NaN from an overflowed power is a miss)
-            const float ar0 = q0.w * exp2_core(pw0), ar1 = q1.w * exp2_core(pw1);
-            const float al0 = fminf(ALPHA_MAX, ar0), al1 = fminf(ALPHA_MAX, ar1);
-            // Gaussian 0
-            const bool live0 = active && pw0 <= 0.0f && ar0 >= ALPHA_MIN;
-            const float tT0 = transmit(T, al0);
-            const bool hit0 = live0 && tT0 >= T_EPS;
-            const bool act1 = active && !(live0 && !hit0);  // transmittance exhausted: pixel finished
-            const float w0 = hit0 ? al0 * T : 0.0f;
-            const float T1 = hit0 ? tT0 : T;
-            // Gaussian 1 (the absent candidate has alpha = 0)
-            const bool live1 = act1 && pw1 <= 0.0f && ar1 >= ALPHA_MIN;
-            const float tT1 = transmit(T1, al1);
-            const bool hit1 = live1 && tT1 >= T_EPS;
-            active = act1 && !(live1 && !hit1);
-            const float w1 = hit1 ? al1 * T1 : 0.0f;
-            T = hit1 ? tT1 : T1;
-            last = hit1 ? idx + (uint32_t)j1 + 1u : (hit0 ? idx + (uint32_t)j0 + 1u : last);
+            const PairAlpha al = pair_alpha(q0, p0.x - fx, p0.y - fy, q1, p1.x - fx, p1.y - fy);
+            const PairWeights wt = transmit_pair(active, T, al.pass0, al.al0, al.pass1, al.al1);
+            last = wt.hit1 ? idx + (uint32_t)j1 + 1u : (wt.hit0 ? idx + (uint32_t)j0 + 1u : last);
             const float fv0[4] = {f0.x, f0.y, f0.z, f0.w}, fv1[4] = {f1.x, f1.y, f1.z, f1.w};
-            // two FMAs in list order per channel
-#pragma unroll
-            for (int ch = 0; ch < NC; ++ch) acc[ch] = fmaf(fv1[ch], w1, fmaf(fv0[ch], w0, acc[ch]));
-            D = fmaf(p1.z, w1, fmaf(p0.z, w0, D));
-            if (part) {     // (wave-uniform) the segment's own sums: never read by this kernel's images
-#pragma unroll
-                for (int ch = 0; ch < NC; ++ch) sacc[ch] = fmaf(fv1[ch], w1, fmaf(fv0[ch], w0, sacc[ch]));
-                sD = fmaf(p1.z, w1, fmaf(p0.z, w0, sD));
-            }
+            accumulate_pair(acc, D, fv0, p0.z, wt.w0, fv1, p1.z, wt.w1);
+            // (wave-uniform) the segment's own sums: never read by this kernel's images
+            if (cur.part) accumulate_pair(sacc, sD, fv0, p0.z, wt.w0, fv1, p1.z, wt.w1);
             if (__builtin_amdgcn_ballot_w64(active) == 0) { wave_done = true; break; }
         }
     }
 
-    if (part) {
-        store_segment(ck_k, false);
-#pragma unroll
-        for (int ch = 0; ch < NC; ++ch) sacc[ch] = 0.0f;
-        sD = 0.0f;
-        for (int k = ck_k + 1; k < np; ++k) store_segment(k, false);   // segments the wave never reached contribute nothing
-    }
-    // compact stream (composite_fwd_kernel): compact position -> n_contrib_c, the list position behind it -> n_contrib
-    if (n_contrib_c_all != nullptr && write_aux && inside) {
-        (n_contrib_c_all + (size_t)view * H * W)[(size_t)py * W + px] = last;
-        if (last) last = __float_as_uint(irec[2 * (size_t)(beg + last - 1u)].w);
-    }
-    if (inside) {
-        const size_t plane = (size_t)H * W;
-        const size_t pix = (size_t)py * W + px;
-#pragma unroll
-        for (int ch = 0; ch < NC; ++ch) {
-            const int c = c0 + ch;
-            out_color[(size_t)c * plane + pix] = acc[ch] + T * (c < bg_channels ? bg[c] : 0.0f);
-        }
+    if (cur.part) store_last_segments<NC>(ckpt_all, F, cur, sacc, sD);
+    if (n_contrib_c_all != nullptr && write_aux && F.inside) last = compact_last(n_contrib_c_all, irec, F, last);
+    if (F.inside) {
+        store_colors(out_color, F, c0, acc, T, bg, bg_channels);
         if (write_aux) {
-            out_depth[pix] = D;
-            out_alpha[pix] = 1.0f - T;
-            final_T[pix] = T;
-            n_contrib[pix] = last;
+            out_depth[F.pix] = D;
+            store_coverage(out_alpha, final_T_all, n_contrib_all, F, T, last);
         }
     }
 }
@@ -538,7 +596,7 @@ composite_fwd_narrow_kernel(SR_FWD_PARAMS, const uint32_t* __restrict__ tile_ord
     __shared__ __attribute__((aligned(16))) float4 s_rec1[WAVE + 1];
     __shared__ __attribute__((aligned(16))) float4 s_fq[WAVE + 1];
     int gtile, quad;   // global tile = view * tiles + tile: the grid covers the V views of the window
-    quadrant_of_block(blockIdx.x, V * tiles, (W + TILE - 1) / TILE, gtile, quad, tile_order);
+    quadrant_of_block(blockIdx.x, V * tiles, tile_columns(W), gtile, quad, tile_order);
     if (gtile >= V * tiles) return;
     narrow_quadrant<NC>(SR_FWD_ARGS, gtile, quad, (int)threadIdx.x, s_rec0, s_rec1, s_fq);
 }
@@ -556,8 +614,8 @@ composite_fwd_narrow_kernel(SR_FWD_PARAMS, const uint32_t* __restrict__ tile_ord
 // candidates, B one step behind A and C one behind B, through three rotating buffers of TEAM_STEP x 64 floats, and meet at one
 // barrier per step.  Every role keeps its candidates' operands SLOT-ordered in LDS (scattered once per step by the chunk's
 // lanes), so that the unrolled pair loops address them with immediates: no bit scans, no address arithmetic per pair.
-// Same operations on the same operands in the same order as the one-wave kernel: images, depth, alpha, final_T, n_contrib and
-// the segment records are bit-identical (tests/test_gpu_edge_cases.py::test_team_forward_changes_nothing).
+// Same operations on the same operands in the same order as the one-wave kernel, whose steps the roles call (A pair_alpha, B
+// transmit_pair, C accumulate_pair): images, depth, alpha, final_T, n_contrib and the segment records are bit-identical (tests/test_gpu_edge_cases.py::test_team_forward_changes_nothing).
 #ifndef SR_FWD_TEAM_STEP
 #define SR_FWD_TEAM_STEP 32   // candidates per pipeline step (a multiple of 4)
 #endif
@@ -588,21 +646,12 @@ __device__ __forceinline__ void team_quadrant(SR_FWD_PARAMS, int gtile, int quad
     float (&s_T)[WAVE] = L.T;
     int& s_fin = L.fin;
 
-    const int gx = (W + TILE - 1) / TILE;
-    const int view = (V == 1) ? 0 : gtile / tiles;
-    const int tile = gtile - view * tiles;
-    const uint32_t row0 = (uint32_t)view * (uint32_t)P;
     const int role = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // 0, 1: A   2: B   3: C
     const int lane = threadIdx.x & (WAVE - 1);
-    const int qx = (tile % gx) * TILE + (quad & 1) * 8, qy = (tile / gx) * TILE + (quad >> 1) * 8;
-    const int px = qx + (lane & 7), py = qy + (lane >> 3);
-    const bool inside = px < W && py < H;
-    const uint32_t beg = ranges[2 * gtile], end = ranges[2 * gtile + 1];
+    const QuadFrame F = quadrant_frame(W, H, tiles, V, P, ranges, gtile, quad, lane);
+    const uint32_t beg = F.beg, end = F.end, row0 = F.row0;
     const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (WAVE - lane));
-    const size_t plane = (size_t)H * W;
-    const size_t pix = (size_t)py * W + px;
-    const int np = (ckpt_all != nullptr && nparts != nullptr) ? (int)nparts[gtile] : SPLIT_PARTS;   // (workgroup-uniform)
-    const uint32_t part = ckpt_all != nullptr ? split_part(end - beg, (uint32_t)np) : 0u;
+    SplitCursor cur = split_cursor(ckpt_all, nparts, gtile, beg, end);   // (workgroup-uniform; B and C walk it, each on its own)
 
     if (threadIdx.x == 0) s_fin = -1;
     __syncthreads();
@@ -616,10 +665,6 @@ __device__ __forceinline__ void team_quadrant(SR_FWD_PARAMS, int gtile, int quad
     uint32_t pw = 0, pw2 = 0;
     float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = r0, c0r = r0, c1r = r0;
     const uint32_t fo = (uint32_t)(c0 >> 2);
-    auto fetch_word = [&](uint32_t at, uint32_t& w_) {
-        w_ = 0u;
-        if (at + (uint32_t)lane < end) w_ = ipack[at + (uint32_t)lane];
-    };
     auto fetch_entry = [&](auto role_c, uint32_t at, uint32_t w_) {
         constexpr int R = decltype(role_c)::value;     // 0: A, 2: B, 3: C
         if (R != 2 && at + (uint32_t)lane < end) {
@@ -645,7 +690,7 @@ __device__ __forceinline__ void team_quadrant(SR_FWD_PARAMS, int gtile, int quad
             next += WAVE;
             pw = pw2;
             fetch_entry(role_c, next, pw);
-            fetch_word(next + WAVE, pw2);
+            pw2 = list_word(ipack, next + WAVE + (uint32_t)lane, end);
         }
         uint64_t m = cand;
         if (__popcll(cand) > STEP) {
@@ -655,13 +700,13 @@ __device__ __forceinline__ void team_quadrant(SR_FWD_PARAMS, int gtile, int quad
         cand &= ~m;
         return m;
     };
-    fetch_word(beg, pw);
-    fetch_word(beg + WAVE, pw2);
+    pw = list_word(ipack, beg + (uint32_t)lane, end);
+    pw2 = list_word(ipack, beg + WAVE + (uint32_t)lane, end);
 
     if (role < 2) {
         // ================================ A: alpha of step `it` into buffer it % 3 ================================
         fetch_entry(std::integral_constant<int, 0>{}, beg, pw);
-        const float fx = (float)px, fy = (float)py;
+        const float fx = (float)F.px, fy = (float)F.py;
         float4* __restrict__ my_q = &s_aq[role][0];
         float2* __restrict__ my_xy = &s_axy[role][0];
         bool a_end = false;
@@ -690,13 +735,9 @@ __device__ __forceinline__ void team_quadrant(SR_FWD_PARAMS, int gtile, int quad
                     if (4 * i + 2 * role >= n) break;
                     const float4 q0 = qs[4 * i], q1 = qs[4 * i + 1];
                     const float4 cc = *reinterpret_cast<const float4*>(&cs[4 * i]);   // both centres
-                    const float dx0 = cc.x - fx, dy0 = cc.y - fy, dx1 = cc.z - fx, dy1 = cc.w - fy;
-                    const float pw0 = gauss_log2(q0, dx0, dy0), pw1 = gauss_log2(q1, dx1, dy1);
-                    // (alpha is tested BEFORE the min with 0.99: a NaN from an overflowed power is a miss)
-                    const float ar0 = q0.w * exp2_core(pw0), ar1 = q1.w * exp2_core(pw1);
-                    const float al0 = fminf(ALPHA_MAX, ar0), al1 = fminf(ALPHA_MAX, ar1);
-                    buf[(4 * i) * WAVE] = (pw0 <= 0.0f && ar0 >= ALPHA_MIN) ? al0 : -1.0f;
-                    buf[(4 * i + 1) * WAVE] = (pw1 <= 0.0f && ar1 >= ALPHA_MIN) ? al1 : -1.0f;
+                    const PairAlpha al = pair_alpha(q0, cc.x - fx, cc.y - fy, q1, cc.z - fx, cc.w - fy);
+                    buf[(4 * i) * WAVE] = al.pass0 ? al.al0 : -1.0f;
+                    buf[(4 * i + 1) * WAVE] = al.pass1 ? al.al1 : -1.0f;
                 }
             }
             __syncthreads();
@@ -707,17 +748,11 @@ __device__ __forceinline__ void team_quadrant(SR_FWD_PARAMS, int gtile, int quad
 
     if (role == 2) {
         // ================================ B: the transmittance chain of step it - 1, in place ================================
-        bool active = inside;
+        bool active = F.inside;
         float T = 1.0f;
         uint32_t last = 0;
-        uint32_t ck_at = part ? beg + part : 0xFFFFFFFFu;
-        int ck_k = 0;
-        auto boundary = [&] {
-            if (base == ck_at) {   // a segment ends in front of this entry: plane 0 of record k + 1 = T in front of it
-                if (inside) ckpt_all[((size_t)view * SPLIT_PARTS_MAX + ck_k) * (NC + 2) * plane + pix + (size_t)(NC + 2) * plane] = T;
-                ++ck_k;
-                ck_at = ck_k < np - 1 ? ck_at + part : 0xFFFFFFFFu;
-            }
+        auto boundary = [&] {   // a segment ends in front of this entry: plane 0 of the next record = T in front of it
+            if (segment_ends(cur, base) && F.inside) *segment_record<NC>(ckpt_all, F, cur.k, 0) = T;
         };
         bool finished = false;
         int fin_it = __builtin_amdgcn_ballot_w64(active) == 0 ? 0 : -1;    // the iteration to announce as the last one
@@ -737,23 +772,10 @@ __device__ __forceinline__ void team_quadrant(SR_FWD_PARAMS, int gtile, int quad
                         if (2 * i >= n) break;
                         const float al0 = buf[(2 * i) * WAVE], al1 = buf[(2 * i + 1) * WAVE];
                         const uint2 jj = *reinterpret_cast<const uint2*>(&s_bj[2 * i]);
-                        // Gaussian 0
-                        const bool live0 = active && al0 >= 0.0f;
-                        const float tT0 = transmit(T, al0);
-                        const bool hit0 = live0 && tT0 >= T_EPS;
-                        const bool act1 = active && !(live0 && !hit0);  // transmittance exhausted: pixel finished
-                        const float w0 = hit0 ? al0 * T : 0.0f;
-                        const float T1 = hit0 ? tT0 : T;
-                        // Gaussian 1
-                        const bool live1 = act1 && al1 >= 0.0f;
-                        const float tT1 = transmit(T1, al1);
-                        const bool hit1 = live1 && tT1 >= T_EPS;
-                        active = act1 && !(live1 && !hit1);
-                        const float w1 = hit1 ? al1 * T1 : 0.0f;
-                        T = hit1 ? tT1 : T1;
-                        last = hit1 ? jj.y : (hit0 ? jj.x : last);
-                        buf[(2 * i) * WAVE] = w0;
-                        buf[(2 * i + 1) * WAVE] = w1;
+                        const PairWeights wt = transmit_pair(active, T, al0 >= 0.0f, al0, al1 >= 0.0f, al1);
+                        last = wt.hit1 ? jj.y : (wt.hit0 ? jj.x : last);
+                        buf[(2 * i) * WAVE] = wt.w0;
+                        buf[(2 * i + 1) * WAVE] = wt.w1;
                     }
                     // (a step is always finished: C reads every slot of it as a weight)
                     if (__builtin_amdgcn_ballot_w64(active) == 0) fin_it = it + 1;   // C composites this step in the next iteration
@@ -767,11 +789,7 @@ __device__ __forceinline__ void team_quadrant(SR_FWD_PARAMS, int gtile, int quad
             __syncthreads();
             if (fin_it >= 0 && it >= fin_it) break;
         }
-        if (inside && write_aux) {
-            outs.alpha[view][pix] = 1.0f - T;
-            (final_T_all + (size_t)view * plane)[pix] = T;
-            (n_contrib_all + (size_t)view * plane)[pix] = last;
-        }
+        if (F.inside && write_aux) store_coverage(outs.alpha[F.view], final_T_all, n_contrib_all, F, T, last);
         return;
     }
 
@@ -781,27 +799,15 @@ __device__ __forceinline__ void team_quadrant(SR_FWD_PARAMS, int gtile, int quad
     float acc[NC];
 #pragma unroll
     for (int ch = 0; ch < NC; ++ch) acc[ch] = 0.0f;
-    uint32_t ck_at = part ? beg + part : 0xFFFFFFFFu;
-    int ck_k = 0;
-    float sacc[NC], sD = 0.0f;     // the current segment's own sums (split launches only; common.h)
+    float sacc[NC], sD = 0.0f;     // the current segment's own sums (split launches only)
 #pragma unroll
     for (int ch = 0; ch < NC; ++ch) sacc[ch] = 0.0f;
-    auto store_sums = [&](int k) {
-        if (inside) {
-            float* ck = ckpt_all + ((size_t)view * SPLIT_PARTS_MAX + k) * (NC + 2) * plane + pix;
-#pragma unroll
-            for (int ch = 0; ch < NC; ++ch) ck[(size_t)(1 + ch) * plane] = sacc[ch];
-            ck[(size_t)(1 + NC) * plane] = sD;
-        }
-    };
     auto boundary = [&] {
-        if (base == ck_at) {   // a segment ends in front of this entry
-            store_sums(ck_k);
+        if (segment_ends(cur, base)) {
+            if (F.inside) store_segment_sums<NC>(ckpt_all, F, cur.k - 1, sacc, sD);
 #pragma unroll
             for (int ch = 0; ch < NC; ++ch) sacc[ch] = 0.0f;
             sD = 0.0f;
-            ++ck_k;
-            ck_at = ck_k < np - 1 ? ck_at + part : 0xFFFFFFFFu;
         }
     };
 #pragma unroll 1
@@ -829,37 +835,18 @@ __device__ __forceinline__ void team_quadrant(SR_FWD_PARAMS, int gtile, int quad
                     const float4 f0 = s_cf[2 * i], f1 = s_cf[2 * i + 1];
                     const float2 zz = *reinterpret_cast<const float2*>(&s_cz[2 * i]);
                     const float fv0[4] = {f0.x, f0.y, f0.z, f0.w}, fv1[4] = {f1.x, f1.y, f1.z, f1.w};
-                    // two FMAs in list order per channel
-#pragma unroll
-                    for (int ch = 0; ch < NC; ++ch) acc[ch] = fmaf(fv1[ch], w1, fmaf(fv0[ch], w0, acc[ch]));
-                    D = fmaf(zz.y, w1, fmaf(zz.x, w0, D));
-                    if (part) {     // (wave-uniform) the segment's own sums
-#pragma unroll
-                        for (int ch = 0; ch < NC; ++ch) sacc[ch] = fmaf(fv1[ch], w1, fmaf(fv0[ch], w0, sacc[ch]));
-                        sD = fmaf(zz.y, w1, fmaf(zz.x, w0, sD));
-                    }
+                    accumulate_pair(acc, D, fv0, zz.x, w0, fv1, zz.y, w1);
+                    if (cur.part) accumulate_pair(sacc, sD, fv0, zz.x, w0, fv1, zz.y, w1);   // (wave-uniform) the segment's own sums
                 }
             }
         }
         __syncthreads();
         if (s_fin >= 0 && it >= s_fin) break;
     }
-    if (part) {
-        store_sums(ck_k);
-#pragma unroll
-        for (int ch = 0; ch < NC; ++ch) sacc[ch] = 0.0f;
-        sD = 0.0f;
-        for (int k = ck_k + 1; k < np; ++k) store_sums(k);   // segments the walk never reached contribute nothing
-    }
-    if (inside) {
-        const float T = s_T[lane];
-        float* __restrict__ out_color = outs.color[view];
-#pragma unroll
-        for (int ch = 0; ch < NC; ++ch) {
-            const int c = c0 + ch;
-            out_color[(size_t)c * plane + pix] = acc[ch] + T * (c < bg_channels ? bg[c] : 0.0f);
-        }
-        if (write_aux) outs.depth[view][pix] = D;
+    if (cur.part) store_last_segments<NC>(ckpt_all, F, cur, sacc, sD);
+    if (F.inside) {
+        store_colors(outs.color[F.view], F, c0, acc, s_T[lane], bg, bg_channels);
+        if (write_aux) outs.depth[F.view][F.pix] = D;
     }
 }
 
@@ -979,10 +966,9 @@ static int launch_one(const splatraster_settings& s, const FramePlan& p, int c0,
     return SPLATRASTER_OK;
 }
 
-int launch_composite_fwd(const splatraster_settings& s, const FramePlan& p, const GeomView& g, const BinView& b,
-                         const ImgView& im, const float* featp, const float* bg, const WinOut& outs, hipStream_t stream)
+int launch_composite_fwd(const splatraster_settings& s, const FramePlan& p, const BinView& b, const ImgView& im, const float* featp,
+                         const float* bg, const WinOut& outs, hipStream_t stream)
 {
-    (void)g;
     const int C = p.C;
     // (a compact stream never meets a team or a split launch: frame_plan, capi.hip)
     const FwdLaunch L{&outs, p.split ? b.ckpt : nullptr, p.team};

@@ -3,6 +3,7 @@
 the headline kernel to code generation nobody had looked at — a "prefetch" whose registers were spilled right behind the
 loads, an epilogue with a wait between every two stores — so the numbers the design depends on (HISTORY.md §9) are
 pinned here: a source or toolchain change that costs a wave per SIMD or re-introduces scratch traffic fails on the CPU."""
+import functools
 import os
 import re
 import shutil
@@ -13,6 +14,7 @@ import pytest
 from splatloc_amd import build as B
 
 
+@functools.lru_cache(maxsize=None)     # one compilation per file, whichever tests read its report
 def _usage(src):
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
@@ -55,6 +57,17 @@ def test_forward_kernels_have_no_scratch_and_keep_their_occupancy():
         assert mixed[nc]["VGPRs"] <= 96 and mixed[nc]["Occupancy"] >= 5 and mixed[nc]["LDS Size"] <= 28 * 1024, (nc, mixed[nc])
     assert fwd[35]["VGPRs"] <= 96 and fwd[35]["Occupancy"] >= 5, fwd[35]      # the headline layout: 5 waves per SIMD
     assert fwd[35]["LDS Size"] <= 5700, fwd[35]                               # 28 workgroups per CU by LDS
+
+
+def test_wide_forward_kernels_of_the_other_layouts_keep_their_occupancy():
+    """composite_fwd_kernel<8>, <16>, <32>: the chunked passes of a generic channel count and the three fixed layouts beside the
+    headline one.  They share every step of the walk with the narrow kernels (HISTORY.md §21): nothing in scratch, and no fewer
+    waves per SIMD than each had with its own copy of those steps (74 / 102 / 91 VGPRs: 6 / 4 / 5 waves)."""
+    u = _usage("composite_fwd.hip")
+    for nc, waves in ((8, 6), (16, 4), (32, 5)):
+        k = _kernel(u, f"_ZN2sr20composite_fwd_kernelILi{nc}EE")
+        assert k["ScratchSize"] == 0 and k["VGPRs Spill"] == 0 and k["SGPRs Spill"] == 0, (nc, k)
+        assert k["Occupancy"] >= waves, (nc, k)
 
 
 def test_backward_kernels_stay_within_their_register_budget():
