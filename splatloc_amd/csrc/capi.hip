@@ -736,8 +736,8 @@ static int window_accumulate(const splatraster_settings* s, int32_t V, const spl
         StageTimer t(SPLATRASTER_STAGE_COMPOSITE_BWD, stream);
         // deterministic mode: the kernel runs twice — per-element max of |partial| (into the zeroed float rows), then the
         // fixed-point sums scaled by that maximum (composite_bwd.hip acc_add)
-        if (det) st = launch_composite_bwd(plan, R, g, cv.b, cv.im, (C % 4) ? b.featp : feat, C, grads, b.gacc, gacc64, 0, stream);
-        if (!st) st = launch_composite_bwd(plan, R, g, cv.b, cv.im, (C % 4) ? b.featp : feat, C, grads, b.gacc, gacc64, 1, stream);
+        if (det) st = launch_composite_bwd(plan, R, cv.b, cv.im, (C % 4) ? b.featp : feat, C, grads, b.gacc, gacc64, 0, stream);
+        if (!st) st = launch_composite_bwd(plan, R, cv.b, cv.im, (C % 4) ? b.featp : feat, C, grads, b.gacc, gacc64, 1, stream);
     }
     if (det) {
         if (!st) st = launch_fixed_to_float((int64_t)gacc_n, gacc64, b.gacc, gacc_det_headroom_drop(C, V), stream);

@@ -425,8 +425,7 @@ int launch_composite_fwd(const splatraster_settings& s /*bg_channels*/, const Fr
 #endif
 constexpr int TILE_ORDER_MAX_WAVES = 32768;
 int launch_tile_order(const FramePlan& p, const BinView& b, hipStream_t stream);   // (nothing unless p.order)
-int launch_composite_bwd(const FramePlan& p, int64_t R, const GeomView& g,
-                         const BinView& b, const ImgView& im, const float* feat, int feat_stride,
+int launch_composite_bwd(const FramePlan& p, int64_t R, const BinView& b, const ImgView& im, const float* feat, int feat_stride,
                          const WinGrad& grads,
                          float* gacc /*GaccLayout: dL/dfeature | moments sum E dx, E dy, E dx^2,
                                       E dx dy, E dy^2, E, w g_D*/,

@@ -152,6 +152,55 @@ __device__ __forceinline__ void acc_add(float* gacc, long long* gacc64, size_t i
     }
 }
 
+// One step of the back-to-front walk (header): the state T, A behind an entry moves in front of it; out come dA = T_i (q_i - A_i)
+// — dL/dalpha_i, finite also for a miss, where E = G dA = 0 — and the blending weight w = alpha_i T_i.  Branch-free: a miss keeps T
+// and A and has w = 0.  ST = double in the accurate mode (DET), else float: there T_i = T_{i+1} / (1 - alpha) goes through the
+// hardware reciprocal (1 ulp; alpha <= 0.99 keeps the argument >= 0.01) — a relative error per step, harmless; the correctly
+// rounded division would be 10 instructions per Gaussian.
+__device__ __forceinline__ float walk_divide(float T, float one_minus_alpha) { return T * __builtin_amdgcn_rcpf(one_minus_alpha); }
+__device__ __forceinline__ double walk_divide(double T, double one_minus_alpha) { return T / one_minus_alpha; }
+__device__ __forceinline__ float walk_fma(float a, float b, float c) { return fmaf(a, b, c); }
+__device__ __forceinline__ double walk_fma(double a, double b, double c) { return fma(a, b, c); }
+template <typename ST>
+__device__ __forceinline__ void walk_entry(ST& T, ST& A, bool hit, float alpha, float q, float& dA, float& w)
+{
+    const ST Ti = hit ? walk_divide(T, (ST)1 - (ST)alpha) : T;
+    const ST d = (ST)q - A;
+    dA = (float)(Ti * d);
+    const ST ah = hit ? (ST)alpha : (ST)0;
+    A = walk_fma(ah, d, A);
+    w = (float)(ah * Ti);
+    T = Ti;
+}
+
+// Where a wave adds its partials: the accumulator (GaccLayout, common.h) as the compositing kernel addresses it — column col of
+// Gaussian id (its index in the view; < 2^24, checked on the host) at  mul24(id, stride) + offset,  stride and offset those of the
+// table the column lives in.  A caller that knows the table at compile time names it and nothing is selected per pair: a kernel of
+// NC >= 32 channels only exists for c0 + 32 <= C, so its flush columns [c0, c0 + 32) all lie in the SHARED table and its butterfly
+// values (channels c0 + 32 .., moments) in the per-VIEW one; the moments are per view in every layout.  The narrower kernels serve
+// any column range (the chunked passes of C = 40, 48 ...; C < 32: everything per view): BY_COLUMN.
+enum class GaccTable { SHARED, VIEW, BY_COLUMN };
+template <bool DET>
+struct GradRows {
+    float* __restrict__ gacc;
+    long long* __restrict__ gacc64;
+    GaccLayout GL;
+    uint32_t row0, pv_base;   // the view's first row; GL.view_base24(row0)
+    int det_pass, det_drop;
+    __device__ __forceinline__ uint32_t stride(uint32_t col, GaccTable tb) const
+    {
+        return tb == GaccTable::SHARED ? GL.SH : (tb == GaccTable::VIEW ? GL.PV : GL.stride24(col));
+    }
+    __device__ __forceinline__ uint32_t offset(uint32_t col, GaccTable tb) const
+    {
+        return (tb == GaccTable::SHARED ? 0u : (tb == GaccTable::VIEW ? pv_base : GL.base24(col, row0))) + col;
+    }
+    // (stride and offset apart: where the column does not change from pair to pair they are hoisted out of the loops)
+    static __device__ __forceinline__ size_t index(uint32_t id, uint32_t stride, uint32_t offset) { return (size_t)(__umul24(id, stride) + offset); }
+    __device__ __forceinline__ size_t index(uint32_t id, uint32_t col, GaccTable tb) const { return index(id, stride(col, tb), offset(col, tb)); }
+    __device__ __forceinline__ void add(size_t idx, float v) const { acc_add<DET>(gacc, gacc64, idx, v, det_pass, det_drop); }
+};
+
 template <int NC, bool SP, bool AUX>
 constexpr int bwd_min_waves() { return (BwdCfg<NC, SP, AUX>::TM && NC >= 32) ? SR_BWD_MINW_TM : SR_BWD_MINW; }
 
@@ -166,7 +215,7 @@ composite_bwd_kernel(int W, int H, int C_total, int CP4, int c0, int first_pass,
                      float* __restrict__ gacc /*GaccLayout (common.h)*/, GaccLayout GL,
                      int MO /*column of the moments*/, long long* __restrict__ gacc64 /*same layout, fixed point, DET only*/,
                      const float* __restrict__ ckpt_all /*split launches (common.h; gridDim.y == SPLIT_PARTS): the forward's segment
-                                                          records [V][SPLIT_PARTS_MAX][NC + 2][H * W], else null*/,
+                                                          records (segment_record), else null*/,
                      const uint32_t* __restrict__ nparts /*split launches: parts of every (view, tile) list, or null: SPLIT_PARTS*/,
                      int extra_blocks /*split launches: workgroups at the head of the grid that walk parts 4 .. of the longest lists*/,
                      const uint32_t* __restrict__ tile_order /*launch order (binning.hip), or null*/,
@@ -198,7 +247,7 @@ composite_bwd_kernel(int W, int H, int C_total, int CP4, int c0, int first_pass,
     __shared__ float2 s_emean[TM ? GROUP : 1];    // projected mean of every parked Gaussian
 
     int gtile, quad;   // global tile = view * tiles + tile: the grid covers the V views of the window
-    const int gx = (W + TILE - 1) / TILE;
+    const int gx = tile_columns(W);
     int seg_y = (int)blockIdx.y;      // split launches: the part of the list this wave walks
     if (NC <= 4 && (int)blockIdx.x < extra_blocks) {
         // EXTRA workgroups (first in the grid: their lists are the launch's longest): group e / (ids of SPLIT_EXTRA_TILES tiles) walks
@@ -215,16 +264,15 @@ composite_bwd_kernel(int W, int H, int C_total, int CP4, int c0, int first_pass,
         quadrant_of_block(blockIdx.x - (NC <= 4 ? (unsigned)extra_blocks : 0u), V * tiles, gx, gtile, quad, tile_order);
         if (gtile >= V * tiles) return;
     }
-    const int view = (V == 1) ? 0 : gtile / tiles;      // wave-uniform (scalar)
-    const int tile = gtile - view * tiles;
-    const uint32_t row0 = (uint32_t)view * (uint32_t)P;  // the view's first row: feature rows (and the accumulator's shared colour rows) are per Gaussian
-    // accumulator addressing (GaccLayout, common.h): column col of Gaussian i at mul24(i, stride) + base + col.  A kernel of
-    // NC >= 32 channels only exists for c0 + 32 <= C, so its flush columns [c0, c0 + 32) all lie in the shared table and its
-    // butterfly values (channels c0 + 32 .., moments) in the per-view one: known at compile time, nothing is selected per pair.
-    // The narrower kernels serve any column range (the chunked passes of C = 40, 48 ...; C < 32: everything per view).
-    constexpr bool WIDE = NC >= 32;
+    const int lane = threadIdx.x;
+    const QuadFrame F = quadrant_frame(W, H, tiles, V, P, ranges, gtile, quad, lane);   // the forward's frame (composite_common.h)
+    const int view = F.view;
+    const uint32_t row0 = F.row0;   // the view's first row: feature rows (and the accumulator's shared colour rows) are per Gaussian
+    const bool inside = F.inside;
+    const size_t plane = F.plane, pix = F.pix;   // (pix: only lanes inside the image use it)
+    constexpr bool WIDE = NC >= 32;   // (accumulator addressing: GradRows)
     const int det_drop = DET ? gacc_det_headroom_drop(C_total, V) : 0;   // fixed-point headroom of a shared table (acc_add, common.h)
-    // what the WIDE shortcuts below rest on: the flush covers exactly the 32 columns [c0, c0 + 32) (c0 + 32 <= C, so <= SH for any
+    // what the WIDE shortcuts of GradRows rest on: the flush covers exactly the 32 columns [c0, c0 + 32) (c0 + 32 <= C, so <= SH for any
     // multiple-of-16 SH >= 32 reached in steps of 32 or with NC < 48), every butterfly column is >= c0 + 32 >= SH or a moment
     static_assert(!WIDE || (Cfg::NM == 32 && NC < 48), "a wide kernel's flush columns are the shared table's, its butterfly columns the per-view row's");
     // (the headline kernel, NC = 35, covers all of C = 35, or of C = 36 without its last channel: gacc_shared_floats = 32 and
@@ -233,7 +281,8 @@ composite_bwd_kernel(int W, int H, int C_total, int CP4, int c0, int first_pass,
     static_assert(!FIXED || (gacc_shared_floats(NC) == 32 && gacc_view_floats(NC) == 16 && gacc_shared_floats(NC + 1) == 32 &&
                              gacc_view_floats(NC + 1) == 16), "the constants of the headline kernel");
     if constexpr (FIXED) { GL.SH = 32u; GL.PV = 16u; }
-    const uint32_t pv_base = GL.view_base24(row0);
+    const GradRows<DET> rows{gacc, gacc64, GL, row0, GL.view_base24(row0), det_pass, det_drop};
+    constexpr GaccTable FLUSH_COLS = WIDE ? GaccTable::SHARED : GaccTable::BY_COLUMN, BUTTERFLY_COLS = WIDE ? GaccTable::VIEW : GaccTable::BY_COLUMN;
     const float* __restrict__ dL_dcolor = grads.dL_dcolor[view];
     const float* __restrict__ dL_ddepth = grads.dL_ddepth[view];
     const float* __restrict__ dL_dalpha = grads.dL_dalpha[view];
@@ -241,27 +290,18 @@ composite_bwd_kernel(int W, int H, int C_total, int CP4, int c0, int first_pass,
     const int gc = grads.gc;   // channel planes behind dL_dcolor; channel C - 1 reads dL_dlast when gc < C; channels between: no gradient
     const float* __restrict__ final_T = final_T_all + (size_t)view * H * W;
     const uint32_t* __restrict__ n_contrib = n_contrib_all + (size_t)view * H * W;
-    const int lane = threadIdx.x;
-    const int qx = (tile % gx) * TILE + (quad & 1) * 8, qy = (tile / gx) * TILE + (quad >> 1) * 8;
-    const int px = qx + (lane & 7), py = qy + (lane >> 3);
-    const bool inside = px < W && py < H;
-    const float fx = (float)px, fy = (float)py;
-    const size_t plane = (size_t)H * W;
-    const size_t pix = inside ? (size_t)py * W + px : 0;
-    uint32_t beg = ranges[2 * gtile], end0 = ranges[2 * gtile + 1];
-    // split launches: wave blockIdx.y of the quadrant takes part blockIdx.y of the tile's list
+    const float fx = (float)F.px, fy = (float)F.py;
+    uint32_t beg = F.beg, end0 = F.end;
+    // split launches: wave blockIdx.y of the quadrant takes part blockIdx.y of the tile's list — the forward's partition (split_parts)
     const uint32_t list0 = beg;                                // list positions (n_contrib) count from the tile's first entry
     const bool split = !DET && NC <= 4 && ckpt_all != nullptr;   // (the accurate mode starts every list at its head)
     const int seg = split ? seg_y : 0;
-    const int np = (split && nparts != nullptr) ? (int)nparts[gtile] : SPLIT_PARTS;   // parts of this list (wave-uniform)
+    const SplitParts parts = split_parts(split, nparts, gtile, end0 - beg);
+    const int np = parts.np;
     if (split) {
-        const uint32_t part = split_part(end0 - beg, (uint32_t)np);
-        beg += (uint32_t)seg * part;
-        if (seg < np - 1) end0 = min(end0, beg + part);
+        take_part(parts, seg, beg, end0);
         if (beg >= end0) return;
     }
-    // (the forward wrote C_total + 2 planes per checkpoint k, taken in front of list entry beg + (k + 1) part: T, its C_total
-    //  colours so far, the depth so far — this pass may cover fewer channels)
     // Leave early: this quadrant only needs the list up to its deepest contributor, and a quadrant without a list or
     // without a contributor (empty regions of real frames, quadrants outside the image) has nothing to add — it returns
     // here, before the set-up loads its NC + 3 planes.
@@ -356,14 +396,13 @@ composite_bwd_kernel(int W, int H, int C_total, int CP4, int c0, int first_pass,
             if (from_ckpt) {
                 // later segments first (the smallest contributions), this boundary's neighbour last
                 float sfx = Tf * s_end;
-                const float* rec0 = ckpt_all + (size_t)view * SPLIT_PARTS_MAX * (C_total + 2) * plane + pix;
                 for (int k = np - 1; k > seg; --k) {
-                    const float* ck = rec0 + (size_t)k * (C_total + 2) * plane;
+                    const float* ck = segment_record(ckpt_all, F, C_total, k, 0);   // (T, the launch's C_total colours, the depth)
 #pragma unroll
                     for (int ch = 0; ch < NC; ++ch) sfx = fmaf(ck[(size_t)(1 + c0 + ch) * plane], g[ch], sfx);
                     if (AUX) sfx = fmaf(ck[(size_t)(1 + C_total) * plane], gD, sfx);
                 }
-                const float Tb = rec0[(size_t)(seg + 1) * (C_total + 2) * plane];
+                const float Tb = *segment_record(ckpt_all, F, C_total, seg + 1, 0);
                 T = (ST)Tb;
                 A = (ST)(sfx / Tb);        // (T_b >= 1e-4: the pixel was still active at the boundary)
             }
@@ -400,8 +439,7 @@ composite_bwd_kernel(int W, int H, int C_total, int CP4, int c0, int first_pass,
     const bool slot_col = sv < NV;
     const bool slot_ok = slotv < 2 * KV;
     const uint32_t slot_colv = (uint32_t)(slot_col ? (c0 + NM + sv) : (TM ? MO + 6 : MO + sv - NV));  // column of the Gaussian's row
-    const uint32_t slot_stride = WIDE ? GL.PV : GL.stride24(slot_colv);
-    const uint32_t slot_off = (WIDE ? pv_base : GL.base24(slot_colv, row0)) + slot_colv;
+    const uint32_t slot_stride = rows.stride(slot_colv, BUTTERFLY_COLS), slot_off = rows.offset(slot_colv, BUTTERFLY_COLS);
     int nslot = 0;  // Gaussians parked in the weight panel (wave-uniform)
     int e0 = 0;     // weight-panel slot of the E panel's column 0 (wave-uniform)
 
@@ -435,8 +473,7 @@ composite_bwd_kernel(int W, int H, int C_total, int CP4, int c0, int first_pass,
                     const bool full = 16 * t + 16 <= NM;   // every column of the block is a channel
                     const bool col_ok = full || c < NM || (XD && c == NM && first_pass);
                     const uint32_t col = (full || c < NM) ? (uint32_t)(c0 + c) : (uint32_t)(MO + 6);
-                    const uint32_t rowi = WIDE ? __umul24(gid, GL.SH) : __umul24(gid, GL.stride24(col)) + GL.base24(col, row0);
-                    if (col_ok) acc_add<DET>(gacc, gacc64, (size_t)(rowi + col), D[t][r], det_pass, det_drop);
+                    if (col_ok) rows.add(rows.index(gid, col, FLUSH_COLS), D[t][r]);
                 }
             }
         }
@@ -452,8 +489,8 @@ composite_bwd_kernel(int W, int H, int C_total, int CP4, int c0, int first_pass,
             __builtin_amdgcn_wave_barrier();
             const int eg = lane & 7, ei = lane >> 3;
             const float2 mu = s_emean[min(e0 + eg, GROUP - 1)];
-            const float dx = mu.x - (float)(qx + ei);
-            const float dy0 = mu.y - (float)qy;
+            const float dx = mu.x - (float)(F.qx + ei);
+            const float dy0 = mu.y - (float)F.qy;
             float m[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // sum E, sum E dy, sum E dy^2 (then the six moments)
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
@@ -470,8 +507,7 @@ composite_bwd_kernel(int W, int H, int C_total, int CP4, int c0, int first_pass,
             const float outv = wave_reduce_hi3<6>(m, lane);
             const int vi = ((lane >> 5) & 1) + 2 * ((lane >> 4) & 1) + 4 * ((lane >> 3) & 1);
             if (eg < count && vi < 6) {
-                const size_t di = (size_t)(__umul24(s_gid[e0 + eg], GL.PV) + pv_base + (uint32_t)(MO + vi));   // (the moments: per view)
-                acc_add<DET>(gacc, gacc64, di, outv, det_pass, det_drop);
+                rows.add(rows.index(s_gid[e0 + eg], (uint32_t)(MO + vi), GaccTable::VIEW), outv);
             }
             __builtin_amdgcn_wave_barrier();
         }
@@ -532,122 +568,81 @@ composite_bwd_kernel(int W, int H, int C_total, int CP4, int c0, int first_pass,
             }
             __builtin_amdgcn_wave_barrier();
             // One pair of candidates (list positions j0 > j1: the deeper one first; staged rows r0, r1); qm0 / qm1 are
-            // their dot products when the matrix pipe already produced them.
+            // their dot products when the matrix pipe already produced them.  What is done per entry is written once, for entry e
+            // of the pair (the compiler unrolls the two-trip loops over e: the arrays are registers; the statements keep the order they
+            // had when every line stood there twice — both loads, both offsets, ... — which the schedule of the pair loop follows).
             auto process_pair = [&](int j0, int j1, bool has1, int r0, int r1, float qm0, float qm1) {
-                const float4 p0 = s_rec0[r0], q0 = s_rec1[r0];
-                const float4 p1 = s_rec0[r1], q1 = s_rec1[r1];
-                const float dx0 = p0.x - fx, dy0 = p0.y - fy, dx1 = p1.x - fx, dy1 = p1.y - fy;
-                const float pw0 = gauss_log2(q0, dx0, dy0), pw1 = gauss_log2(q1, dx1, dy1);  // log2 of the weight
-                // (alpha is tested before the min with 0.99: same decision as the forward's, and a NaN from an overflowed power
-                //  is a miss — exp2_core; for the same reason a miss zeroes G below, not dL/dalpha)
-                const float Gr0 = exp2_core(pw0), Gr1 = exp2_core(pw1);
-                const float ar0 = q0.w * Gr0, ar1 = q1.w * Gr1;
-                const float al0 = fminf(ALPHA_MAX, ar0), al1 = fminf(ALPHA_MAX, ar1);
-                const bool hit0 = (idx0 + (uint32_t)j0 < last) && pw0 <= 0.0f && ar0 >= ALPHA_MIN;
-                const bool hit1 = has1 && (idx0 + (uint32_t)j1 < last) && pw1 <= 0.0f && ar1 >= ALPHA_MIN;
-                const float G0 = hit0 ? Gr0 : 0.0f, G1 = hit1 ? Gr1 : 0.0f;
+                const int r[2] = {r0, r1};
+                float4 p[2], q[2];
+                float dx[2], dy[2];
+                for (int e = 0; e < 2; ++e) p[e] = s_rec0[r[e]], q[e] = s_rec1[r[e]];
+                for (int e = 0; e < 2; ++e) dx[e] = p[e].x - fx, dy[e] = p[e].y - fy;
+                // alpha and its tests are the forward's (pair_alpha: a NaN from an overflowed power is a miss, which is why a miss
+                // zeroes G below, not dL/dalpha); which entries contribute is the forward's decision too (last = n_contrib)
+                const PairAlpha pa = pair_alpha(q[0], dx[0], dy[0], q[1], dx[1], dy[1]);
+                const float al[2] = {pa.al0, pa.al1}, Gr[2] = {pa.G0, pa.G1};
+                // (the flags stay scalars: as elements of an array they were materialised as bytes)
+                auto contributes = [&](int je, bool pass) { return (idx0 + (uint32_t)je < last) && pass; };
+                const bool hit0 = contributes(j0, pa.pass0), hit1 = has1 && contributes(j1, pa.pass1);
+                const float G[2] = {hit0 ? Gr[0] : 0.0f, hit1 ? Gr[1] : 0.0f};
                 // ---- dot products q = f . g (+ depth) of both Gaussians ----
-                float qd0 = qm0, qd1 = qm1;
+                float qd[2] = {qm0, qm1};
                 if (!DOTM) {
-                    const float* f0 = &s_feat[r0 * NCP];
-                    const float* f1 = &s_feat[r1 * NCP];
-                    qd0 = AUX ? p0.z * gD : 0.0f;
-                    qd1 = AUX ? p1.z * gD : 0.0f;
+                    for (int e = 0; e < 2; ++e) qd[e] = AUX ? p[e].z * gD : 0.0f;
 #pragma unroll
                     for (int ch = 0; ch < NC; ++ch) {
-                        qd0 += f0[ch] * g[ch];
-                        qd1 += f1[ch] * g[ch];
+                        for (int e = 0; e < 2; ++e) qd[e] += s_feat[r[e] * NCP + ch] * g[ch];
                     }
                     // a round's last pair may have no second member: row r0 + 1 is then stale (or never written: any bit
                     // pattern), and d = q - A with q = NaN would poison the chain — everything else of that half is masked
-                    qd1 = has1 ? qd1 : 0.0f;
+                    qd[1] = has1 ? qd[1] : 0.0f;
                 }
-                // ---- Gaussian 0 (the deeper one), then Gaussian 1: sequential in T and A ----
-                // Branch-free: a miss keeps T and A and has w = 0, E = G dA = 0.  T_i = T_{i+1} / (1 - alpha) through the hardware
-                // reciprocal (1 ulp; alpha <= 0.99 keeps the argument >= 0.01) — a relative error per step, harmless; the correctly
-                // rounded division would be 10 instructions per Gaussian.
-                float dA0, dA1, w0, w1;
-                if constexpr (DET) {
-                    const double Ti0 = hit0 ? T / (1.0 - (double)al0) : T;
-                    const double d0 = (double)qd0 - A;
-                    dA0 = (float)(Ti0 * d0);
-                    const double ah0 = hit0 ? (double)al0 : 0.0;
-                    A = fma(ah0, d0, A);
-                    w0 = (float)(ah0 * Ti0);
-                    const double Ti1 = hit1 ? Ti0 / (1.0 - (double)al1) : Ti0;
-                    const double d1 = (double)qd1 - A;
-                    dA1 = (float)(Ti1 * d1);
-                    const double ah1 = hit1 ? (double)al1 : 0.0;
-                    A = fma(ah1, d1, A);
-                    w1 = (float)(ah1 * Ti1);
-                    T = Ti1;
-                } else {
-                    const float Ti0 = hit0 ? T * __builtin_amdgcn_rcpf(1.0f - al0) : T;
-                    const float d0 = qd0 - A;
-                    dA0 = Ti0 * d0;                               // (finite also for a miss; E = G dA = 0 there)
-                    const float ah0 = hit0 ? al0 : 0.0f;
-                    A = fmaf(ah0, d0, A);
-                    w0 = ah0 * Ti0;
-                    const float Ti1 = hit1 ? Ti0 * __builtin_amdgcn_rcpf(1.0f - al1) : Ti0;
-                    const float d1 = qd1 - A;
-                    dA1 = Ti1 * d1;
-                    const float ah1 = hit1 ? al1 : 0.0f;
-                    A = fmaf(ah1, d1, A);
-                    w1 = ah1 * Ti1;
-                    T = Ti1;
-                }
-                const float E0 = G0 * dA0, E1 = G1 * dA1;   // (0 for a miss)
-                const uint32_t gi0 = s_cgid[r0], gi1 = s_cgid[r1];
+                // ---- Gaussian 0 (the deeper one), then Gaussian 1: sequential in T and A (walk_entry) ----
+                float dA[2], w[2], E[2];
+                uint32_t gi[2];
+                walk_entry<ST>(T, A, hit0, al[0], qd[0], dA[0], w[0]);
+                walk_entry<ST>(T, A, hit1, al[1], qd[1], dA[1], w[1]);
+                for (int e = 0; e < 2; ++e) E[e] = G[e] * dA[e];   // (0 for a miss)
+                for (int e = 0; e < 2; ++e) gi[e] = s_cgid[r[e]];
                 if constexpr (KV > 0) {
-                    float red[2 * KV];
+                    float red[2 * KV];   // [0, KV): entry 0, [KV, 2 KV): entry 1; of an entry: NV colours, the moments, the depth weight
 #pragma unroll
                     for (int ch = 0; ch < NV; ++ch) {
-                        red[ch] = w0 * g[NM + ch];
-                        red[KV + ch] = w1 * g[NM + ch];
+                        for (int e = 0; e < 2; ++e) red[e * KV + ch] = w[e] * g[NM + ch];
                     }
                     // geometric partials as raw moments of E = G dL/dalpha over the pixel offset d;
                     // the per-Gaussian factors (conic, opacity, 0.5 W / 0.5 H) are applied once per
                     // Gaussian in preprocess_bwd instead of once per (pixel, Gaussian) here
                     if constexpr (!TM) {
-                        const float Ex0 = E0 * dx0, Ey0 = E0 * dy0, Ex1 = E1 * dx1, Ey1 = E1 * dy1;
-                        red[NV + 0] = Ex0;
-                        red[NV + 1] = Ey0;
-                        red[NV + 2] = Ex0 * dx0;
-                        red[NV + 3] = Ex0 * dy0;
-                        red[NV + 4] = Ey0 * dy0;
-                        red[NV + 5] = E0;
-                        red[KV + NV + 0] = Ex1;
-                        red[KV + NV + 1] = Ey1;
-                        red[KV + NV + 2] = Ex1 * dx1;
-                        red[KV + NV + 3] = Ex1 * dy1;
-                        red[KV + NV + 4] = Ey1 * dy1;
-                        red[KV + NV + 5] = E1;
+                        for (int e = 0; e < 2; ++e) {
+                            const float Ex = E[e] * dx[e], Ey = E[e] * dy[e];
+                            red[e * KV + NV + 0] = Ex;
+                            red[e * KV + NV + 1] = Ey;
+                            red[e * KV + NV + 2] = Ex * dx[e];
+                            red[e * KV + NV + 3] = Ex * dy[e];
+                            red[e * KV + NV + 4] = Ey * dy[e];
+                            red[e * KV + NV + 5] = E[e];
+                        }
                     }
                     if constexpr (!XD && AUX) {
-                        red[KV - 1] = w0 * gD;
-                        red[2 * KV - 1] = w1 * gD;
+                        for (int e = 0; e < 2; ++e) red[e * KV + KV - 1] = w[e] * gD;
                     }
                     {
                         const float outv = wave_reduce_pack<2 * KV>(red, lane);
-                        const uint32_t gi = slot_second ? gi1 : gi0;
-                        const size_t di = (size_t)(__umul24(gi, slot_stride) + slot_off);   // gi < 2^24 (checked on the host)
-                        if (slot_ok && (has1 || !slot_second)) acc_add<DET>(gacc, gacc64, di, outv, det_pass, det_drop);
+                        const uint32_t gid = slot_second ? gi[1] : gi[0];
+                        if (slot_ok && (has1 || !slot_second)) rows.add(rows.index(gid, slot_stride, slot_off), outv);
                     }
                 }
                 if constexpr (MFMA) {
                     // park the weights (0 for pixels that miss); a pair never straddles a flush
-                    s_w[lane * WS + nslot] = w0;
-                    s_w[lane * WS + nslot + 1] = w1;
+                    for (int e = 0; e < 2; ++e) s_w[lane * WS + nslot + e] = w[e];
                     if constexpr (TM) {   // and E = G dL/dalpha in the 8-column panel (column = slot - e0)
-                        s_e[lane * ES + (nslot - e0)] = E0;
-                        s_e[lane * ES + (nslot - e0) + 1] = E1;
+                        for (int e = 0; e < 2; ++e) s_e[lane * ES + (nslot - e0) + e] = E[e];
                     }
                     if (lane == 0) {
-                        s_gid[nslot] = gi0;
-                        s_gid[nslot + 1] = gi1;
+                        for (int e = 0; e < 2; ++e) s_gid[nslot + e] = gi[e];
                         if constexpr (TM) {
-                            s_emean[nslot] = make_float2(p0.x, p0.y);
-                            s_emean[nslot + 1] = make_float2(p1.x, p1.y);
+                            for (int e = 0; e < 2; ++e) s_emean[nslot + e] = make_float2(p[e].x, p[e].y);
                         }
                     }
                     nslot += has1 ? 2 : 1;
@@ -775,11 +770,9 @@ static int launch_one_bwd(const FramePlan& p, int c0, int first, const BinView& 
     return SPLATRASTER_OK;
 }
 
-int launch_composite_bwd(const FramePlan& p, int64_t R, const GeomView& g,
-                         const BinView& b, const ImgView& im, const float* feat, int feat_stride,
+int launch_composite_bwd(const FramePlan& p, int64_t R, const BinView& b, const ImgView& im, const float* feat, int feat_stride,
                          const WinGrad& grads, float* gacc, long long* gacc64, int det_pass, hipStream_t stream)
 {
-    (void)g;
     if (R == 0) return SPLATRASTER_OK;
     const bool det = gacc64 != nullptr;
     int C = p.C;
@@ -803,14 +796,7 @@ int launch_composite_bwd(const FramePlan& p, int64_t R, const GeomView& g,
         return launch_one_bwd<3, false, false>(p, 0, 1, b, im, feat, feat_stride, L, gacc, gacc64, stream);
 #define SR_BWD_ARGS b, im, feat, feat_stride, L, gacc, gacc64, stream
 #define SR_BWD_ONE(N, c0_, first_) (det ? launch_one_bwd<N, true>(p, c0_, first_, SR_BWD_ARGS) : launch_one_bwd<N, false>(p, c0_, first_, SR_BWD_ARGS))
-#define SR_BWD_CASE(N) \
-    case N: return SR_BWD_ONE(N, 0, 1);
-    switch (C) {
-        SR_BWD_CASE(1) SR_BWD_CASE(2) SR_BWD_CASE(3) SR_BWD_CASE(4) SR_BWD_CASE(8) SR_BWD_CASE(16)
-        SR_BWD_CASE(32) SR_BWD_CASE(35)
-        default: break;
-    }
-#undef SR_BWD_CASE
+    if (C == 35) return SR_BWD_ONE(35, 0, 1);   // the headline layout has a kernel of its own; everything else is tiled greedily
     int c0 = 0, first = 1, st = SPLATRASTER_OK;
     while (c0 < C && st == SPLATRASTER_OK) {
         const int left = C - c0;

@@ -1,5 +1,8 @@
-// composite_common.h — pieces shared by the forward and backward compositing kernels.
+// composite_common.h — pieces shared by the forward and backward compositing kernels: the reach test, the alpha arithmetic, the
+// quadrant's frame, the split partition and the segment records (everything both passes must agree on), block ids, reductions.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 namespace sr {
@@ -48,31 +51,6 @@ __device__ __forceinline__ unsigned quadrant_reach_mask(const float4 r0, const f
         if (qmin <= lim) mask |= 1u << q;
     }
     return mask;
-}
-
-// Same test for ONE quadrant whose first pixel centre is (bx0, by0).
-__device__ __forceinline__ bool quadrant_reach(const float4 r0, const float4 r1, float bx0, float by0)
-{
-    const float A = r1.x, B = r1.y, C = r1.z;
-    const float lim0 = 2.0f * __logf(255.0f * r1.w);
-    const float lim = lim0 + 0.02f + 1e-4f * fabsf(lim0);
-    const float u0 = r0.x - (bx0 + 7.0f), u1 = r0.x - bx0;
-    const float v0 = r0.y - (by0 + 7.0f), v1 = r0.y - by0;
-    float qmin = 0.0f;
-    if (!(u0 <= 0.0f && u1 >= 0.0f && v0 <= 0.0f && v1 >= 0.0f)) {
-        const float nBrA = -B * __frcp_rn(A), nBrC = -B * __frcp_rn(C);
-        qmin = 3.0e38f;
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            const float ue = e ? u1 : u0;
-            const float vs = fminf(v1, fmaxf(v0, nBrC * ue));
-            qmin = fminf(qmin, A * ue * ue + 2.0f * B * ue * vs + C * vs * vs);
-            const float ve = e ? v1 : v0;
-            const float us = fminf(u1, fmaxf(u0, nBrA * ve));
-            qmin = fminf(qmin, A * us * us + 2.0f * B * us * ve + C * ve * ve);
-        }
-    }
-    return (lim > 0.0f) && (qmin <= lim);
 }
 
 // The per-instance payload stores the conic pre-scaled for the compositing kernels:
@@ -160,11 +138,112 @@ __host__ __device__ static inline unsigned quadrant_blocks(int tiles, int gx)
     return (unsigned)((tiles + 7) / 8) * 32u;
 }
 
-__device__ __forceinline__ uint64_t uniform_u64(uint64_t v)
+// ---- what the forward and the backward must agree on: each is written once, here ---------------------------------
+// The forward's three walkers (composite_fwd.hip) and the backward (composite_bwd.hip) build their quadrant's frame, evaluate alpha
+// and its two tests, cut a split list into parts and address a segment record through these bodies and no others.
+
+__device__ __forceinline__ int tile_columns(int W) { return (W + TILE - 1) / TILE; }
+
+// what a wave knows about its 8x8 quadrant of global tile `gtile` (= view * tiles + tile) and about its lane's pixel in it
+struct QuadFrame {
+    int view;            // wave-uniform (scalar)
+    uint32_t row0;       // the view's first row: feature row of row g is g - row0
+    int qx, qy, px, py;  // the quadrant's and the lane's first / own pixel
+    bool inside;
+    uint32_t beg, end;   // the tile's list
+    size_t plane, pix;   // H * W; the pixel's offset in a plane
+};
+__device__ __forceinline__ QuadFrame quadrant_frame(int W, int H, int tiles, int V, int P, const uint32_t* __restrict__ ranges, int gtile,
+                                                    int quad, int lane)
 {
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v);
-    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return ((uint64_t)hi << 32) | lo;
+    QuadFrame F;
+    const int gx = tile_columns(W);
+    F.view = (V == 1) ? 0 : gtile / tiles;
+    const int tile = gtile - F.view * tiles;
+    F.row0 = (uint32_t)F.view * (uint32_t)P;
+    F.qx = (tile % gx) * TILE + (quad & 1) * 8, F.qy = (tile / gx) * TILE + (quad >> 1) * 8;
+    F.px = F.qx + (lane & 7), F.py = F.qy + (lane >> 3);
+    F.inside = F.px < W && F.py < H;
+    F.beg = ranges[2 * gtile], F.end = ranges[2 * gtile + 1];
+    F.plane = (size_t)H * W;
+    F.pix = (size_t)F.py * W + F.px;
+    return F;
+}
+
+// the packed word (id | reach bits << 24) of list entry `at`; 0 (reaches nothing) behind the list's end
+__device__ __forceinline__ uint32_t list_word(const uint32_t* __restrict__ ipack, uint32_t at, uint32_t end) { return at < end ? ipack[at] : 0u; }
+
+// alpha of two Gaussians (q: pre-scaled conic, opacity) at offsets d = centre - pixel, and whether each passes the tests.  Alpha is
+// tested BEFORE the min with 0.99: a NaN from an overflowed power is a miss, which is the only thing the argument clamp of exp2_shared
+// was there for.  The absent candidate (opacity 0) never passes.  G = the raw weight 2^power, which the backward multiplies dL/dalpha
+// with (zeroed there for a miss: G, not dL/dalpha — the same NaN); the forward leaves it unused.
+struct PairAlpha { float al0, al1; bool pass0, pass1; float G0, G1; };
+__device__ __forceinline__ PairAlpha pair_alpha(const float4& q0, float dx0, float dy0, const float4& q1, float dx1, float dy1)
+{
+    const float pw0 = gauss_log2(q0, dx0, dy0), pw1 = gauss_log2(q1, dx1, dy1);  // log2 of the weight
+    const float G0 = exp2_core(pw0), ar0 = q0.w * G0, G1 = exp2_core(pw1), ar1 = q1.w * G1;
+    return {fminf(ALPHA_MAX, ar0), fminf(ALPHA_MAX, ar1), pw0 <= 0.0f && ar0 >= ALPHA_MIN, pw1 <= 0.0f && ar1 >= ALPHA_MIN, G0, G1};
+}
+
+// ---- split launches (common.h): the backward runs several waves per quadrant, one per part of the list.  Segment record k
+// = { T in front of the segment's first entry, the colours and the depth the segment ALONE contributes } — segment sums are
+// accumulated from zero, so they are accurate relative to their own (transmittance-scaled) magnitude; the backward rebuilds "what
+// lies behind a boundary" from the sums of the later segments (a prefix C_k subtracted from the image would carry the image's
+// rounding, 1e-7 |C|, into a remainder of size T_k |C|).
+// THE partition of a split list of `len` entries: part k = entries [k part, (k + 1) part) of the list, the last part to its end
+struct SplitParts {
+    int np;         // parts of this list (wave-uniform)
+    uint32_t part;  // entries per part; 0: not a split launch
+};
+__device__ __forceinline__ SplitParts split_parts(bool split, const uint32_t* __restrict__ nparts, int gtile, uint32_t len)
+{
+    SplitParts s;
+    s.np = (split && nparts != nullptr) ? (int)nparts[gtile] : SPLIT_PARTS;
+    s.part = split ? split_part(len, (uint32_t)s.np) : 0u;
+    return s;
+}
+// the backward's wave of part k: [beg, end) shrinks from the list to that part
+__device__ __forceinline__ void take_part(const SplitParts& s, int k, uint32_t& beg, uint32_t& end)
+{
+    beg += (uint32_t)k * s.part;
+    if (k < s.np - 1) end = min(end, beg + s.part);
+}
+// the forward walks all parts in one go
+struct SplitCursor {
+    int np;         // parts of this list (wave-uniform)
+    uint32_t part;  // entries per part; 0: not a split launch
+    uint32_t at;    // the entry the current segment ends in front of
+    int k;          // the current segment
+};
+__device__ __forceinline__ SplitCursor split_cursor(const float* ckpt_all, const uint32_t* __restrict__ nparts, int gtile, uint32_t beg,
+                                                    uint32_t end)
+{
+    const SplitParts s = split_parts(ckpt_all != nullptr, nparts, gtile, end - beg);
+    SplitCursor c;
+    c.np = s.np;
+    c.part = s.part;
+    c.at = c.part ? beg + c.part : 0xFFFFFFFFu;
+    c.k = 0;
+    return c;
+}
+// a segment ends in front of entry `base`: the cursor moves on to the next one (the segment that ended is c.k - 1)
+__device__ __forceinline__ bool segment_ends(SplitCursor& c, uint32_t base)
+{
+    if (base != c.at) return false;
+    ++c.k;
+    c.at = c.k < c.np - 1 ? c.at + c.part : 0xFFFFFFFFu;
+    return true;
+}
+// plane `pl` of the pixel's segment record k: ckpt_all is [V][SPLIT_PARTS_MAX][nc + 2][H * W], plane 0 = T, 1 .. nc colours, nc + 1 depth.
+// nc = the channels of the LAUNCH: the forward's template constant, handed over as Channels<NC> (a type, so that the record's stride is
+// a constant where the address is formed); the backward's runtime C_total, whose pass may cover fewer.  F32 = float for the forward,
+// which writes the records, const float for the backward.
+template <int N>
+using Channels = std::integral_constant<int, N>;
+template <typename F32, typename Count>
+__device__ __forceinline__ F32* segment_record(F32* __restrict__ ckpt_all, const QuadFrame& F, Count nc, int k, int pl)
+{
+    return ckpt_all + (((size_t)F.view * SPLIT_PARTS_MAX + k) * (nc + 2) + pl) * F.plane + F.pix;
 }
 
 // ---- DPP helpers (wave64 = 4 rows of 16 lanes) -----------------------------------------

@@ -97,38 +97,9 @@ __device__ __forceinline__ int first_bit(uint64_t m)
 
 // ---- the steps every walker of a tile list shares -------------------------------------------------------------------------------
 // composite_fwd_kernel (wide layouts), narrow_quadrant (C <= 4, one wave) and team_quadrant (C <= 4, four waves) do the same
-// operations on the same operands in the same order because each of these steps is written once, here.
-
-__device__ __forceinline__ int tile_columns(int W) { return (W + TILE - 1) / TILE; }
-
-// what a wave knows about its 8x8 quadrant of global tile `gtile` (= view * tiles + tile) and about its lane's pixel in it
-struct QuadFrame {
-    int view;            // wave-uniform (scalar)
-    uint32_t row0;       // the view's first row: feature row of row g is g - row0
-    int qx, qy, px, py;  // the quadrant's and the lane's first / own pixel
-    bool inside;
-    uint32_t beg, end;   // the tile's list
-    size_t plane, pix;   // H * W; the pixel's offset in a plane
-};
-__device__ __forceinline__ QuadFrame quadrant_frame(int W, int H, int tiles, int V, int P, const uint32_t* __restrict__ ranges, int gtile,
-                                                    int quad, int lane)
-{
-    QuadFrame F;
-    const int gx = tile_columns(W);
-    F.view = (V == 1) ? 0 : gtile / tiles;
-    const int tile = gtile - F.view * tiles;
-    F.row0 = (uint32_t)F.view * (uint32_t)P;
-    F.qx = (tile % gx) * TILE + (quad & 1) * 8, F.qy = (tile / gx) * TILE + (quad >> 1) * 8;
-    F.px = F.qx + (lane & 7), F.py = F.qy + (lane >> 3);
-    F.inside = F.px < W && F.py < H;
-    F.beg = ranges[2 * gtile], F.end = ranges[2 * gtile + 1];
-    F.plane = (size_t)H * W;
-    F.pix = (size_t)F.py * W + F.px;
-    return F;
-}
-
-// the packed word (id | reach bits << 24) of list entry `at`; 0 (reaches nothing) behind the list's end
-__device__ __forceinline__ uint32_t list_word(const uint32_t* __restrict__ ipack, uint32_t at, uint32_t end) { return at < end ? ipack[at] : 0u; }
+// operations on the same operands in the same order because each of these steps is written once: here, or
+// — what the backward shares too: quadrant_frame, list_word, pair_alpha, split_cursor / segment_ends, segment_record — in
+// composite_common.h.
 
 // the next two candidates of a chunk, front to back; j1 = -1 when one was left: the ABSENT candidate (an empty mask stays empty)
 __device__ __forceinline__ void next_pair(uint64_t& cand, int& j0, int& j1)
@@ -137,17 +108,6 @@ __device__ __forceinline__ void next_pair(uint64_t& cand, int& j0, int& j1)
     cand &= cand - 1;
     j1 = first_bit(cand);
     cand &= cand - 1;
-}
-
-// alpha of two Gaussians (q: pre-scaled conic, opacity) at offsets d = centre - pixel, and whether each passes the tests.  Alpha is
-// tested BEFORE the min with 0.99, like the backward: a NaN from an overflowed power is a miss, which is the only thing the argument
-// clamp of exp2_shared was there for (composite_common.h).  The absent candidate (opacity 0) never passes.
-struct PairAlpha { float al0, al1; bool pass0, pass1; };
-__device__ __forceinline__ PairAlpha pair_alpha(const float4& q0, float dx0, float dy0, const float4& q1, float dx1, float dy1)
-{
-    const float pw0 = gauss_log2(q0, dx0, dy0), pw1 = gauss_log2(q1, dx1, dy1);  // log2 of the weight
-    const float ar0 = q0.w * exp2_core(pw0), ar1 = q1.w * exp2_core(pw1);
-    return {fminf(ALPHA_MAX, ar0), fminf(ALPHA_MAX, ar1), pw0 <= 0.0f && ar0 >= ALPHA_MIN, pw1 <= 0.0f && ar1 >= ALPHA_MIN};
 }
 
 // the transmittance chain over a pair: the blending weights w = alpha T (0: no hit), T and `active` (pixel still accumulating) moved on
@@ -181,45 +141,10 @@ __device__ __forceinline__ void accumulate_pair(float (&acc)[N], float& D, const
     D = fmaf(z1, w1, fmaf(z0, w0, D));
 }
 
-// ---- split launches (common.h): the backward runs several waves per quadrant, one per part of the list.  Segment record k
-// = { T in front of the segment's first entry, the colours and the depth the segment ALONE contributes } — segment sums are
-// accumulated from zero, so they are accurate relative to their own (transmittance-scaled) magnitude; the backward rebuilds "what
-// lies behind a boundary" from the sums of the later segments (a prefix C_k subtracted from the image would carry the image's
-// rounding, 1e-7 |C|, into a remainder of size T_k |C|).
-struct SplitCursor {
-    int np;         // parts of this list (wave-uniform)
-    uint32_t part;  // entries per part; 0: not a split launch
-    uint32_t at;    // the entry the current segment ends in front of
-    int k;          // the current segment
-};
-__device__ __forceinline__ SplitCursor split_cursor(const float* ckpt_all, const uint32_t* __restrict__ nparts, int gtile, uint32_t beg,
-                                                    uint32_t end)
-{
-    SplitCursor c;
-    c.np = (ckpt_all != nullptr && nparts != nullptr) ? (int)nparts[gtile] : SPLIT_PARTS;
-    c.part = ckpt_all != nullptr ? split_part(end - beg, (uint32_t)c.np) : 0u;
-    c.at = c.part ? beg + c.part : 0xFFFFFFFFu;
-    c.k = 0;
-    return c;
-}
-// a segment ends in front of entry `base`: the cursor moves on to the next one (the segment that ended is c.k - 1)
-__device__ __forceinline__ bool segment_ends(SplitCursor& c, uint32_t base)
-{
-    if (base != c.at) return false;
-    ++c.k;
-    c.at = c.k < c.np - 1 ? c.at + c.part : 0xFFFFFFFFu;
-    return true;
-}
-// plane `pl` of the pixel's segment record k: ckpt_all is [V][SPLIT_PARTS_MAX][NC + 2][H * W], plane 0 = T, 1 .. NC colours, NC + 1 depth
-template <int NC>
-__device__ __forceinline__ float* segment_record(float* __restrict__ ckpt_all, const QuadFrame& F, int k, int pl)
-{
-    return ckpt_all + (((size_t)F.view * SPLIT_PARTS_MAX + k) * (NC + 2) + pl) * F.plane + F.pix;
-}
 template <int NC>
 __device__ __forceinline__ void store_segment_sums(float* __restrict__ ckpt_all, const QuadFrame& F, int k, const float (&sacc)[NC], float sD)
 {
-    float* ck = segment_record<NC>(ckpt_all, F, k, 1);
+    float* ck = segment_record(ckpt_all, F, Channels<NC>{}, k, 1);
 #pragma unroll
     for (int ch = 0; ch < NC; ++ch) ck[(size_t)ch * F.plane] = sacc[ch];
     ck[(size_t)NC * F.plane] = sD;
@@ -539,7 +464,7 @@ __device__ __forceinline__ void narrow_quadrant(SR_FWD_PARAMS, int gtile, int qu
         if (segment_ends(cur, base)) {   // its sums, and T in front of the next one (plane 0 of that record)
             if (F.inside) {
                 store_segment_sums<NC>(ckpt_all, F, cur.k - 1, sacc, sD);
-                *segment_record<NC>(ckpt_all, F, cur.k, 0) = T;
+                *segment_record(ckpt_all, F, Channels<NC>{}, cur.k, 0) = T;
             }
 #pragma unroll
             for (int ch = 0; ch < NC; ++ch) sacc[ch] = 0.0f;
@@ -752,7 +677,7 @@ __device__ __forceinline__ void team_quadrant(SR_FWD_PARAMS, int gtile, int quad
         float T = 1.0f;
         uint32_t last = 0;
         auto boundary = [&] {   // a segment ends in front of this entry: plane 0 of the next record = T in front of it
-            if (segment_ends(cur, base) && F.inside) *segment_record<NC>(ckpt_all, F, cur.k, 0) = T;
+            if (segment_ends(cur, base) && F.inside) *segment_record(ckpt_all, F, Channels<NC>{}, cur.k, 0) = T;
         };
         bool finished = false;
         int fin_it = __builtin_amdgcn_ballot_w64(active) == 0 ? 0 : -1;    // the iteration to announce as the last one

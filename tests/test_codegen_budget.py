@@ -82,6 +82,15 @@ def test_backward_kernels_stay_within_their_register_budget():
     assert ref["ScratchSize"] == 0 and ref["Occupancy"] >= 5, ref
     refine = _kernel(u, "_ZN2sr20composite_bwd_kernelILi3ELb0ELb0ELb0E")       # color_refinement: 3 channels, no depth / alpha terms
     assert refine["ScratchSize"] == 0 and refine["Occupancy"] == 8, refine
+    # every other instantiation <NC, DET, SP> (AUX = true), each at the waves per SIMD and the scratch it had before the kernel took its
+    # frame, alpha test, partition and segment records from composite_common.h (HISTORY.md §22)
+    others = {(8, 0, 0): (7, 0), (8, 0, 1): (5, 0), (16, 0, 0): (5, 0), (4, 1, 1): (5, 0), (4, 1, 0): (7, 0), (8, 1, 0): (6, 0),
+              (8, 1, 1): (4, 0), (16, 1, 0): (4, 0), (32, 0, 0): (4, 8),
+              (1, 1, 0): (8, 0), (2, 1, 0): (8, 0), (3, 1, 0): (8, 0), (4, 0, 0): (8, 0), (32, 1, 0): (4, 12), (35, 1, 0): (4, 20)}
+    for (nc, det, sp), (waves, scratch) in others.items():
+        k = _kernel(u, f"_ZN2sr20composite_bwd_kernelILi{nc}ELb{det}ELb{sp}ELb1E")
+        assert k["Occupancy"] >= waves and k["ScratchSize"] <= scratch, ((nc, det, sp), k)
+    assert len([k for k in u if "composite_bwd_kernel" in k]) == 6 + len(others), list(u)   # all 21 are named above
 
 
 def test_per_gaussian_backward_kernels_keep_their_occupancy():

@@ -490,19 +490,30 @@ def test_device_exp2_is_the_oracles_exp2_bit_for_bit():
 @pytest.mark.parametrize("cfg", [
     dict(P=6_000, W=320, H=240, C=4, seed=81, scale_median=0.03),     # reference channel layout (VALU reductions)
     dict(P=4_000, W=333, H=201, C=35, seed=82, scale_median=0.03),    # matrix-pipe reductions + butterfly
+    # every other instantiation of the deterministic walk (its state in double), on one small frame, ragged on both axes (110 = 13 x 8
+    # + 6, 76 = 9 x 8 + 4): all 35 lists longer than 128 entries (median 242, longest 285: four to five chunks, several flushes per
+    # walk), 8 360 pixels with their last contributor beyond position 64, 27.5 % ending with final_T < 1e-3 (early end and full walk)
+    *[dict(P=2_500, W=110, H=76, C=c, seed=58, scale_median=0.06) for c in (1, 2, 3, 8, 16, 32, 40)],   # 40 = passes of 32 + 8
+    # the butterfly variants <4, true, false> and <8, true, false>, which a frame this small does not take on its own
+    *[dict(P=2_500, W=110, H=76, C=c, seed=58, scale_median=0.06, small_panel_max_waves=0) for c in (4, 8)],
 ])
 def test_deterministic_sum_mode_is_bit_reproducible_and_strict(cfg):
     """Deterministic-sum debug mode (splatraster_debug_set_deterministic): the per-Gaussian gradient rows are summed
     with 64-bit integer atomics in 2^-40 fixed point, so two runs agree BIT FOR BIT (the float-atomic mode agrees
     only to rounding), and the gradients meet a 20x tighter bar against the oracle's double-precision sums."""
     from splatloc_amd import _native
+    cfg = dict(cfg)
+    panel_waves = cfg.pop("small_panel_max_waves", -1)   # -1: the library's own threshold
     sc = make_scene(**cfg)
     b = oracle_backward(oracle_forward(sc), sc)
+    lib = _native.load()
     _native.set_deterministic(True)
     try:
+        lib.splatraster_debug_set_small_panel_max_waves(panel_waves)
         runs = [HipRun(sc) for _ in range(3)]
     finally:
         _native.set_deterministic(False)
+        lib.splatraster_debug_set_small_panel_max_waves(-1)
     names = ["means3D", "means2D", "opacities", "colors", "scales", "rotations"]
     for r in runs[1:]:
         for n in names:

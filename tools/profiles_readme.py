@@ -57,6 +57,7 @@ WHAT = [   # (file name regex, description; {placeholders} are filled by the ext
     (r"^payload_compact_kernel_stats\.txt$", "`rocprofv3 --kernel-trace --stats` of the default bench, parent (first listing) and the compact payload (second; DESIGN §3.1), us per launch: {pc_kstats}"),
     (r"^payload_compact_pmc_hbm\.json$", "separate `--pmc FETCH_SIZE` / `--pmc WRITE_SIZE` runs of the default bench, parent and change, for the payload and the two compositing kernels, and the live fraction of the window's tile instances read through `introspect.payload_state`: {pc_pmc}"),
     (r"^fwd_shared_steps_ab\.json$", "`tools/ab.py`, base = the change (the forward walkers' shared steps, HISTORY §21), variant `parent` = the parent commit's library (differences are parent minus change): {ab}; the other workloads, `--stage refine_step`, the `composite_fwd` stage in ms and cycles and the bit-for-bit comparison of the outputs under `other_runs` / `outputs_parent_vs_change`"),
+    (r"^bwd_shared_contract_ab\.json$", "`tools/ab.py`, base = the change (the backward takes its frame, alpha test, partition and segment records from `composite_common.h`, HISTORY §22), variant `parent` = the parent commit's library (differences are parent minus change): {ab}; the other runs that were made, `--stage refine_step`, the `composite_bwd` stage in ms and cycles and the bit-for-bit comparison of outputs and deterministic-mode gradients under `other_runs` / `outputs_parent_vs_change`"),
     (r"^payload_compact_ab.*\.json$", "`tools/ab.py`, base = the change (compact payload), variant `parent` = the parent commit's library (differences are parent minus change): {ab}; {pc_ab}"),
     (r"traffic\.json$", "per-stage HBM bytes per launch that `bench.py` replays as `roofline.traffic` (recorded workload / launch mode inside)"),
     (r"valu\.json$", "VALU / MFMA / SALU wave-instructions, busy fractions of the two compositing kernels per launch (replayed by `bench.py` as `frame_valu` / `roofline_valu`)"),
