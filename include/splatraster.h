@@ -447,10 +447,37 @@ int splatraster_get_window_binning_layout(int32_t P, int32_t n_views, int64_t R_
 int splatraster_get_window_image_layout(int32_t width, int32_t height, int32_t n_views, splatraster_image_layout* out);
 
 /* Stable LSD radix sort of (key, value) pairs on key bits [0, key_bits); exposed so the
- * sort can be tested and timed on its own.  tmp must hold splatraster_sort_tmp_bytes(n). */
+ * sort can be tested and timed on its own.  tmp must hold splatraster_sort_tmp_bytes(n).  The sort moves whole 8-bit
+ * digits: it orders by bits [0, 8 * ceil(key_bits / 8)), and key bits at or above that ride along unsorted. */
 size_t splatraster_sort_tmp_bytes(int64_t n);
 int splatraster_sort_pairs_u32(int64_t n, uint32_t* keys, uint32_t* vals, int32_t key_bits,
                                void* tmp, void* stream);
+
+/* ---- test hooks of the scan and the sort (tests/test_gpu_scan_sort_edges.py); no product code calls them ---- */
+
+/* Host only, no HIP call: the form a sort of n keys takes.  0 nothing to do (n or key_bits 0), 1 one-sweep with 2048-key
+ * tiles, 2 one-sweep with 4096-key tiles, 3 histogram / scan / scatter kernels per pass, 4 the same on uint16_t keys
+ * (keys16 != 0: the answer for splatraster_debug_sort_pairs_k16); +8 when the table scan of a pass takes three kernels.
+ * -1: arguments the sort itself refuses (n < 0, key_bits outside [0, 32], keys16 where the sort has no uint16_t form). */
+int splatraster_debug_sort_path(int64_t n, int32_t key_bits, int32_t keys16);
+/* Host only: the form a scan of n words takes.  0 nothing to do, 1 one-pass decoupled look-back, 2 three kernels; -1: n < 0. */
+int splatraster_debug_scan_path(int64_t n);
+/* bytes of `tmp` for splatraster_debug_scan_u32 */
+size_t splatraster_debug_scan_tmp_bytes(int64_t n);
+/* The device-wide prefix sum that every stage uses.  out[i] = sum of v[0..i] (inclusive) or v[0..i) (exclusive) mod 2^32,
+ * *total (optional) the exact 64-bit sum; a tile of 2048 consecutive values must sum below 2^32.  v[i] = in[i], or with `perm`
+ * in[perm[i] & 0xFFFFFF], where bits 24..31 of perm[i] hold min(in[row], 255) and rows are < n (the packed depth order of the
+ * rasterizer).  in == out is allowed without `perm`; `exclusive` requires it, and takes no perm and no span_owner.  span_owner
+ * (inclusive only, span > 0): for every b < span_cap with b * span < total, span_owner[b] = the i with
+ * out[i - 1] <= b * span < out[i]; other entries are not written, and the three-kernel form writes none.  The call clears the
+ * state it needs in `tmp` itself.  Bad arguments are refused before any HIP call. */
+int splatraster_debug_scan_u32(int64_t n, const uint32_t* in, const uint32_t* perm, uint32_t* out, uint64_t* total,
+                               int32_t exclusive, uint32_t* span_owner, uint32_t span, uint32_t span_cap, void* tmp,
+                               void* stream);
+/* splatraster_sort_pairs_u32 in the uint16_t form of the tile sort: on entry the first half of `keys` holds n uint16_t keys,
+ * on return `keys` holds the n sorted keys as uint32_t.  key_bits <= 16 and a size at which splatraster_debug_sort_path(n,
+ * key_bits, 1) is not -1, else SPLATRASTER_ERR_BAD_ARG.  tmp must hold splatraster_sort_tmp_bytes(n). */
+int splatraster_debug_sort_pairs_k16(int64_t n, uint32_t* keys, uint32_t* vals, int32_t key_bits, void* tmp, void* stream);
 
 /* ---- parameter activations + SH / feature packing -------------------- */
 

@@ -192,6 +192,11 @@ SYMBOLS = {
     "splatraster_get_image_layout": (C.c_int, [_i32, _i32, C.POINTER(ImageLayout)]),
     "splatraster_sort_tmp_bytes": (_sz, [_i64]),
     "splatraster_sort_pairs_u32": (C.c_int, [_i64, _vp, _vp, _i32, _vp, _vp]),
+    "splatraster_debug_sort_path": (C.c_int, [_i64, _i32, _i32]),
+    "splatraster_debug_scan_path": (C.c_int, [_i64]),
+    "splatraster_debug_scan_tmp_bytes": (_sz, [_i64]),
+    "splatraster_debug_scan_u32": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _i32, _vp, C.c_uint32, C.c_uint32, _vp, _vp]),
+    "splatraster_debug_sort_pairs_k16": (C.c_int, [_i64, _vp, _vp, _i32, _vp, _vp]),
     "splatraster_timing_enable": (C.c_int, [C.c_int]),
     "splatraster_timing_select": (C.c_int, [C.c_uint32]),
     "splatraster_timing_collect": (C.c_int, [_vp, _vp]),

@@ -1153,11 +1153,9 @@ size_t splatraster_sort_tmp_bytes(int64_t n)
     return align_up(4 * m, 256) * 2 + sort_tmp_bytes(n);
 }
 
-int splatraster_sort_pairs_u32(int64_t n, uint32_t* keys, uint32_t* vals, int32_t key_bits, void* tmp,
-                               void* stream_)
+// keys / vals sorted in place: the alternate arrays are the first two sections of tmp, the sort's own scratch the third
+static int sort_in_place(bool keys16, int64_t n, uint32_t* keys, uint32_t* vals, int32_t key_bits, void* tmp, void* stream_)
 {
-    if (n < 0 || key_bits < 0 || key_bits > 32) return SPLATRASTER_ERR_BAD_ARG;
-    if (n == 0 || key_bits == 0) return SPLATRASTER_OK;
     if (!keys || !vals || !tmp) return SPLATRASTER_ERR_BAD_ARG;
     {
         int st0 = lookback_error_init();
@@ -1169,13 +1167,57 @@ int splatraster_sort_pairs_u32(int64_t n, uint32_t* keys, uint32_t* vals, int32_
     uint32_t* ka = reinterpret_cast<uint32_t*>(t);
     uint32_t* va = reinterpret_cast<uint32_t*>(t + stride);
     bool in_alt = false;
-    int st = sort_pairs_u32(n, keys, vals, ka, va, key_bits, t + 2 * stride, stream, &in_alt);
+    int st = keys16 ? sort_pairs_k16(n, keys, vals, ka, va, key_bits, t + 2 * stride, stream, &in_alt)
+                    : sort_pairs_u32(n, keys, vals, ka, va, key_bits, t + 2 * stride, stream, &in_alt);
     if (st) return st;
     if (in_alt) {
         SR_HIP_CHECK(hipMemcpyAsync(keys, ka, 4 * (size_t)n, hipMemcpyDeviceToDevice, stream));
         SR_HIP_CHECK(hipMemcpyAsync(vals, va, 4 * (size_t)n, hipMemcpyDeviceToDevice, stream));
     }
     return SPLATRASTER_OK;
+}
+
+int splatraster_sort_pairs_u32(int64_t n, uint32_t* keys, uint32_t* vals, int32_t key_bits, void* tmp,
+                               void* stream_)
+{
+    if (n < 0 || key_bits < 0 || key_bits > 32) return SPLATRASTER_ERR_BAD_ARG;
+    if (n == 0 || key_bits == 0) return SPLATRASTER_OK;
+    return sort_in_place(false, n, keys, vals, key_bits, tmp, stream_);
+}
+
+int splatraster_debug_sort_pairs_k16(int64_t n, uint32_t* keys, uint32_t* vals, int32_t key_bits, void* tmp, void* stream_)
+{
+    if (n < 0 || key_bits < 0 || key_bits > 32 || !sort_keys16(n, key_bits)) return SPLATRASTER_ERR_BAD_ARG;
+    return sort_in_place(true, n, keys, vals, key_bits, tmp, stream_);
+}
+
+int splatraster_debug_sort_path(int64_t n, int32_t key_bits, int32_t keys16)
+{
+    if (n < 0 || key_bits < 0 || key_bits > 32 || (keys16 && !sort_keys16(n, key_bits))) return -1;
+    return sort_path(n, key_bits, keys16 != 0);
+}
+
+int splatraster_debug_scan_path(int64_t n) { return n < 0 ? -1 : scan_path(n); }
+
+size_t splatraster_debug_scan_tmp_bytes(int64_t n) { return scan_tmp_bytes(n > 0 ? n : 0); }
+
+int splatraster_debug_scan_u32(int64_t n, const uint32_t* in, const uint32_t* perm, uint32_t* out, uint64_t* total,
+                               int32_t exclusive, uint32_t* span_owner, uint32_t span, uint32_t span_cap, void* tmp, void* stream_)
+{
+    if (n < 0) return SPLATRASTER_ERR_BAD_ARG;
+    if (exclusive && (perm || in != out || span_owner)) return SPLATRASTER_ERR_BAD_ARG;
+    if (span_owner && span == 0) return SPLATRASTER_ERR_BAD_ARG;
+    if (n > 0 && (!in || !out || !tmp)) return SPLATRASTER_ERR_BAD_ARG;
+    if (n > 0 && perm && in == out) return SPLATRASTER_ERR_BAD_ARG;   // the gather would read rows that other blocks overwrite
+    if (n == 0 && !total) return SPLATRASTER_OK;
+    {
+        int st0 = lookback_error_init();
+        if (st0) return st0;
+    }
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    uint32_t* total32 = reinterpret_cast<uint32_t*>(total);
+    if (exclusive) return exclusive_scan_u32(n, out, total32, tmp, stream, false);
+    return inclusive_scan_u32(n, in, perm, out, total32, tmp, stream, false, span_owner, span, span_cap);
 }
 
 int splatraster_timing_enable(int on)

@@ -230,6 +230,9 @@ int sort_pairs_u32(int64_t n, uint32_t* keys, uint32_t* vals, uint32_t* keys_alt
 bool sort_keys16(int64_t n, int key_bits);
 int sort_pairs_k16(int64_t n, uint32_t* keys, uint32_t* vals, uint32_t* keys_alt, uint32_t* vals_alt, int key_bits, void* tmp,
                    hipStream_t stream, bool* result_in_alt);
+// which form a sort / a scan of this size takes (the values of splatraster_debug_sort_path / _scan_path); host only
+int sort_path(int64_t n, int key_bits, bool keys16);
+int scan_path(int64_t n);
 // inclusive scan of in[perm[i] & 0xFFFFFF] (perm may be null; its words carry min(in[row], 255) in bits 24..31:
 // scan_sort.hip perm_value) into out[i]; total (u64 as 2 words) optional
 size_t scan_tmp_bytes(int64_t n);

@@ -327,6 +327,9 @@ size_t scan_state_bytes(int64_t n)
     return align_up(sizeof(ScanState) + (size_t)(nb > 0 ? nb : 1) * sizeof(uint64_t), 256);
 }
 
+// which of the two forms below a scan of n words takes: 0 nothing to do, 1 the one-pass look-back, 2 three kernels
+int scan_path(int64_t n) { return n <= 0 ? 0 : (scan_state_bytes(n) ? 1 : 2); }
+
 size_t scan_tmp_bytes(int64_t n)
 {
     const int64_t nb = (n + SCAN_TILE - 1) / SCAN_TILE;
@@ -725,6 +728,9 @@ size_t sort_zero_bytes(int64_t n, int key_bits)
 // histogram / scan / scatter passes over 8-bit digits, ping-ponging between (kin, vin) and (kout, vout).  KIn = uint16_t:
 // the key arrays hold uint16_t (in the first half of their uint32_t storage) up to the input of the last pass, which
 // writes uint32_t keys — a pass never reads and writes the same buffer, so the two widths cannot overlap.
+// words of the [digit][block] table that every such pass scans
+static int64_t sort_table_words(int64_t nb) { return nb * RADIX; }
+
 template <typename KIn>
 static int sort_passes(int64_t n, int64_t nb, int passes, uint32_t* kin, uint32_t* vin, uint32_t* kout, uint32_t* vout, void* tmp,
                        hipStream_t stream, bool* result_in_alt)
@@ -733,7 +739,7 @@ static int sort_passes(int64_t n, int64_t nb, int passes, uint32_t* kin, uint32_
     void* scan_tmp = reinterpret_cast<char*>(tmp) + align_up((size_t)nb * RADIX * sizeof(uint32_t), 256);
     for (int p = 0; p < passes; ++p) {
         const int shift = p * 8;
-        const int64_t cnt = nb * RADIX;
+        const int64_t cnt = sort_table_words(nb);
         const size_t sstate = scan_state_bytes(cnt);
         hipLaunchKernelGGL(sort_hist_kernel<KIn>, dim3((unsigned)nb), dim3(SORT_THREADS), 0, stream, n,
                            reinterpret_cast<const KIn*>(kin), shift, (uint32_t)nb, table, reinterpret_cast<uint32_t*>(scan_tmp),
@@ -819,6 +825,17 @@ int sort_pairs_k16(int64_t n, uint32_t* keys, uint32_t* vals, uint32_t* keys_alt
     if (n >= (int64_t)1 << 32) return SPLATRASTER_ERR_OVERFLOW;
     const int64_t nb = (n + SORT_TILE - 1) / SORT_TILE;
     return sort_passes<uint16_t>(n, nb, (key_bits + 7) / 8, keys, vals, keys_alt, vals_alt, tmp, stream, result_in_alt);
+}
+
+// the decisions above, for the tests (splatraster_debug_sort_path): 0 nothing to do, 1 / 2 one-sweep with 2048- / 4096-key
+// tiles, 3 histogram / scan / scatter passes, 4 the same on uint16_t keys; +8 when the table scan of a pass takes three kernels
+int sort_path(int64_t n, int key_bits, bool keys16)
+{
+    if (n <= 0 || key_bits <= 0) return 0;
+    const int items = sweep_items(n);
+    if (items) return items == 8 ? 1 : 2;
+    const int64_t nb = (n + SORT_TILE - 1) / SORT_TILE;
+    return (keys16 ? 4 : 3) + (scan_path(sort_table_words(nb)) == 2 ? 8 : 0);
 }
 
 }  // namespace sr

@@ -75,6 +75,27 @@ def test_bad_arguments_return_status_not_crash():
     assert lib.splatknn_dist2(-1, None, None, None, None) == 1
     assert lib.splatknn_dist2(0, None, None, None, None) == 0
     assert lib.splatraster_sort_pairs_u32(5, None, None, 8, None, None) == 1
+    # the scan / sort test hooks: null pointers with n > 0, exclusive with a perm, a span_owner or in != out, span 0, a gathered
+    # scan in place, and the uint16_t sort at a size or width that has no such form
+    a, b = C.c_void_p(256), C.c_void_p(512)                             # never dereferenced: refused first
+    scan = lib.splatraster_debug_scan_u32
+    assert scan(-1, a, None, b, None, 0, None, 0, 0, a, None) == 1
+    assert scan(5, None, None, b, None, 0, None, 0, 0, a, None) == 1
+    assert scan(5, a, None, None, None, 0, None, 0, 0, a, None) == 1
+    assert scan(5, a, None, b, None, 0, None, 0, 0, None, None) == 1
+    assert scan(5, a, None, b, None, 1, None, 0, 0, a, None) == 1      # exclusive, in != out
+    assert scan(5, a, b, a, None, 1, None, 0, 0, a, None) == 1         # exclusive with a perm
+    assert scan(5, a, None, a, None, 1, b, 1024, 4, a, None) == 1      # exclusive with a span_owner
+    assert scan(5, a, None, b, None, 0, b, 0, 4, a, None) == 1         # span 0
+    assert scan(5, a, b, a, None, 0, None, 0, 0, a, None) == 1         # gathered and in place
+    assert scan(0, None, None, None, None, 0, None, 0, 0, None, None) == 0
+    k16 = lib.splatraster_debug_sort_pairs_k16
+    assert k16(1_048_577, None, None, 8, None, None) == 1
+    assert k16(1_048_577, a, b, 8, None, None) == 1
+    assert k16(1_048_576, a, b, 8, a, None) == 1                        # one-sweep size: no uint16_t form
+    assert k16(1_048_577, a, b, 17, a, None) == 1 and k16(1_048_577, a, b, 0, a, None) == 1 and k16(0, a, b, 8, a, None) == 1
+    assert k16(-1, a, b, 8, a, None) == 1
+    assert lib.splatraster_debug_sort_path(1_048_576, 8, 1) == -1 and lib.splatraster_debug_scan_path(-1) == -1
     # the §8f stages validate before any HIP call too
     N13, N19 = [None] * 13, [None] * 19
     assert lib.splatraster_activate_forward(0, 1, 0, 3, 0, *N13) == 0                   # P = 0: nothing to do

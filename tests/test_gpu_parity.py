@@ -226,6 +226,7 @@ def test_radix_sort_is_stable_and_exact(n, bits):
     lib = _native.load()
     rng = np.random.default_rng(n)
     hi = (1 << bits) - 1
+    # deliberately narrow keys (many ties); the upper digits, every path boundary and sort_pairs_k16: tests/test_gpu_scan_sort_edges.py
     keys = rng.integers(0, min(hi, 5000 if n > 4096 else hi), size=n, endpoint=True, dtype=np.uint64).astype(np.uint32)
     vals = np.arange(n, dtype=np.uint32)
     dev = torch.device("cuda:0")
