@@ -642,7 +642,8 @@ int splatraster_isotropic_loss(int32_t P, int32_t scaling_cols, const float* sca
  * in one pass.  image / g_image are 3 planes of H*W floats with plane stride H*W (they may point
  * into a [C,H,W] render and its gradient), marker / g_marker one plane.  kp is the float32
  * key-point score map used as the (soft) BCE target, `gt.view(-1).float()` at train_gaussians.py:40
- * (a bool mask is passed as 0.0 / 1.0).  out[4] = { rgbd loss, marker loss, dL/dexposure_a, dL/dexposure_b } (device). */
+ * (a bool mask is passed as 0.0 / 1.0).  out[4] = { rgbd loss, marker loss, dL/dexposure_a, dL/dexposure_b } (device).
+ * pixels <= 0: SPLATRASTER_ERR_BAD_ARG, and a workspace size of 0 (as the other loss stages answer a non-positive size). */
 size_t splatraster_mapping_loss_workspace_bytes(int32_t pixels);
 int splatraster_mapping_loss(int32_t pixels, const float* image, const float* depth, const float* marker,
                              const float* gt_image, const float* gt_depth, const float* kp,

@@ -20,15 +20,16 @@ import numpy as np
 
 def mapping_loss(image, depth, marker, gt_image, gt_depth, kp, rgb_boundary_threshold, exposure_a=None,
                  exposure_b=None):
-    """Returns dict(loss_rgbd, loss_bce, dL_dimage, dL_ddepth, dL_dmarker, dL_dexposure_a, dL_dexposure_b);
-    the forward sums in float32 like torch, the gradients are exact (float64)."""
+    """Returns dict(loss_rgbd, loss_bce, dL_dimage, dL_ddepth, dL_dmarker, dL_dexposure_a, dL_dexposure_b).
+    Every element of a loss term is formed by the reference's float32 operations, with exact transcendentals.
+    The terms are summed in float64.  The gradients are exact (float64)."""
     f32 = np.float32
     image, depth, marker = np.asarray(image, f32), np.asarray(depth, f32).reshape(1, *np.shape(marker)), np.asarray(marker, f32)
     gt_image, gt_depth = np.asarray(gt_image, f32), np.asarray(gt_depth, f32).reshape(depth.shape)
     y = np.asarray(kp).astype(f32)
     H, W = marker.shape
     use_exp = exposure_a is not None
-    ea = f32(np.exp(f32(exposure_a))) if use_exp else f32(1.0)
+    ea = f32(np.exp(np.float64(f32(exposure_a)))) if use_exp else f32(1.0)      # exp(a), correctly rounded to float32
     eb = f32(exposure_b) if use_exp else f32(0.0)
     x = ea * image + eb if use_exp else image
     m_rgb = (gt_image.sum(axis=0) > f32(rgb_boundary_threshold)).reshape(1, H, W).astype(f32)
@@ -36,11 +37,16 @@ def mapping_loss(image, depth, marker, gt_image, gt_depth, kp, rgb_boundary_thre
     diff = x * m_rgb - gt_image * m_rgb
     diffd = depth * m_d - gt_depth * m_d
     l_rgbd = np.abs(diff).mean(dtype=np.float64) + np.abs(diffd).mean(dtype=np.float64)
+    # sigmoid as the float32 operations the reference and the kernel perform (the sum and the division are IEEE operations: at a
+    # logit of 17 the sum rounds to 1 and s IS 1), with the transcendental functions exact: exp correctly rounded to the float32 the
+    # sum takes, the logarithms of s and of the float32 difference 1 - s in float64.  (A float32 libm here made the oracle as far
+    # off as what it judges: one ulp of s moves log(1 - s) by s / (1 - s) ulps.)
     with np.errstate(over="ignore"):
-        p = (1.0 / (1.0 + np.exp(-marker))).astype(f32)
+        e = np.exp(-marker.astype(np.float64)).astype(f32)
+        p = (f32(1.0) / (f32(1.0) + e)).astype(f32)
     with np.errstate(divide="ignore"):
-        logp = np.maximum(np.log(p), f32(-100.0))
-        log1p = np.maximum(np.log(f32(1.0) - p), f32(-100.0))
+        logp = np.maximum(np.log(p.astype(np.float64)), -100.0)
+        log1p = np.maximum(np.log((f32(1.0) - p).astype(np.float64)), -100.0)
     l_bce = (-(y * logp + (1.0 - y) * log1p)).mean(dtype=np.float64)
     n_rgb, n = 3.0 * H * W, 1.0 * H * W
     g_x = np.sign(diff).astype(np.float64) * m_rgb / n_rgb

@@ -69,8 +69,10 @@ mapping_loss_kernel(int HW, LossViews lv, float threshold, double* __restrict__ 
         g_depth[p] = sgn(dd) * md * inv_n;
         const float s = 1.0f / (1.0f + expf(-marker[p]));
         const float y = kp[p];   // soft target: the raw key-point score map (utils/dataset.py:94, camera_utils.py:75)
-        const float lp = fmaxf(logf(s), -100.0f), lq = fmaxf(logf(1.0f - s), -100.0f);
-        acc[2] += (double)(-(y * lp + (1.0f - y) * lq));
+        // the logarithms reach 8 and more, where one float32 ulp of logf is 5e-7 of a term: over a small frame that is more
+        // than an ulp of the mean.  s and 1 - s stay the reference's float32 values (at a logit of 17 s is 1 and the clamp acts)
+        const double lp = fmax(log((double)s), -100.0), lq = fmax(log((double)(1.0f - s)), -100.0);
+        acc[2] -= (double)y * lp + (1.0 - (double)y) * lq;
         const float sq = s * (1.0f - s);
         g_marker[p] = (s - y) / fmaxf(sq, 1e-12f) * sq * inv_n;
     }
@@ -171,9 +173,9 @@ static int launch_mapping_loss(int32_t HW, const float* image, const float* dept
 // sigma 1.5, zero padding, C1 = 0.01^2, C2 = 0.03^2, mean over all elements).
 // The reference runs 5 dense 11x11 grouped convolutions forward and their autograd backward;
 // here the window is applied separably out of LDS, in two kernels:
-//   refine_fwd: per 16x16 tile (+5 halo) blur(x, y, x^2, y^2, xy) -> SSIM map value and its
-//               partials dm/dmu1, dm/ds1, dm/ds12 (s1 = blur(x^2), s12 = blur(xy)); tile sums of m
-//               and |x - y|
+//   refine_fwd: per 32x16 tile (+5 halo) the blurred first and second moments of x and y (about a per-tile shift: SHIFTED
+//               MOMENTS below) -> SSIM map value and its partials dm/dmu1, dm/ds1, dm/ds12 (s1 = blur(x^2),
+//               s12 = blur(xy)); tile sums of m and |x - y|
 //   refine_bwd: dL/dx = (1-lambda) sign(x-y)/n - lambda/n (blur(dm/dmu1) + 2 x blur(dm/ds1) + y blur(dm/ds12))
 // (the window is symmetric, so the adjoint of the zero-padded convolution is the same blur).
 // ---------------------------------------------------------------------------------------------
@@ -182,13 +184,66 @@ constexpr int RH = 5;             // window radius
 constexpr int RW = 2 * RH + 1;    // 11 taps
 constexpr int RE = RT + 2 * RH;   // 26: tile + halo
 
-struct RefineWindow { float w[RW]; };
+struct RefineWindow { float w[RW]; double mass; /* sum w in double: the float32 window does not sum to 1 */ };
+
+// SHIFTED MOMENTS.  sigma = E[x^2] - mu^2 cancels in float32: over a smooth bright region both terms are ~0.6 and their
+// rounding, ~3e-8, stands against C2 = 9e-4 — 1e-4 of every pixel's SSIM, and that is the regime the refinement loop
+// converges into.  A variance does not depend on a shift, so both blur bodies accumulate the moments of d = x - c and
+// e = y - c: the tile loader subtracts c, one value per tile, the median of three gt samples of the tile (one bright pixel on
+// a dark ground leaves c dark).  Zero padding stays exact: a pixel outside the image contributes 0 to the shifted sums,
+// and with S = the window mass inside the image and U = 1 - S
+//     mu    = E0[d] + c S
+//     sigma = E0[d^2] - E0[d]^2 + c U (2 E0[d] + c S)            (sigma12: E0[d e] - E0[d] E0[e] + c U (E0[d] + E0[e] + c S))
+// S, U and these few terms are formed in double and rounded once: at an image border U is most of the window and the terms
+// are as large as the unshifted ones.  Inside, U = 1 - mass^2 = 9e-8.  Where c = 0 these are the unshifted forms.
+// For finite inputs only: a NaN or an infinity among the three samples reaches every statistic of its tile (inf - inf), where
+// the unshifted sums carried it no further than the windows that touch it.  Images and ground truth are finite by contract.
+__device__ __forceinline__ float tile_shift(const float* __restrict__ gt_plane, int H, int W, int y0, int x0, int th, int tw)
+{
+    const float a = gt_plane[(size_t)min(y0 + th / 4, H - 1) * W + min(x0 + tw / 4, W - 1)];
+    const float b = gt_plane[(size_t)min(y0 + th / 2, H - 1) * W + min(x0 + tw / 2, W - 1)];
+    const float c = gt_plane[(size_t)min(y0 + 3 * th / 4, H - 1) * W + min(x0 + 3 * tw / 4, W - 1)];
+    return fmaxf(fminf(a, b), fminf(fmaxf(a, b), c));   // the median
+}
+
+__device__ __forceinline__ double window_cover(const RefineWindow& win, int g, int n)
+{
+    if (g >= RH && g + RH < n) return win.mass;
+    double inside = 0.0;
+#pragma unroll
+    for (int k = 0; k < RW; ++k) {
+        const int gk = g + k - RH;
+        if (gk >= 0 && gk < n) inside += (double)win.w[k];
+    }
+    return inside;
+}
+
+struct SsimStats { float mu1, mu2, sig1, sig2, sig12; };
+
+// v = E0[d], E0[e], E0[d^2], E0[e^2], E0[d e] of the output at (gy, gx)
+__device__ __forceinline__ SsimStats ssim_stats(const RefineWindow& win, const float v[5], float c, int gy, int gx, int H, int W)
+{
+    const double S = window_cover(win, gx, W) * window_cover(win, gy, H), U = 1.0 - S;
+    const double cs = (double)c * S, cu = (double)c * U;
+    const double d = (double)v[0], e = (double)v[1];
+    SsimStats t;
+    t.mu1 = (float)(d + cs);
+    t.mu2 = (float)(e + cs);
+    t.sig1 = (float)(((double)v[2] - d * d) + cu * (d + d + cs));
+    t.sig2 = (float)(((double)v[3] - e * e) + cu * (e + e + cs));
+    t.sig12 = (float)(((double)v[4] - d * e) + cu * (d + e + cs));
+    return t;
+}
 
 // Round 5: both kernels work on 32x16 tiles with REGISTER-BLOCKED passes — a horizontal work item loads 14 consecutive taps
 // once and produces 4 adjacent outputs, a vertical one loads 12 rows and produces 2 (the 16x16 / one-output-per-thread form
 // read LDS 22 + 55 times per output): refine_fwd 22.1 -> 18.4 us, refine_bwd 16.1 -> 14.4 us (profiles/r05_ab_probes.txt #8;
-// what is left is the load -> barrier -> pass -> barrier -> pass -> store chain, not arithmetic).  Every output is still
-// accumulated tap by tap in ascending order with the same fused multiply-adds: the maps and the gradient are bit-identical.
+// what was left then was the load -> barrier -> pass -> barrier -> pass -> store chain, not arithmetic).  Every output is
+// accumulated tap by tap in ascending order.
+// The shifted moments and the double-precision statistics and partials that followed (about 60 FP64 operations and one FP64
+// division per output, for the edge suite's 4 x E_ref bounds) are arithmetic the forward did not have, and they cost: at
+// 3x1080x1920 on an MI355X (kernel trace, mean of 1530 launches) refine_fwd 76.5 -> 94.0 us, eval_metrics_kernel
+// 111.0 -> 123.7 us, refine_bwd unchanged at 62.8 us; the maps and the gradient are no longer bit-identical to Round 5's.
 constexpr int FW = 32, FH = 16;               // tile of the refinement kernels
 constexpr int FEW = FW + 2 * RH, FEH = FH + 2 * RH;   // 42 x 26 with halo
 constexpr int FHG = FW / 4;                   // horizontal work items per row (4 outputs each)
@@ -204,12 +259,17 @@ refine_fwd_kernel(int H, int W, const float* __restrict__ img, const float* __re
     const int tid = threadIdx.x;
     const int x0 = blockIdx.x * FW, y0 = blockIdx.y * FH;
     const size_t plane = (size_t)blockIdx.z * H * W;
+    const float shift = tile_shift(gt + plane, H, W, y0, x0, FH, FW);   // SHIFTED MOMENTS: LDS holds x - shift, y - shift
+    double msum = 0.0, lsum = 0.0;
     for (int e = tid; e < FEH * FEW; e += 256) {
         const int r = e / FEW, c = e - r * FEW;
         const int gy = y0 + r - RH, gx = x0 + c - RH;
         const bool in = gy >= 0 && gy < H && gx >= 0 && gx < W;
-        s_x[r][c] = in ? img[plane + (size_t)gy * W + gx] : 0.0f;
-        s_y[r][c] = in ? gt[plane + (size_t)gy * W + gx] : 0.0f;
+        const float xr = in ? img[plane + (size_t)gy * W + gx] : 0.0f;
+        const float yr = in ? gt[plane + (size_t)gy * W + gx] : 0.0f;
+        s_x[r][c] = in ? xr - shift : 0.0f;
+        s_y[r][c] = in ? yr - shift : 0.0f;
+        if (in && r >= RH && r < RH + FH && c >= RH && c < RH + FW) lsum += (double)fabsf(xr - yr);   // the tile's own pixels
     }
     __syncthreads();
     if (tid < FEH * FHG) {   // horizontal pass: FEH rows x FHG groups of 4 columns
@@ -241,7 +301,6 @@ refine_fwd_kernel(int H, int W, const float* __restrict__ img, const float* __re
     __syncthreads();
     const int tx = tid & (FW - 1), ty0 = (tid / FW) * 2;   // two vertically adjacent outputs per thread
     const int gx = x0 + tx;
-    double msum = 0.0, lsum = 0.0;
     float col[5][RW + 1];
 #pragma unroll
     for (int k = 0; k < RW + 1; ++k)
@@ -259,18 +318,23 @@ refine_fwd_kernel(int H, int W, const float* __restrict__ img, const float* __re
                 for (int q = 0; q < 5; ++q) v[q] += wk * col[q][o + k];
             }
             const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
-            const float mu1 = v[0], mu2 = v[1];
-            const float sig1 = v[2] - mu1 * mu1, sig2 = v[3] - mu2 * mu2, sig12 = v[4] - mu1 * mu2;
+            const SsimStats st = ssim_stats(win, v, shift, gy, gx, H, W);
+            const float mu1 = st.mu1, mu2 = st.mu2, sig1 = st.sig1, sig2 = st.sig2, sig12 = st.sig12;
             const float A = 2.0f * mu1 * mu2 + C1, B = 2.0f * sig12 + C2;
             const float Cc = mu1 * mu1 + mu2 * mu2 + C1, D = sig1 + sig2 + C2;
             const float icd = 1.0f / (Cc * D);
             const float m = A * B * icd;
             const size_t oo = plane + (size_t)gy * W + gx;
-            dm_dmu1[oo] = (2.0f * mu2 * (B - A) * Cc * D - A * B * 2.0f * mu1 * (D - Cc)) * icd * icd;
-            dm_ds1[oo] = -m / D;
-            dm_ds12[oo] = 2.0f * A * icd;
+            // the partials in double, rounded once: the two halves of dm/dmu1 cancel where x is near y, and in float32 the
+            // roundings of A, B, C and D alone put a one-pixel image's gradient an ulp off
+            const double Ad = 2.0 * (double)mu1 * (double)mu2 + (double)C1, Bd = 2.0 * (double)sig12 + (double)C2;
+            const double Cd = (double)mu1 * (double)mu1 + (double)mu2 * (double)mu2 + (double)C1;
+            const double Dd = (double)sig1 + (double)sig2 + (double)C2;
+            const double icdd = 1.0 / (Cd * Dd);
+            dm_dmu1[oo] = (float)((2.0 * (double)mu2 * (Bd - Ad) * Cd * Dd - Ad * Bd * 2.0 * (double)mu1 * (Dd - Cd)) * icdd * icdd);
+            dm_ds1[oo] = (float)(-Ad * Bd * icdd * icdd * Cd);
+            dm_ds12[oo] = (float)(2.0 * Ad * icdd);
             msum += (double)m;
-            lsum += (double)fabsf(s_x[ty + RH][tx + RH] - s_y[ty + RH][tx + RH]);
         }
     }
 #pragma unroll
@@ -390,6 +454,9 @@ static RefineWindow refine_window()
         sum += win.w[k];
     }
     for (int k = 0; k < RW; ++k) win.w[k] /= sum;
+    double mass = 0.0;
+    for (int k = 0; k < RW; ++k) mass += (double)win.w[k];
+    win.mass = mass;
     return win;
 }
 
@@ -419,12 +486,21 @@ eval_metrics_kernel(int H, int W, const float* __restrict__ img, const float* __
     const int tid = threadIdx.x;
     const int x0 = blockIdx.x * RT, y0 = blockIdx.y * RT;
     const size_t plane = (size_t)blockIdx.z * H * W;
+    const float shift = tile_shift(gt + plane, H, W, y0, x0, RT, RT);   // SHIFTED MOMENTS: LDS holds x - shift, y - shift
+    double acc[EVAL_SUMS] = {0.0, 0.0, 0.0};
     for (int e = tid; e < RE * RE; e += RT * RT) {
         const int r = e / RE, c = e - r * RE;
         const int gy = y0 + r - RH, gx = x0 + c - RH;
         const bool in = gy >= 0 && gy < H && gx >= 0 && gx < W;
-        s_x[r][c] = in ? fminf(fmaxf(img[plane + (size_t)gy * W + gx], 0.0f), 1.0f) : 0.0f;   // torch.clamp(rendering, 0.0, 1.0)
-        s_y[r][c] = in ? gt[plane + (size_t)gy * W + gx] : 0.0f;
+        const float xr = in ? fminf(fmaxf(img[plane + (size_t)gy * W + gx], 0.0f), 1.0f) : 0.0f;   // torch.clamp(rendering, 0.0, 1.0)
+        const float yr = in ? gt[plane + (size_t)gy * W + gx] : 0.0f;
+        s_x[r][c] = in ? xr - shift : 0.0f;
+        s_y[r][c] = in ? yr - shift : 0.0f;
+        if (in && r >= RH && r < RH + RT && c >= RH && c < RH + RT && yr > 0.0f) {   // the tile's own pixels, masked per element
+            const float d = xr - yr;
+            acc[1] += (double)(d * d);
+            acc[2] += 1.0;
+        }
     }
     __syncthreads();
     for (int e = tid; e < RE * RT; e += RT * RT) {
@@ -444,7 +520,6 @@ eval_metrics_kernel(int H, int W, const float* __restrict__ img, const float* __
     __syncthreads();
     const int ty = tid / RT, tx = tid - ty * RT;
     const int gy = y0 + ty, gx = x0 + tx;
-    double acc[EVAL_SUMS] = {0.0, 0.0, 0.0};
     if (gy < H && gx < W) {
         float v[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -454,17 +529,11 @@ eval_metrics_kernel(int H, int W, const float* __restrict__ img, const float* __
             for (int q = 0; q < 5; ++q) v[q] += wk * s_h[q][ty + k][tx];
         }
         const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
-        const float mu1 = v[0], mu2 = v[1];
-        const float sig1 = v[2] - mu1 * mu1, sig2 = v[3] - mu2 * mu2, sig12 = v[4] - mu1 * mu2;
+        const SsimStats st = ssim_stats(win, v, shift, gy, gx, H, W);
+        const float mu1 = st.mu1, mu2 = st.mu2, sig1 = st.sig1, sig2 = st.sig2, sig12 = st.sig12;
         const float A = 2.0f * mu1 * mu2 + C1, B = 2.0f * sig12 + C2;
         const float Cc = mu1 * mu1 + mu2 * mu2 + C1, D = sig1 + sig2 + C2;
         acc[0] = (double)(A * B / (Cc * D));
-        const float x = s_x[ty + RH][tx + RH], y = s_y[ty + RH][tx + RH];
-        if (y > 0.0f) {
-            const float d = x - y;
-            acc[1] = (double)(d * d);
-            acc[2] = 1.0;
-        }
     }
 #pragma unroll
     for (int k = 0; k < EVAL_SUMS; ++k) {
@@ -555,7 +624,7 @@ using namespace sr;
 
 extern "C" {
 
-size_t splatraster_mapping_loss_workspace_bytes(int32_t pixels) { return mapping_loss_workspace_bytes(pixels); }
+size_t splatraster_mapping_loss_workspace_bytes(int32_t pixels) { return pixels > 0 ? mapping_loss_workspace_bytes(pixels) : 0; }
 
 int splatraster_mapping_loss(int32_t pixels, const float* image, const float* depth, const float* marker,
                              const float* gt_image, const float* gt_depth, const float* kp,
