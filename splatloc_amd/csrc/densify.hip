@@ -15,6 +15,7 @@
 // classes are four sections of ONE flag array of 4 P entries, so a single exclusive scan yields every
 // destination.  HBM-bound integer/byte work; nothing here is reshaped into a GEMM.
 #include "common.h"
+#include "reduce.h"
 
 namespace sr {
 
@@ -454,7 +455,7 @@ __global__ void __launch_bounds__(256)
 isotropic_fwd_kernel(int P, int SC, const float* __restrict__ scaling /*activated [P,SC]*/, const float* __restrict__ marker,
                      float* __restrict__ row_grad /*[P]*/, double* __restrict__ partial /*[blocks,2]*/)
 {
-    double acc = 0.0, cnt = 0.0;
+    double sums[2] = {0.0, 0.0};   // sum |x - 1|, count
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < P; i += gridDim.x * blockDim.x) {
         const float mk = marker[i];
         float rg = 0.0f;
@@ -463,25 +464,17 @@ isotropic_fwd_kernel(int P, int SC, const float* __restrict__ scaling /*activate
             for (int k = 0; k < SC; ++k) s += scaling[(size_t)SC * i + k];
             const float inv = 1.0f / (0.02f * (1.0f - mk));
             const float x = (s / (float)SC) * inv - 1.0f;
-            acc += (double)fabsf(x);
-            cnt += 1.0;
+            sums[0] += (double)fabsf(x);
+            sums[1] += 1.0;
             rg = (float)((x > 0.f) - (x < 0.f)) * inv / (float)SC;
         }
         row_grad[i] = rg;
     }
     __shared__ double s_red[256 / WAVE][2];
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) {
-        acc += __shfl_xor(acc, d, WAVE);
-        cnt += __shfl_xor(cnt, d, WAVE);
-    }
-    if ((threadIdx.x & (WAVE - 1)) == 0) { s_red[threadIdx.x / WAVE][0] = acc; s_red[threadIdx.x / WAVE][1] = cnt; }
-    __syncthreads();
+    block_sum<256>(sums, s_red);
     if (threadIdx.x == 0) {
-        double a = 0, c = 0;
-        for (int w = 0; w < 256 / WAVE; ++w) { a += s_red[w][0]; c += s_red[w][1]; }
-        partial[2 * (size_t)blockIdx.x] = a;
-        partial[2 * (size_t)blockIdx.x + 1] = c;
+        partial[2 * (size_t)blockIdx.x] = block_total(s_red, 0);
+        partial[2 * (size_t)blockIdx.x + 1] = block_total(s_red, 1);
     }
 }
 __global__ void isotropic_finish_kernel(int blocks, const double* __restrict__ partial, float* __restrict__ out)
@@ -489,13 +482,9 @@ __global__ void isotropic_finish_kernel(int blocks, const double* __restrict__ p
     // one wave: lane l sums partials l, l + 64, ... in order, then a fixed butterfly — deterministic, and 16 dependent
     // loads per lane instead of 1024 in one thread (81 -> 4 us at 500k Gaussians)
     if (blockIdx.x != 0) return;
-    double a = 0, c = 0;
-    for (int b = threadIdx.x; b < blocks; b += WAVE) { a += partial[2 * (size_t)b]; c += partial[2 * (size_t)b + 1]; }
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) {
-        a += __shfl_xor(a, d, WAVE);
-        c += __shfl_xor(c, d, WAVE);
-    }
+    double t[2];
+    partials_sum<WAVE>(blocks, partial, t);
+    const double a = wave_sum(t[0]), c = wave_sum(t[1]);
     if (threadIdx.x != 0) return;
     out[0] = c > 0 ? (float)(a / c) : 0.0f;
     out[1] = c > 0 ? (float)(1.0 / c) : 0.0f;

@@ -11,6 +11,7 @@
 // terms, dL/da, dL/db) are reduced per block in double and finished by a one-block kernel:
 // deterministic, no atomics.
 #include "common.h"
+#include "reduce.h"
 
 namespace sr {
 
@@ -77,19 +78,8 @@ mapping_loss_kernel(int HW, LossViews lv, float threshold, double* __restrict__ 
         g_marker[p] = (s - y) / fmaxf(sq, 1e-12f) * sq * inv_n;
     }
     __shared__ double s_red[LOSS_BLOCK / WAVE][LOSS_SUMS];
-#pragma unroll
-    for (int k = 0; k < LOSS_SUMS; ++k) {
-        double v = acc[k];
-#pragma unroll
-        for (int d = 1; d < WAVE; d <<= 1) v += __shfl_xor(v, d, WAVE);
-        if ((threadIdx.x & (WAVE - 1)) == 0) s_red[threadIdx.x / WAVE][k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < LOSS_SUMS) {
-        double v = 0;
-        for (int w = 0; w < LOSS_BLOCK / WAVE; ++w) v += s_red[w][threadIdx.x];
-        partial[(size_t)blockIdx.x * LOSS_SUMS + threadIdx.x] = v;
-    }
+    block_sum<LOSS_BLOCK>(acc, s_red);
+    if (threadIdx.x < LOSS_SUMS) partial[(size_t)blockIdx.x * LOSS_SUMS + threadIdx.x] = block_total(s_red, threadIdx.x);
 }
 
 __global__ void __launch_bounds__(LOSS_BLOCK)
@@ -101,23 +91,9 @@ mapping_loss_finish_kernel(int blocks, int HW, const double* __restrict__ partia
     const float* __restrict__ exposure = lv.exposure[view];
     float* __restrict__ out = out_all + 4 * view;
     __shared__ double s_red[LOSS_BLOCK / WAVE][LOSS_SUMS];
-    double acc[LOSS_SUMS] = {0, 0, 0, 0, 0};
-    for (int b = threadIdx.x; b < blocks; b += blockDim.x)
-        for (int k = 0; k < LOSS_SUMS; ++k) acc[k] += partial[(size_t)b * LOSS_SUMS + k];
-#pragma unroll
-    for (int k = 0; k < LOSS_SUMS; ++k) {
-        double v = acc[k];
-#pragma unroll
-        for (int d = 1; d < WAVE; d <<= 1) v += __shfl_xor(v, d, WAVE);
-        if ((threadIdx.x & (WAVE - 1)) == 0) s_red[threadIdx.x / WAVE][k] = v;
-    }
-    __syncthreads();
+    double t[LOSS_SUMS];
+    partials_block_sum<LOSS_BLOCK>(blocks, partial, s_red, t);
     if (threadIdx.x == 0) {
-        double t[LOSS_SUMS];
-        for (int k = 0; k < LOSS_SUMS; ++k) {
-            t[k] = 0;
-            for (int w = 0; w < LOSS_BLOCK / WAVE; ++w) t[k] += s_red[w][k];
-        }
         const double n = (double)HW;
         out[0] = (float)(t[0] / (3.0 * n) + t[1] / n);                 // get_loss_mapping
         out[1] = (float)(t[2] / n);                                    // get_loss_marker
@@ -179,17 +155,16 @@ static int launch_mapping_loss(int32_t HW, const float* image, const float* dept
 //   refine_bwd: dL/dx = (1-lambda) sign(x-y)/n - lambda/n (blur(dm/dmu1) + 2 x blur(dm/ds1) + y blur(dm/ds12))
 // (the window is symmetric, so the adjoint of the zero-padded convolution is the same blur).
 // ---------------------------------------------------------------------------------------------
-constexpr int RT = 16;            // tile edge
+constexpr int RT = 16;            // tile edge of eval_metrics_kernel
 constexpr int RH = 5;             // window radius
 constexpr int RW = 2 * RH + 1;    // 11 taps
-constexpr int RE = RT + 2 * RH;   // 26: tile + halo
 
 struct RefineWindow { float w[RW]; double mass; /* sum w in double: the float32 window does not sum to 1 */ };
 
 // SHIFTED MOMENTS.  sigma = E[x^2] - mu^2 cancels in float32: over a smooth bright region both terms are ~0.6 and their
 // rounding, ~3e-8, stands against C2 = 9e-4 — 1e-4 of every pixel's SSIM, and that is the regime the refinement loop
-// converges into.  A variance does not depend on a shift, so both blur bodies accumulate the moments of d = x - c and
-// e = y - c: the tile loader subtracts c, one value per tile, the median of three gt samples of the tile (one bright pixel on
+// converges into.  A variance does not depend on a shift, so the SSIM kernels blur the moments of d = x - c and
+// e = y - c: their loader functors subtract c, one value per tile, the median of three gt samples of the tile (one bright pixel on
 // a dark ground leaves c dark).  Zero padding stays exact: a pixel outside the image contributes 0 to the shifted sums,
 // and with S = the window mass inside the image and U = 1 - S
 //     mu    = E0[d] + c S
@@ -219,11 +194,18 @@ __device__ __forceinline__ double window_cover(const RefineWindow& win, int g, i
 }
 
 struct SsimStats { float mu1, mu2, sig1, sig2, sig12; };
+constexpr float SSIM_C1 = 0.01f * 0.01f, SSIM_C2 = 0.03f * 0.03f;
 
-// v = E0[d], E0[e], E0[d^2], E0[e^2], E0[d e] of the output at (gy, gx)
-__device__ __forceinline__ SsimStats ssim_stats(const RefineWindow& win, const float v[5], float c, int gy, int gx, int H, int W)
+// S: the window mass inside the image at the output (gy, gx)
+__device__ __forceinline__ double ssim_cover(const RefineWindow& win, int gy, int gx, int H, int W)
 {
-    const double S = window_cover(win, gx, W) * window_cover(win, gy, H), U = 1.0 - S;
+    return window_cover(win, gx, W) * window_cover(win, gy, H);
+}
+
+// v = E0[d], E0[e], E0[d^2], E0[e^2], E0[d e] of an output whose window has the mass S inside the image
+__device__ __forceinline__ SsimStats ssim_stats(const float v[5], float c, double S)
+{
+    const double U = 1.0 - S;
     const double cs = (double)c * S, cu = (double)c * U;
     const double d = (double)v[0], e = (double)v[1];
     SsimStats t;
@@ -235,8 +217,8 @@ __device__ __forceinline__ SsimStats ssim_stats(const RefineWindow& win, const f
     return t;
 }
 
-// Round 5: both kernels work on 32x16 tiles with REGISTER-BLOCKED passes — a horizontal work item loads 14 consecutive taps
-// once and produces 4 adjacent outputs, a vertical one loads 12 rows and produces 2 (the 16x16 / one-output-per-thread form
+// Round 5: the two refinement kernels work on 32x16 tiles with REGISTER-BLOCKED passes — a horizontal work item loads 14
+// consecutive taps once and produces 4 adjacent outputs, a vertical one loads 12 rows and produces 2 (the 16x16 / one-output-per-thread form
 // read LDS 22 + 55 times per output): refine_fwd 22.1 -> 18.4 us, refine_bwd 16.1 -> 14.4 us (profiles/r05_ab_probes.txt #8;
 // what was left then was the load -> barrier -> pass -> barrier -> pass -> store chain, not arithmetic).  Every output is
 // accumulated tap by tap in ascending order.
@@ -245,111 +227,160 @@ __device__ __forceinline__ SsimStats ssim_stats(const RefineWindow& win, const f
 // 3x1080x1920 on an MI355X (kernel trace, mean of 1530 launches) refine_fwd 76.5 -> 94.0 us, eval_metrics_kernel
 // 111.0 -> 123.7 us, refine_bwd unchanged at 62.8 us; the maps and the gradient are no longer bit-identical to Round 5's.
 constexpr int FW = 32, FH = 16;               // tile of the refinement kernels
-constexpr int FEW = FW + 2 * RH, FEH = FH + 2 * RH;   // 42 x 26 with halo
-constexpr int FHG = FW / 4;                   // horizontal work items per row (4 outputs each)
+
+// THE SEPARABLE BLUR OUT OF LDS, written once for the three kernels below: a TW x TH tile and its halo of RH are loaded as QI
+// planes, blurred along the rows into Q planes (HO adjacent outputs per work item) and along the columns into the tile's
+// outputs (VO per thread); a barrier stands between the steps, in the kernel.  Every output is accumulated tap by tap in
+// ascending order as  wk * plane, so a tile shape and a blocking decide who computes a blurred value, never its bits (what
+// the SSIM kernels blur does depend on the tile: tile_shift takes its three samples at fractions of the tile's edges).
+//   refine_fwd, refine_bwd: 32x16, HO = 4, VO = 2 (5 and 3 planes);   eval_metrics: 16x16, HO = VO = 1 (5 planes).
+// Loader: pixel(o, own, v) is called for every element of tile + halo INSIDE the image (o = gy W + gx, own = one of the tile's
+// own pixels) and fills the QI values LDS is to hold; outside the image LDS holds 0 (zero padding).  What a kernel does to a
+// pixel on the way in (the shift, eval's clamp) and the sums it takes over its own pixels live in that functor.
+template <int TW, int TH, int THREADS, int QI, class Pixel>
+__device__ __forceinline__ void blur_load_tile(float (&s_in)[QI][TH + 2 * RH][TW + 2 * RH + 1], int H, int W, int y0, int x0,
+                                               Pixel&& pixel)
+{
+    constexpr int EW = TW + 2 * RH, EH = TH + 2 * RH;
+    for (int e = threadIdx.x; e < EH * EW; e += THREADS) {
+        const int r = e / EW, c = e - r * EW;
+        const int gy = y0 + r - RH, gx = x0 + c - RH;
+        float v[QI];
+#pragma unroll
+        for (int q = 0; q < QI; ++q) v[q] = 0.0f;
+        if (gy >= 0 && gy < H && gx >= 0 && gx < W) pixel((size_t)gy * W + gx, r >= RH && r < RH + TH && c >= RH && c < RH + TW, v);
+#pragma unroll
+        for (int q = 0; q < QI; ++q) s_in[q][r][c] = v[q];
+    }
+}
+
+// rows: MOMENTS blurs x, y, x^2, y^2, x y of the two planes loaded (Q = 5), else the QI planes as they are
+template <int TW, int TH, int THREADS, int HO, bool MOMENTS, int QI, int Q>
+__device__ __forceinline__ void blur_rows(const RefineWindow& win, const float (&s_in)[QI][TH + 2 * RH][TW + 2 * RH + 1],
+                                          float (&s_h)[Q][TH + 2 * RH][TW + 1])
+{
+    static_assert(MOMENTS ? (QI == 2 && Q == 5) : Q == QI, "planes");
+    constexpr int G = TW / HO, NT = RW + HO - 1;   // work items per row; taps an item loads
+    for (int e = threadIdx.x; e < (TH + 2 * RH) * G; e += THREADS) {
+        const int r = e / G, c0 = (e - r * G) * HO;
+        float p[Q][NT];
+#pragma unroll
+        for (int k = 0; k < NT; ++k) {
+#pragma unroll
+            for (int q = 0; q < QI; ++q) p[q][k] = s_in[q][r][c0 + k];
+            if constexpr (MOMENTS) {
+                p[2][k] = p[0][k] * p[0][k];
+                p[3][k] = p[1][k] * p[1][k];
+                p[4][k] = p[0][k] * p[1][k];
+            }
+        }
+#pragma unroll
+        for (int o = 0; o < HO; ++o) {
+            float a[Q];
+#pragma unroll
+            for (int q = 0; q < Q; ++q) a[q] = 0.f;
+#pragma unroll
+            for (int k = 0; k < RW; ++k) {
+                const float wk = win.w[k];
+#pragma unroll
+                for (int q = 0; q < Q; ++q) a[q] += wk * p[q][o + k];
+            }
+#pragma unroll
+            for (int q = 0; q < Q; ++q) s_h[q][r][c0 + o] = a[q];
+        }
+    }
+}
+
+// columns: thread t's VO vertically adjacent outputs, rows (t / TW) VO + o of column t % TW of the tile (blur_out_row / _col), as
+// v[o][0 .. Q).  Computed whether or not the output lies inside the image (LDS holds zeros there): the caller tests that.
+template <int TW, int TH, int THREADS, int VO, int Q>
+__device__ __forceinline__ void blur_cols(const RefineWindow& win, const float (&s_h)[Q][TH + 2 * RH][TW + 1], float (&v)[VO][Q])
+{
+    static_assert(TW * (TH / VO) == THREADS, "one work item per thread");
+    const int tx = threadIdx.x % TW, ty0 = (threadIdx.x / TW) * VO;
+    float col[Q][RW + VO - 1];
+#pragma unroll
+    for (int k = 0; k < RW + VO - 1; ++k)
+#pragma unroll
+        for (int q = 0; q < Q; ++q) col[q][k] = s_h[q][ty0 + k][tx];
+#pragma unroll
+    for (int o = 0; o < VO; ++o) {
+#pragma unroll
+        for (int q = 0; q < Q; ++q) v[o][q] = 0.f;
+#pragma unroll
+        for (int k = 0; k < RW; ++k) {
+            const float wk = win.w[k];
+#pragma unroll
+            for (int q = 0; q < Q; ++q) v[o][q] += wk * col[q][o + k];
+        }
+    }
+}
+template <int TW, int VO> __device__ __forceinline__ int blur_out_row(int o) { return (threadIdx.x / TW) * VO + o; }
+template <int TW> __device__ __forceinline__ int blur_out_col() { return threadIdx.x % TW; }
+
+// the SSIM map value m = A B / (C D).  RECIPROCAL: A B * (1 / (C D)), two roundings, as the refinement forward has always formed
+// it; the evaluation divides once.  Both are pinned bit for bit by their callers' tests, so each keeps its form.
+template <bool RECIPROCAL>
+__device__ __forceinline__ float ssim_value(const SsimStats& st)
+{
+    const float A = 2.0f * st.mu1 * st.mu2 + SSIM_C1, B = 2.0f * st.sig12 + SSIM_C2;
+    // mu1^2 + mu2^2 contracts to one fma either way round, and the two ways round differ by an ulp: the way is written down
+    const float Cc = fmaf(st.mu1, st.mu1, st.mu2 * st.mu2) + SSIM_C1, D = st.sig1 + st.sig2 + SSIM_C2;
+    if constexpr (RECIPROCAL) return A * B * (1.0f / (Cc * D));
+    else return A * B / (Cc * D);
+}
 
 __global__ void __launch_bounds__(256)
 refine_fwd_kernel(int H, int W, const float* __restrict__ img, const float* __restrict__ gt, RefineWindow win,
                   float* __restrict__ dm_dmu1, float* __restrict__ dm_ds1, float* __restrict__ dm_ds12,
                   double* __restrict__ partial /*[blocks][2]: sum m, sum |x-y|*/)
 {
-    __shared__ float s_x[FEH][FEW + 1], s_y[FEH][FEW + 1];
-    __shared__ float s_h[5][FEH][FW + 1];
+    __shared__ float s_in[2][FH + 2 * RH][FW + 2 * RH + 1];   // x - shift, y - shift
+    __shared__ float s_h[5][FH + 2 * RH][FW + 1];
     __shared__ double s_red[256 / WAVE][2];
-    const int tid = threadIdx.x;
     const int x0 = blockIdx.x * FW, y0 = blockIdx.y * FH;
     const size_t plane = (size_t)blockIdx.z * H * W;
-    const float shift = tile_shift(gt + plane, H, W, y0, x0, FH, FW);   // SHIFTED MOMENTS: LDS holds x - shift, y - shift
-    double msum = 0.0, lsum = 0.0;
-    for (int e = tid; e < FEH * FEW; e += 256) {
-        const int r = e / FEW, c = e - r * FEW;
-        const int gy = y0 + r - RH, gx = x0 + c - RH;
-        const bool in = gy >= 0 && gy < H && gx >= 0 && gx < W;
-        const float xr = in ? img[plane + (size_t)gy * W + gx] : 0.0f;
-        const float yr = in ? gt[plane + (size_t)gy * W + gx] : 0.0f;
-        s_x[r][c] = in ? xr - shift : 0.0f;
-        s_y[r][c] = in ? yr - shift : 0.0f;
-        if (in && r >= RH && r < RH + FH && c >= RH && c < RH + FW) lsum += (double)fabsf(xr - yr);   // the tile's own pixels
-    }
+    const float shift = tile_shift(gt + plane, H, W, y0, x0, FH, FW);   // SHIFTED MOMENTS
+    double sums[2] = {0.0, 0.0};   // m, |x - y|
+    blur_load_tile<FW, FH, 256>(s_in, H, W, y0, x0, [&](size_t o, bool own, float (&v)[2]) {
+        const float xr = img[plane + o], yr = gt[plane + o];
+        v[0] = xr - shift;
+        v[1] = yr - shift;
+        if (own) sums[1] += (double)fabsf(xr - yr);
+    });
     __syncthreads();
-    if (tid < FEH * FHG) {   // horizontal pass: FEH rows x FHG groups of 4 columns
-        const int r = tid / FHG, c0 = (tid - r * FHG) * 4;
-        float xv[RW + 3], yv[RW + 3], xx[RW + 3], yy[RW + 3], xy[RW + 3];
-#pragma unroll
-        for (int k = 0; k < RW + 3; ++k) {
-            xv[k] = s_x[r][c0 + k];
-            yv[k] = s_y[r][c0 + k];
-            xx[k] = xv[k] * xv[k];
-            yy[k] = yv[k] * yv[k];
-            xy[k] = xv[k] * yv[k];
-        }
-#pragma unroll
-        for (int o = 0; o < 4; ++o) {
-            float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, a4 = 0.f;
-#pragma unroll
-            for (int k = 0; k < RW; ++k) {
-                const float wk = win.w[k];
-                a0 += wk * xv[o + k];
-                a1 += wk * yv[o + k];
-                a2 += wk * xx[o + k];
-                a3 += wk * yy[o + k];
-                a4 += wk * xy[o + k];
-            }
-            s_h[0][r][c0 + o] = a0; s_h[1][r][c0 + o] = a1; s_h[2][r][c0 + o] = a2; s_h[3][r][c0 + o] = a3; s_h[4][r][c0 + o] = a4;
-        }
-    }
+    blur_rows<FW, FH, 256, 4, true>(win, s_in, s_h);
     __syncthreads();
-    const int tx = tid & (FW - 1), ty0 = (tid / FW) * 2;   // two vertically adjacent outputs per thread
-    const int gx = x0 + tx;
-    float col[5][RW + 1];
+    const int gx = x0 + blur_out_col<FW>();
+    double cover[2];   // ahead of the column pass: its eleven weights in double are dead before the pass needs its registers
 #pragma unroll
-    for (int k = 0; k < RW + 1; ++k)
-#pragma unroll
-        for (int q = 0; q < 5; ++q) col[q][k] = s_h[q][ty0 + k][tx];
+    for (int o = 0; o < 2; ++o) cover[o] = ssim_cover(win, y0 + blur_out_row<FW, 2>(o), gx, H, W);
+    float v[2][5];
+    blur_cols<FW, FH, 256>(win, s_h, v);
 #pragma unroll
     for (int o = 0; o < 2; ++o) {
-        const int ty = ty0 + o, gy = y0 + ty;
-        if (gy < H && gx < W) {
-            float v[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int k = 0; k < RW; ++k) {
-                const float wk = win.w[k];
-#pragma unroll
-                for (int q = 0; q < 5; ++q) v[q] += wk * col[q][o + k];
-            }
-            const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
-            const SsimStats st = ssim_stats(win, v, shift, gy, gx, H, W);
-            const float mu1 = st.mu1, mu2 = st.mu2, sig1 = st.sig1, sig2 = st.sig2, sig12 = st.sig12;
-            const float A = 2.0f * mu1 * mu2 + C1, B = 2.0f * sig12 + C2;
-            const float Cc = mu1 * mu1 + mu2 * mu2 + C1, D = sig1 + sig2 + C2;
-            const float icd = 1.0f / (Cc * D);
-            const float m = A * B * icd;
-            const size_t oo = plane + (size_t)gy * W + gx;
-            // the partials in double, rounded once: the two halves of dm/dmu1 cancel where x is near y, and in float32 the
-            // roundings of A, B, C and D alone put a one-pixel image's gradient an ulp off
-            const double Ad = 2.0 * (double)mu1 * (double)mu2 + (double)C1, Bd = 2.0 * (double)sig12 + (double)C2;
-            const double Cd = (double)mu1 * (double)mu1 + (double)mu2 * (double)mu2 + (double)C1;
-            const double Dd = (double)sig1 + (double)sig2 + (double)C2;
-            const double icdd = 1.0 / (Cd * Dd);
-            dm_dmu1[oo] = (float)((2.0 * (double)mu2 * (Bd - Ad) * Cd * Dd - Ad * Bd * 2.0 * (double)mu1 * (Dd - Cd)) * icdd * icdd);
-            dm_ds1[oo] = (float)(-Ad * Bd * icdd * icdd * Cd);
-            dm_ds12[oo] = (float)(2.0 * Ad * icdd);
-            msum += (double)m;
-        }
+        const int gy = y0 + blur_out_row<FW, 2>(o);
+        if (gy >= H || gx >= W) continue;
+        const float C1 = SSIM_C1, C2 = SSIM_C2;
+        const SsimStats st = ssim_stats(v[o], shift, cover[o]);
+        const float mu1 = st.mu1, mu2 = st.mu2, sig1 = st.sig1, sig2 = st.sig2, sig12 = st.sig12;
+        const size_t oo = plane + (size_t)gy * W + gx;
+        // the partials in double, rounded once: the two halves of dm/dmu1 cancel where x is near y, and in float32 the
+        // roundings of A, B, C and D alone put a one-pixel image's gradient an ulp off
+        const double Ad = 2.0 * (double)mu1 * (double)mu2 + (double)C1, Bd = 2.0 * (double)sig12 + (double)C2;
+        const double Cd = (double)mu1 * (double)mu1 + (double)mu2 * (double)mu2 + (double)C1;
+        const double Dd = (double)sig1 + (double)sig2 + (double)C2;
+        const double icdd = 1.0 / (Cd * Dd);
+        dm_dmu1[oo] = (float)((2.0 * (double)mu2 * (Bd - Ad) * Cd * Dd - Ad * Bd * 2.0 * (double)mu1 * (Dd - Cd)) * icdd * icdd);
+        dm_ds1[oo] = (float)(-Ad * Bd * icdd * icdd * Cd);
+        dm_ds12[oo] = (float)(2.0 * Ad * icdd);
+        sums[0] += (double)ssim_value<true>(st);
     }
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) {
-        msum += __shfl_xor(msum, d, WAVE);
-        lsum += __shfl_xor(lsum, d, WAVE);
-    }
-    if ((tid & (WAVE - 1)) == 0) { s_red[tid / WAVE][0] = msum; s_red[tid / WAVE][1] = lsum; }
-    __syncthreads();
-    if (tid == 0) {
-        double a = 0, bsum = 0;
-        for (int w = 0; w < 256 / WAVE; ++w) { a += s_red[w][0]; bsum += s_red[w][1]; }
+    block_sum<256>(sums, s_red);
+    if (threadIdx.x == 0) {
         const size_t bid = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-        partial[2 * bid] = a;
-        partial[2 * bid + 1] = bsum;
+        partial[2 * bid] = block_total(s_red, 0);
+        partial[2 * bid + 1] = block_total(s_red, 1);
     }
 }
 
@@ -359,16 +390,10 @@ __device__ __forceinline__ void refine_finish_block(int blocks, double n_total, 
                                                     float* __restrict__ out /*[3] = l1, ssim, loss*/)
 {
     __shared__ double s_red[LOSS_BLOCK / WAVE][2];
-    double a = 0, b = 0;
-    for (int i = threadIdx.x; i < blocks; i += LOSS_BLOCK) { a += partial[2 * (size_t)i]; b += partial[2 * (size_t)i + 1]; }
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) { a += __shfl_xor(a, d, WAVE); b += __shfl_xor(b, d, WAVE); }
-    if ((threadIdx.x & (WAVE - 1)) == 0) { s_red[threadIdx.x / WAVE][0] = a; s_red[threadIdx.x / WAVE][1] = b; }
-    __syncthreads();
+    double t[2];   // sum m, sum |x - y|
+    partials_block_sum<LOSS_BLOCK>(blocks, partial, s_red, t);
     if (threadIdx.x == 0) {
-        double m = 0, l = 0;
-        for (int w = 0; w < LOSS_BLOCK / WAVE; ++w) { m += s_red[w][0]; l += s_red[w][1]; }
-        const double ssim = m / n_total, l1 = l / n_total;
+        const double ssim = t[0] / n_total, l1 = t[1] / n_total;
         out[0] = (float)l1;
         out[1] = (float)ssim;
         out[2] = (float)((1.0 - (double)lambda) * l1 + (double)lambda * (1.0 - ssim));
@@ -381,65 +406,29 @@ refine_bwd_kernel(int H, int W, float n_total, float lambda, const float* __rest
                   const float* __restrict__ dm_ds1, const float* __restrict__ dm_ds12, float* __restrict__ g_img,
                   int blocks, double n_total_d, const double* __restrict__ partial, float* __restrict__ out)
 {
-    __shared__ float s_m[3][FEH][FEW + 1];
-    __shared__ float s_h[3][FEH][FW + 1];
-    const int tid = threadIdx.x;
+    __shared__ float s_in[3][FH + 2 * RH][FW + 2 * RH + 1];   // dm/dmu1, dm/ds1, dm/ds12
+    __shared__ float s_h[3][FH + 2 * RH][FW + 1];
     const int x0 = blockIdx.x * FW, y0 = blockIdx.y * FH;
     const size_t plane = (size_t)blockIdx.z * H * W;
-    for (int e = tid; e < FEH * FEW; e += 256) {
-        const int r = e / FEW, c = e - r * FEW;
-        const int gy = y0 + r - RH, gx = x0 + c - RH;
-        const bool in = gy >= 0 && gy < H && gx >= 0 && gx < W;
-        const size_t o = plane + (size_t)gy * W + gx;
-        s_m[0][r][c] = in ? dm_dmu1[o] : 0.0f;
-        s_m[1][r][c] = in ? dm_ds1[o] : 0.0f;
-        s_m[2][r][c] = in ? dm_ds12[o] : 0.0f;
-    }
+    blur_load_tile<FW, FH, 256>(s_in, H, W, y0, x0, [&](size_t o, bool, float (&v)[3]) {
+        v[0] = dm_dmu1[plane + o];
+        v[1] = dm_ds1[plane + o];
+        v[2] = dm_ds12[plane + o];
+    });
     __syncthreads();
-    if (tid < FEH * FHG) {
-        const int r = tid / FHG, c0 = (tid - r * FHG) * 4;
-        float mv[3][RW + 3];
-#pragma unroll
-        for (int k = 0; k < RW + 3; ++k)
-#pragma unroll
-            for (int q = 0; q < 3; ++q) mv[q][k] = s_m[q][r][c0 + k];
-#pragma unroll
-        for (int o = 0; o < 4; ++o) {
-            float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-#pragma unroll
-            for (int k = 0; k < RW; ++k) {
-                const float wk = win.w[k];
-                a0 += wk * mv[0][o + k];
-                a1 += wk * mv[1][o + k];
-                a2 += wk * mv[2][o + k];
-            }
-            s_h[0][r][c0 + o] = a0; s_h[1][r][c0 + o] = a1; s_h[2][r][c0 + o] = a2;
-        }
-    }
+    blur_rows<FW, FH, 256, 4, false>(win, s_in, s_h);
     __syncthreads();
-    const int tx = tid & (FW - 1), ty0 = (tid / FW) * 2;
-    const int gx = x0 + tx;
-    float col[3][RW + 1];
-#pragma unroll
-    for (int k = 0; k < RW + 1; ++k)
-#pragma unroll
-        for (int q = 0; q < 3; ++q) col[q][k] = s_h[q][ty0 + k][tx];
+    float b[2][3];
+    blur_cols<FW, FH, 256>(win, s_h, b);
+    const int gx = x0 + blur_out_col<FW>();
 #pragma unroll
     for (int o = 0; o < 2; ++o) {
-        const int gy = y0 + ty0 + o;
+        const int gy = y0 + blur_out_row<FW, 2>(o);
         if (gy >= H || gx >= W) continue;
-        float b0 = 0.f, b1 = 0.f, b2 = 0.f;
-#pragma unroll
-        for (int k = 0; k < RW; ++k) {
-            const float wk = win.w[k];
-            b0 += wk * col[0][o + k];
-            b1 += wk * col[1][o + k];
-            b2 += wk * col[2][o + k];
-        }
         const size_t oo = plane + (size_t)gy * W + gx;
         const float x = img[oo], y = gt[oo];
         const float inv_n = 1.0f / n_total;
-        g_img[oo] = (1.0f - lambda) * sgn(x - y) * inv_n - lambda * inv_n * (b0 + 2.0f * x * b1 + y * b2);
+        g_img[oo] = (1.0f - lambda) * sgn(x - y) * inv_n - lambda * inv_n * (b[o][0] + 2.0f * x * b[o][1] + y * b[o][2]);
     }
     if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) refine_finish_block(blocks, n_total_d, lambda, partial, out);
 }
@@ -480,74 +469,37 @@ __global__ void __launch_bounds__(RT * RT)
 eval_metrics_kernel(int H, int W, const float* __restrict__ img, const float* __restrict__ gt, RefineWindow win,
                     double* __restrict__ partial /*[blocks][EVAL_SUMS]*/)
 {
-    __shared__ float s_x[RE][RE + 1], s_y[RE][RE + 1];
-    __shared__ float s_h[5][RE][RT + 1];
+    __shared__ float s_in[2][RT + 2 * RH][RT + 2 * RH + 1];   // clamped x - shift, y - shift
+    __shared__ float s_h[5][RT + 2 * RH][RT + 1];
     __shared__ double s_red[RT * RT / WAVE][EVAL_SUMS];
     const int tid = threadIdx.x;
     const int x0 = blockIdx.x * RT, y0 = blockIdx.y * RT;
     const size_t plane = (size_t)blockIdx.z * H * W;
-    const float shift = tile_shift(gt + plane, H, W, y0, x0, RT, RT);   // SHIFTED MOMENTS: LDS holds x - shift, y - shift
+    const float shift = tile_shift(gt + plane, H, W, y0, x0, RT, RT);   // SHIFTED MOMENTS
     double acc[EVAL_SUMS] = {0.0, 0.0, 0.0};
-    for (int e = tid; e < RE * RE; e += RT * RT) {
-        const int r = e / RE, c = e - r * RE;
-        const int gy = y0 + r - RH, gx = x0 + c - RH;
-        const bool in = gy >= 0 && gy < H && gx >= 0 && gx < W;
-        const float xr = in ? fminf(fmaxf(img[plane + (size_t)gy * W + gx], 0.0f), 1.0f) : 0.0f;   // torch.clamp(rendering, 0.0, 1.0)
-        const float yr = in ? gt[plane + (size_t)gy * W + gx] : 0.0f;
-        s_x[r][c] = in ? xr - shift : 0.0f;
-        s_y[r][c] = in ? yr - shift : 0.0f;
-        if (in && r >= RH && r < RH + RT && c >= RH && c < RH + RT && yr > 0.0f) {   // the tile's own pixels, masked per element
+    blur_load_tile<RT, RT, RT * RT>(s_in, H, W, y0, x0, [&](size_t o, bool own, float (&v)[2]) {
+        const float xr = fminf(fmaxf(img[plane + o], 0.0f), 1.0f);   // torch.clamp(rendering, 0.0, 1.0)
+        const float yr = gt[plane + o];
+        v[0] = xr - shift;
+        v[1] = yr - shift;
+        if (own && yr > 0.0f) {   // masked per element
             const float d = xr - yr;
             acc[1] += (double)(d * d);
             acc[2] += 1.0;
         }
-    }
+    });
     __syncthreads();
-    for (int e = tid; e < RE * RT; e += RT * RT) {
-        const int r = e / RT, c = e - r * RT;
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, a4 = 0.f;
-#pragma unroll
-        for (int k = 0; k < RW; ++k) {
-            const float xv = s_x[r][c + k], yv = s_y[r][c + k], wk = win.w[k];
-            a0 += wk * xv;
-            a1 += wk * yv;
-            a2 += wk * (xv * xv);
-            a3 += wk * (yv * yv);
-            a4 += wk * (xv * yv);
-        }
-        s_h[0][r][c] = a0; s_h[1][r][c] = a1; s_h[2][r][c] = a2; s_h[3][r][c] = a3; s_h[4][r][c] = a4;
-    }
+    blur_rows<RT, RT, RT * RT, 1, true>(win, s_in, s_h);
     __syncthreads();
-    const int ty = tid / RT, tx = tid - ty * RT;
-    const int gy = y0 + ty, gx = x0 + tx;
-    if (gy < H && gx < W) {
-        float v[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int k = 0; k < RW; ++k) {
-            const float wk = win.w[k];
-#pragma unroll
-            for (int q = 0; q < 5; ++q) v[q] += wk * s_h[q][ty + k][tx];
-        }
-        const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
-        const SsimStats st = ssim_stats(win, v, shift, gy, gx, H, W);
-        const float mu1 = st.mu1, mu2 = st.mu2, sig1 = st.sig1, sig2 = st.sig2, sig12 = st.sig12;
-        const float A = 2.0f * mu1 * mu2 + C1, B = 2.0f * sig12 + C2;
-        const float Cc = mu1 * mu1 + mu2 * mu2 + C1, D = sig1 + sig2 + C2;
-        acc[0] = (double)(A * B / (Cc * D));
-    }
-#pragma unroll
-    for (int k = 0; k < EVAL_SUMS; ++k) {
-        double t = acc[k];
-#pragma unroll
-        for (int d = 1; d < WAVE; d <<= 1) t += __shfl_xor(t, d, WAVE);
-        if ((tid & (WAVE - 1)) == 0) s_red[tid / WAVE][k] = t;
-    }
-    __syncthreads();
+    const int gy = y0 + blur_out_row<RT, 1>(0), gx = x0 + blur_out_col<RT>();
+    const double cover = ssim_cover(win, gy, gx, H, W);   // ahead of the column pass, as in refine_fwd_kernel
+    float v[1][5];
+    blur_cols<RT, RT, RT * RT>(win, s_h, v);
+    if (gy < H && gx < W) acc[0] = (double)ssim_value<false>(ssim_stats(v[0], shift, cover));
+    block_sum<RT * RT>(acc, s_red);
     if (tid < EVAL_SUMS) {
-        double t = 0;
-        for (int w = 0; w < RT * RT / WAVE; ++w) t += s_red[w][tid];
         const size_t bid = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-        partial[EVAL_SUMS * bid + tid] = t;
+        partial[EVAL_SUMS * bid + tid] = block_total(s_red, tid);
     }
 }
 
@@ -556,23 +508,9 @@ eval_metrics_finish_kernel(int blocks, double n_total, const double* __restrict_
                            float* __restrict__ out /*[4] = psnr, ssim, masked mse, mask count*/)
 {
     __shared__ double s_red[LOSS_BLOCK / WAVE][EVAL_SUMS];
-    double acc[EVAL_SUMS] = {0.0, 0.0, 0.0};
-    for (int i = threadIdx.x; i < blocks; i += blockDim.x)
-        for (int k = 0; k < EVAL_SUMS; ++k) acc[k] += partial[EVAL_SUMS * (size_t)i + k];
-#pragma unroll
-    for (int k = 0; k < EVAL_SUMS; ++k) {
-        double t = acc[k];
-#pragma unroll
-        for (int d = 1; d < WAVE; d <<= 1) t += __shfl_xor(t, d, WAVE);
-        if ((threadIdx.x & (WAVE - 1)) == 0) s_red[threadIdx.x / WAVE][k] = t;
-    }
-    __syncthreads();
+    double t[EVAL_SUMS];
+    partials_block_sum<LOSS_BLOCK>(blocks, partial, s_red, t);
     if (threadIdx.x == 0) {
-        double t[EVAL_SUMS];
-        for (int k = 0; k < EVAL_SUMS; ++k) {
-            t[k] = 0;
-            for (int w = 0; w < LOSS_BLOCK / WAVE; ++w) t[k] += s_red[w][k];
-        }
         const double mse = t[2] > 0 ? t[1] / t[2] : 0.0 / 0.0;     // an empty mask: the reference's mean over nothing is NaN
         out[0] = (float)(20.0 * log10(1.0 / sqrt(mse)));
         out[1] = (float)(t[0] / n_total);

@@ -15,6 +15,7 @@
 // The whole file is compiled without FP contraction (build.py NO_CONTRACT): the residuals and the minimal solver round like
 // the f64 restatement of tests/test_host_pnp.py.
 #include "common.h"
+#include "reduce.h"
 
 #include <math.h>
 
@@ -269,18 +270,6 @@ __device__ __forceinline__ bool pnp_better(int32_t c1, double s1, int32_t k1, in
     return c1 > c2 || (c1 == c2 && (s1 < s2 || (s1 == s2 && k1 < k2)));
 }
 
-__device__ __forceinline__ double wave_sum(double v)
-{
-    for (int d = 1; d < WAVE; d <<= 1) v += __shfl_xor(v, d, WAVE);
-    return v;
-}
-
-__device__ __forceinline__ int wave_sum_i(int v)
-{
-    for (int d = 1; d < WAVE; d <<= 1) v += __shfl_xor(v, d, WAVE);
-    return v;
-}
-
 // ---------------------------------------------------------------------------------------------------------------- kernels
 __global__ void pnp_init_kernel(int32_t B, const splatraster_pnp_problem* probs, PnpState* state)
 {
@@ -357,7 +346,7 @@ __global__ void __launch_bounds__(256) pnp_score_kernel(int32_t B, const splatra
             s += r;
         }
     }
-    c = wave_sum_i(c);
+    c = wave_sum(c);
     s = wave_sum(s);
     if (lane == 0) {
         count[slot] = c;
@@ -460,7 +449,7 @@ __device__ void pnp_block_score(const splatraster_pnp_problem* prp, const double
             s += r;
         }
     }
-    c = wave_sum_i(c);
+    c = wave_sum(c);
     s = wave_sum(s);
     if (lane == 0) {
         red[w * 2] = (double)c;

@@ -1,6 +1,6 @@
 // pose.hip — the two small kernels that close the pose-refinement loop on the device (splatloc_amd/pose.py refine_pose), and
 // their forms for the frames of a window (refine_poses: blockIdx.y = view of the loss, one thread per camera of the step):
-//   l1_rgbd_loss_kernel  L = mean |colour - target| + w_d mean |depth - target_d| and its gradient planes, one pass;
+//   l1_rgbd_loss_window_kernel  L = mean |colour - target| + w_d mean |depth - target_d| and its gradient planes, one pass;
 //   pose_step_kernel     ONE thread: chains dL/dviewmatrix, dL/dprojmatrix, dL/dcampos (what the rasterizer's backward
 //                        returns, preprocess_bwd.hip) through  view = (T(w, t) W2C0)^T,  proj = view P,  campos = -R^T t  to the
 //                        six pose parameters (axis-angle w, translation t; utils/optimization_utils.py:31-42's
@@ -42,35 +42,7 @@ __device__ __forceinline__ float l1_region(int64_t n, const float* __restrict__ 
     return acc;
 }
 
-// (round 5's first version: one element per thread and iteration, 1 200 blocks each ending in an atomic on the one loss word —
-//  23.6 us for 1.2 M elements, most of it the atomics' queue; now at most 256 blocks and 16-byte accesses)
-__global__ void __launch_bounds__(L1_THREADS)
-l1_rgbd_loss_kernel(int64_t n_color, const float* __restrict__ color, const float* __restrict__ tgt_c, int64_t n_depth,
-                    const float* __restrict__ depth, const float* __restrict__ tgt_d, float depth_weight,
-                    float* __restrict__ g_color, float* __restrict__ g_depth, float* __restrict__ loss_out)
-{
-    __shared__ float s_sum[L1_THREADS / WAVE];
-    const float wc = 1.0f / (float)n_color, wd = (tgt_d && n_depth) ? depth_weight / (float)n_depth : 0.0f;
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthreads = (int64_t)gridDim.x * blockDim.x;
-    float acc = l1_region(n_color, color, tgt_c, wc, g_color, tid, nthreads);
-    if (tgt_d) {
-        acc += l1_region(n_depth, depth, tgt_d, wd, g_depth, tid, nthreads);
-    } else if (g_depth) {
-        for (int64_t e = tid; e < n_depth; e += nthreads) g_depth[e] = 0.0f;
-    }
-#pragma unroll
-    for (int o = WAVE / 2; o > 0; o >>= 1) acc += __shfl_xor(acc, o, WAVE);
-    if ((threadIdx.x & (WAVE - 1)) == 0) s_sum[threadIdx.x / WAVE] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float t = 0.0f;
-#pragma unroll
-        for (int k = 0; k < L1_THREADS / WAVE; ++k) t += s_sum[k];
-        atomicAdd(loss_out, t);
-    }
-}
-
-// the same for the V views of a window, blockIdx.y = view: a view's blocks do what l1_rgbd_loss_kernel's do on its planes
+// the V views of a window, blockIdx.y = view; a single frame is a window of one view (launch_l1_rgbd_loss)
 struct L1Views {
     const float* color[MAX_VIEWS];
     const float* tgt_c[MAX_VIEWS];
@@ -79,6 +51,8 @@ struct L1Views {
     float* g_color[MAX_VIEWS];
     float* g_depth[MAX_VIEWS];
 };
+// (round 5's first version: one element per thread and iteration, 1 200 blocks each ending in an atomic on the one loss word —
+//  23.6 us for 1.2 M elements, most of it the atomics' queue; now at most 256 blocks and 16-byte accesses)
 __global__ void __launch_bounds__(L1_THREADS)
 l1_rgbd_loss_window_kernel(int64_t n_color, int64_t n_depth, L1Views views, float depth_weight, float* __restrict__ loss_out)
 {
@@ -125,10 +99,10 @@ static int launch_l1_rgbd_loss(int64_t n_color, const float* color, const float*
                         const float* tgt_d, float depth_weight, float* g_color, float* g_depth, float* loss_out,
                         hipStream_t stream)
 {
-    hipLaunchKernelGGL(l1_rgbd_loss_kernel, dim3(l1_blocks(n_color + n_depth)), dim3(L1_THREADS), 0, stream, n_color, color, tgt_c,
-                       n_depth, depth, tgt_d, depth_weight, g_color, g_depth, loss_out);
-    SR_LAUNCH_CHECK();
-    return SPLATRASTER_OK;
+    L1Views one{};
+    one.color[0] = color; one.tgt_c[0] = tgt_c; one.depth[0] = depth; one.tgt_d[0] = tgt_d;
+    one.g_color[0] = g_color; one.g_depth[0] = g_depth;
+    return launch_l1_rgbd_loss_window(1, one, n_color, n_depth, depth_weight, loss_out, stream);
 }
 
 // forward-mode derivative with respect to the three components of w

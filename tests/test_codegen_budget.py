@@ -112,3 +112,21 @@ def test_per_gaussian_backward_kernels_keep_their_occupancy():
         assert k["Occupancy"] >= 3 and k["LDS Size"] == 516, (tq, k)
     k = _kernel(cam, "_ZN2sr17camera_bwd_kernelE")
     assert k["Occupancy"] >= 8 and k["LDS Size"] == 516, k
+
+
+def test_loss_stage_kernels_keep_their_occupancy_and_lds():
+    """The loss stage's kernels since they share their block sums (reduce.h), one blur body and one L1 kernel: nothing in scratch,
+    no spill, and no kernel below the waves per SIMD or above the LDS footprint it had with its own copy of each (refine_fwd_kernel
+    then needed 115 VGPRs for 4 waves; LDS may only shrink)."""
+    losses, densify, pose = _usage("losses.hip"), _usage("densify.hip"), _usage("pose.hip")
+    pins = ((losses, "_ZN2sr17refine_fwd_kernelE", 4, 26192), (losses, "_ZN2sr17refine_bwd_kernelE", 6, 23792),
+            (losses, "_ZN2sr19eval_metrics_kernelE", 6, 14576), (losses, "_ZN2sr19mapping_loss_kernelE", 8, 160),
+            (losses, "_ZN2sr26mapping_loss_finish_kernelE", 8, 160), (losses, "_ZN2sr26eval_metrics_finish_kernelE", 8, 96),
+            (densify, "_ZN2sr20isotropic_fwd_kernelE", 8, 64), (densify, "_ZN2sr23isotropic_finish_kernelE", 8, 0),
+            (pose, "_ZN2sr26l1_rgbd_loss_window_kernelE", 8, 16))
+    for u, name, waves, lds in pins:
+        k = _kernel(u, name)
+        assert k["ScratchSize"] == 0 and k["VGPRs Spill"] == 0 and k["SGPRs Spill"] == 0, (name, k)
+        assert k["Occupancy"] >= waves and k["LDS Size"] <= lds, (name, k)
+    assert _kernel(losses, "_ZN2sr17refine_fwd_kernelE")["VGPRs"] <= 115
+    assert len(losses) == 6 and not [k for k in pose if "l1_rgbd_loss_kernel" in k], (list(losses), list(pose))

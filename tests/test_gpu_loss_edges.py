@@ -7,8 +7,8 @@ Needs an MI355X.
 Measured on an MI355X (device error) / E_ref, the bound being 4: per-pixel maps (the image gradient at lambda 0.2 and 1.0; for the mapping
 loss dL/dmarker) and the worst scalar of the case (the largest error / bound over the lambdas / exposure variants), with its error / bound
 where the one-ulp floor decided.  The mapping gradients g_image and g_depth are 0 ulp from the reference's elements in every case and
-variant (1 ulp from the rounded oracle in the grid-stride case).  The SSIM of the two blur bodies is bit-identical in every case but
-shape 1x1x1, where it is 1 ulp apart (the two tiles, 16x16 and 32x16, take their shift from different samples).
+variant (1 ulp from the rounded oracle in the grid-stride case).  The SSIM of the one blur body at its two tile shapes is bit-identical in
+every case but shape 1x1x1, where it is 1 ulp apart (the two tiles, 16x16 and 32x16, take their shift from different samples).
 
     stage    case                     map, lambda 0.2   map, lambda 1.0   worst scalar: error/E_ref  error/bound  (which)
                                      (mapping: g_marker)
@@ -55,7 +55,7 @@ flat_equal has no meaningful E_ref (a reference error of 7e-9): its gradient is 
 
 Two scalars missed their bound when these tests were first run, and the kernels were changed for it (csrc/losses.hip):
   * content smooth_converged, SSIM mean: 4.11 times E_ref.  Every pixel's SSIM carried a float32 cancellation error of about 1e-4
-    (sigma = E[x^2] - mu^2 against C2 = 9e-4).  Both blur bodies now accumulate the moments of x - c and y - c, c one value per tile (the
+    (sigma = E[x^2] - mu^2 against C2 = 9e-4).  The SSIM kernels now blur the moments of x - c and y - c, c one value per tile (the
     median of three gt samples), with the zero padding accounted for exactly (SHIFTED MOMENTS in losses.hip): 0.40 times E_ref, and
     flat_offset went from 0.24 to 0.12.  The SSIM partials are formed in double and rounded once: in float32 the roundings of the four
     factors alone put the gradient of shape 1x1x1 one ulp of itself off, over its bound.
@@ -211,8 +211,9 @@ def test_refinement_loss_non_contiguous_input_and_upstream_gradient(name):
 
 @pytest.mark.parametrize("name", [R.shape_name(s) for s in R.REFINE_SHAPES] + ["content noise", "content l1_ties", "content black"])
 def test_the_two_blur_bodies_agree(name):
-    """eval_metrics_kernel restates the blur on its own 16x16 tile with its own loader: on inputs already in [0, 1] its SSIM and that of the
-    refinement kernels (32x16 tiles, register-blocked passes) agree to one float32 ulp"""
+    """one blur body, two tile shapes: eval_metrics_kernel instantiates it on a 16x16 tile with one output per work item, the refinement
+    kernels on 32x16 tiles with register-blocked passes; the blurred values do not depend on that, the per-tile shift does: on inputs
+    already in [0, 1] the two SSIM means agree to one float32 ulp"""
     from splatloc_amd.evaluation import eval_metrics
     from splatloc_amd.losses import ssim
     c = R.refine_case(name)

@@ -244,6 +244,65 @@ def test_l1_rgbd_loss_window_matches_single_calls(V, odd):
         assert (l1 > 0).all() and ((lw - l1).abs() <= 2e-6 * l1).all()
 
 
+@pytest.mark.parametrize("with_depth", [True, False])
+@pytest.mark.parametrize("offset", [0, 1])
+def test_the_single_view_l1_entry_is_the_window_kernel(offset, with_depth):
+    """splatraster_l1_rgbd_loss launches l1_rgbd_loss_window_kernel with one view.  Colour 3x5x7 = 105 elements (26 float4 and a
+    tail of one) and depth 1x5x7 are ONE block, so the loss is summed in one fixed order and can be compared bit for bit:
+    the single-view call, the window call at V = 1 and view 3 of a window of eight whose other views hold other data give the
+    same loss word and the same gradient planes.  offset = 1: colour, target and gradient start one float behind a 16-byte
+    boundary, which takes the kernel's scalar path.  The loss itself: within 2e-6 of a float64 sum, the bound of
+    test_l1_rgbd_loss_window_matches_single_calls (at most 12 float32 roundings per partial sum here: 7e-7)."""
+    from splatloc_amd import _native
+    lib = _native.load()
+    dev = torch.device("cuda:0")
+    n_c, n_d, V, slot, wd = 3 * 5 * 7, 5 * 7, 8, 3, 0.2
+    g = torch.Generator().manual_seed(41 + offset)
+    pad = 4 + ((n_c + 3) & ~3)                     # a view's row: 16-byte aligned, room for the offset
+    col, tc = torch.rand(V, pad, generator=g).to(dev), torch.rand(V, pad, generator=g).to(dev)
+    dep, td = torch.rand(V, 36, generator=g).to(dev), torch.rand(V, 36, generator=g).to(dev)
+    tc[:, offset:offset + n_c:7] = col[:, offset:offset + n_c:7]      # exact zeros of the difference: gradient 0
+    assert all(t[v].data_ptr() % 16 == 0 for t in (col, tc, dep, td) for v in range(V))
+
+    def view(lv, k, v, gc, gd):
+        lv[k].color, lv[k].target_color = col[v].data_ptr() + 4 * offset, tc[v].data_ptr() + 4 * offset
+        lv[k].depth, lv[k].target_depth = dep[v].data_ptr(), td[v].data_ptr() if with_depth else None
+        lv[k].g_color, lv[k].g_depth = gc.data_ptr() + 4 * offset, gd.data_ptr()
+
+    def planes(n):
+        return torch.full((n, pad), 7.0, device=dev), torch.ones(n, 36, device=dev), torch.zeros(n, device=dev)
+
+    gc1, gd1, l1 = planes(1)
+    _native.check(lib.splatraster_l1_rgbd_loss(n_c, C.c_void_p(col[slot].data_ptr() + 4 * offset), C.c_void_p(tc[slot].data_ptr() + 4 * offset),
+                                               n_d, _ptr(dep[slot]), _ptr(td[slot]) if with_depth else None, wd,
+                                               C.c_void_p(gc1.data_ptr() + 4 * offset), _ptr(gd1), _ptr(l1), None), "l1")
+    gcw, gdw, lw = planes(1)
+    lv = (_native.L1View * 1)()
+    view(lv, 0, slot, gcw[0], gdw[0])
+    _native.check(lib.splatraster_l1_rgbd_loss_window(1, lv, n_c, n_d, wd, _ptr(lw), None), "l1_window 1")
+    gc8, gd8, l8 = planes(V)
+    lv = (_native.L1View * V)()
+    for v in range(V):
+        view(lv, v, v, gc8[v], gd8[v])
+    _native.check(lib.splatraster_l1_rgbd_loss_window(V, lv, n_c, n_d, wd, _ptr(l8), None), "l1_window 8")
+    torch.cuda.synchronize()
+    for name, gc, gd, loss in (("V = 1", gcw[0], gdw[0], lw), ("view 3 of 8", gc8[slot], gd8[slot], l8[slot:slot + 1])):
+        assert torch.equal(gc, gc1[0]) and torch.equal(gd, gd1[0]), name
+        assert torch.equal(loss.view(torch.int32), l1.view(torch.int32)), (name, float(loss), float(l1))
+    assert not torch.equal(gc8[0], gc8[slot]) and l8[0] != l8[slot]            # the other views did hold other data
+    own = gc1[0, offset:offset + n_c]
+    assert (own[::7] == 0).all() and own.abs().max() > 0 and (gc1[0, :offset] == 7).all() and (gc1[0, offset + n_c:] == 7).all()
+    assert (gd1[0, n_d:] == 1).all()                                            # nothing written behind the planes
+    if not with_depth:
+        assert not gd1[0, :n_d].any()                                           # no depth target: the plane is zeroed
+    x, t = col[slot, offset:offset + n_c].cpu().double().numpy(), tc[slot, offset:offset + n_c].cpu().double().numpy()
+    ref = np.abs(x - t).sum() / n_c
+    if with_depth:
+        ref += wd * np.abs(dep[slot, :n_d].cpu().double().numpy() - td[slot, :n_d].cpu().double().numpy()).sum() / n_d
+    print(f"offset={offset} depth={with_depth}: loss {float(l1[0]):.9g}, float64 {ref:.9g}, rel {abs(float(l1[0]) - ref) / ref:.2e}")
+    assert abs(float(l1[0]) - ref) <= 2e-6 * ref
+
+
 # ---- the Adam step of a window ---------------------------------------------------------------------------------------------
 
 def test_pose_step_window_matches_autograd_adam_and_is_slot_independent():

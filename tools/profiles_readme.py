@@ -58,6 +58,7 @@ WHAT = [   # (file name regex, description; {placeholders} are filled by the ext
     (r"^payload_compact_pmc_hbm\.json$", "separate `--pmc FETCH_SIZE` / `--pmc WRITE_SIZE` runs of the default bench, parent and change, for the payload and the two compositing kernels, and the live fraction of the window's tile instances read through `introspect.payload_state`: {pc_pmc}"),
     (r"^fwd_shared_steps_ab\.json$", "`tools/ab.py`, base = the change (the forward walkers' shared steps, HISTORY §21), variant `parent` = the parent commit's library (differences are parent minus change): {ab}; the other workloads, `--stage refine_step`, the `composite_fwd` stage in ms and cycles and the bit-for-bit comparison of the outputs under `other_runs` / `outputs_parent_vs_change`"),
     (r"^bwd_shared_contract_ab\.json$", "`tools/ab.py`, base = the change (the backward takes its frame, alpha test, partition and segment records from `composite_common.h`, HISTORY §22), variant `parent` = the parent commit's library (differences are parent minus change): {ab}; the other runs that were made, `--stage refine_step`, the `composite_bwd` stage in ms and cycles and the bit-for-bit comparison of outputs and deterministic-mode gradients under `other_runs` / `outputs_parent_vs_change`"),
+    (r"^loss_shared_bodies_ab\.json$", "the loss stage's shared bodies (HISTORY §23) against the parent commit's library: interleaved pairs of fresh `bench.py --stage loss` / `refine_step` / `eval_rendering` / `pose_refine` processes on one box (200 steps, 20 warm-up), every run, and per stage the medians, the parent's spread and the paired difference (head minus parent) with its 95 % interval under `summary`; per-kernel means of one `rocprofv3 --kernel-trace --stats` run per side under `kernel_trace`"),
     (r"^payload_compact_ab.*\.json$", "`tools/ab.py`, base = the change (compact payload), variant `parent` = the parent commit's library (differences are parent minus change): {ab}; {pc_ab}"),
     (r"traffic\.json$", "per-stage HBM bytes per launch that `bench.py` replays as `roofline.traffic` (recorded workload / launch mode inside)"),
     (r"valu\.json$", "VALU / MFMA / SALU wave-instructions, busy fractions of the two compositing kernels per launch (replayed by `bench.py` as `frame_valu` / `roofline_valu`)"),
