@@ -74,8 +74,10 @@ typedef struct splatraster_settings {
     int32_t channels;    /* C: composited channels. colors_precomp is [P, C]; with shs, C must be 3 */
     int32_t bg_channels; /* number of valid floats behind bg; channels >= bg_channels read 0 (train_gaussians.py:70 passes 3 for C = 4) */
     int32_t prefiltered;
-    int32_t debug;
+    int32_t debug;       /* bit 1 (SPLATRASTER_SETTINGS_FORWARD_ONLY): no backward will read this frame's buffers — the render stage
+                          * then skips what only a backward uses (the dead marks of the wide forward); other bits: unused */
 } splatraster_settings;
+#define SPLATRASTER_SETTINGS_FORWARD_ONLY 2
 
 /* ---- buffer sizing ------------------------------------------------------------------ */
 
@@ -1123,6 +1125,13 @@ int splatraster_debug_set_payload_stream_min(int64_t instances);
  * alpha are bit-identical for C <= 4 and C = 32..35 (C >= 36: which candidates share a pair-sum changes the last bit).  The
  * backward reads a binning buffer the way its render stage wrote it, whatever the switch says by then. */
 int splatraster_debug_set_payload_compact(int mode);
+/* A/B / test hook: the forward of wide layouts (C > 4) marks, in bits 28..31 of the payload word, the list entries it evaluated for a
+ * quadrant without any pixel still accumulating AND past the alpha test (occluded footprints, Gaussians that pass between pixel
+ * centres), and the backward does not walk them.  A render whose settings carry SPLATRASTER_SETTINGS_FORWARD_ONLY writes
+ * no marks (a backward over it would walk every entry: correct, only slower).  1 (default): on; 0: the backward ignores the marks (the forward keeps
+ * writing them).  Images, final_T, n_contrib and the lists never depend on it; gradients are bit-identical in the deterministic mode
+ * and sums over the same pixels in the same order otherwise (which candidates share a pair or a flush group changes). */
+int splatraster_debug_set_dead_marks(int on);
 /* A/B / test hook: which front end orders the tile instances.  -1 (default): the binned front end (counting sort by
  * (view, tile) + one LDS sort per tile) for windows of at most 6144 (view, tile) lists — SplatLoc's own
  * 640x480 frames, singly or five at a time — and the two global radix sorts otherwise; 0: the radix sorts always; 1: the

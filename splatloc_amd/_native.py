@@ -186,6 +186,7 @@ SYMBOLS = {
     "splatraster_debug_set_sort_fork": (C.c_int, [C.c_int]),
     "splatraster_debug_set_payload_stream_min": (C.c_int, [C.c_int64]),
     "splatraster_debug_set_payload_compact": (C.c_int, [C.c_int]),
+    "splatraster_debug_set_dead_marks": (C.c_int, [C.c_int]),
     "splatraster_mark_visible": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp]),
     "splatraster_get_geometry_layout": (C.c_int, [_i32, C.POINTER(GeometryLayout)]),
     "splatraster_get_binning_layout": (C.c_int, [_i32, _i64, _i32, _i32, _i32, C.POINTER(BinningLayout)]),
@@ -314,6 +315,8 @@ def load(build_if_missing: bool = True):
         lib.splatraster_debug_set_front_end(int(os.environ["SPLATRASTER_FRONT_END"]))
     if os.environ.get("SPLATRASTER_PAYLOAD_COMPACT"):   # -1 default (compact stream behind the radix front end), 0 the full stream
         lib.splatraster_debug_set_payload_compact(int(os.environ["SPLATRASTER_PAYLOAD_COMPACT"]))
+    if os.environ.get("SPLATRASTER_DEAD_MARKS"):   # 1 default (the backward skips the entries the forward marked dead), 0 it walks them
+        lib.splatraster_debug_set_dead_marks(int(os.environ["SPLATRASTER_DEAD_MARKS"]))
     if os.environ.get("SPLATRASTER_TILE_SORT_CAP"):
         lib.splatraster_debug_set_tile_sort_cap(int(os.environ["SPLATRASTER_TILE_SORT_CAP"]))
     if os.environ.get("SPLATRASTER_SORT_FORK"):
@@ -376,6 +379,15 @@ def set_payload_compact(mode: int) -> None:
     """-1: default (the compositing kernels stream only the instances that reach a quadrant, behind the radix front end);
     0: the full stream (splatraster_debug_set_payload_compact)."""
     check(load().splatraster_debug_set_payload_compact(int(mode)), "set_payload_compact")
+
+
+SETTINGS_FORWARD_ONLY = 2   # == SPLATRASTER_SETTINGS_FORWARD_ONLY: a bit of Settings.debug
+
+
+def set_dead_marks(on: bool) -> None:
+    """True (default): the backward skips the list entries the forward marked dead for a quadrant; False: it walks them
+    (splatraster_debug_set_dead_marks)."""
+    check(load().splatraster_debug_set_dead_marks(int(bool(on))), "set_dead_marks")
 
 
 def poll_stall() -> bool:

@@ -20,6 +20,7 @@ static int g_deterministic = 0;   // splatraster_debug_set_deterministic
 static int g_split_max_waves = SPLIT_MAX_WAVES;   // quadrant-waves up to which a narrow launch is split
 static int g_fwd_team = -1;         // -1: automatic (the split launches' condition), 0: never, 1: every narrow launch that has a launch order, 2: and a team for each of its first TEAM_MAX lists
 static int g_payload_compact = -1;  // -1 default (on), 0 off (payload_kernel, the full stream)
+static int g_dead_marks = 1;        // the backward skips the entries the forward marked dead (0: it walks them)
 static int g_bin_mode = -1;         // front end: -1 auto, 0 radix always, 1 binned whenever the shape allows
 
 void set_hip_error(hipError_t e, const char* what)
@@ -434,6 +435,7 @@ static FramePlan frame_plan(int32_t W, int32_t H, int C, int32_t P, int32_t V, i
     // whole lists — the binned front end writes its own payload, a team or a split launch walks full list positions
     p.compact = rendered ? w.compact : g_payload_compact != 0 && R > 0 && !p.binned && !p.split && !p.team;
     assert(!p.compact || (!p.binned && !p.split && !p.team && R > 0));
+    p.dead_marks = g_dead_marks != 0;   // (read by the backward alone: an unmarked stream and an ignored mark are both walked in full)
     return p;
 }
 
@@ -1076,6 +1078,12 @@ int splatraster_debug_set_payload_stream_min(int64_t instances)
 int splatraster_debug_set_payload_compact(int mode)
 {
     g_payload_compact = mode < 0 ? -1 : (mode ? 1 : 0);
+    return SPLATRASTER_OK;
+}
+
+int splatraster_debug_set_dead_marks(int on)
+{
+    g_dead_marks = on ? 1 : 0;
     return SPLATRASTER_OK;
 }
 

@@ -111,7 +111,11 @@ struct BinView {
     void* sort_tmp;       // radix sort scratch
     float4* irec;         // [2R] per-instance copy of the 32-byte record, in sorted order
     uint32_t* ipack;      // [R] point_list[j] (a row id < 2^24) | reach bits << 24 (bit q: the Gaussian may reach quadrant q of its tile):
-                          //     ONE word per entry is all a compositing wave prefetches
+                          //     ONE word per entry is all a compositing wave prefetches.  Bits 28..31 are the DEAD MARKS, written as 0 by
+                          //     every front end and ORed in by composite_fwd_kernel (wide layouts) in the pass that writes the auxiliary
+                          //     planes: bit 28 + q = the forward evaluated the entry for quadrant q and NO lane was live at it (still
+                          //     accumulating and past the alpha test), so no pixel of q has it as a contributor and the backward skips it.
+                          //     Forwards read bits 24..27 and the id only: an entry that merely FINISHES pixels is live and never marked.
     float* featp;         // [P * CP] feature rows padded to CP = roundup4(C) floats (16-byte aligned rows); shared by the views
     float* gacc;          // [gacc_total_floats(C, P, V)] backward gradient accumulator: the shared colour rows, then one row per (view, Gaussian) (GaccLayout)
     float* pose_acc;      // right behind gacc (one fill zeroes both): POSE_SETS replicated accumulator sets of the camera gradients + the ticket word
@@ -119,8 +123,9 @@ struct BinView {
     float* ckpt;          // [V][SPLIT_PARTS_MAX][C + 2][H * W] segment records of the forward (T in front of the segment, its own colours, depth), split launches only
     uint32_t* tile_order; // [V * tiles] global tile ids, longest list first: the launch order of the compositing kernels
 };
+constexpr uint32_t IPACK_REACH0 = 1u << 24, IPACK_DEAD0 = 1u << 28;   // quadrant 0's reach bit and dead mark of an ipack word (quadrant q: << q)
 struct ImgView {
-    float* final_T;         // [V][H * W]
+    float* final_T;        // [V][H * W]
     uint32_t* n_contrib;    // [V][H * W] a pixel's last contributor: its position in the tile's list + 1 (0: none)
     // compact payload (binning.hip payload_tile_kernel; behind the plain planes, whose offsets are what they always were):
     uint32_t* n_contrib_c;  // [V][H * W] the same contributor's position + 1 in the list's COMPACT stream: what the backward bounds its walk by.
@@ -144,6 +149,7 @@ struct FramePlan {
     bool team;            // forward: composite_fwd_mixed_kernel where the launch has an order (follows `split` unless forced)
     int team_every;       // ... and a team for each of its first TEAM_MAX lists
     bool order;           // the compositing grids run in launch order (tile_order, nparts)
+    bool dead_marks;      // the backward skips the entries the forward marked dead (BinView::ipack); off: it walks them as unmarked ones
 };
 
 GeomView geom_view(void* base, int32_t P, int32_t V);

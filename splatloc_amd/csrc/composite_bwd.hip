@@ -219,7 +219,9 @@ composite_bwd_kernel(int W, int H, int C_total, int CP4, int c0, int first_pass,
                      const uint32_t* __restrict__ nparts /*split launches: parts of every (view, tile) list, or null: SPLIT_PARTS*/,
                      int extra_blocks /*split launches: workgroups at the head of the grid that walk parts 4 .. of the longest lists*/,
                      const uint32_t* __restrict__ tile_order /*launch order (binning.hip), or null*/,
-                     int det_pass /*DET only: 0 = per-element max of |partial|, 1 = fixed-point sums (acc_add)*/)
+                     int det_pass /*DET only: 0 = per-element max of |partial|, 1 = fixed-point sums (acc_add)*/,
+                     uint32_t cand_bits /*quadrant 0's bits of a list word that decide a candidate: IPACK_REACH0 | IPACK_DEAD0, or
+                                          IPACK_REACH0 alone (the forward's dead marks ignored: splatraster_debug_set_dead_marks)*/)
 {
     using Cfg = BwdCfg<NC, SP, AUX>;
     // DET (the accurate mode): the walk's state T, A and everything derived from it in double; else float
@@ -534,7 +536,9 @@ composite_bwd_kernel(int W, int H, int C_total, int CP4, int c0, int first_pass,
 #pragma unroll 1
     for (int chunk = nchunks - 1; chunk >= 0; --chunk) {
         const uint32_t base = beg + (uint32_t)chunk * WAVE;
-        const bool cur_reach = (pw >> (24 + quad)) & 1u;
+        // a candidate may reach this quadrant AND the forward did not find it dead there (no lane live: then no pixel has
+        // `idx < last && pass`, the entry leaves T and A alone and adds zeros — DESIGN.md §6.2)
+        const bool cur_reach = (pw & (cand_bits << quad)) == (IPACK_REACH0 << quad);
         uint64_t cand = __builtin_amdgcn_ballot_w64(cur_reach);
         const uint32_t cur_gid = (pw & 0xFFFFFFu) - row0;   // the Gaussian's index in its view: what the feature and accumulator rows are addressed with
         // the chunk in front: requested now, consumed after this one (the loop's last iteration requests nothing: the guard
@@ -754,7 +758,7 @@ static int launch_one_bwd(const FramePlan& p, int c0, int first, const BinView& 
                        b.ranges, b.ipack, b.irec, reinterpret_cast<const float4*>(feat), *L.grads,       \
                        im.final_T, im.n_contrib, gacc, GL,                                                             \
                        gacc_moment_offset(p.C), gacc64, ckpt, extras ? b.nparts : nullptr, (int)extra_blocks,                      \
-                       p.order ? b.tile_order : nullptr, L.det_pass)
+                       p.order ? b.tile_order : nullptr, L.det_pass, p.dead_marks ? IPACK_REACH0 | IPACK_DEAD0 : IPACK_REACH0)
     if constexpr (NC >= 4 && NC <= 15 && AUX) {   // C = 3 and below: the flush costs what the 8 saved butterfly values gain (A/B: S0 0.036 vs 0.041 ms)
         // per VIEW: small frames (SplatLoc's 640x480) take the panel variant — also as a window of V views (A/B at the
         // reference layout, 5 views: 0.816 vs 0.869 ms); large frames the butterfly variant at full occupancy

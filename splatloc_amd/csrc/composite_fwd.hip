@@ -109,9 +109,20 @@ __device__ __forceinline__ void next_pair(uint64_t& cand, int& j0, int& j1)
     j1 = first_bit(cand);
     cand &= cand - 1;
 }
+// the same, and the pair's chunk positions as one-hot masks (m1 = 0 for the absent candidate): scalar bookkeeping for the dead marks
+__device__ __forceinline__ void next_pair(uint64_t& cand, int& j0, int& j1, uint64_t& m0, uint64_t& m1)
+{
+    const uint64_t rest = cand & (cand - 1);
+    j0 = first_bit(cand);
+    m0 = cand ^ rest;
+    j1 = first_bit(rest);
+    cand = rest & (rest - 1);
+    m1 = rest ^ cand;
+}
 
 // the transmittance chain over a pair: the blending weights w = alpha T (0: no hit), T and `active` (pixel still accumulating) moved on
-struct PairWeights { float w0, w1; bool hit0, hit1; };
+// live0 / live1: the pixel evaluated the candidate (still accumulating, alpha test passed) — a hit, or the entry that finishes the pixel
+struct PairWeights { float w0, w1; bool hit0, hit1, live0, live1; };
 __device__ __forceinline__ PairWeights transmit_pair(bool& active, float& T, bool pass0, float al0, bool pass1, float al1)
 {
     // Gaussian 0
@@ -128,7 +139,7 @@ __device__ __forceinline__ PairWeights transmit_pair(bool& active, float& T, boo
     active = act1 && !(live1 && !hit1);
     const float w1 = hit1 ? al1 * T1 : 0.0f;
     T = hit1 ? tT1 : T1;
-    return {w0, w1, hit0, hit1};
+    return {w0, w1, hit0, hit1, live0, live1};
 }
 
 // two FMAs in list order per channel and for the depth (forward -2.7 % at C = 3 / 4 against the pair-sum form)
@@ -200,16 +211,19 @@ struct FwdCfg {
     static constexpr int FS = SR_FWD_FS;             // feature rows staged per round
 };
 
-template <int NC>
-__global__ void __launch_bounds__(WAVE, SR_FWD_MINW)   // (layouts of <= 4 channels: composite_fwd_narrow_kernel / _mixed_kernel below)
-composite_fwd_kernel(int W, int H, int CP4, int c0, int bg_channels, int write_aux, int tiles /*per view*/, int V,
-                     int P /*rows per view*/,
-                     const uint32_t* __restrict__ ranges, const uint32_t* __restrict__ ipack /*id | reach bits << 24*/,
-                     const float4* __restrict__ irec, const float4* __restrict__ featp4,
-                     const float* __restrict__ bg, WinOut outs,
-                     float* __restrict__ final_T_all, uint32_t* __restrict__ n_contrib_all,
-                     const uint32_t* __restrict__ tile_order /*launch order (binning.hip), or null*/,
-                     uint32_t* __restrict__ n_contrib_c_all /*non-null: `ranges` / ipack / irec are the COMPACT stream (binning.hip payload_tile_kernel)*/)
+// one quadrant of a wide layout (NC > 4) by one wave: the body of the two kernels below.  MARK: a backward follows — the walk also
+// finds the dead marks of common.h and ORs them into bits 28..31 of ipack; without it the code is what it was before the marks,
+// but for `ipack`, which is no longer `const __restrict__` in either instantiation (measured: +0.13 % +- 0.5 % on a C = 35 window).
+#define SR_WIDE_PARAMS                                                                                                        \
+    int W, int H, int CP4, int c0, int bg_channels, int write_aux, int tiles /*per view*/, int V, int P /*rows per view*/,   \
+        const uint32_t *__restrict__ ranges, uint32_t *ipack /*id | reach bits << 24 (| dead marks << 28: written here)*/,    \
+        const float4 *__restrict__ irec, const float4 *__restrict__ featp4, const float *__restrict__ bg, WinOut outs,       \
+        float *__restrict__ final_T_all, uint32_t *__restrict__ n_contrib_all,                                               \
+        const uint32_t *__restrict__ tile_order /*launch order (binning.hip), or null*/,                                      \
+        uint32_t *__restrict__ n_contrib_c_all /*non-null: `ranges` / ipack / irec are the COMPACT stream (binning.hip payload_tile_kernel)*/
+#define SR_WIDE_ARGS W, H, CP4, c0, bg_channels, write_aux, tiles, V, P, ranges, ipack, irec, featp4, bg, outs, final_T_all, n_contrib_all, tile_order, n_contrib_c_all
+template <int NC, bool MARK>
+__device__ __forceinline__ void wide_quadrant(SR_WIDE_PARAMS)
 {
     static_assert(NC > 4, "narrow layouts have their own kernels");
     using Cfg = FwdCfg<NC>;
@@ -283,6 +297,9 @@ composite_fwd_kernel(int W, int H, int CP4, int c0, int bg_channels, int write_a
         }
         // next chunk: issued now, consumed after this chunk has been composited
         fetch(base + WAVE, pw, a0, a1);
+        // chunk positions of the candidates this quadrant evaluated with NO lane live (still accumulating and past the alpha test):
+        // the dead marks of common.h.  Scalar registers only; a candidate the walk never reaches (wave_done) stays unmarked.
+        uint64_t dead = 0;
 #pragma unroll 1
         while (cand != 0 && !wave_done) {
             // ---- stage the feature rows of the next <= FS candidates ----
@@ -310,7 +327,9 @@ composite_fwd_kernel(int W, int H, int CP4, int c0, int bg_channels, int write_a
 #pragma unroll 1
             for (int slot = 0; slot < ncand; slot += 2) {
                 int j0, j1;                       // j1 = -1 in the last pair of an odd round
-                next_pair(cand, j0, j1);
+                uint64_t m0 = 0, m1 = 0;          // MARK: their chunk positions, one-hot
+                if constexpr (MARK) next_pair(cand, j0, j1, m0, m1);
+                else next_pair(cand, j0, j1);
                 const float4 p0 = s_rec0[1 + j0], q0 = s_rec1[1 + j0];
                 const float4 p1 = s_rec0[1 + j1], q1 = s_rec1[1 + j1];
                 const int s1 = slot + 1;          // row ncand of an odd round was zeroed while staging
@@ -329,9 +348,12 @@ composite_fwd_kernel(int W, int H, int CP4, int c0, int bg_channels, int write_a
                 const float w0 = wt.w0, w1 = wt.w1;
                 const uint32_t idx = base - beg;
                 last = wt.hit1 ? idx + (uint32_t)j1 + 1u : (wt.hit0 ? idx + (uint32_t)j0 + 1u : last);
-                // No "skip if nobody hit" branch here on purpose: with the reach masks ~95 % of the
-                // candidates hit, and a conditional around the accumulation makes hipcc merge the two
-                // paths by copying all 32 accumulator registers per pair (seen in the .s).
+                if constexpr (MARK)
+                    dead |= (__builtin_amdgcn_ballot_w64(wt.live0) == 0 ? m0 : 0ull) | (__builtin_amdgcn_ballot_w64(wt.live1) == 0 ? m1 : 0ull);
+                // No "skip if nobody is live" branch here on purpose: with the reach masks 95.6 % of the
+                // candidates are live in some lane (S2: profiles/dead_marks_share.json), and a conditional
+                // around the accumulation makes hipcc merge the two paths by copying all 32 accumulator
+                // registers per pair (seen in the .s).
                 const float* f0 = &s_feat[slot * NCP + NM];
                 const float* f1 = &s_feat[s1 * NCP + NM];
                 if constexpr (M4) {
@@ -354,6 +376,11 @@ composite_fwd_kernel(int W, int H, int CP4, int c0, int bg_channels, int write_a
                 }
                 if (__builtin_amdgcn_ballot_w64(active) == 0) { wave_done = true; break; }
             }
+        }
+        // the chunk is left (or the quadrant has finished): its lanes mark their own entries for the backward, in the pass that
+        // writes the auxiliary planes.  An atomic because the tile's four quadrant waves share the word; they read their own bits and the id.
+        if (MARK && write_aux && dead != 0) {
+            if ((dead >> lane) & 1ull) atomicOr(&ipack[base + (uint32_t)lane], 1u << (28 + quad));
         }
     }
 
@@ -390,6 +417,20 @@ composite_fwd_kernel(int W, int H, int CP4, int c0, int bg_channels, int write_a
             store_coverage(out_alpha, final_T_all, n_contrib_all, F, T, last);
         }
     }
+}
+
+template <int NC>
+__global__ void __launch_bounds__(WAVE, SR_FWD_MINW)   // (layouts of <= 4 channels: composite_fwd_narrow_kernel / _mixed_kernel below)
+composite_fwd_kernel(SR_WIDE_PARAMS)
+{
+    wide_quadrant<NC, true>(SR_WIDE_ARGS);
+}
+// the same render when no backward follows (SPLATRASTER_SETTINGS_FORWARD_ONLY): no marks, and nothing spent on finding them
+template <int NC>
+__global__ void __launch_bounds__(WAVE, SR_FWD_MINW)
+composite_fwd_only_kernel(SR_WIDE_PARAMS)
+{
+    wide_quadrant<NC, false>(SR_WIDE_ARGS);
 }
 
 // ---- narrow layouts (C <= 4: SplatLoc's own RGB / RGB + key-point frames) ----------------------------------------------------
@@ -882,7 +923,8 @@ static int launch_one(const splatraster_settings& s, const FramePlan& p, int c0,
                                im.n_contrib_c, p.order ? b.tile_order : nullptr);
         }
     } else {
-        hipLaunchKernelGGL(composite_fwd_kernel<NC>, dim3(blocks), dim3(WAVE), 0, stream, p.W,
+        const auto kernel = (s.debug & SPLATRASTER_SETTINGS_FORWARD_ONLY) ? composite_fwd_only_kernel<NC> : composite_fwd_kernel<NC>;
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(WAVE), 0, stream, p.W,
                            p.H, padded_channels(feat_stride) / 4, c0, s.bg_channels, write_aux, tiles, p.V, p.P, b.ranges,
                            b.ipack, b.irec, reinterpret_cast<const float4*>(featp), bg, *L.outs, im.final_T,
                            im.n_contrib, p.order ? b.tile_order : nullptr, im.n_contrib_c);

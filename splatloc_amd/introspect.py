@@ -98,7 +98,7 @@ def payload_state(fn_ctx_tensors, R: int, W: int, H: int, V: int = 1, compact: b
         irec, ipack = irec[idx], ipack[idx]
         out.update(cranges=cr.int(), n_contrib_c=_view(img, 2 * plane, V * W * H, torch.int32).view(V, H, W),
                    back=irec[:, 3].contiguous().view(torch.int32))
-    out.update(irec=irec, ids=ipack & 0xFFFFFF, imask=(ipack >> 24) & 0xF)
+    out.update(irec=irec, ids=ipack & 0xFFFFFF, imask=(ipack >> 24) & 0xF, idead=(ipack >> 28) & 0xF)
     return out
 
 

@@ -41,14 +41,23 @@ class GaussianRasterizationSettings(NamedTuple):
     debug: bool
 
 
+def _no_backward_follows(*inputs) -> bool:
+    """Decided where the grad mode is still visible, in front of Function.apply: inside Function.forward grad mode is off and
+    `ctx.needs_input_grad` only repeats every input's own `requires_grad` — true for trained parameters rendered under
+    torch.no_grad() (evaluation renders), where no graph is recorded and no backward can follow."""
+    return not (torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in inputs))
+
+
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                         raster_settings):
     # the camera tensors are passed as explicit autograd inputs as well, so that a pose
     # parametrisation upstream of viewmatrix / projmatrix / campos receives gradients
     # (pose-gradient extension; the reference has no such path, SURVEY.md F4)
+    rs = raster_settings
+    tensors = (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, rs.viewmatrix, rs.projmatrix, rs.campos)
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings, raster_settings.viewmatrix,
-                                     raster_settings.projmatrix, raster_settings.campos)
+                                     cov3Ds_precomp, raster_settings, rs.viewmatrix, rs.projmatrix, rs.campos,
+                                     _no_backward_follows(*tensors))
 
 
 # A forward returns a FRAME (SimpleNamespace): its outputs and everything its backward reads, by name.  An autograd adapter
@@ -97,8 +106,9 @@ def _grad_pieces(flat: torch.Tensor, shapes: dict, offs: dict) -> dict:
 
 
 def view_forward(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                 raster_settings: GaussianRasterizationSettings, viewmatrix=None, projmatrix=None, campos=None):
+                 raster_settings: GaussianRasterizationSettings, viewmatrix=None, projmatrix=None, campos=None, forward_only=False):
     """One view: splatraster_forward_geometry + splatraster_forward_render.  The camera tensors default to the settings'.
+    `forward_only`: no backward will read the frame (Settings.debug bit SETTINGS_FORWARD_ONLY: the wide forward writes no dead marks).
     Returns the frame: dev, P, st, num_rendered, the prepared inputs (`_VIEW_INPUTS`, None when absent) and the buffers
     radii [P], geom, binning, img, color [C,H,W], depth [1,H,W], alpha [1,H,W]."""
     lib = _native.load()
@@ -130,7 +140,7 @@ def view_forward(means3D, sh, colors_precomp, opacities, scales, rotations, cov3
         Cn, M = (3, 0)
     st = _native.Settings(H, W, float(rs.tanfovx), float(rs.tanfovy), float(rs.scale_modifier),
                           int(rs.sh_degree), M, Cn, 0 if bg is None else int(bg.numel()),
-                          int(bool(rs.prefiltered)), int(bool(rs.debug)))
+                          int(bool(rs.prefiltered)), int(bool(rs.debug)) | (_native.SETTINGS_FORWARD_ONLY if forward_only else 0))
 
     color = torch.empty((Cn, H, W), dtype=torch.float32, device=dev)
     depth = torch.empty((1, H, W), dtype=torch.float32, device=dev)
@@ -192,9 +202,10 @@ class _RasterizeGaussians(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings: GaussianRasterizationSettings, viewmatrix=None, projmatrix=None, campos=None):
+                raster_settings: GaussianRasterizationSettings, viewmatrix=None, projmatrix=None, campos=None, forward_only=False):
+        # forward_only: no backward follows (_no_backward_follows, decided by the caller of apply); the render is told so
         f = view_forward(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
-                         viewmatrix, projmatrix, campos)
+                         viewmatrix, projmatrix, campos, forward_only=bool(forward_only))
         ctx.dev, ctx.P, ctx.st, ctx.num_rendered = f.dev, f.P, f.st, f.num_rendered
         _save(ctx, f, [getattr(f, k) for k in _VIEW_INPUTS])
         ctx.mark_non_differentiable(f.radii)
@@ -209,8 +220,8 @@ class _RasterizeGaussians(torch.autograd.Function):
         want_pose = any(ctx.needs_input_grad[9:12]) if len(ctx.needs_input_grad) >= 12 else False
         d = view_backward(f, grad_color, grad_depth, grad_alpha, want_pose)
         # (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings,
-        #  viewmatrix, projmatrix, campos)
-        return d["m3"], d["m2"], d["sh"], d["col"], d["op"], d["sca"], d["rot"], d["cov"], None, d["view"], d["proj"], d["campos"]
+        #  viewmatrix, projmatrix, campos, forward_only)
+        return d["m3"], d["m2"], d["sh"], d["col"], d["op"], d["sca"], d["rot"], d["cov"], None, d["view"], d["proj"], d["campos"], None
 
 
 def window_grad_layout(P: int, Cn: int, have_scales: bool = True, have_cov: bool = False):
@@ -341,7 +352,8 @@ class BoundedWindow:
             self.status.close()
 
 
-def window_forward(means3D, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings, raw=None, bounded=None):
+def window_forward(means3D, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings, raw=None, bounded=None,
+                   forward_only=False):
     """The views of `settings` (1 <= V <= MAX_WINDOW_VIEWS, `_window_compatible`) as ONE launch sequence:
     splatraster_forward_window_geometry (+ _render).  Returns the frame: dev, P, V, st, R (instances per view), tanfov,
     the prepared inputs (`_WINDOW_INPUTS` and bg, None when absent), cams [(view, proj, campos)] per view and the buffers
@@ -353,7 +365,8 @@ def window_forward(means3D, colors_precomp, opacities, scales, rotations, cov3Ds
     `bounded.capacity` instances; reserved here on first use or when the shape changed) with the tag `bounded.next_tag`, which
     is then advanced: no host wait for the instance count and no allocation of `binning` per frame.  The frame's `R` is None
     (the count stays on the device: `bounded.status`), `capacity` is set, and `binning` is the shared tensor — valid until the
-    next bounded forward.  Only where the binned front end runs: else RuntimeError ("unsupported configuration")."""
+    next bounded forward.  Only where the binned front end runs: else RuntimeError ("unsupported configuration").
+    `forward_only`: no backward will read the frame (Settings.debug bit SETTINGS_FORWARD_ONLY: the wide forward writes no dead marks)."""
     lib = _native.load()
     _require_gpu(means3D, "means3D")
     dev = means3D.device
@@ -372,7 +385,7 @@ def window_forward(means3D, colors_precomp, opacities, scales, rotations, cov3Ds
     bg = _prep(rs0.bg, dev)
     Cn = int(colors_precomp.shape[1])
     st = _native.Settings(H, W, float(rs0.tanfovx), float(rs0.tanfovy), float(rs0.scale_modifier), 0, 0, Cn,
-                          0 if bg is None else int(bg.numel()), 0, 0)
+                          0 if bg is None else int(bg.numel()), 0, _native.SETTINGS_FORWARD_ONLY if forward_only else 0)
     # one allocation per kind; the per-view outputs are its slices (plain tensors for autograd: they do not
     # alias any input)
     f = SimpleNamespace(dev=dev, P=P, V=V, st=st, tanfov=[(float(rs.tanfovx), float(rs.tanfovy)) for rs in settings],
@@ -588,13 +601,15 @@ class _RasterizeWindow(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means3D, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings, split_last, grad_span,
-                *rest):
+                forward_only, *rest):
         # rest: one means2D carrier per view, then (viewmatrix, projmatrix, campos) of every view — the settings' own tensors as
         # explicit autograd inputs, the way _RasterizeGaussians takes them (inputs 9-11 there), so that a pose parametrisation
         # upstream of them receives gradients
         V = len(settings)
         assert len(rest) in (V, 4 * V)
-        f = window_forward(means3D, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings)
+        # forward_only: no backward follows (_no_backward_follows, decided by the caller of apply); the render is told so
+        f = window_forward(means3D, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings,
+                           forward_only=bool(forward_only))
         ctx.dev, ctx.P, ctx.st, ctx.R, ctx.tanfov = f.dev, f.P, f.st, f.R, f.tanfov
         ctx.head, ctx.grad_span = _split_head(split_last, f.st.channels), grad_span
         _save(ctx, f, [getattr(f, k) for k in _WINDOW_INPUTS], [t for cam in f.cams for t in cam] + [f.bg])
@@ -615,12 +630,12 @@ class _RasterizeWindow(torch.autograd.Function):
         else:
             grads = [(gouts[4 * v], None, gouts[4 * v + 1], gouts[4 * v + 2]) for v in range(V)]
         # the joint call only when a camera tensor needs a gradient: otherwise the launch sequence is the plain one
-        need = ctx.needs_input_grad[9 + V:]
+        need = ctx.needs_input_grad[10 + V:]
         d = window_backward(f, grads, ctx.head, ctx.grad_span, cameras=any(need))
-        # (means3D, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings, split_last, grad_span, *means2D,
-        #  *(viewmatrix, projmatrix, campos per view))
+        # (means3D, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings, split_last, grad_span, forward_only,
+        #  *means2D, *(viewmatrix, projmatrix, campos per view))
         cams = tuple(d[("view", "proj", "campos")[j % 3]][j // 3] if on else None for j, on in enumerate(need))
-        return (d["m3"], d["col"], d["op"], d["sca"], d["rot"], d["cov"], None, None, None) + tuple(d["m2"][v] for v in range(V)) + cams
+        return (d["m3"], d["col"], d["op"], d["sca"], d["rot"], d["cov"], None, None, None, None) + tuple(d["m2"][v] for v in range(V)) + cams
 
 
 def rasterize_window(settings, means3D, means2D, colors_precomp, opacities, scales=None, rotations=None,
@@ -655,9 +670,10 @@ def rasterize_window(settings, means3D, means2D, colors_precomp, opacities, scal
     # and the depth-order words keep the row in 24 bits (a scene of > 2 M Gaussians renders its window in smaller chunks)
     K = max(1, min(_native.MAX_WINDOW_VIEWS, (1 << 24) // max(int(means3D.shape[0]), 1)))
     for a in range(0, len(settings), K):
+        cams = [t for rs in settings[a:a + K] for t in (rs.viewmatrix, rs.projmatrix, rs.campos)]
+        forward_only = _no_backward_follows(means3D, colors_precomp, opacities, scales, rotations, cov3D_precomp, *means2D[a:a + K], *cams)
         flat = _RasterizeWindow.apply(means3D, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                                      tuple(settings[a:a + K]), split_last, grad_span, *means2D[a:a + K],
-                                      *(t for rs in settings[a:a + K] for t in (rs.viewmatrix, rs.projmatrix, rs.campos)))
+                                      tuple(settings[a:a + K]), split_last, grad_span, forward_only, *means2D[a:a + K], *cams)
         n = 5 if _split_head(split_last, int(colors_precomp.shape[1])) else 4
         out += [tuple(flat[n * v:n * v + n]) for v in range(len(flat) // n)]
     return out

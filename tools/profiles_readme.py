@@ -59,6 +59,10 @@ WHAT = [   # (file name regex, description; {placeholders} are filled by the ext
     (r"^fwd_shared_steps_ab\.json$", "`tools/ab.py`, base = the change (the forward walkers' shared steps, HISTORY §21), variant `parent` = the parent commit's library (differences are parent minus change): {ab}; the other workloads, `--stage refine_step`, the `composite_fwd` stage in ms and cycles and the bit-for-bit comparison of the outputs under `other_runs` / `outputs_parent_vs_change`"),
     (r"^bwd_shared_contract_ab\.json$", "`tools/ab.py`, base = the change (the backward takes its frame, alpha test, partition and segment records from `composite_common.h`, HISTORY §22), variant `parent` = the parent commit's library (differences are parent minus change): {ab}; the other runs that were made, `--stage refine_step`, the `composite_bwd` stage in ms and cycles and the bit-for-bit comparison of outputs and deterministic-mode gradients under `other_runs` / `outputs_parent_vs_change`"),
     (r"^loss_shared_bodies_ab\.json$", "the loss stage's shared bodies (HISTORY §23) against the parent commit's library: interleaved pairs of fresh `bench.py --stage loss` / `refine_step` / `eval_rendering` / `pose_refine` processes on one box (200 steps, 20 warm-up), every run, and per stage the medians, the parent's spread and the paired difference (head minus parent) with its 95 % interval under `summary`; per-kernel means of one `rocprofv3 --kernel-trace --stats` run per side under `kernel_trace`"),
+    (r"^dead_marks_share\.json$", "the forward's dead marks after one S2 window of five views, read through `introspect.payload_state` (`idead` against `imask`, bounded by `n_contrib_c`): {dm_share}"),
+    (r"^dead_marks_share_room\.json$", "the same share on the reconstructed room of `tools/scene_lists.py`, its views rendered at C = 8 (colour table padded by zero columns) so that the wide forward marks: {dm_room}"),
+    (r"^dead_marks_kernel_stats\.txt$", "`rocprofv3 --kernel-trace --stats` of the default bench, parent (first listing) and the dead marks as shipped (second; DESIGN §6.2b, §13.9), one run each, us per launch: {pc_kstats}"),
+    (r"^dead_marks_ab\.json$", "`tools/ab.py`, base = the change (dead marks), variant `parent` = the parent commit's library (differences are parent minus change): {ab}"),
     (r"^payload_compact_ab.*\.json$", "`tools/ab.py`, base = the change (compact payload), variant `parent` = the parent commit's library (differences are parent minus change): {ab}; {pc_ab}"),
     (r"traffic\.json$", "per-stage HBM bytes per launch that `bench.py` replays as `roofline.traffic` (recorded workload / launch mode inside)"),
     (r"valu\.json$", "VALU / MFMA / SALU wave-instructions, busy fractions of the two compositing kernels per launch (replayed by `bench.py` as `frame_valu` / `roofline_valu`)"),
@@ -359,6 +363,17 @@ def pc_ab(path):
                         for k, v in c["stages"].items()))
 
 
+def dm_share(path):
+    j = _load(path) or {}
+    return (f"{j['marked_dead_among_walked']} of the {j['walked_by_backward']} candidate-quadrants the backward walks are marked "
+            f"({100.0 * j['share_of_walked']:.2f} %; the issue's CPU estimate: {100.0 * j['cpu_estimate_of_the_issue']:.1f} %)")
+
+
+def dm_room(path):
+    j = _load(path) or {}
+    return f"{j['marked_dead_among_walked']} of {j['walked_by_backward']} walked candidate-quadrants ({100.0 * j['share_of_walked']:.2f} %), {j['rows']} rows, {j['keyframes']} key-frames"
+
+
 def fe_kstats(path):
     """the two listings' large launches of the front-end kernels (the tile sort's; the depth sort's small ones share the names)"""
     halves, out = open(path).read().split("# rocprofv3")[1:], []
@@ -385,7 +400,7 @@ def fe_ab(path):
             f"{c['payload_ms']['change']:.4f} ms ({', '.join(f'{k} {v:.4f}' for k, v in c['payload_ms_of_band_variants'].items())})")
 
 
-EXTRACT = {"pc_kstats": pc_kstats, "pc_pmc": pc_pmc, "pc_ab": pc_ab, "fe_kstats": fe_kstats, "fe_pmc": fe_pmc, "fe_ab": fe_ab, "setup_pmc": setup_pmc, "kstats2": kstats2, "setup_ab": setup_ab, "scenelists": scenelists, "scene": scene, "ab": ab, "perview": perview, "mapidle": mapidle, "rccl": rccl, "kstats": kstats, "hbm": hbm, "sq": sq, "timeline": timeline, "bench": bench, "clocks": clocks, "gradbars": gradbars, "idle": idle, "landmark": landmark, "matching": matching, "pnp": pnp, "decoder": decoder, "fusion": fusion, "localize": localize, "jointwindow": jointwindow, "posewindow": posewindow, "refinebounded": refinebounded}
+EXTRACT = {"dm_share": dm_share, "dm_room": dm_room, "pc_kstats": pc_kstats, "pc_pmc": pc_pmc, "pc_ab": pc_ab, "fe_kstats": fe_kstats, "fe_pmc": fe_pmc, "fe_ab": fe_ab, "setup_pmc": setup_pmc, "kstats2": kstats2, "setup_ab": setup_ab, "scenelists": scenelists, "scene": scene, "ab": ab, "perview": perview, "mapidle": mapidle, "rccl": rccl, "kstats": kstats, "hbm": hbm, "sq": sq, "timeline": timeline, "bench": bench, "clocks": clocks, "gradbars": gradbars, "idle": idle, "landmark": landmark, "matching": matching, "pnp": pnp, "decoder": decoder, "fusion": fusion, "localize": localize, "jointwindow": jointwindow, "posewindow": posewindow, "refinebounded": refinebounded}
 
 
 def describe(name, path):
