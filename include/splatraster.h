@@ -573,6 +573,15 @@ int splatraster_densify_plan(const splatraster_model* model, const float* xyz_gr
                              const float* denom /* [P,1] */, float max_grad, float min_opacity, float extent,
                              float percent_dense, int32_t use_size_prune, int32_t primitive_reg, void* workspace,
                              int32_t* new_P, void* stream);
+/* The same plan from the two FINISHED size thresholds.  The reference compares float32 scales with the Python
+ * doubles `percent_dense * extent` and `0.1 * extent`, i.e. with the float32 rounding of a DOUBLE product; the
+ * float32 product splatraster_densify_plan forms from its float arguments differs from that by one ulp for about
+ * a quarter of all extents, which moves a Gaussian whose largest scale sits on the threshold from split to clone.
+ * size_split = (float)(percent_dense * extent), size_prune = (float)(0.1 * extent), both products in double. */
+int splatraster_densify_plan_thresholds(const splatraster_model* model, const float* xyz_gradient_accum /* [P,1] */,
+                                        const float* denom /* [P,1] */, float max_grad, float min_opacity,
+                                        float size_split, float size_prune, int32_t use_size_prune,
+                                        int32_t primitive_reg, void* workspace, int32_t* new_P, void* stream);
 int splatraster_densify_apply(const splatraster_model* model, const splatraster_model* exp_avg /* or NULL */,
                               const splatraster_model* exp_avg_sq /* or NULL */, const float* unit_noise /* or NULL */,
                               uint64_t seed, uint64_t draw_id, void* workspace /* from plan */, int32_t new_P,

@@ -240,6 +240,8 @@ SYMBOLS = {
     "splatraster_densify_workspace_bytes": (_sz, [_i32]),
     "splatraster_densify_plan": (C.c_int, [C.POINTER(Model), _vp, _vp, C.c_float, C.c_float, C.c_float, C.c_float, _i32,
                                            _i32, _vp, C.POINTER(_i32), _vp]),
+    "splatraster_densify_plan_thresholds": (C.c_int, [C.POINTER(Model), _vp, _vp, C.c_float, C.c_float, C.c_float,
+                                                      C.c_float, _i32, _i32, _vp, C.POINTER(_i32), _vp]),
     "splatraster_densify_apply": (C.c_int, [C.POINTER(Model), C.POINTER(Model), C.POINTER(Model), _vp, C.c_uint64,
                                             C.c_uint64, _vp, _i32, C.POINTER(Model), C.POINTER(Model), C.POINTER(Model),
                                             _vp, _vp, _vp]),

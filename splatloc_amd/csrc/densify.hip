@@ -47,12 +47,12 @@ densify_flags_kernel(int P, int SC, const float* __restrict__ scaling, const flo
     if (i >= P) return;
     float g = accum[i] / denom[i];                  // grads = xyz_gradient_accum / denom
     if (g != g) g = 0.0f;                           // grads[grads.isnan()] = 0
-    g = fabsf(g);                                   // torch.norm over the 1-wide last dim
     float s[3];
     const float smax = row_max_exp(scaling, SC, (size_t)i, s);
-    const bool hot = g >= h.max_grad;
-    const bool clone = hot && smax <= h.size_split;
-    const bool split = hot && smax > h.size_split;
+    // the clone tests torch.norm over the 1-wide last dim (gaussian_model.py:634), the split the padded gradient itself
+    // (:595): a negative quotient of magnitude >= max_grad clones a small Gaussian and leaves a large one alone
+    const bool clone = fabsf(g) >= h.max_grad && smax <= h.size_split;
+    const bool split = g >= h.max_grad && smax > h.size_split;
     const float op = 1.0f / (1.0f + expf(-opacity[i]));
     const bool gate = !h.primitive_reg || marker[i] <= 0.005f;   // key primitives are never pruned
     const bool low = op < h.min_opacity;
@@ -195,11 +195,11 @@ static DensifyWs densify_ws(void* base, int32_t P)
 }
 
 int densify_plan(int32_t P, int SC, const float* scaling, const float* opacity, const float* marker, const float* accum,
-                 const float* denom, float max_grad, float min_opacity, float extent, float percent_dense,
+                 const float* denom, float max_grad, float min_opacity, float size_split, float size_prune,
                  int use_size_prune, int primitive_reg, void* workspace, int32_t* new_P, hipStream_t stream)
 {
     DensifyWs w = densify_ws(workspace, P);
-    DensifyHyper h{max_grad, min_opacity, percent_dense * extent, 0.1f * extent, use_size_prune, primitive_reg};
+    DensifyHyper h{max_grad, min_opacity, size_split, size_prune, use_size_prune, primitive_reg};
     hipLaunchKernelGGL(densify_flags_kernel, dim3((P + DN_BLOCK - 1) / DN_BLOCK), dim3(DN_BLOCK), 0, stream, P, SC, scaling,
                        opacity, marker, accum, denom, h, w.flags);
     SR_LAUNCH_CHECK();
@@ -532,6 +532,17 @@ int splatraster_densify_plan(const splatraster_model* model, const float* xyz_gr
                              float max_grad, float min_opacity, float extent, float percent_dense,
                              int32_t use_size_prune, int32_t primitive_reg, void* workspace, int32_t* new_P, void* stream)
 {
+    // float32 products of the float arguments: within one ulp of the reference's thresholds, not always equal to them
+    // (splatraster_densify_plan_thresholds takes the finished ones)
+    return splatraster_densify_plan_thresholds(model, xyz_gradient_accum, denom, max_grad, min_opacity, percent_dense * extent,
+                                               0.1f * extent, use_size_prune, primitive_reg, workspace, new_P, stream);
+}
+
+int splatraster_densify_plan_thresholds(const splatraster_model* model, const float* xyz_gradient_accum, const float* denom,
+                                        float max_grad, float min_opacity, float size_split, float size_prune,
+                                        int32_t use_size_prune, int32_t primitive_reg, void* workspace, int32_t* new_P,
+                                        void* stream)
+{
     int st = check_model(model, 1);
     if (st) return st;
     if (!new_P || !(max_grad > 0.0f)) return SPLATRASTER_ERR_BAD_ARG;   // clones are kept out of the split by their zero gradient
@@ -543,7 +554,7 @@ int splatraster_densify_plan(const splatraster_model* model, const float* xyz_gr
     st = lookback_error_init();
     if (st) return st;
     st = densify_plan(model->P, model->scaling_width, model->scaling, model->opacity, model->marker, xyz_gradient_accum,
-                      denom, max_grad, min_opacity, extent, percent_dense, use_size_prune, primitive_reg, workspace, new_P,
+                      denom, max_grad, min_opacity, size_split, size_prune, use_size_prune, primitive_reg, workspace, new_P,
                       reinterpret_cast<hipStream_t>(stream));
     return st;
 }

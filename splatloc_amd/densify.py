@@ -124,10 +124,14 @@ def densify_tensors(params: dict, exp_avg: dict, exp_avg_sq: dict, xyz_gradient_
     den = denom.to(torch.float32).contiguous()
     ws = torch.empty((lib.splatraster_densify_workspace_bytes(P),), dtype=torch.uint8, device=dev)
     new_P = C.c_int32(0)
+    # the reference compares float32 scales with the Python doubles `percent_dense * extent` and `0.1 * extent`
+    # (gaussian_model.py:596, 635, 668), i.e. with the float32 rounding of the DOUBLE product: formed here, where the
+    # Python values still are doubles (c_float rounds once)
+    size_split, size_prune = float(percent_dense) * float(extent), 0.1 * float(extent)
     with _on_device(dev):
-        _native.check(lib.splatraster_densify_plan(
-            C.byref(src), _ptr(acc), _ptr(den), C.c_float(max_grad), C.c_float(min_opacity), C.c_float(extent),
-            C.c_float(percent_dense), int(bool(max_screen_size)), int(bool(primitive_reg)), _ptr(ws), C.byref(new_P),
+        _native.check(lib.splatraster_densify_plan_thresholds(
+            C.byref(src), _ptr(acc), _ptr(den), C.c_float(max_grad), C.c_float(min_opacity), C.c_float(size_split),
+            C.c_float(size_prune), int(bool(max_screen_size)), int(bool(primitive_reg)), _ptr(ws), C.byref(new_P),
             _stream(dev)), "densify_plan")
     n = int(new_P.value)
     f32 = dict(dtype=torch.float32, device=dev)
