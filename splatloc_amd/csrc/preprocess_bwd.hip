@@ -162,13 +162,18 @@ preprocess_bwd_kernel(int P, int V, int W, int H, float mod, int sh_degree, int 
         projection_row_bwd<POSE>(W, H, Vm, PM, tanfovx, tanfovy, px, py, pz, S3, mrow, &rec[2 * gr + 1],
                                  dm2x, dm2y, dop, dmean, G3s, pose);
         if (shs) {   // single-view calls only
-            const float sm0 = dmean[0], sm1 = dmean[1], sm2 = dmean[2];
+            // the direction's term on its own, then joined to dmean (the same sum as adding it in place: 0 + term is exact).  Taken
+            // back out of dmean as (dmean - before), it came with the rounding of the projection's part, often tens of times larger
+            float dsh_mean[3] = {0.f, 0.f, 0.f};
             sh_backward(sh_degree, M, shs + (size_t)i * 3 * M, dL_dshs + (size_t)i * 3 * M, clamped + 3 * (size_t)i,
-                        gacc + GL.index(gr, (size_t)i, 0u), px - campos_p[0], py - campos_p[1], pz - campos_p[2], dmean);
+                        gacc + GL.index(gr, (size_t)i, 0u), px - campos_p[0], py - campos_p[1], pz - campos_p[2], dsh_mean);
+            dmean[0] += dsh_mean[0];
+            dmean[1] += dsh_mean[1];
+            dmean[2] += dsh_mean[2];
             if (POSE) {  // direction = normalize(p - campos)
-                pose[24] = -(dmean[0] - sm0);
-                pose[25] = -(dmean[1] - sm1);
-                pose[26] = -(dmean[2] - sm2);
+                pose[24] = -dsh_mean[0];
+                pose[25] = -dsh_mean[1];
+                pose[26] = -dsh_mean[2];
             }
         }
     } else if (shs && dL_dshs) {

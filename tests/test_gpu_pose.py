@@ -1,5 +1,6 @@
 """Pose-gradient extension on the GPU: dL/dviewmatrix, dL/dprojmatrix, dL/dcampos vs the oracle
-(itself checked against fp64 autograd in tests/test_oracle_autograd.py), and a pose refinement
+(itself checked against fp64 autograd in tests/test_oracle_autograd.py, and at the 1.3 tanfov clamp and the cull plane, which no scene
+here or there reaches, in tests/test_host_projection_edges.py), and a pose refinement
 loop in the shape the reference's utils/optimization_utils.py helpers are meant for
 (axis-angle + translation -> 4x4 transform -> viewmatrix -> rasterizer)."""
 import numpy as np

@@ -55,7 +55,7 @@ def quat_to_rot(q):
 
 def render_dense(H, W, tanfovx, tanfovy, bg, means3D, opacities, viewmatrix, projmatrix, campos=None,
                  colors_precomp=None, shs=None, sh_degree=0, scales=None, rotations=None,
-                 cov3D_precomp=None, scale_modifier=1.0, means2D_probe=None, rows=None):
+                 cov3D_precomp=None, scale_modifier=1.0, means2D_probe=None, rows=None, projection=None):
     """Returns (color [C,H,W], depth [1,H,W], alpha [1,H,W], radii [P]).
 
     rows = (y0, y1): only the image rows [y0, y1) of the H x W frame are composited (outputs [C, y1-y0, W], ...): the
@@ -63,60 +63,68 @@ def render_dense(H, W, tanfovx, tanfovy, bg, means3D, opacities, viewmatrix, pro
 
     means2D_probe: optional [P,2] zero tensor added to the NDC centre, so that its .grad is
     the dL/dmeans2D the extension reports.
+
+    projection: optional dict that replaces this function's own per-Gaussian projection — tz, ok, con_a, con_b, con_c, pix [P,2],
+    rminx, rminy, rmaxx, rmaxy, radii (tests/projection_reference.py: its float64 statement of the projection and the wrong
+    models derived from it); scales / rotations / cov3D_precomp / means2D_probe are then not read.
     """
     dt = means3D.dtype
     dev = means3D.device      # fp64 on the GPU as well (tests/test_gpu_dense_ref.py): every tensor follows means3D
     P = means3D.shape[0]
-    V, PM = viewmatrix.to(dt), projmatrix.to(dt)
-    ones = torch.ones(P, 1, dtype=dt, device=dev)
-    hom = torch.cat([means3D, ones], dim=1)
-    pv = hom @ V          # [P,4] view space (row-vector convention)
-    ph = hom @ PM
-    tz = pv[:, 2]
-    in_front = tz > 0.2
-    pw = 1.0 / (ph[:, 3] + 1e-7)
-    ndc = ph[:, :2] * pw[:, None]
-    if means2D_probe is not None:
-        ndc = ndc + means2D_probe
-    if cov3D_precomp is not None:
-        c = cov3D_precomp
-        Sigma = torch.stack([c[:, 0], c[:, 1], c[:, 2], c[:, 1], c[:, 3], c[:, 4], c[:, 2], c[:, 4], c[:, 5]],
-                            dim=1).view(P, 3, 3)
+    if projection is not None:
+        tz, ok, con_a, con_b, con_c, pix, rminx, rminy, rmaxx, rmaxy, radii = (
+            projection[k] for k in ("tz", "ok", "con_a", "con_b", "con_c", "pix", "rminx", "rminy", "rmaxx", "rmaxy", "radii"))
     else:
-        L = quat_to_rot(rotations) * (scale_modifier * scales)[:, None, :]
-        Sigma = L @ L.transpose(1, 2)
-    fx, fy = W / (2.0 * tanfovx), H / (2.0 * tanfovy)
-    limx, limy = 1.3 * tanfovx, 1.3 * tanfovy
-    txtz, tytz = pv[:, 0] / tz, pv[:, 1] / tz
-    cx_ = (txtz < -limx) | (txtz > limx)
-    cy_ = (tytz < -limy) | (tytz > limy)
-    tx = torch.where(cx_, (txtz.clamp(-limx, limx) * tz).detach(), pv[:, 0])
-    ty = torch.where(cy_, (tytz.clamp(-limy, limy) * tz).detach(), pv[:, 1])
-    # (the lineage treats a clamped t.x / t.y as a constant but keeps t.z live in J)
-    zero = torch.zeros_like(tz)
-    J = torch.stack([fx / tz, zero, -(fx * tx) / (tz * tz), zero, fy / tz, -(fy * ty) / (tz * tz)], dim=1).view(P, 2, 3)
-    Wv = V[:3, :3].transpose(0, 1)  # Wv[r][c] = V[c][r]
-    A = J @ Wv
-    cov2 = A @ Sigma @ A.transpose(1, 2)
-    a = cov2[:, 0, 0] + 0.3
-    b = cov2[:, 0, 1]
-    c = cov2[:, 1, 1] + 0.3
-    det = a * c - b * b
-    ok = in_front & (det != 0)
-    det_s = torch.where(det != 0, det, torch.ones_like(det))
-    con_a, con_b, con_c = c / det_s, -b / det_s, a / det_s
-    mid = 0.5 * (a + c)
-    lam = mid + torch.sqrt(torch.clamp_min(mid * mid - det, 0.1))
-    radius = torch.ceil(3.0 * torch.sqrt(lam)).detach()
-    pix = torch.stack([((ndc[:, 0] + 1.0) * W - 1.0) * 0.5, ((ndc[:, 1] + 1.0) * H - 1.0) * 0.5], dim=1)
-    gx, gy = (W + TILE - 1) // TILE, (H + TILE - 1) // TILE
-    pd = pix.detach()
-    rminx = torch.trunc((pd[:, 0] - radius) / TILE).clamp(0, gx)
-    rminy = torch.trunc((pd[:, 1] - radius) / TILE).clamp(0, gy)
-    rmaxx = torch.trunc((pd[:, 0] + radius + TILE - 1) / TILE).clamp(0, gx)
-    rmaxy = torch.trunc((pd[:, 1] + radius + TILE - 1) / TILE).clamp(0, gy)
-    ok = ok & ((rmaxx - rminx) * (rmaxy - rminy) > 0)
-    radii = torch.where(ok, radius, torch.zeros_like(radius)).to(torch.int32)
+        V, PM = viewmatrix.to(dt), projmatrix.to(dt)
+        ones = torch.ones(P, 1, dtype=dt, device=dev)
+        hom = torch.cat([means3D, ones], dim=1)
+        pv = hom @ V          # [P,4] view space (row-vector convention)
+        ph = hom @ PM
+        tz = pv[:, 2]
+        in_front = tz > 0.2
+        pw = 1.0 / (ph[:, 3] + 1e-7)
+        ndc = ph[:, :2] * pw[:, None]
+        if means2D_probe is not None:
+            ndc = ndc + means2D_probe
+        if cov3D_precomp is not None:
+            c = cov3D_precomp
+            Sigma = torch.stack([c[:, 0], c[:, 1], c[:, 2], c[:, 1], c[:, 3], c[:, 4], c[:, 2], c[:, 4], c[:, 5]],
+                                dim=1).view(P, 3, 3)
+        else:
+            L = quat_to_rot(rotations) * (scale_modifier * scales)[:, None, :]
+            Sigma = L @ L.transpose(1, 2)
+        fx, fy = W / (2.0 * tanfovx), H / (2.0 * tanfovy)
+        limx, limy = 1.3 * tanfovx, 1.3 * tanfovy
+        txtz, tytz = pv[:, 0] / tz, pv[:, 1] / tz
+        cx_ = (txtz < -limx) | (txtz > limx)
+        cy_ = (tytz < -limy) | (tytz > limy)
+        tx = torch.where(cx_, (txtz.clamp(-limx, limx) * tz).detach(), pv[:, 0])
+        ty = torch.where(cy_, (tytz.clamp(-limy, limy) * tz).detach(), pv[:, 1])
+        # (the lineage treats a clamped t.x / t.y as a constant but keeps t.z live in J)
+        zero = torch.zeros_like(tz)
+        J = torch.stack([fx / tz, zero, -(fx * tx) / (tz * tz), zero, fy / tz, -(fy * ty) / (tz * tz)], dim=1).view(P, 2, 3)
+        Wv = V[:3, :3].transpose(0, 1)  # Wv[r][c] = V[c][r]
+        A = J @ Wv
+        cov2 = A @ Sigma @ A.transpose(1, 2)
+        a = cov2[:, 0, 0] + 0.3
+        b = cov2[:, 0, 1]
+        c = cov2[:, 1, 1] + 0.3
+        det = a * c - b * b
+        ok = in_front & (det != 0)
+        det_s = torch.where(det != 0, det, torch.ones_like(det))
+        con_a, con_b, con_c = c / det_s, -b / det_s, a / det_s
+        mid = 0.5 * (a + c)
+        lam = mid + torch.sqrt(torch.clamp_min(mid * mid - det, 0.1))
+        radius = torch.ceil(3.0 * torch.sqrt(lam)).detach()
+        pix = torch.stack([((ndc[:, 0] + 1.0) * W - 1.0) * 0.5, ((ndc[:, 1] + 1.0) * H - 1.0) * 0.5], dim=1)
+        gx, gy = (W + TILE - 1) // TILE, (H + TILE - 1) // TILE
+        pd = pix.detach()
+        rminx = torch.trunc((pd[:, 0] - radius) / TILE).clamp(0, gx)
+        rminy = torch.trunc((pd[:, 1] - radius) / TILE).clamp(0, gy)
+        rmaxx = torch.trunc((pd[:, 0] + radius + TILE - 1) / TILE).clamp(0, gx)
+        rmaxy = torch.trunc((pd[:, 1] + radius + TILE - 1) / TILE).clamp(0, gy)
+        ok = ok & ((rmaxx - rminx) * (rmaxy - rminy) > 0)
+        radii = torch.where(ok, radius, torch.zeros_like(radius)).to(torch.int32)
 
     if shs is not None:
         d = means3D - campos.to(device=dev, dtype=dt)[None]
