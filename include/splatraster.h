@@ -869,6 +869,35 @@ int splatraster_fusion_surface_count(const splatraster_fusion_volume* volume, in
 int splatraster_fusion_surface_extract(const splatraster_fusion_volume* volume, const void* workspace, double voxel_size,
                                        const double* origin, int64_t M, float* verts, double* points, int64_t* index,
                                        uint8_t* colors, float* feats, void* stream);
+/* Surface mesh over those vertices (get_mesh of utils/fusion_utils.py:271-289; the triangulation and the normals are the
+ * project's own rule).  A cell is the cube of 8 voxels from (x, y, z) to (x+1, y+1, z+1); cells are walked in
+ * linear [X-1, Y-1, Z-1] order.  Corner c of a cell lies at (c & 1, (c >> 1) & 1, (c >> 2) & 1); bit c of its case is set when
+ * tsdf(corner c) < level (NaN: not set); edge e = axis * 4 + k runs along `axis` from the corner whose offset along the lower of
+ * the two other axes is k & 1 and along the higher one (k >> 1) & 1.  The table (csrc/fusion_mesh.h, derived at compile time)
+ * gives each case up to 5 triangles as edge ids; the vertex of an edge is the surface vertex of (the voxel the edge starts at,
+ * axis).  (p1 - p0) x (p2 - p0) of every triangle points towards increasing tsdf.
+ * Host only: bytes of the mesh workspace.  SPLATRASTER_ERR_BAD_ARG as splatraster_fusion_bytes; SPLATRASTER_ERR_OVERFLOW when
+ * 5 * cells does not fit 32 bits. */
+int splatraster_fusion_mesh_bytes(int32_t X, int32_t Y, int32_t Z, size_t* mesh_bytes);
+/* Counts the triangles of every cell, scans the counts and returns the total in *n_faces (HOST); synchronises the stream once.
+ * splatraster_fusion_surface_count must have run on surface_workspace for the same, unchanged tsdf: it supplies the level and the
+ * vertex offsets.  SPLATRASTER_ERR_OVERFLOW when the vertex total or the face total exceeds 2^31 - 1 (the faces are int32). */
+int splatraster_fusion_mesh_count(const splatraster_fusion_volume* volume, const void* surface_workspace, void* mesh_workspace,
+                                  int64_t* n_faces, void* stream);
+/* Writes faces [F,3] i32 (vertex ids into the surface extract's rows, cells ascending, a cell's triangles in table order) and
+ * normals [M,3] f32, one per vertex in the surface extract's order.  Normal of the vertex on the edge from voxel n to its
+ * neighbour n' along an axis, end values a and b, every operation rounded to f32 on its own: the gradient g(v) of the tsdf at a
+ * voxel is 0.5f * (t[i+1] - t[i-1]) per axis (t[1] - t[0] and t[last] - t[last-1] at the ends, 0 on an axis of one voxel);
+ * q = (level - a) / (b - a); g = g(n) + q * (g(n') - g(n)); len = sqrtf((g0 g0 + g1 g1) + g2 g2); normal = g / len when len is
+ * positive and finite, else (0, 0, 0).  M and F as returned by the two counts.  A smaller F (M) writes the first F (M) rows only;
+ * a larger F writes the counted faces and leaves the remaining rows at -1; a larger M leaves the remaining rows untouched.
+ * F = 0 writes no face, M = 0 no normal (the pointer may then be NULL).  SPLATRASTER_ERR_BAD_ARG for F > 5 * cells, M > 3 * voxels,
+ * a negative count or a missing pointer.  No host synchronisation. */
+int splatraster_fusion_mesh_extract(const splatraster_fusion_volume* volume, const void* surface_workspace,
+                                    const void* mesh_workspace, int64_t M, int64_t F, int32_t* faces, float* normals, void* stream);
+/* Host only: copies the 256 x 16 bytes of the triangulation table (row of a case: byte 0 the triangle count, bytes 1..15 edge
+ * ids, 0xFF where unused). */
+int splatraster_debug_mc_table(uint8_t* out);
 
 /* ---- 2D-3D matching: test.py:247-378 (get_frusm_pts, match_feature), utils/match_utils.py (hungarian_solve), INTEGRATION.md §17
  * Exact rectangular assignment (scipy.optimize.linear_sum_assignment, Crouse's shortest augmenting path): for the same f64 cost

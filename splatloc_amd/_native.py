@@ -218,6 +218,10 @@ SYMBOLS = {
     "splatraster_fusion_integrate": (C.c_int, [C.POINTER(FusionVolume), _i32, _i32, _i32] + [_vp] * 5 + [C.c_float, C.c_float, _vp]),
     "splatraster_fusion_surface_count": (C.c_int, [C.POINTER(FusionVolume), _i32, C.c_float, _vp, C.POINTER(_i64), _vp]),
     "splatraster_fusion_surface_extract": (C.c_int, [C.POINTER(FusionVolume), _vp, C.c_double, _vp, _i64] + [_vp] * 6),
+    "splatraster_fusion_mesh_bytes": (C.c_int, [_i32] * 3 + [C.POINTER(_sz)]),
+    "splatraster_fusion_mesh_count": (C.c_int, [C.POINTER(FusionVolume), _vp, _vp, C.POINTER(_i64), _vp]),
+    "splatraster_fusion_mesh_extract": (C.c_int, [C.POINTER(FusionVolume), _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
+    "splatraster_debug_mc_table": (C.c_int, [_vp]),
     "splatraster_lsap_workspace_bytes": (_sz, [_i32, _vp]),
     "splatraster_lsap": (C.c_int, [_i32, _vp, _vp, _i32] + [_vp] * 6),
     "splatraster_debug_set_lsap_lds": (C.c_int, [C.c_int]),

@@ -14,18 +14,11 @@
 // Surface: min / max reduction -> level, a count pass over the +x, +y, +z edges of every voxel, exclusive_scan_u32, a write pass
 // in (voxel, axis) order, and a row gather (one wave per vertex).  Everything is order-independent or ordered: two runs agree
 // bit for bit.
-#include "common.h"
+#include "fusion.h"
 
 #include <math.h>
 
 namespace sr {
-
-constexpr int FUS_THREADS = 256;
-constexpr int FUS_MAX_FRAMES = SPLATRASTER_FUSION_MAX_FRAMES;
-constexpr int FUS_MAX_FEAT = SPLATRASTER_FUSION_MAX_FEAT_DIM;
-constexpr int64_t FUS_MAX_VOXELS = (int64_t)1 << 30;   // 3 edges per voxel stay below 2^32 in the u32 scan
-constexpr int FUS_MAX_IMAGE = 32768;                    // H, W: a pixel index fits an int, (float)W is exact
-constexpr int FUS_MINMAX_BLOCKS = 1024;
 
 struct FusFrames {
     float w2c[FUS_MAX_FRAMES][12];   // rows 0..2 of world-to-camera, row-major
@@ -141,41 +134,7 @@ fusion_integrate_kernel(int64_t N, int32_t Y, int32_t Z, int32_t C, const float*
     }
 }
 
-static bool bad_volume(const splatraster_fusion_volume* v, bool need_feat)
-{
-    if (!v) return true;
-    if (v->dim[0] < 1 || v->dim[1] < 1 || v->dim[2] < 1) return true;
-    if ((int64_t)v->dim[0] * v->dim[1] > FUS_MAX_VOXELS || (int64_t)v->dim[0] * v->dim[1] * v->dim[2] > FUS_MAX_VOXELS) return true;
-    if (v->feat_dim < 4 || v->feat_dim > FUS_MAX_FEAT || v->feat_dim % 4) return true;
-    if (!v->tsdf || !v->weight || !v->color) return true;
-    if (need_feat && (!v->feat || (reinterpret_cast<uintptr_t>(v->feat) & 15))) return true;
-    return false;
-}
-
 // ---- surface -------------------------------------------------------------------------------------------------------------
-struct FusWs {
-    float* level;
-    uint64_t* total;
-    uint32_t* counts;
-    float* partial;
-    void* scan_tmp;
-};
-
-static FusWs fus_layout(void* workspace, int64_t N)
-{
-    char* p = reinterpret_cast<char*>(workspace);
-    FusWs w;
-    w.level = reinterpret_cast<float*>(p);
-    w.total = reinterpret_cast<uint64_t*>(p + 128);
-    p += 256;
-    w.counts = reinterpret_cast<uint32_t*>(p);
-    p += align_up((size_t)N * sizeof(uint32_t), 256);
-    w.partial = reinterpret_cast<float*>(p);
-    p += align_up(2 * FUS_MINMAX_BLOCKS * sizeof(float), 256);
-    w.scan_tmp = p;
-    return w;
-}
-
 // min and max of the block's values (NaN ignored, as fminf / fmaxf do), valid in thread 0
 __device__ __forceinline__ void fus_block_minmax(float& lo, float& hi)
 {
@@ -225,38 +184,6 @@ fusion_level_kernel(int32_t G, const float* __restrict__ partial, float* __restr
 }
 
 __global__ void fusion_set_level_kernel(float value, float* __restrict__ level) { *level = value; }
-
-__device__ __forceinline__ bool fus_cross(float a, float b, float level) { return (a < level) != (b < level); }
-
-// the +x, +y, +z neighbours of voxel n that exist, and which of the three edges cross the level (bit a: axis a)
-__device__ __forceinline__ uint32_t fus_edges(int64_t n, int32_t X, int32_t Y, int32_t Z, const float* __restrict__ tsdf, float level,
-                                              int32_t* ijk, float* a, float* b)
-{
-    const int64_t YZ = (int64_t)Y * Z;
-    const int32_t x = (int32_t)(n / YZ);
-    const int32_t r = (int32_t)(n - (int64_t)x * YZ);
-    const int32_t y = r / Z;
-    const int32_t z = r - y * Z;
-    ijk[0] = x;
-    ijk[1] = y;
-    ijk[2] = z;
-    *a = tsdf[n];
-    uint32_t bits = 0;
-    b[0] = b[1] = b[2] = 0.f;
-    if (x + 1 < X) {
-        b[0] = tsdf[n + YZ];
-        bits |= fus_cross(*a, b[0], level) ? 1u : 0u;
-    }
-    if (y + 1 < Y) {
-        b[1] = tsdf[n + Z];
-        bits |= fus_cross(*a, b[1], level) ? 2u : 0u;
-    }
-    if (z + 1 < Z) {
-        b[2] = tsdf[n + 1];
-        bits |= fus_cross(*a, b[2], level) ? 4u : 0u;
-    }
-    return bits;
-}
 
 __global__ void __launch_bounds__(FUS_THREADS)
 fusion_count_kernel(int64_t N, int32_t X, int32_t Y, int32_t Z, const float* __restrict__ tsdf, const float* __restrict__ level,

@@ -2,9 +2,10 @@
 
 The volume update and the surface extraction are the HIP of csrc/fusion.hip behind the C ABI (include/splatraster.h,
 splatraster_fusion_*).  `TSDFVolume` has the reference class's constructor, `integrate`, `get_volume`, `sdf_trunc` and
-`voxel_size`; `integrate_frames` takes stacked frames in batches of up to 8 per launch; `feature_cloud` replaces `get_mesh` for the
-decoder's input (vertices and their feature rows; no faces: INTEGRATION.md §20).  There is no CPU fallback: without the device the
-calls raise, and host tensors are refused for the volume.
+`voxel_size`; `integrate_frames` takes stacked frames in batches of up to 8 per launch; `feature_cloud` gives the decoder's input
+(vertices and their feature rows); `get_mesh`, `meshwrite` and `save_mesh` give the reference's triangle mesh and its mesh.ply
+(csrc/fusion_mesh.hip).  There is no CPU fallback: without the device the calls raise, and host tensors are
+refused for the volume.
 """
 from __future__ import annotations
 
@@ -106,6 +107,36 @@ def _free_bytes(dev) -> int:
     volume freed a moment ago sits there, and mem_get_info does not count it)"""
     free, _ = torch.cuda.mem_get_info(dev)
     return int(free) + int(torch.cuda.memory_reserved(dev)) - int(torch.cuda.memory_allocated(dev))
+
+
+def meshwrite(filename, verts, faces, norms, colors):
+    """The reference's meshwrite (fusion_utils.py:35-76), byte for byte: an ASCII PLY of vertices "x y z nx ny nz r g b" (%f and
+    %d) and faces "3 a b c"."""
+    verts, norms = np.asarray(verts, np.float64).reshape(-1, 3), np.asarray(norms, np.float64).reshape(-1, 3)
+    colors, faces = np.asarray(colors).reshape(-1, 3), np.asarray(faces).reshape(-1, 3)
+    if not (verts.shape[0] == norms.shape[0] == colors.shape[0]):
+        raise ValueError(f"meshwrite: {verts.shape[0]} vertices, {norms.shape[0]} normals, {colors.shape[0]} colours")
+    props = [f"property float {n}" for n in ("x", "y", "z", "nx", "ny", "nz")] + [f"property uchar {n}" for n in ("red", "green", "blue")]
+    header = ["ply", "format ascii 1.0", f"element vertex {verts.shape[0]}", *props, f"element face {faces.shape[0]}",
+              "property list uchar int vertex_index", "end_header"]
+    # %d truncates a float towards zero, as astype(int64) does
+    c = np.char.mod("%d", colors.astype(np.int64))
+    cols = [np.char.mod("%f", a[:, k]) for a in (verts, norms) for k in range(3)] + [c[:, k] for k in range(3)]
+    with open(filename, "w") as f:
+        f.write("\n".join(header) + "\n")
+        _write_rows(f, cols)
+        fc = np.char.mod("%d", faces.astype(np.int64))
+        _write_rows(f, [np.full(faces.shape[0], "3")] + [fc[:, k] for k in range(3)])
+
+
+def _write_rows(f, cols):
+    """one line per row: the columns (arrays of strings) joined by blanks"""
+    if cols[0].shape[0] == 0:
+        return
+    line = cols[0]
+    for c in cols[1:]:
+        line = np.char.add(np.char.add(line, " "), c)
+    f.write("\n".join(line.tolist()) + "\n")
 
 
 class TSDFVolume:
@@ -245,6 +276,10 @@ class TSDFVolume:
         project's own: INTEGRATION.md §20).  level None: 0.5 * (min + max) of the TSDF.  Device tensors: `verts` [M,3] f32 in
         voxel units, `points` [M,3] f64 in world units, `index` [M] i64 (voxel of each vertex, rounded half to even), `colors`
         [M,3] u8, `feats` [M,C] f32, `level` (0-dim f32)."""
+        return self._surface(level)[0]
+
+    def _surface(self, level):
+        """(surface()'s dictionary, the surface workspace the counts and the level live in)"""
         dev = self.device
         check_memory(self.surface_bytes, _free_bytes(dev), "the surface workspace")
         ws = torch.empty(self.surface_bytes, dtype=torch.uint8, device=dev)
@@ -267,7 +302,50 @@ class TSDFVolume:
                 *[_ptr(out[k]) if m else None for k in ("verts", "points", "index", "colors", "feats")], _stream(dev))
         _native.check(st, "splatraster_fusion_surface_extract")
         out["level"] = ws[:4].view(torch.float32)[0].clone()
+        return out, ws
+
+    def mesh(self, level=None) -> dict:
+        """surface()'s dictionary plus the triangles over its vertices and the vertex normals (the rule is the project's own:
+        INTEGRATION.md §20): `faces` [F,3] i32 (rows of `verts`; cells in ascending order; the geometric normal of a face points
+        towards increasing TSDF) and `normals` [M,3] f32 (the normalised TSDF gradient at the vertex, zero where it vanishes)."""
+        dev = self.device
+        d = self._vol_dim
+        lib, vol = _native.load(), self._native()
+        nbytes = C.c_size_t(0)
+        _native.check(lib.splatraster_fusion_mesh_bytes(d[0], d[1], d[2], C.byref(nbytes)), "splatraster_fusion_mesh_bytes")
+        out, ws = self._surface(level)
+        check_memory(int(nbytes.value), _free_bytes(dev), "the mesh workspace")
+        mws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=dev)
+        F = C.c_int64(0)
+        with torch.cuda.device(dev):
+            st = lib.splatraster_fusion_mesh_count(C.byref(vol), _ptr(ws), _ptr(mws), C.byref(F), _stream(dev))
+        _native.check(st, "splatraster_fusion_mesh_count")
+        m, f = int(out["verts"].shape[0]), int(F.value)
+        out["faces"] = torch.empty((f, 3), dtype=torch.int32, device=dev)
+        out["normals"] = torch.empty((m, 3), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            st = lib.splatraster_fusion_mesh_extract(C.byref(vol), _ptr(ws), _ptr(mws), m, f, _ptr(out["faces"]) if f else None,
+                                                     _ptr(out["normals"]) if m else None, _stream(dev))
+        _native.check(st, "splatraster_fusion_mesh_extract")
         return out
+
+    def get_mesh(self, level=None):
+        """The reference's get_mesh (fusion_utils.py:271-289): (verts [M,3] f64 in world units, faces [F,3] i32, norms [M,3] f32,
+        colors [M,3] u8, feats [M,C] f32) as numpy arrays."""
+        s = self.mesh(level)
+        return tuple(s[k].cpu().numpy() for k in ("points", "faces", "normals", "colors", "feats"))
+
+    def save_mesh(self, ply_path, npy_path=None, level=None):
+        """mesh.ply with faces, as the reference's meshwrite writes it, and (npy_path given) the vertices' feature rows:
+        gen_3d_fusion_feature.py:91-94 in one call.  Returns (vertices, faces)."""
+        verts, faces, norms, colors, feats = self.get_mesh(level)
+        for p in (ply_path, npy_path):
+            if p is not None:
+                os.makedirs(os.path.dirname(os.fspath(p)) or ".", exist_ok=True)
+        meshwrite(ply_path, verts, faces, norms, colors)
+        if npy_path is not None:
+            np.save(npy_path, feats)
+        return int(verts.shape[0]), int(faces.shape[0])
 
     def feature_cloud(self, level=None):
         """(points [M,3] f64, colors [M,3] u8, feats [M,C] f32) on the device: what get_mesh returns as verts, colors and feats,

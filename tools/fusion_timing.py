@@ -7,6 +7,9 @@ the median of the regions per path is reported, and the paired ratio with its mi
 pair the image row (C * 4 bytes); per voxel row read and written, once per frame for single launches and once per batch for a batch;
 the scalar volumes (20 bytes per voxel read, 20 per valid voxel written) are listed apart.
     python tools/fusion_timing.py [--rounds 7] [--out profiles/fusion_time.json]
+    python tools/fusion_timing.py --mesh [--rounds 7] [--out profiles/fusion_mesh_time.json]
+        the surface mesh (csrc/fusion_mesh.hip) on a synthetic TSDF of the same room at the same grid: surface() and the three mesh
+        passes, interleaved with a device copy of 1 GiB whose rate the achieved bytes/s are set against
     python tools/fusion_timing.py --reference <checkout of the reference>     CPU only: the reference's own class on the toy volume of
                                                                               tests/golden (50 x 40 x 30 voxels, 80 x 60 x 256 frames)"""
 import argparse
@@ -138,14 +141,95 @@ def reference_cpu(ref, repeats=3):
             "free_space_frame": {"valid_share": round(share, 3), "ms_per_frame_median": round(1e3 * float(np.median(all_valid[1:])), 2)}}
 
 
+def mesh_timing(rounds, out_path, inner=100):
+    """surface() and the mesh passes at office_0's grid.  The TSDF is the room's own: the distance to the nearest wall (7 cm inside
+    the bounds) over the truncation, clamped to [-1, 1], so the level set 0 is the six walls.  Regions: surface(0.0) as a user calls
+    it (allocation, both passes, the gather of C = 256 feature rows, one host wait); splatraster_fusion_mesh_count (count kernel,
+    scan, one host wait); the faces pass (memset + kernel); the normals pass; a 1 GiB device copy.  A region is `inner` calls of
+    one path between two events (a single call is 0.1-0.6 ms: too short a window); milliseconds are per call.  Bytes of a pass: what it must
+    read and write once (the TSDF, the offsets it uses, its output).  The TSDF (4 bytes per voxel) fits the 256 MiB Infinity Cache,
+    so a pass can exceed the HBM copy rate."""
+    import ctypes as Ct
+    from splatloc_amd import _native
+    from splatloc_amd import fusion as F
+    vol = F.volume_from_bounds(BOUNDS, VOXEL, C, margin=MARGIN)
+    dev = vol.device
+    b = np.array(BOUNDS)
+    dist = None
+    for a in range(3):
+        shape = [1, 1, 1]
+        shape[a] = -1
+        p = vol._axis[a].double()
+        d = torch.minimum(p - (b[a, 0] + 0.07), (b[a, 1] - 0.07) - p).view(shape)
+        dist = d if dist is None else torch.minimum(dist, d)
+    vol.get_volume()[0].copy_(torch.clamp(dist / vol.sdf_trunc, -1, 1).float())
+    X, Y, Z = vol.voxel_dim
+    N, cells = X * Y * Z, (X - 1) * (Y - 1) * (Z - 1)
+    lib, v = _native.load(), vol._native()
+    nb = Ct.c_size_t(0)
+    _native.check(lib.splatraster_fusion_mesh_bytes(X, Y, Z, Ct.byref(nb)), "splatraster_fusion_mesh_bytes")
+    ws = torch.empty(vol.surface_bytes, dtype=torch.uint8, device=dev)
+    mws = torch.empty(nb.value, dtype=torch.uint8, device=dev)
+    n_v, n_f = Ct.c_int64(0), Ct.c_int64(0)
+    _native.check(lib.splatraster_fusion_surface_count(Ct.byref(v), 1, 0.0, ws.data_ptr(), Ct.byref(n_v), None), "surface_count")
+    _native.check(lib.splatraster_fusion_mesh_count(Ct.byref(v), ws.data_ptr(), mws.data_ptr(), Ct.byref(n_f), None), "mesh_count")
+    M, Fc = int(n_v.value), int(n_f.value)
+    faces = torch.empty((Fc, 3), dtype=torch.int32, device=dev)
+    normals = torch.empty((M, 3), dtype=torch.float32, device=dev)
+    src = torch.empty(1 << 30, dtype=torch.uint8, device=dev).fill_(1)
+    dst = torch.empty_like(src)
+
+    def count():
+        _native.check(lib.splatraster_fusion_mesh_count(Ct.byref(v), ws.data_ptr(), mws.data_ptr(), Ct.byref(n_f), None), "mesh_count")
+
+    def extract(m, f):
+        _native.check(lib.splatraster_fusion_mesh_extract(Ct.byref(v), ws.data_ptr(), mws.data_ptr(), m, f, faces.data_ptr() if f else None,
+                                                          normals.data_ptr() if m else None, None), "mesh_extract")
+
+    paths = {"surface": lambda: vol.surface(0.0), "mesh_count": count, "mesh_faces": lambda: extract(0, Fc),
+             "mesh_normals": lambda: extract(M, 0), "copy_1GiB": lambda: dst.copy_(src)}
+    with torch.cuda.device(dev):
+        for fn in paths.values():
+            fn()
+        torch.cuda.synchronize()
+        ms = {k: [] for k in paths}
+        names = list(paths)
+        for r in range(rounds):
+            for k in (names if r % 2 == 0 else names[::-1]):
+                ms[k].append(region(lambda fn=paths[k]: [fn() for _ in range(inner)]) / inner)
+    med = {k: float(np.median(t)) for k, t in ms.items()}
+    copy_rate = 2 * src.numel() / (med["copy_1GiB"] * 1e-3)
+    nbytes = {"mesh_count": 4 * N + 4 * cells + 8 * cells, "mesh_faces": 4 * N + 4 * cells + 12 * Fc + 12 * Fc,
+              "mesh_normals": 4 * N + 4 * N + 12 * M}
+    out = {"what": "surface mesh on MI355X at office_0's grid, synthetic room TSDF, level 0; HIP events, interleaved regions, medians, ms per call",
+           "voxel_dim": [X, Y, Z], "voxels": N, "cells": cells, "feat_dim": C, "vertices": M, "faces": Fc, "rounds": rounds, "calls_per_region": inner,
+           "ms": {k: round(t, 4) for k, t in med.items()},
+           "ms_min_max": {k: [round(min(t), 4), round(max(t), 4)] for k, t in ms.items()},
+           "measured_copy_TB_per_s": round(copy_rate / 1e12, 3),
+           "bytes": nbytes,
+           "achieved_TB_per_s": {k: round(nbytes[k] / (med[k] * 1e-3) / 1e12, 3) for k in nbytes},
+           "share_of_measured_copy_rate": {k: round(nbytes[k] / (med[k] * 1e-3) / copy_rate, 3) for k in nbytes},
+           "notes": "mesh_count includes the scan of the cell counts and one host wait; mesh_faces includes the memset of the faces "
+                    "(counted as 12 F bytes written twice); the 4-byte TSDF (%d MB) fits the Infinity Cache" % (4 * N // 10 ** 6)}
+    text = json.dumps(out, indent=1)
+    print(text)
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write(text + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--mesh", action="store_true")
     ap.add_argument("--out", default=None)
     ap.add_argument("--reference", default=None)
     args = ap.parse_args()
     if args.reference:
         print(json.dumps(reference_cpu(args.reference), indent=1))
+        return
+    if args.mesh:
+        mesh_timing(args.rounds, args.out)
         return
     from splatloc_amd import fusion as F
     vol = F.volume_from_bounds(BOUNDS, VOXEL, C, margin=MARGIN)

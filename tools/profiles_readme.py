@@ -31,6 +31,7 @@ WHAT = [   # (file name regex, description; {placeholders} are filled by the ext
     (r"r\d+_knn\.json$", "`distCUDA2` wall times, brute force vs exact grid"),
     (r"^decoder_time\.json$", "fused FeatureDecoder against the composed path (`tinycudann.Encoding` + torch layers + `torch.optim.Adam`), HIP events, interleaved regions (`tools/decoder_time.py`): {decoder}"),
     (r"^fusion_time\.json$", "feature-TSDF fusion at office_0's size (21.9 M voxels x 256 channels, 640 x 480 frames) against the same update composed from torch operators, HIP events, interleaved regions (`tools/fusion_timing.py`): {fusion}"),
+    (r"^fusion_mesh_time\.json$", "surface mesh at office_0's grid (21.9 M voxels) on a synthetic room TSDF, HIP events, interleaved regions beside a 1 GiB device copy (`tools/fusion_timing.py --mesh`): {fusionmesh}"),
     (r"^pnp_time\.json$", "absolute pose (`solve_pose`: P3P LO-RANSAC + Cauchy refinement) on planted scenes, HIP events (`tools/pnp_time.py`): {pnp}"),
     (r"^localize_time\.json$", "localisation (`tools/localize_time.py`), HIP events, interleaved medians: fused retrieval against `torch.einsum(...).topk` and the batched `Localizer.localize` against the per-query loop: {localize}"),
     (r"^pose_window_time\.json$", "pose refinement of 8 query frames at 640x480, `pose.refine_poses` per `window` against the loop of 8 `pose.refine_pose` calls, ms per frame-iteration, host clock around a device synchronise, alternating regions (`tools/pose_window_time.py`): {posewindow}"),
@@ -307,6 +308,16 @@ def decoder(path):
     return ", ".join(parts) + (f" ({tf} TFLOPS)" if tf is not None else "")
 
 
+def fusionmesh(path):
+    j = _load(path) or {}
+    ms, tb = j.get("ms") or {}, j.get("achieved_TB_per_s") or {}
+    if not ms:
+        return "(no rows)"
+    return (f"{j.get('vertices')} vertices, {j.get('faces')} faces; surface() {ms['surface']:.2f} ms, count + scan {ms['mesh_count']:.2f} "
+            f"({tb.get('mesh_count')} TB/s), faces {ms['mesh_faces']:.2f} ({tb.get('mesh_faces')} TB/s), normals {ms['mesh_normals']:.2f} "
+            f"({tb.get('mesh_normals')} TB/s); the copy {j.get('measured_copy_TB_per_s')} TB/s")
+
+
 def fusion(path):
     j = _load(path) or {}
     ms, tb = j.get("ms_per_frame") or {}, j.get("achieved_TB_per_s") or {}
@@ -400,7 +411,7 @@ def fe_ab(path):
             f"{c['payload_ms']['change']:.4f} ms ({', '.join(f'{k} {v:.4f}' for k, v in c['payload_ms_of_band_variants'].items())})")
 
 
-EXTRACT = {"dm_share": dm_share, "dm_room": dm_room, "pc_kstats": pc_kstats, "pc_pmc": pc_pmc, "pc_ab": pc_ab, "fe_kstats": fe_kstats, "fe_pmc": fe_pmc, "fe_ab": fe_ab, "setup_pmc": setup_pmc, "kstats2": kstats2, "setup_ab": setup_ab, "scenelists": scenelists, "scene": scene, "ab": ab, "perview": perview, "mapidle": mapidle, "rccl": rccl, "kstats": kstats, "hbm": hbm, "sq": sq, "timeline": timeline, "bench": bench, "clocks": clocks, "gradbars": gradbars, "idle": idle, "landmark": landmark, "matching": matching, "pnp": pnp, "decoder": decoder, "fusion": fusion, "localize": localize, "jointwindow": jointwindow, "posewindow": posewindow, "refinebounded": refinebounded}
+EXTRACT = {"dm_share": dm_share, "dm_room": dm_room, "pc_kstats": pc_kstats, "pc_pmc": pc_pmc, "pc_ab": pc_ab, "fe_kstats": fe_kstats, "fe_pmc": fe_pmc, "fe_ab": fe_ab, "setup_pmc": setup_pmc, "kstats2": kstats2, "setup_ab": setup_ab, "scenelists": scenelists, "scene": scene, "ab": ab, "perview": perview, "mapidle": mapidle, "rccl": rccl, "kstats": kstats, "hbm": hbm, "sq": sq, "timeline": timeline, "bench": bench, "clocks": clocks, "gradbars": gradbars, "idle": idle, "landmark": landmark, "matching": matching, "pnp": pnp, "decoder": decoder, "fusion": fusion, "fusionmesh": fusionmesh, "localize": localize, "jointwindow": jointwindow, "posewindow": posewindow, "refinebounded": refinebounded}
 
 
 def describe(name, path):
