@@ -1115,6 +1115,55 @@ int splatraster_timing_select(uint32_t stage_mask); /* bit s set: time stage s o
  * ms[SPLATRASTER_STAGE_COUNT] / counts[SPLATRASTER_STAGE_COUNT], then clears the records. */
 int splatraster_timing_collect(double* ms, int64_t* counts);
 
+/* ---- frame preparation: image gradients, grad mask, masked medians (csrc/image_ops.hip) ----------- */
+
+/* The frame-preparation step of SplatLoc's key-frame loop and of test.py: image_gradient / image_gradient_mask (utils/utils.py:4-38),
+ * Camera.compute_grad_mask (utils/camera_utils.py:145-172) and get_median_depth (utils/utils.py:85-96), for N frames per call,
+ * asynchronous on `stream`, nothing read back.  All tensors are contiguous device arrays; argument checks come before any launch.
+ *
+ * Arithmetic (float32, every operation rounding on its own, no contraction): gray = ((r + g) + b) / 3; the plane is padded by one
+ * pixel with reflect padding (the border is not repeated); grad_v = (1/32) sum of [[3,10,3],[0,0,0],[-3,-10,-3]] * p and
+ * grad_h = (1/32) sum of [[3,0,-3],[10,0,-10],[3,0,-3]] * p, cross-correlation, the nine products added row-major starting from
+ * the first (zero taps included: 0 * NaN is NaN); a pixel is valid when all nine |p| > eps; the intensity is
+ * x = sqrt((grad_v valid)^2 + (grad_h valid)^2) with a correctly rounded square root.  A median is the LOWER median, element
+ * (n - 1) / 2 of the ascending order, and NaN when any selected element is NaN. */
+
+/* Gradients and validity of every plane of image [N,C,H,W] (H, W >= 2; N * C <= 65535): grad_v, grad_h [N,C,H,W] float and
+ * valid [N,C,H,W] bytes (1 / 0); each output may be NULL, not all three.  Needs no workspace. */
+int splatraster_image_gradient(int32_t N, int32_t C, int32_t H, int32_t W, const float* image, float eps, float* grad_v,
+                               float* grad_h, uint8_t* valid, void* stream);
+
+#define SPLATRASTER_GRAD_MASK_REPLICA 0  /* per-block medians on a 32 x 32 grid of blocks */
+#define SPLATRASTER_GRAD_MASK_GLOBAL 1   /* one median per frame (every other dataset type) */
+/* Bytes of workspace a grad-mask call of this shape needs (0 is possible: then workspace may be NULL); have_intensity: the call
+ * passes an intensity output. */
+int splatraster_grad_mask_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t mode, int32_t have_intensity, size_t* bytes);
+/* images [N,3,H,W] -> out [N,1,H,W].
+ * REPLICA: bh = H / 32, bw = W / 32 (integer division); for block (r, c), t = median(x over the block) * edge_threshold and
+ *   out = (x > t && t < 1) ? 1 : 0 (the reference writes 1 where x > t, then 0 where the result <= t: with t >= 1 its ones go too);
+ *   t NaN (a NaN in the block, inf * 0): the block keeps x.  Rows at or beyond 32 bh and columns at or beyond 32 bw keep x.  The
+ *   output is float (out_u8 != 0: SPLATRASTER_ERR_UNSUPPORTED); H < 32 or W < 32 (the reference takes the median of an empty block
+ *   and raises): SPLATRASTER_ERR_BAD_ARG.  thresholds (optional): [N,32,32], t of every block.
+ * GLOBAL: out = x > median(x over the frame) * edge_threshold, as float 0 / 1 or, with out_u8, as bytes.  thresholds (optional): [N].
+ * intensity (optional): [N,1,H,W], x of every pixel.  workspace_bytes below the query's answer: SPLATRASTER_ERR_BAD_ARG. */
+int splatraster_grad_mask(int32_t N, int32_t H, int32_t W, const float* images, float edge_threshold, float eps, int32_t mode,
+                          int32_t out_u8, void* out, float* intensity, float* thresholds, void* workspace, size_t workspace_bytes,
+                          void* stream);
+/* Test hook, host only: the internal path the REPLICA mode takes for H x W frames.  0: none (H or W below 32 or above 65536);
+ * 1: fused, a block's halo and intensities in 19 KB of LDS (n = bh bw <= 2048, halo (bh + 2)(bw + 2) <= 2560); 2: fused in 145 KB
+ * (n <= 16384, halo <= 20480); 3: the gradient kernel, then a per-block select over global memory. */
+int splatraster_debug_image_ops_path(int32_t H, int32_t W);
+
+/* Lower median of the selected elements of each of N rows of n <= 2^31 values [N,n]: element i is selected when
+ * (!positive_only || value > 0) && (!opacity || opacity[i] > opacity_min) && (!mask || mask[i] != 0) (get_median_depth:
+ * positive_only = 1, opacity_min = 0.95).  Negative values order correctly (-0 below +0).  Outputs per row: median [N] (NaN for an
+ * empty selection: the reference raises there); optional std [N] (unbiased, NaN for fewer than two elements), count [N] and
+ * valid [N,n] bytes (the selection).  The count, the rank and the result stay on the device. */
+int splatraster_masked_median_workspace_bytes(int32_t N, int64_t n, size_t* bytes);
+int splatraster_masked_median(int32_t N, int64_t n, const float* values, int32_t positive_only, const float* opacity,
+                              float opacity_min, const uint8_t* mask, float* median, float* std, int64_t* count, uint8_t* valid,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- misc ---------------------------------------------------------------------------- */
 
 /* The decoupled look-backs of the one-pass scan and of the one-sweep radix sort never give up with a

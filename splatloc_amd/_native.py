@@ -222,6 +222,12 @@ SYMBOLS = {
     "splatraster_fusion_mesh_count": (C.c_int, [C.POINTER(FusionVolume), _vp, _vp, C.POINTER(_i64), _vp]),
     "splatraster_fusion_mesh_extract": (C.c_int, [C.POINTER(FusionVolume), _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     "splatraster_debug_mc_table": (C.c_int, [_vp]),
+    "splatraster_image_gradient": (C.c_int, [_i32] * 4 + [_vp, C.c_float, _vp, _vp, _vp, _vp]),
+    "splatraster_grad_mask_workspace_bytes": (C.c_int, [_i32] * 5 + [C.POINTER(_sz)]),
+    "splatraster_grad_mask": (C.c_int, [_i32] * 3 + [_vp, C.c_float, C.c_float, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "splatraster_debug_image_ops_path": (C.c_int, [_i32, _i32]),
+    "splatraster_masked_median_workspace_bytes": (C.c_int, [_i32, _i64, C.POINTER(_sz)]),
+    "splatraster_masked_median": (C.c_int, [_i32, _i64, _vp, _i32, _vp, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "splatraster_lsap_workspace_bytes": (_sz, [_i32, _vp]),
     "splatraster_lsap": (C.c_int, [_i32, _vp, _vp, _i32] + [_vp] * 6),
     "splatraster_debug_set_lsap_lds": (C.c_int, [C.c_int]),

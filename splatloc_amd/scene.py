@@ -28,15 +28,17 @@ import torch
 
 from .camera import PinholeCamera
 from .densify import ATTR, GROUPS
+from .image_ops import compute_grad_mask
 from .keyframe import extend_from_pcd_seq
 from .training import LAST_STEP_INFO, color_refinement_step, map_step, refine_bounded
 
 # configs/replica_nerf/base_config.yaml (the values train_gaussians.py reads)
 DEFAULT_CONFIG = {
-    "Dataset": {"pcd_downsample": 64, "pcd_downsample_init": 32, "adaptive_pointsize": True, "point_size": 0.05},
+    "Dataset": {"pcd_downsample": 64, "pcd_downsample_init": 32, "adaptive_pointsize": True, "point_size": 0.05,
+                "type": "replica"},
     "Training": {"mapping_itr_num": 10, "gaussian_update_every": 150, "gaussian_update_offset": 50, "gaussian_th": 0.7,
                  "gaussian_extent": 1.0, "gaussian_reset": 2001, "size_threshold": 20, "window_size": 5,
-                 "rgb_boundary_threshold": 0.01, "primitive_reg": True},
+                 "rgb_boundary_threshold": 0.01, "primitive_reg": True, "edge_threshold": 4},
     "opt_params": {"position_lr_init": 0.00016, "position_lr_final": 0.0000016, "position_lr_delay_mult": 0.01,
                    "position_lr_max_steps": 30000, "feature_lr": 0.0025, "opacity_lr": 0.05, "marker_lr": 0.05,
                    "kp_score_lr": 0.05, "scaling_lr": 0.001, "rotation_lr": 0.001, "percent_dense": 0.01, "lambda_dssim": 0.2,
@@ -173,7 +175,8 @@ def load_depth(config, viewpoint):
 
 
 def do_recon(gaussians, keyframes, pipe=None, background=None, config=None, refine_iterations: int = 26000, seed: int = 0,
-             batched: bool = True, group=None, on_event=None, distributed: bool = True, bounded_refine: bool = False) -> dict:
+             batched: bool = True, group=None, on_event=None, distributed: bool = True, bounded_refine: bool = False,
+             grad_masks: bool = False) -> dict:
     """SplatLoc.do_recon (train_gaussians.py:310-355) on `keyframes` (the reference: every `kf_interval`-th dataset frame).
     `batched = False` renders every window — and every refinement iteration — as the reference does: one `render()` per view
     through the drop-in autograd.Function (`render_path="per-view"` of training.map_step / color_refinement_step) instead of
@@ -183,7 +186,9 @@ def do_recon(gaussians, keyframes, pipe=None, background=None, config=None, refi
     group exists — every rank reconstructs a scene of its own (one scene per GPU: /root/reference/replica.sh).
     `bounded_refine = True`: the refinement phase runs through training.refine_bounded (the same iterations and the same draws of
     the view, without the host wait for every frame's instance count; 500 iterations per call, between the "refine" events);
-    stats["refine_rewinds"] counts its replays.  Returns counters and timings; the model is updated in place."""
+    stats["refine_rewinds"] counts its replays.  `grad_masks = True`: every key-frame gets its `grad_mask` at insertion, as
+    `viewpoint.compute_grad_mask(self.config)` of train_gaussians.py:327 leaves it (image_ops.compute_grad_mask; the active loss
+    does not read it, so the default leaves the step out).  Returns counters and timings; the model is updated in place."""
     cfg = config or gaussians.config
     tr, opt = cfg["Training"], cfg["opt_params"]
     dev = gaussians._xyz.device
@@ -202,6 +207,8 @@ def do_recon(gaussians, keyframes, pipe=None, background=None, config=None, refi
     path = "auto" if batched else "per-view"
     stats["render_paths"] = set()
     for kf_id, viewpoint in enumerate(keyframes):
+        if grad_masks:
+            compute_grad_mask(viewpoint, cfg)                                              # train_gaussians.py:327
         viewpoints[kf_id] = viewpoint
         extend_from_pcd_seq(gaussians, viewpoint, kf_id=kf_id, depthmap=load_depth(cfg, viewpoint), seed=seed)
         stats["rows_after_keyframe"].append(gaussians.num_points if hasattr(gaussians, "num_points") else int(gaussians._xyz.shape[0]))

@@ -34,6 +34,7 @@ WHAT = [   # (file name regex, description; {placeholders} are filled by the ext
     (r"^fusion_mesh_time\.json$", "surface mesh at office_0's grid (21.9 M voxels) on a synthetic room TSDF, HIP events, interleaved regions beside a 1 GiB device copy (`tools/fusion_timing.py --mesh`): {fusionmesh}"),
     (r"^pnp_time\.json$", "absolute pose (`solve_pose`: P3P LO-RANSAC + Cauchy refinement) on planted scenes, HIP events (`tools/pnp_time.py`): {pnp}"),
     (r"^localize_time\.json$", "localisation (`tools/localize_time.py`), HIP events, interleaved medians: fused retrieval against `torch.einsum(...).topk` and the batched `Localizer.localize` against the per-query loop: {localize}"),
+    (r"^image_ops_time\.json$", "frame preparation (`tools/time_image_ops.py`), HIP events, alternating medians, ms per call: `image_ops.compute_grad_masks` against the per-block loop of `Camera.compute_grad_mask` written with torch operators: {imageops}"),
     (r"^pose_window_time\.json$", "pose refinement of 8 query frames at 640x480, `pose.refine_poses` per `window` against the loop of 8 `pose.refine_pose` calls, ms per frame-iteration, host clock around a device synchronise, alternating regions (`tools/pose_window_time.py`): {posewindow}"),
     (r"^refine_bounded_time\.json$", "`training.refine_bounded` (no host wait for the instance count) against this tree's plain loop of `color_refinement_step` calls (not a build of the parent commit), us per iteration, host clock around a device synchronise, interleaved regions in one process (`tools/refine_bounded_time.py`): {refinebounded}"),
     (r"^joint_window_time\.json$", "one backward of a 5-view window that returns parameter AND camera gradients, ms per backward, host clock around a device synchronise, alternating regions (`tools/joint_window_time.py`): {jointwindow}"),
@@ -254,6 +255,15 @@ def localize(path):
             f"{d['per_query_loop_ms']:.0f} ms ({d['ratio_loop_over_localize']:.2f} x), bit-identical {d['bit_identical_to_loop']}")
 
 
+def imageops(path):
+    j = _load(path) or {}
+    if not j.get("rows"):
+        return str(j.get("status", "not measured"))
+    return "; ".join(f"{r['dataset_type']} {r['W']}x{r['H']} N = {r['N']}: {r['hip']['median_ms']:.4f} ({r['hip']['min_ms']:.4f} - {r['hip']['max_ms']:.4f}) "
+                     f"vs {r['torch_operators']['median_ms']:.3f} ({r['torch_operators']['min_ms']:.3f} - {r['torch_operators']['max_ms']:.3f}), "
+                     f"{r['pixels_that_differ']} pixels differ" for r in j["rows"])
+
+
 def jointwindow(path):
     j = _load(path) or {}
     if not j.get("results"):
@@ -411,7 +421,7 @@ def fe_ab(path):
             f"{c['payload_ms']['change']:.4f} ms ({', '.join(f'{k} {v:.4f}' for k, v in c['payload_ms_of_band_variants'].items())})")
 
 
-EXTRACT = {"dm_share": dm_share, "dm_room": dm_room, "pc_kstats": pc_kstats, "pc_pmc": pc_pmc, "pc_ab": pc_ab, "fe_kstats": fe_kstats, "fe_pmc": fe_pmc, "fe_ab": fe_ab, "setup_pmc": setup_pmc, "kstats2": kstats2, "setup_ab": setup_ab, "scenelists": scenelists, "scene": scene, "ab": ab, "perview": perview, "mapidle": mapidle, "rccl": rccl, "kstats": kstats, "hbm": hbm, "sq": sq, "timeline": timeline, "bench": bench, "clocks": clocks, "gradbars": gradbars, "idle": idle, "landmark": landmark, "matching": matching, "pnp": pnp, "decoder": decoder, "fusion": fusion, "fusionmesh": fusionmesh, "localize": localize, "jointwindow": jointwindow, "posewindow": posewindow, "refinebounded": refinebounded}
+EXTRACT = {"dm_share": dm_share, "dm_room": dm_room, "pc_kstats": pc_kstats, "pc_pmc": pc_pmc, "pc_ab": pc_ab, "fe_kstats": fe_kstats, "fe_pmc": fe_pmc, "fe_ab": fe_ab, "setup_pmc": setup_pmc, "kstats2": kstats2, "setup_ab": setup_ab, "scenelists": scenelists, "scene": scene, "ab": ab, "perview": perview, "mapidle": mapidle, "rccl": rccl, "kstats": kstats, "hbm": hbm, "sq": sq, "timeline": timeline, "bench": bench, "clocks": clocks, "gradbars": gradbars, "idle": idle, "landmark": landmark, "matching": matching, "pnp": pnp, "decoder": decoder, "fusion": fusion, "fusionmesh": fusionmesh, "localize": localize, "imageops": imageops, "jointwindow": jointwindow, "posewindow": posewindow, "refinebounded": refinebounded}
 
 
 def describe(name, path):
