@@ -1164,6 +1164,49 @@ int splatraster_masked_median(int32_t N, int64_t n, const float* values, int32_t
                               float opacity_min, const uint8_t* mask, float* median, float* std, int64_t* count, uint8_t* valid,
                               void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- SuperPoint head: scores, NMS, keypoint selection, descriptors (csrc/superpoint_head.hip) ------ */
+
+/* Everything behind SuperPoint's two convolution heads, for B images per call, asynchronous on `stream`, nothing read back.  Inputs
+ * are the raw head outputs: semi [B,65,Hc,Wc] (the logits of convPb) and coarse [B,256,Hc,Wc] (the output of convDb); H = 8 Hc,
+ * W = 8 Wc.  All tensors are contiguous float32 device arrays.  Argument checks come before any launch: B, Hc, Wc (H, W) >= 1, else
+ * SPLATRASTER_ERR_BAD_ARG; B H W < 2^31, else SPLATRASTER_ERR_UNSUPPORTED; null or misaligned pointers, a radius outside 0..8,
+ * max_keypoints outside 1..65535, a negative (or NaN) threshold, a negative border: SPLATRASTER_ERR_BAD_ARG.
+ *
+ * hloc's SuperPoint is not part of the reference tree; these definitions are the contract:
+ *  scores   p = softmax(semi) over the 65 channels in float32: m = max, e_c = expf(x_c - m), s = e_0 + e_1 + ... + e_64 in that order,
+ *           p_c = e_c / s.  Channel 64 is dropped; S[b, 8i + u, 8j + v] = p[b, 8u + v, i, j].
+ *  NMS      pool(X) = maximum over the (2r + 1)^2 window clipped to the image.  M0 = (S == pool(S)); twice: Supp = pool(M) > 0,
+ *           Q = where(Supp, 0, S), M |= (Q == pool(Q)) & ~Supp; N = where(M, S, 0).  Equal scores on a plateau all survive; r = 0: N = S.
+ *  select   candidates: N > threshold (strict), border <= row < H - border, border <= col < W - border; n of them in an image.
+ *           n <= K: the keypoints in row-major order.  n > K: the K largest scores in descending order, equal scores by ascending
+ *           row-major index.  keypoints [B,K,2] as (x, y) = (col, row), scores [B,K], count [B] = min(n, K), candidates [B] = n;
+ *           rows at and beyond count are zero.  Candidate scores are positive.
+ *  sample   d^ = coarse / max(|coarse|, 1e-12) over the channels.  For a keypoint (x, y), in float32 without contraction:
+ *           gx = ((x - 3.5) / (8 Wc - 4.5)) * 2 - 1, ix = ((gx + 1) / 2) * (Wc - 1), gy and iy likewise with Hc; the bilinear
+ *           interpolation of d^ at (ix, iy), neighbours outside the grid reading 0, normalised once more with the same eps.
+ *           descriptors [B,256,K], columns at and beyond count[b] zero.
+ *  dense    the same at every pixel (x, y) of rows [row0, row0 + rows): out [B,rows,W,256], channel-last. */
+
+/* Host only, never touches the device: the tile of outputs one NMS workgroup owns for radii 0..4.  Radii 5..8 use tiles of half
+ * that side, so every edge of the reported tile is a tile edge at every radius. */
+int splatraster_sp_nms_tile(int32_t* tile_h, int32_t* tile_w);
+/* Host only: bytes of workspace for B images of H x W pixels and up to max_keypoints keypoints; serves every call below of that
+ * shape (sample and dense_descriptors use only its first part and accept any max_keypoints in the query). */
+int splatraster_sp_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t max_keypoints, size_t* bytes);
+/* scores [B,8 Hc,8 Wc], 16-byte aligned. */
+int splatraster_sp_scores(int32_t B, int32_t Hc, int32_t Wc, const float* semi, float* scores, void* stream);
+/* out [B,H,W]; any H, W >= 1; out must not alias scores unless radius is 0. */
+int splatraster_sp_nms(int32_t B, int32_t H, int32_t W, const float* scores, int32_t radius, float* out, void* stream);
+int splatraster_sp_select(int32_t B, int32_t H, int32_t W, const float* nms, float threshold, int32_t max_keypoints, int32_t border,
+                          float* keypoints, float* scores, int32_t* count, int32_t* candidates, void* workspace, size_t workspace_bytes,
+                          void* stream);
+/* keypoints [B,K,2] need not be integers; count [B] (clamped to 0..K). */
+int splatraster_sp_sample(int32_t B, int32_t Hc, int32_t Wc, const float* coarse, int32_t K, const float* keypoints, const int32_t* count,
+                          float* descriptors, void* workspace, size_t workspace_bytes, void* stream);
+/* 0 <= row0, rows >= 1, row0 + rows <= 8 Hc; out 16-byte aligned. */
+int splatraster_sp_dense_descriptors(int32_t B, int32_t Hc, int32_t Wc, const float* coarse, int32_t row0, int32_t rows, float* out,
+                                     void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- misc ---------------------------------------------------------------------------- */
 
 /* The decoupled look-backs of the one-pass scan and of the one-sweep radix sort never give up with a

@@ -228,6 +228,13 @@ SYMBOLS = {
     "splatraster_debug_image_ops_path": (C.c_int, [_i32, _i32]),
     "splatraster_masked_median_workspace_bytes": (C.c_int, [_i32, _i64, C.POINTER(_sz)]),
     "splatraster_masked_median": (C.c_int, [_i32, _i64, _vp, _i32, _vp, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "splatraster_sp_nms_tile": (C.c_int, [C.POINTER(_i32), C.POINTER(_i32)]),
+    "splatraster_sp_workspace_bytes": (C.c_int, [_i32] * 4 + [C.POINTER(_sz)]),
+    "splatraster_sp_scores": (C.c_int, [_i32] * 3 + [_vp, _vp, _vp]),
+    "splatraster_sp_nms": (C.c_int, [_i32] * 3 + [_vp, _i32, _vp, _vp]),
+    "splatraster_sp_select": (C.c_int, [_i32] * 3 + [_vp, C.c_float, _i32, _i32] + [_vp] * 5 + [_sz, _vp]),
+    "splatraster_sp_sample": (C.c_int, [_i32] * 3 + [_vp, _i32] + [_vp] * 4 + [_sz, _vp]),
+    "splatraster_sp_dense_descriptors": (C.c_int, [_i32] * 3 + [_vp, _i32, _i32, _vp, _vp, _sz, _vp]),
     "splatraster_lsap_workspace_bytes": (_sz, [_i32, _vp]),
     "splatraster_lsap": (C.c_int, [_i32, _vp, _vp, _i32] + [_vp] * 6),
     "splatraster_debug_set_lsap_lds": (C.c_int, [C.c_int]),
