@@ -3,7 +3,10 @@
 `restated()` is the grid encoding's definition, the same as in tests/test_gpu_grid_encoding.py; `RestatedEncoding` wraps it as a
 CPU-or-device module with tinycudann.Encoding's interface (float64 table, initialised exactly as
 splatloc_amd.grid_encoding.Encoding(seed=1337) initialises its own); `RestatedDecoder` is the whole decoder in float64 with the
-reference's state_dict keys, able to report every layer's pre-activation and the worst-case f32 rounding bar that goes with it."""
+reference's state_dict keys, able to report every layer's pre-activation and the worst-case f32 rounding bar that goes with it.
+For the edge tests: LAYOUTS and `layout_decoder` (a FeatureDecoder-shaped module for every layout the kernels take), the batches and
+cases of those tests, `float64_gradients` with the conditioning term of its weight gradients, and `tiled_backward32`, a float32 model
+of the backward in the kernel's stated order with deliberately wrong variants (WRONG)."""
 import os
 
 import numpy as np
@@ -25,18 +28,17 @@ def gamma(k):
     return k * U / (1.0 - k * U)
 
 
-def restated(x, params, lay):
-    """out [N, L*F] (float64) of the grid encoding for f32-valued points x [N, D] and a table `params` [n_params]"""
+def corner_terms(x, lay):
+    """(level, rows [N, F] into the table, weight [N] float64) of every (level, corner) of the grid encoding for f32-valued points x
+    [N, D], levels ascending and corners ascending inside a level: the encoding's definition, shared by `restated` and the scatter"""
     D, F = lay.n_input_dims, lay.n_features_per_level
     x32 = x.detach().float()
-    outs = []
     for lvl in range(lay.n_levels):
         scale, res, size, off = lay.scales[lvl], lay.resolutions[lvl], lay.sizes[lvl], lay.offsets[lvl]
         pos = (x32.double() * scale + 0.5).float()          # fmaf(scale, x, 0.5f): exact in f64, rounded to f32 once
         fl = torch.floor(pos)
         cell = fl.to(torch.int64) & M32
         frac = (pos - fl).double()
-        acc = torch.zeros((x.shape[0], F), dtype=torch.float64, device=x.device)
         for c in range(1 << D):
             g = [(cell[:, d] + ((c >> d) & 1)) & M32 for d in range(D)]
             stride, index = 1, torch.zeros_like(g[0])
@@ -52,9 +54,19 @@ def restated(x, params, lay):
             w = torch.ones_like(frac[:, 0])
             for d in range(D):
                 w = w * (frac[:, d] if (c >> d) & 1 else 1.0 - frac[:, d])
-            rows = (off + index)[:, None] * F + torch.arange(F, device=x.device)[None, :]
-            acc = acc + w[:, None] * params.double()[rows]
-        outs.append(acc)
+            yield lvl, (off + index)[:, None] * F + torch.arange(F, device=x.device)[None, :], w
+
+
+def restated(x, params, lay):
+    """out [N, L*F] (float64) of the grid encoding for f32-valued points x [N, D] and a table `params` [n_params]"""
+    F = lay.n_features_per_level
+    outs = [torch.zeros((x.shape[0], F), dtype=torch.float64, device=x.device) for _ in range(lay.n_levels)]
+    terms = list(corner_terms(x, lay))
+    # one gather for all corners (the same values summed in the same order as a gather per corner; its backward is one scatter
+    # into the table instead of one table-sized temporary per corner)
+    vals = params.double()[torch.stack([rows for _, rows, _ in terms])].unbind(0)
+    for (lvl, _, w), v in zip(terms, vals):
+        outs[lvl] = outs[lvl] + w[:, None] * v
     return torch.cat(outs, 1)
 
 
@@ -174,14 +186,23 @@ def fixture_config(fx):
                         "num_layers": int(fx["config_num_layers"]), "final_dim": int(fx["config_final_dim"])}}
 
 
-def decided_pool_batch(ref, k, n=256, pool=320, bound=OFFICE_0):
-    """the fixture generator's batch rule for any model: the first n points of a fixed pool of uniform points (numpy
-    default_rng(100 + k)) whose hidden pre-activations all lie outside their rounding bar of zero under `ref`; unit targets"""
+def pool_size(n):
+    """points drawn for a batch of n: 1.1 n (the largest share of undecided points measured in a pool is 3 %, layout `deep`), and
+    never fewer than the 320 the 256-point batches have always drawn.  The generator fills a pool row by row, so a larger pool
+    only appends points: the batch is the same whenever the smaller pool suffices."""
+    return max(320, -(-11 * n // 10))
+
+
+def decided_pool_batch(ref, k, n=256, pool=None, bound=OFFICE_0, width=256):
+    """the fixture generator's batch rule for any model, batch size and output width: the first n points of a fixed pool of uniform
+    points (numpy default_rng(100 + k)) whose hidden pre-activations all lie outside their rounding bar of zero under `ref`, so the
+    batch holds no undecided point; unit targets [n, width]"""
+    pool = pool_size(n) if pool is None else pool
     lo, hi = np.array(bound, np.float64).T
     pts = torch.from_numpy(lo + np.random.default_rng(100 + k).random((pool, 3)) * (hi - lo))
     pts = pts[ref.decided(pts).cpu()][:n]
-    assert pts.shape[0] == n
-    return pts, unit_targets(n, 256, 300 + k)
+    assert pts.shape[0] == n, (pts.shape[0], n, pool)
+    return pts, unit_targets(n, width, 300 + k)
 
 
 def targets(k, n=256, width=256):
@@ -193,3 +214,331 @@ def unit_targets(n, width, seed):
     g = torch.Generator().manual_seed(seed)
     t = torch.randn((n, width), generator=g)
     return t / t.norm(dim=-1, keepdim=True)
+
+
+# ---- the layouts, batches and cases of the edge tests (tests/test_gpu_decoder_edges.py, tests/test_host_decoder_edges.py) --------
+
+def _hash_grid(levels, features, log2_t, base, scale):
+    return {"otype": "HashGrid", "n_levels": levels, "n_features_per_level": features, "log2_hashmap_size": log2_t,
+            "base_resolution": base, "per_level_scale": scale}
+
+
+# layer widths and grid of every tested layout; `grid` None = the package's own configuration of office_0 (HashGrid, 16 x 2).
+# narrow: E = 16 and a single column block everywhere; three: E = 48, an odd layer count, 12 levels (not a power of two), F = 4;
+# five160: F = 8, O = 160 (wave 0 alone owns a second block); deep: E = 64 and the most layers the kernels take.
+LAYOUTS = {
+    "office_0": {"dims": [32, 128, 128, 128, 256], "grid": None},
+    "narrow": {"dims": [16, 32, 32], "grid": _hash_grid(8, 2, 10, 4, 1.5)},
+    "three": {"dims": [48, 64, 64, 96], "grid": _hash_grid(12, 4, 12, 4, 1.4)},
+    "five160": {"dims": [32, 64, 64, 64, 64, 160], "grid": _hash_grid(4, 8, 11, 8, 2.0)},
+    "deep": {"dims": [64] + [128] * 7 + [256], "grid": _hash_grid(16, 4, 12, 4, 1.3)},
+}
+NEW_LAYOUTS = ("narrow", "three", "five160", "deep")
+GRADIENT_NS = (1, 33, 2048, 2049, 2081)          # one tile; a partial second; 64 tiles = one full round; 65 and 66 tiles
+LONG_N, LONG_LAYOUTS = 8225, ("office_0", "narrow")      # 258 tiles: the strided part of the loss reduction
+ISOLATION_N, ISOLATION_ROWS = 2081, (0, 31, 32, 2047, 2048, 2079, 2080)
+ISOLATION_LAYOUTS = ("office_0", "narrow", "three")
+EPS_N, EPS_LAYOUTS = 33, ("office_0", "five160")
+BOX_N, BOX_LAYOUTS = 33, ("office_0", "three")
+TRAINER_NS = (2081, 33, 2081, 1)
+
+
+def gradient_cases():
+    return [(name, n) for name in LAYOUTS for n in GRADIENT_NS] + [(name, LONG_N) for name in LONG_LAYOUTS]
+
+
+def layout_decoder(name):
+    """A FeatureDecoder-shaped module for LAYOUTS[name] (a test-side subclass: the package's configuration path reaches office_0's
+    shape only): office_0's bound, FeatureNet under torch.manual_seed(3), a table of uniform(-1, 1) entries from generator seed 5.
+    On the device when there is one, otherwise a CPU module (enough for the float64 restatement and the f32 model)."""
+    from splatloc_amd.decoder import DecoderLayout, FeatureDecoder, FeatureNet, _Table, _encoding_config
+    from splatloc_amd.grid_encoding import GridLayout
+    spec = LAYOUTS[name]
+
+    class LayoutDecoder(FeatureDecoder):
+        def __init__(self):
+            torch.nn.Module.__init__(self)
+            dims = list(spec["dims"])
+            grid = GridLayout(3, spec["grid"] or _encoding_config("HashGrid", 108))
+            self.name = name
+            self.bounding_box = torch.tensor(OFFICE_0, dtype=torch.float64)
+            self.embed_dim = grid.n_output_dims
+            self.layout = DecoderLayout(grid, OFFICE_0, dims)
+            self.encoding = _Table(grid)
+            self.feature_net = FeatureNet(dims[0], dims[1], len(dims) - 1, dims[-1])
+
+    torch.manual_seed(3)
+    dec = LayoutDecoder()
+    if torch.cuda.is_available():
+        dec.cuda()
+    return trained_scale_(dec)
+
+
+def edge_batch(name, ref, n):
+    """the decided batch of (layout, N): points [n, 3] float64 on the CPU, unit targets [n, O]"""
+    k = 10_000 * (1 + list(LAYOUTS).index(name)) + n
+    return decided_pool_batch(ref, k, n=n, width=LAYOUTS[name]["dims"][-1])
+
+
+EPS_ROWS = {"zero": 3, "tiny": 7, "seven": 11, "milli": 32}      # row 32 is the one live row of the second tile
+
+
+def eps_targets(tgt):
+    """unit targets with one all-zero row, one of norm 1e-10 (below the eps of the cosine), one of norm 7 and one of norm 1e-3"""
+    t = tgt.clone()
+    t[EPS_ROWS["zero"]] = 0.0
+    t[EPS_ROWS["tiny"]] *= 1e-10
+    t[EPS_ROWS["seven"]] *= 7.0
+    t[EPS_ROWS["milli"]] *= 1e-3
+    return t
+
+
+def eps_scale(kind):
+    """[EPS_N, 1] row factors of the scaled eps cases.  `eps_x4`: every row times 4.  `eps_x4_above`: every row above the eps of
+    the cosine times 4, which must change nothing (a power of two: the scaling itself rounds nowhere).  The row below eps is left
+    out of that one because its clamped norm makes its term linear in the target, in torch.cosine_similarity as on the device:
+    `eps_x4` holds it to float64 instead."""
+    s = torch.ones((EPS_N, 1))
+    if kind != "eps":
+        s *= 4.0
+    if kind == "eps_x4_above":
+        s[EPS_ROWS["tiny"]] = 1.0
+    return s
+
+
+BOX_ROWS = (0, 5, 31, 32)
+
+
+def box_batch(ref, pts, seed=77, bound=OFFICE_0):
+    """`pts` with four points replaced: the bound's two corners, a point 0.5 outside the box on each axis and a point on a face.
+    A replacement is kept only if it is decided under `ref`; the outside point and the face point have further draws to fall back
+    on, the corners have none (the host test checks that every replacement was found)."""
+    lo, hi = torch.tensor(bound, dtype=torch.float64).unbind(1)
+    g = torch.Generator().manual_seed(seed)
+    inside = lo + torch.rand((8, 3), generator=g, dtype=torch.float64) * (hi - lo)
+    faces = inside.clone()
+    faces[:, 0] = lo[0]
+    mixed = torch.stack([lo[0] - 0.5, hi[1] + 0.5, lo[2] - 0.5])
+    options = [lo[None], hi[None], torch.stack([hi + 0.5, lo - 0.5, mixed]), faces]
+    out = pts.clone()
+    for row, cand in zip(BOX_ROWS, options):
+        ok = ref.decided(cand).cpu()
+        assert bool(ok.any()), f"no decided replacement for row {row}"
+        out[row] = cand[int(torch.nonzero(ok)[0])]
+    return out
+
+
+KAPPA = 1e-6      # weight of the conditioning term of a weight gradient's bar, as in test_first_three_reference_steps
+
+
+def float64_gradients(ref, pts, targets=None, dL_dout=None):
+    """(loss, [dL/dW_l], dL/dtable, [terms_l]) by float64 autograd of the restatement `ref`: of cos_loss (torch.cosine_similarity,
+    eps 1e-8) against `targets`, or of sum(out * dL_dout).
+    terms_l [O_l, K_l] is the conditioning of dW_l, from float64 alone: sum_p A_l[p][o] |H_l[p][k]|, where A_l[p][o] is the sum of
+    the absolute terms of the chain that forms dPre_l[p][o], sum_j |dPre_{l+1}[p][j] W_{l+1}[j][o]| behind the ReLU mask (|dPre| itself
+    for the last layer).  An f32 chain of those terms is off by up to gamma_128 of their absolute sum however small the sum itself
+    comes out, so an entry whose terms cancel carries an error that much larger relative to itself; and with few points a whole
+    gradient row is one such entry times the activations, so the row's maximum does not cover it."""
+    for p in ref.parameters():
+        p.grad = None
+    out, pres, _ = ref.trace(pts)
+    for p in pres:
+        p.retain_grad()
+    loss = None
+    if targets is not None:
+        loss64 = 1 - torch.cosine_similarity(out, targets.to(out.device).double(), dim=1, eps=1e-8).mean()
+        loss64.backward()
+        loss = float(loss64.detach())
+    else:
+        out.backward(dL_dout.to(out.device).double())
+    with torch.no_grad():
+        ws = [w.detach() for w in ref.weights()]
+        h = restated(ref.normalised(pts), ref.encoding.params, ref.layout)
+        terms = []
+        for l in range(len(ws)):
+            A = pres[l].grad.abs() if l + 1 == len(ws) else (pres[l + 1].grad.abs() @ ws[l + 1].abs()) * (pres[l] > 0)
+            terms.append(A.t() @ h.abs())
+            h = torch.relu(pres[l])
+    return loss, [w.grad.clone() for w in ref.weights()], ref.encoding.params.grad.clone(), terms
+
+
+def level_rows(grid, g):
+    """the table gradient as one row per level"""
+    F = grid.n_features_per_level
+    return [g[o * F:(o + s) * F] for o, s in zip(grid.offsets, grid.sizes)]
+
+
+def row_bar_ratio(got, want, terms=None):
+    """worst |got - want| / bar under the project's gradient bar, 1e-4 |want| + 1e-3 of the row's own maximum (inf for a NaN).
+    Where a conditioning term is given, an entry gets KAPPA * terms on top, but only if that exceeds 1e-3 of the entry itself, i.e.
+    if its terms cancel more than a thousandfold under float64: below that the row-maximum part of the bar covers the entry even
+    when it is its own row's maximum, so every other entry is held to the project's bar as it stands."""
+    got, want = got.double().reshape(want.shape[0], -1), want.double().reshape(want.shape[0], -1)
+    bar = 1e-4 * want.abs() + 1e-3 * want.abs().max(dim=1, keepdim=True).values
+    if terms is not None:
+        extra = KAPPA * terms.to(want.device).reshape(want.shape)
+        bar = bar + torch.where(extra > 1e-3 * want.abs(), extra, torch.zeros_like(extra))
+    ratio = ((got - want).abs() / bar.clamp_min(1e-300)).max()
+    return float("inf") if bool(torch.isnan(ratio)) else float(ratio)
+
+
+def gradient_ratios(grid, gw, gt, want_w, want_t, terms=None):
+    """{name: worst |got - want| / bar} per weight matrix (bar per output row, with the conditioning term if given) and per table
+    level (bar per level)"""
+    out = {f"dW{l}": row_bar_ratio(g, w, None if terms is None else terms[l]) for l, (g, w) in enumerate(zip(gw, want_w))}
+    for lvl, (g, w) in enumerate(zip(level_rows(grid, gt), level_rows(grid, want_t))):
+        out[f"dtable{lvl}"] = row_bar_ratio(g[None], w.to(g.device)[None])
+    return out
+
+
+def worst_entry(got, want, terms):
+    """(plain ratio, row, column, kappa) of the entry of a weight gradient that is worst under the bar without its conditioning
+    term; kappa = terms / |want| there"""
+    want = want.double()
+    bar = 1e-4 * want.abs() + 1e-3 * want.abs().max(dim=1, keepdim=True).values
+    r = (got.double() - want).abs() / bar.clamp_min(1e-300)
+    i = int(r.argmax())
+    o, k = divmod(i, want.shape[1])
+    return float(r.reshape(-1)[i]), o, k, float(terms[o, k] / want[o, k].abs().clamp_min(1e-300))
+
+
+# ---- float32 model of the backward in the kernel's stated order (csrc/decoder.hip, header comment) ---------------------------------
+# Not a bit-exact oracle of the MFMA: it exists to show that the checks of the edge tests tell a correct backward from a wrong one,
+# and that a correct f32 implementation can meet their bars.  `wrong` names one deliberate defect.
+WRONG = ("second_round_dropped",            # tiles past the first G are never added to their slab
+         "second_round_overwrites",         # ... or replace what the slab held
+         "dead_rows_live",                  # rows past N in the last tile are a copy of point 0, not zeros
+         "mask_ge_zero",                    # ReLU mask >= 0 instead of > 0
+         "norm_from_first_four_blocks",     # the squared norm misses the column blocks past the fourth
+         "loss_first_256_tiles",            # the loss reduction stops after its first strided round
+         "cos_eps_ignored")                 # no eps clamp of the two norms of the cosine
+BWD_TM, BWD_MAX_WG, REDUCE_THREADS = 32, 64, 256
+
+
+def _fma(a, b, c):
+    """fmaf on f32 tensors: the product of two f32 is exact in f64; the sum is rounded to f64 and then to f32 (a double rounding
+    differs from fmaf's single one only at ties of the second)"""
+    return (a.double() * b.double() + c.double()).float()
+
+
+def _chain(a, b):
+    """[N, K] x [M, K] -> [N, M]: every dot product one k-ascending f32 fma chain from zero, each row on its own (a row's result
+    does not depend on the batch it stands in, as on the device)"""
+    acc = torch.zeros((a.shape[0], b.shape[0]), dtype=torch.float32)
+    for k in range(a.shape[1]):
+        acc = _fma(a[:, k:k + 1], b[:, k][None, :], acc)
+    return acc
+
+
+def _butterfly(v, distances):
+    idx = torch.arange(v.shape[-1])
+    for m in distances:
+        v = v + v[..., idx ^ m]
+    return v[..., 0]
+
+
+def tiled_forward32(dec, pts, wrong=None):
+    """the training forward in f32: normalised points, every layer's input, the unnormalised output and its norm"""
+    bb = dec.bounding_box.double()
+    xn = ((pts.detach().cpu().double() - bb[:, 0]) / (bb[:, 1] - bb[:, 0])).float()
+    h = restated(xn, dec.encoding.params.detach().cpu(), dec.layout.grid).float()
+    ws = [w.detach().cpu().float() for w in dec.feature_net.weights()]
+    inputs = []
+    for l, w in enumerate(ws):
+        inputs.append(h)
+        h = _chain(h, w)
+        if l + 1 < len(ws):
+            h = torch.relu(h)
+    blocks = _butterfly((h * h).view(h.shape[0], -1, 32), (16, 8, 4, 2, 1))
+    ss = blocks[:, 0]
+    for b in range(1, min(blocks.shape[1], 4) if wrong == "norm_from_first_four_blocks" else blocks.shape[1]):
+        ss = ss + blocks[:, b]
+    return {"xn": xn, "inputs": inputs, "f": h, "norm": torch.sqrt(ss), "weights": ws}
+
+
+def tiled_backward32(dec, pts, targets=None, dL_dout=None, inv_n=None, wrong=None):
+    """(loss or None, [dW_l], dtable) of the f32 model: tiles of 32 points, G = min(tiles, 64) slabs with tile t added to slab
+    t mod G, the slabs summed in ascending order; per-tile cosine sums in row order, then 256 strided ascending chains, then a
+    binary tree.  A tile's 32-term sums of dW are in the order of the host's batched product; everything whose bits the isolation
+    property needs (each row's own forward, dL/df and dH) is an elementwise chain."""
+    assert wrong is None or wrong in WRONG, wrong
+    fw = tiled_forward32(dec, pts, wrong)
+    f, nrm, ws = fw["f"], fw["norm"], fw["weights"]
+    N, O = f.shape
+    T = -(-N // BWD_TM)
+    G, NP = min(T, BWD_MAX_WG), T * BWD_TM
+    inv_N = torch.tensor(1.0 / N if inv_n is None else inv_n, dtype=torch.float32)
+    eps = torch.tensor(1e-8, dtype=torch.float32)
+    g = (targets if targets is not None else dL_dout).detach().cpu().float()
+    y = f / nrm[:, None]
+
+    def dot8(a, b):      # 8 ascending partial chains of O / 8 columns, combined by an xor butterfly (1, 2, 4)
+        a, b = a.reshape(N, 8, O // 8), b.reshape(N, 8, O // 8)
+        acc = torch.zeros((N, 8), dtype=torch.float32)
+        for k in range(O // 8):
+            acc = _fma(a[:, :, k], b[:, :, k], acc)
+        return _butterfly(acc, (1, 2, 4))
+
+    yg, yy, gg = dot8(y, g), dot8(y, y), dot8(g, g)
+    loss = None
+    if targets is not None:
+        ny, nt = torch.sqrt(yy), torch.sqrt(gg)
+        clamp = wrong != "cos_eps_ignored"
+        cy, ct = (torch.maximum(ny, eps), torch.maximum(nt, eps)) if clamp else (ny, nt)
+        ia = 1.0 / (cy * ct)
+        cosv = yg * ia
+        ca = -inv_N * ia
+        cb = inv_N * (cosv / (cy * ny))
+        if clamp:
+            cb = torch.where(ny > eps, cb, torch.zeros_like(cb))
+        part = torch.zeros((T,), dtype=torch.float32)
+        cos_t = torch.cat([cosv, torch.zeros((NP - N,), dtype=torch.float32)]).view(T, BWD_TM)
+        for r in range(BWD_TM):
+            part = part + cos_t[:, r]
+        chains = torch.zeros((REDUCE_THREADS,), dtype=torch.float32)
+        for r0 in range(0, REDUCE_THREADS if wrong == "loss_first_256_tiles" else T, REDUCE_THREADS):
+            seg = part[r0:r0 + REDUCE_THREADS]
+            chains[:seg.shape[0]] = chains[:seg.shape[0]] + seg
+        m = REDUCE_THREADS // 2
+        while m >= 1:
+            chains[:m] = chains[:m] + chains[m:2 * m]
+            m //= 2
+        loss = 1.0 - chains[0] * inv_N
+    else:
+        ca, cb = torch.ones((N,), dtype=torch.float32), torch.zeros((N,), dtype=torch.float32)
+    s = ca * yg + cb * yy
+    d = ((ca[:, None] * g + cb[:, None] * y) - y * s[:, None]) / nrm[:, None]
+
+    def padded(a):       # the rows past N of the last tile
+        tail = a[:1].expand(NP - N, -1) if wrong == "dead_rows_live" else torch.zeros((NP - N, a.shape[1]), dtype=a.dtype)
+        return torch.cat([a, tail])
+
+    d = padded(d)
+    grads, denc = [None] * len(ws), None
+    for l in range(len(ws) - 1, -1, -1):
+        H = padded(fw["inputs"][l])
+        No, K = ws[l].shape
+        part = torch.bmm(d.view(T, BWD_TM, No).transpose(1, 2), H.view(T, BWD_TM, K))        # [T, No, K]
+        slabs = part[:G].clone()
+        for t0 in range(G, T, G):
+            seg = part[t0:t0 + G]
+            if wrong == "second_round_dropped":
+                continue
+            slabs[:seg.shape[0]] = seg if wrong == "second_round_overwrites" else slabs[:seg.shape[0]] + seg
+        dw = slabs[0]
+        for k in range(1, G):
+            dw = dw + slabs[k]
+        grads[l] = dw
+        dh = _chain(d, ws[l].t().contiguous())                                             # o ascending
+        if l > 0:
+            keep = H >= 0 if wrong == "mask_ge_zero" else H > 0
+            d = torch.where(keep, dh, torch.zeros_like(dh))
+        else:
+            denc = dh[:N]
+    # the scatter: every (level, corner) adds weight * dL/d(encoded) to its table rows (f64 accumulation, rounded once)
+    grid = dec.layout.grid
+    F = grid.n_features_per_level
+    dtable = torch.zeros((grid.n_params,), dtype=torch.float64)
+    for lvl, rows, w in corner_terms(fw["xn"], grid):
+        dtable.index_add_(0, rows.reshape(-1), (w[:, None] * denc[:, lvl * F:(lvl + 1) * F].double()).reshape(-1))
+    return loss, grads, dtable.float()

@@ -83,7 +83,8 @@ def test_layers_within_the_fma_chain_bound(N, trained):
     and the sum at most 255 more, so s = S (1 + d1) with |d1| <= gamma_256 and S the exact sum of squares of the device's f;
     sqrtf and the division are correctly rounded (one u each), hence out = f / sqrt(S) * (1 + d1)^(-1/2) (1 + d2)(1 + d3) and
     |out - f / sqrt(S)| <= (gamma_256 / 2 + 3 u) |f| / sqrt(S): the third u absorbs every second-order term.  The stored norm
-    meets (gamma_256 / 2 + 2 u) sqrt(S).  N = 40000 runs the 64-point tiles, the others the 32-point tiles."""
+    meets (gamma_256 / 2 + 2 u) sqrt(S).  N = 40000 runs the 64-point tiles, the others the 32-point tiles; that the two tile
+    heights give the same bits is tests/test_gpu_decoder_edges.py::test_tile_heights_give_the_same_bits."""
     dec = _decoder(trained=trained)
     pts = R.points_in_bound(N, 100 + N)
     out, rec = _training_forward(dec, pts)
