@@ -1184,7 +1184,8 @@ int splatraster_masked_median(int32_t N, int64_t n, const float* values, int32_t
  *  sample   d^ = coarse / max(|coarse|, 1e-12) over the channels.  For a keypoint (x, y), in float32 without contraction:
  *           gx = ((x - 3.5) / (8 Wc - 4.5)) * 2 - 1, ix = ((gx + 1) / 2) * (Wc - 1), gy and iy likewise with Hc; the bilinear
  *           interpolation of d^ at (ix, iy), neighbours outside the grid reading 0, normalised once more with the same eps.
- *           descriptors [B,256,K], columns at and beyond count[b] zero.
+ *           descriptors [B,256,K], columns at and beyond count[b] zero.  A finite keypoint far outside the image has no neighbour
+ *           inside the grid: a zero column.  Non-finite keypoints give NaN in the restatement and are outside the contract.
  *  dense    the same at every pixel (x, y) of rows [row0, row0 + rows): out [B,rows,W,256], channel-last. */
 
 /* Host only, never touches the device: the tile of outputs one NMS workgroup owns for radii 0..4.  Radii 5..8 use tiles of half

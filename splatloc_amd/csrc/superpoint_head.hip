@@ -452,8 +452,9 @@ sp_normalize_kernel(int cells, int groups, const float* __restrict__ coarse, flo
     for (int k = 0; k < SP_NORM_CELLS && cell0 + k < cells; ++k) dst[(int64_t)k * SP_DESC + tid] = s_d[k][tid] / s_norm[k];
 }
 
-// The four bilinear taps of pixel position (x, y): the north-west cell (clamped to [-2, Wc] x [-2, Hc]: a position far outside the
-// grid, or NaN, has no neighbour inside it) and the weights of nw, ne, sw, se.
+// The four bilinear taps of pixel position (x, y): the north-west cell (clamped to [-2, Wc] x [-2, Hc]: a finite position far
+// outside the grid has no neighbour inside it and gives a zero descriptor) and the weights of nw, ne, sw, se.  The clamp also keeps
+// the reads of a non-finite position in bounds, but its weights are NaN and so is its descriptor: outside the contract.
 struct SpTaps {
     int cx, cy;
     float w[4];
