@@ -1,6 +1,6 @@
 """Float64 restatement of FeatureDecoder for the decoder tests and the fixture generator (no test lives here).
 
-`restated()` is the grid encoding's definition, the same as in tests/test_gpu_grid_encoding.py; `RestatedEncoding` wraps it as a
+`restated()` is the grid encoding's definition, the same as in tests/grid_encoding_reference.py; `RestatedEncoding` wraps it as a
 CPU-or-device module with tinycudann.Encoding's interface (float64 table, initialised exactly as
 splatloc_amd.grid_encoding.Encoding(seed=1337) initialises its own); `RestatedDecoder` is the whole decoder in float64 with the
 reference's state_dict keys, able to report every layer's pre-activation and the worst-case f32 rounding bar that goes with it.

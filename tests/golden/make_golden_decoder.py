@@ -5,7 +5,7 @@
 
 on the office_0 configuration read from the reference's yaml files.  `tinycudann` is stubbed with a CPU module whose `Encoding`
 is the float64 restatement of the grid (tests/decoder_reference.py: the definition of `restated()` in
-tests/test_gpu_grid_encoding.py) on the f32-cast input, its table initialised exactly as splatloc_amd.grid_encoding.Encoding(seed=
+tests/grid_encoding_reference.py) on the f32-cast input, its table initialised exactly as splatloc_amd.grid_encoding.Encoding(seed=
 1337) initialises its own, so the table is not stored.  `.cuda()`, open3d and the dataset modules are stubbed as the other
 generators stub what this machine lacks.  The MLP is moved to float64 after construction (its initial values are nn.Linear's f32
 ones under torch.manual_seed(0)), so every stored result is a float64 one.

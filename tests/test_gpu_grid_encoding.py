@@ -1,5 +1,6 @@
-"""tinycudann.Encoding on the MI355X: forward and both gradients against a float64 torch restatement of the grid encoding that
-lives here (same host level table), the CPU-input path, a FeatureDecoder-shaped training loop and the kernels' codegen."""
+"""tinycudann.Encoding on the MI355X: forward and both gradients against a float64 torch restatement of the grid encoding
+(tests/grid_encoding_reference.py, same host level table), the CPU-input path, a FeatureDecoder-shaped training loop and the
+kernels' codegen."""
 import os
 import re
 import shutil
@@ -11,82 +12,16 @@ import pytest
 import torch
 
 from splatloc_amd import build as B
+from tests.grid_encoding_reference import points as _points, restated
 
 pytestmark = pytest.mark.gpu
 
-M32 = 0xFFFFFFFF
-PRIMES = (1, 2654435761, 805459861)
 OFFICE_0 = [[-3.0, 3.0], [-4.0, 2.5], [-2.0, 2.5]]     # configs/replica_nerf/office_0.yaml: desired resolution 108
 
 
 def splatloc_config(desired=108, otype="HashGrid"):
     return {"otype": otype, "n_levels": 16, "n_features_per_level": 2, "log2_hashmap_size": 19, "base_resolution": 16,
             "per_level_scale": float(np.exp2(np.log2(desired / 16) / 15))}
-
-
-def restated(x, params, lay, want_x_grad=False, G=None):
-    """out [N, L*F] (float64) of the grid encoding, plus the per-element sum of |terms|.  `x` f32 [N, D]; `params` [n_params]
-    (any float dtype, may require grad).  With want_x_grad, `x` must be float64 requiring grad: its value must be f32-exact;
-    the cell and frac come from the f32 arithmetic, frac's derivative is scale.  With G (dL/dout), a third result [N, 1]:
-    sum over levels of scale * sum over corners |<G, corner feature>|, which bounds every term of dL/dx."""
-    D, F = lay.n_input_dims, lay.n_features_per_level
-    x32 = x.detach().float()
-    outs, abss = [], []
-    xbound = torch.zeros((x.shape[0], 1), dtype=torch.float64, device=x.device)
-    for lvl in range(lay.n_levels):
-        scale, res, size, off = lay.scales[lvl], lay.resolutions[lvl], lay.sizes[lvl], lay.offsets[lvl]
-        pos = (x32.double() * scale + 0.5).float()          # fmaf(scale, x, 0.5f): exact in f64, rounded to f32 once
-        fl = torch.floor(pos)
-        cell = fl.to(torch.int64) & M32
-        frac = (pos - fl).double()
-        if want_x_grad:
-            frac = frac + (x - x.detach()) * scale
-        acc = torch.zeros((x.shape[0], F), dtype=torch.float64, device=x.device)
-        sabs = torch.zeros_like(acc)
-        for c in range(1 << D):
-            g = [(cell[:, d] + ((c >> d) & 1)) & M32 for d in range(D)]
-            stride, index = 1, torch.zeros_like(g[0])
-            for d in range(D):
-                if stride <= size:
-                    index = (index + g[d] * stride) & M32
-                    stride = stride * res & M32
-            if lay.grid_type == 0 and size < stride:
-                index = torch.zeros_like(g[0])
-                for d in range(D):
-                    index = index ^ ((g[d] * PRIMES[d]) & M32)
-            index = index % size
-            w = torch.ones_like(frac[:, 0])
-            for d in range(D):
-                w = w * (frac[:, d] if (c >> d) & 1 else 1.0 - frac[:, d])
-            rows = (off + index)[:, None] * F + torch.arange(F, device=x.device)[None, :]
-            v = params.double()[rows]
-            acc = acc + w[:, None] * v
-            sabs = sabs + (w[:, None] * v).abs().detach()
-            if G is not None:
-                xbound += scale * (G[:, lvl * F:(lvl + 1) * F].double() * v.detach()).sum(1, keepdim=True).abs()
-        outs.append(acc)
-        abss.append(sabs)
-    if G is not None:
-        return torch.cat(outs, 1), torch.cat(abss, 1), xbound
-    return torch.cat(outs, 1), torch.cat(abss, 1)
-
-
-def _points(n, seed, lay):
-    """uniform points plus points on cell faces (pos = scale x + 0.5 an integer, up to the f32 rounding of x) of every level,
-    at 0 and 1, and a few outside [0, 1]"""
-    D = lay.n_input_dims
-    g = torch.Generator().manual_seed(seed)
-    x = torch.rand((n, D), generator=g)
-    if n >= 64:
-        k = n // 8
-        lvl = torch.randint(0, lay.n_levels, (k, D), generator=g)
-        scale = torch.tensor(lay.scales, dtype=torch.float64)[lvl]
-        x[:k] = ((torch.floor(x[:k].double() * scale) + 0.5) / scale).float()
-        x[k:2 * k, 0] = 0.0
-        x[2 * k:3 * k, 1] = 1.0
-        x[3 * k:3 * k + 8] = torch.tensor([[-0.25, 0.5, 1.5], [1.0, 1.0, 1.0], [0.0, 0.0, 0.0], [-1.0, 2.0, 0.5],
-                                           [0.5, -0.01, 1.01], [1.25, 0.75, -0.5], [0.0, 1.0, 0.0], [3.0, -2.0, 0.25]])[:, :D]
-    return x
 
 
 def _encoding(cfg, D=3, seed=1337):
