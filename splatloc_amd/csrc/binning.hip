@@ -247,7 +247,7 @@ payload_tile_kernel(int gx, int tiles_per_view, const uint32_t* __restrict__ ran
     const float ox = (float)(tx * TILE), oy = (float)(ty * TILE);
     const int lane = threadIdx.x & (WAVE - 1);
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (WAVE - lane));
+    const uint64_t lt_mask = lanes_below(lane);
     uint32_t running = 0;   // live entries of the earlier steps
 #pragma unroll 1
     for (uint32_t base = beg; base < end; base += 256u) {

@@ -25,6 +25,7 @@
 // Compiled without FP contraction: the nine taps are summed row-major, every product and sum rounding on its own, which
 // tests/image_ops_reference.py restates bit for bit.
 #include "common.h"
+#include "scan.h"
 
 #include <math.h>
 
@@ -121,46 +122,6 @@ img_gradient_kernel(int H, int W, int x0, int y0, int rw, int rh, const float* _
     }
 }
 
-// All 64 lanes of one wave: the digit whose bin holds rank k of the 256 counts (k = (total - 1) / 2 when `median`), the rank left
-// inside that bin and the total.  With k beyond the total (an empty histogram) the digit is 0.
-__device__ __forceinline__ void img_wave_pick(const uint32_t* hist, bool median, uint32_t k, uint32_t* digit, uint32_t* rank,
-                                              uint32_t* total)
-{
-    const int lane = threadIdx.x & 63;
-    uint32_t c[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) c[j] = hist[4 * lane + j];
-    const uint32_t s = (c[0] + c[1]) + (c[2] + c[3]);
-    uint32_t incl = s;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t t = __shfl_up(incl, d);
-        if (lane >= d) incl += t;
-    }
-    const uint32_t tot = __shfl(incl, 63);
-    if (median) k = tot ? (tot - 1) / 2 : 0;
-    const uint32_t excl = incl - s;
-    const bool mine = excl <= k && k < incl;
-    uint32_t dg = 0, kr = 0;
-    if (mine) {
-        uint32_t cum = excl;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (k < cum + c[j]) {
-                dg = 4 * lane + j;
-                kr = k - cum;
-                break;
-            }
-            cum += c[j];
-        }
-    }
-    const unsigned long long owners = __ballot(mine);
-    const int src = owners ? __ffsll((long long)owners) - 1 : 0;
-    *digit = __shfl(dg, src);
-    *rank = __shfl(kr, src);
-    *total = tot;
-}
-
 // The Replica branch: workgroup (c, r, f) owns block (r, c) of frame f.  NCAP > 0: the fused form (halo and intensities in LDS);
 // NCAP == 0: the block's intensities are read from xg, where img_gradient_kernel wrote them.
 template <int THREADS, int NCAP, int HCAP>
@@ -208,36 +169,17 @@ img_block_mask_kernel(int H, int W, int bh, int bw, const float* __restrict__ im
         return xg[frame + (int64_t)(y0 + by) * W + x0 + (i - by * bw)];
     };
 
-    // lower median: element (n - 1) / 2 of the ascending order, by radix select over the bits (every value is >= +0 or NaN)
-    uint32_t prefix = 0, k = (uint32_t)(n - 1) / 2;
-    int any_nan = 0;
-    for (int shift = 24; shift >= 0; shift -= 8) {
-        if (tid < 256) s_hist[tid] = 0;
-        __syncthreads();   // (also: s_x complete, the previous pick read)
-        const uint32_t hi = shift == 24 ? 0u : 0xFFFFFFFFu << (shift + 8);
-        int nan = 0;
-        for (int i = tid; i < n; i += THREADS) {
-            const float v = value(i);
+    // lower median: element (n - 1) / 2 of the ascending order, by radix select over the bits (every value is >= +0 or NaN; s_x is
+    // complete behind the select's first barrier).  The NaN vote is the barrier behind the select's first pass.
+    int nan = 0, any_nan = 0;
+    const uint32_t prefix = radix_select_block<THREADS, false>(
+        (uint32_t)n,
+        [&](uint32_t i) {
+            const float v = value((int)i);
             nan |= v != v;
-            const uint32_t u = __float_as_uint(v);
-            if ((u & hi) == prefix) atomicAdd(&s_hist[(u >> shift) & 255u], 1u);
-        }
-        if (shift == 24)
-            any_nan = __syncthreads_or(nan);
-        else
-            __syncthreads();
-        if (tid < 64) {
-            uint32_t digit, rank, total;
-            img_wave_pick(s_hist, false, k, &digit, &rank, &total);
-            if (tid == 0) {
-                s_sel[0] = prefix | (digit << shift);
-                s_sel[1] = rank;
-            }
-        }
-        __syncthreads();
-        prefix = s_sel[0];
-        k = s_sel[1];
-    }
+            return __float_as_uint(v);
+        },
+        (uint32_t)(n - 1) / 2, s_hist, s_sel, nullptr, [&]() { any_nan = __syncthreads_or(nan); });
     // block[block > t] = 1; block[block <= t] = 0: a 1 written by the first statement is zeroed by the second when t >= 1; both
     // comparisons are false everywhere when t is NaN (a NaN in the block, or inf * 0)
     const float t = any_nan ? __uint_as_float(0x7FC00000u) : __uint_as_float(prefix) * edge_threshold;
@@ -297,14 +239,6 @@ static SelWs sel_layout(void* workspace, int32_t N, int64_t n)
     return w;
 }
 
-__device__ __forceinline__ uint32_t sel_key(float v)
-{
-    const uint32_t u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ float sel_unkey(uint32_t key) { return __uint_as_float((key & 0x80000000u) ? (key ^ 0x80000000u) : ~key); }
-
 __device__ __forceinline__ double sel_wave_sum(double v)
 {
 #pragma unroll
@@ -341,7 +275,7 @@ img_select_hist_kernel(int64_t n, const float* __restrict__ values, int positive
             sum += (double)v;
             sq += (double)v * (double)v;
         }
-        const uint32_t key = sel_key(v);
+        const uint32_t key = float_order_key(v);
         if ((key & hi) == prefix) atomicAdd(&s_hist[(key >> shift) & 255u], 1u);
     }
     __syncthreads();
@@ -379,7 +313,7 @@ img_select_pick_kernel(int pass, int blocks, uint32_t* __restrict__ state_all, c
     const int shift = 24 - 8 * pass;
     uint32_t digit, rank, total;
     const uint32_t prefix_in = pass ? state[0] : 0u, k_in = pass ? state[1] : 0u;
-    img_wave_pick(hist_all + ((int64_t)f * 4 + pass) * 256, pass == 0, k_in, &digit, &rank, &total);
+    radix_pick<false>(hist_all + ((int64_t)f * 4 + pass) * 256, pass == 0, k_in, &digit, &rank, &total);
     const uint32_t prefix = prefix_in | (digit << shift);
     const uint32_t cnt = pass == 0 ? total : state[2];
     __syncthreads();   // every lane has read the state
@@ -392,7 +326,7 @@ img_select_pick_kernel(int pass, int blocks, uint32_t* __restrict__ state_all, c
     const float nanf_ = __uint_as_float(0x7FC00000u);
     const bool none = cnt == 0 || state[3] != 0;
     if (lane == 0) {
-        median[f] = none ? nanf_ : sel_unkey(prefix);
+        median[f] = none ? nanf_ : float_from_order_key(prefix);
         if (count) count[f] = (int64_t)cnt;
     }
     if (std_out) {

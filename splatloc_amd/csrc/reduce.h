@@ -6,7 +6,9 @@
 //   partials: thread t adds partial[b][k] for b = t, t + THREADS, ... in that order, then the block (or wave) sum.
 // NOT for sums that associate differently — a float butterfly in another order rounds differently, and these results are
 // compared bit for bit: pose.hip's L1 loss (descending float butterfly), decoder.hip's 32-lane butterfly32 and
-// grid_encoding.hip's reductions keep their own code, as do the min / max reductions of knn.hip and fusion.hip.
+// grid_encoding.hip's reductions keep their own code, as do the min / max reductions of knn.hip and fusion.hip, and image_ops.hip's
+// sel_wave_sum (a descending __shfl_down sum of doubles: the frame statistics would round differently through the butterfly).
+// The integer scans, ranks and selects, where no order matters, are scan.h.
 #pragma once
 #include "common.h"
 

@@ -4,6 +4,7 @@
 //   pose_errors      utils/eval_utils.py:75-145                  SO3_to_quat, compute_quaternion_dist, eval_pose
 //   pose_invert      test.py:81-82                               camera-to-world from the world-to-camera PnP result
 #include "common.h"
+#include "scan.h"
 
 namespace sr {
 
@@ -31,16 +32,9 @@ __device__ __forceinline__ int acc_row(int reg, int half) { return (reg & 3) + 8
 __device__ __forceinline__ unsigned long long pack_key(float s, uint32_t n)
 {
     s += 0.f;   // -0 -> +0: equal similarities must give equal high words
-    uint32_t u = __float_as_uint(s);
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return ((unsigned long long)u << 32) | (unsigned long long)(0xFFFFFFFFu - n);
+    return ((unsigned long long)float_order_key(s) << 32) | (unsigned long long)(0xFFFFFFFFu - n);
 }
-__device__ __forceinline__ float key_sim(unsigned long long key)
-{
-    uint32_t u = (uint32_t)(key >> 32);
-    u = (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u;
-    return __uint_as_float(u);
-}
+__device__ __forceinline__ float key_sim(unsigned long long key) { return float_from_order_key((uint32_t)(key >> 32)); }
 __device__ __forceinline__ int64_t key_index(unsigned long long key) { return (int64_t)(0xFFFFFFFFu - (uint32_t)key); }
 
 // A wave's running list: entry j (descending) in l0 of lane j (j < 64) or l1 of lane j - 64; entries from k on stay 0.

@@ -12,6 +12,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "scan.h"
 
 namespace sr {
 
@@ -30,16 +31,6 @@ constexpr int SORT_ITEMS = SR_SORT_ITEMS;
 constexpr int SORT_TILE = SORT_THREADS * SORT_ITEMS;  // 4096
 constexpr int SORT_WAVES = SORT_THREADS / WAVE;
 constexpr int RADIX = 256;
-
-__device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v, int lane)
-{
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) {
-        const uint32_t t = __shfl_up(v, d, WAVE);
-        if (lane >= d) v += t;
-    }
-    return v;
-}
 
 // ---------------------------------------------------------------------------------------
 // scan
@@ -80,31 +71,18 @@ scan_reduce_kernel(int64_t n, const uint32_t* __restrict__ in, const uint32_t* _
 __global__ void __launch_bounds__(1024)
 scan_partials_kernel(int64_t nb, uint64_t* __restrict__ partial, uint64_t* __restrict__ total)
 {
-    __shared__ uint64_t wsum[16];
-    __shared__ uint64_t carry_s;
-    const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
-    if (threadIdx.x == 0) carry_s = 0;
-    __syncthreads();
+    __shared__ uint64_t wsum[1024 / WAVE];
+    uint64_t carry = 0;
     for (int64_t start = 0; start < nb; start += 1024) {
         const int64_t i = start + threadIdx.x;
         const uint64_t v = i < nb ? partial[i] : 0;
-        uint64_t s = v;
-#pragma unroll
-        for (int d = 1; d < WAVE; d <<= 1) {
-            const uint64_t t = __shfl_up(s, d, WAVE);
-            if (lane >= d) s += t;
-        }
-        if (lane == WAVE - 1) wsum[w] = s;
-        __syncthreads();
-        uint64_t woff = 0;
-        for (int k = 0; k < w; ++k) woff += wsum[k];
-        const uint64_t carry = carry_s;
-        if (i < nb) partial[i] = carry + woff + s - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry_s = carry + woff + s;
-        __syncthreads();
+        uint64_t step;
+        const uint64_t excl = block_exclusive_scan<1024>(v, wsum, &step);
+        if (i < nb) partial[i] = carry + excl;
+        carry += step;
+        __syncthreads();   // (the next step overwrites the wave sums)
     }
-    if (threadIdx.x == 0 && total) *total = carry_s;
+    if (threadIdx.x == 0 && total) *total = carry;
 }
 
 template <bool EXCLUSIVE>
@@ -113,7 +91,6 @@ scan_apply_kernel(int64_t n, const uint32_t* in, const uint32_t* __restrict__ pe
                   const uint64_t* __restrict__ partial, uint32_t* out)  // in may alias out
 {
     __shared__ uint32_t wsum[SCAN_THREADS / WAVE];
-    const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
     // blocked arrangement: thread t owns items [t*ITEMS, (t+1)*ITEMS)
     const int64_t base = (int64_t)blockIdx.x * SCAN_TILE + (int64_t)threadIdx.x * SCAN_ITEMS;
     uint32_t v[SCAN_ITEMS];
@@ -124,12 +101,7 @@ scan_apply_kernel(int64_t n, const uint32_t* in, const uint32_t* __restrict__ pe
         v[k] = i < n ? (perm ? perm_value(in, perm[i]) : in[i]) : 0u;
         s += v[k];
     }
-    const uint32_t incl = wave_inclusive_scan(s, lane);
-    if (lane == WAVE - 1) wsum[w] = incl;
-    __syncthreads();
-    uint32_t woff = 0;
-    for (int k = 0; k < w; ++k) woff += wsum[k];
-    uint32_t run = (uint32_t)partial[blockIdx.x] + woff + incl - s;
+    uint32_t run = (uint32_t)partial[blockIdx.x] + block_exclusive_scan<SCAN_THREADS>(s, wsum);
 #pragma unroll
     for (int k = 0; k < SCAN_ITEMS; ++k) {
         const int64_t i = base + k;
@@ -248,15 +220,8 @@ scan_onepass_kernel(int64_t n, const uint32_t* in, const uint32_t* __restrict__ 
         v[k] = i < n ? (perm ? perm_value(in, perm[i]) : in[i]) : 0u;
         s += v[k];
     }
-    const uint32_t incl = wave_inclusive_scan(s, lane);
-    if (lane == WAVE - 1) wsum[w] = incl;
-    __syncthreads();
-    uint32_t woff = 0, btotal = 0;
-#pragma unroll
-    for (int k = 0; k < SCAN_THREADS / WAVE; ++k) {
-        if (k < w) woff += wsum[k];
-        btotal += wsum[k];
-    }
+    uint32_t btotal;
+    const uint32_t excl_in_tile = block_exclusive_scan<SCAN_THREADS>(s, wsum, &btotal);
     if (w == 0) {
         uint64_t* mine = st->status + bid;
         uint64_t excl = 0;
@@ -298,7 +263,7 @@ scan_onepass_kernel(int64_t n, const uint32_t* in, const uint32_t* __restrict__ 
         }
     }
     __syncthreads();
-    uint32_t run = (uint32_t)s_excl + woff + incl - s;
+    uint32_t run = (uint32_t)s_excl + excl_in_tile;
 #pragma unroll
     for (int k = 0; k < SCAN_ITEMS; ++k) {
         const int64_t i = base + k;
@@ -414,6 +379,59 @@ sort_hist_kernel(int64_t n, const KIn* __restrict__ keys, int shift, uint32_t nb
     table[(size_t)threadIdx.x * nblocks + blockIdx.x] = hist[threadIdx.x];
 }
 
+// ---- the three steps that both scatter kernels share; a wave owns the ITEMS * WAVE keys from wbase on, lane l those at k * WAVE + l ----
+template <int ITEMS, typename KIn>
+__device__ __forceinline__ void sort_load(int64_t n, int64_t wbase, const KIn* __restrict__ keys_in, const uint32_t* __restrict__ vals_in,
+                                          uint32_t (&key)[ITEMS], uint32_t (&val)[ITEMS])
+{
+    const int lane = threadIdx.x & (WAVE - 1);
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k) {
+        const int64_t i = wbase + (int64_t)k * WAVE + lane;
+        const bool valid = i < n;
+        key[k] = valid ? (uint32_t)keys_in[i] : 0u;
+        val[k] = valid ? vals_in[i] : 0u;
+    }
+}
+
+// rank[k]: the keys of this wave with key k's digit that come before it; hist (this wave's 256 zeroed counters) ends as the counts
+template <int ITEMS>
+__device__ __forceinline__ void sort_rank(int64_t n, int64_t wbase, int shift, const uint32_t (&key)[ITEMS], uint32_t* hist,
+                                          uint32_t (&rank)[ITEMS])
+{
+    const int lane = threadIdx.x & (WAVE - 1);
+    const uint64_t lt_mask = lanes_below(lane);
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k) {
+        const int64_t i = wbase + (int64_t)k * WAVE + lane;
+        const bool valid = i < n;
+        const uint32_t digit = (key[k] >> shift) & (RADIX - 1);
+        uint64_t mask = __ballot(valid);
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            const bool bit = (digit >> b) & 1u;
+            const uint64_t bal = __ballot(bit);
+            mask &= bit ? bal : ~bal;
+        }
+        uint32_t prev = 0;
+        if (valid) prev = hist[digit];
+        rank[k] = prev + (uint32_t)__popcll(mask & lt_mask);
+        // lowest lane of each equal-digit group publishes the new count
+        if (valid && (mask & lt_mask) == 0) hist[digit] = prev + (uint32_t)__popcll(mask);
+    }
+}
+
+// thread d: the per-wave counts of digit d become the bases of (wave k, digit d), from `run` on
+__device__ __forceinline__ void sort_bases(uint32_t (&wave_hist)[SORT_WAVES][RADIX], int d, uint32_t run)
+{
+#pragma unroll
+    for (int k = 0; k < SORT_WAVES; ++k) {
+        const uint32_t c = wave_hist[k][d];
+        wave_hist[k][d] = run;
+        run += c;
+    }
+}
+
 template <typename KIn, typename KOut>
 __global__ void __launch_bounds__(SORT_THREADS)
 sort_scatter_kernel(int64_t n, const KIn* __restrict__ keys_in, const uint32_t* __restrict__ vals_in,
@@ -429,32 +447,8 @@ sort_scatter_kernel(int64_t n, const KIn* __restrict__ keys_in, const uint32_t* 
 
     const int64_t wbase = (int64_t)blockIdx.x * SORT_TILE + (int64_t)w * (SORT_ITEMS * WAVE);
     uint32_t key[SORT_ITEMS], val[SORT_ITEMS], rank[SORT_ITEMS];
-    const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (WAVE - lane));
-#pragma unroll
-    for (int k = 0; k < SORT_ITEMS; ++k) {
-        const int64_t i = wbase + (int64_t)k * WAVE + lane;
-        const bool valid = i < n;
-        key[k] = valid ? (uint32_t)keys_in[i] : 0u;
-        val[k] = valid ? vals_in[i] : 0u;
-    }
-#pragma unroll
-    for (int k = 0; k < SORT_ITEMS; ++k) {
-        const int64_t i = wbase + (int64_t)k * WAVE + lane;
-        const bool valid = i < n;
-        const uint32_t digit = (key[k] >> shift) & (RADIX - 1);
-        uint64_t mask = __ballot(valid);
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            const bool bit = (digit >> b) & 1u;
-            const uint64_t bal = __ballot(bit);
-            mask &= bit ? bal : ~bal;
-        }
-        uint32_t prev = 0;
-        if (valid) prev = wave_hist[w][digit];
-        rank[k] = prev + (uint32_t)__popcll(mask & lt_mask);
-        // lowest lane of each equal-digit group publishes the new count
-        if (valid && (mask & lt_mask) == 0) wave_hist[w][digit] = prev + (uint32_t)__popcll(mask);
-    }
+    sort_load(n, wbase, keys_in, vals_in, key, val);
+    sort_rank(n, wbase, shift, key, wave_hist[w], rank);
     __syncthreads();
     // Block-local reorder through LDS before the global scatter: elements of one digit become
     // consecutive, so consecutive threads write consecutive addresses (runs of ~16 elements at
@@ -469,26 +463,9 @@ sort_scatter_kernel(int64_t n, const KIn* __restrict__ keys_in, const uint32_t* 
 #pragma unroll
         for (int k = 0; k < SORT_WAVES; ++k) total += wave_hist[k][d];
         // exclusive prefix of `total` over the 256 digits
-        uint32_t incl = total;
-#pragma unroll
-        for (int o = 1; o < WAVE; o <<= 1) {
-            const uint32_t up = (uint32_t)__shfl_up((int)incl, o, WAVE);
-            if (lane >= o) incl += up;
-        }
-        if (lane == WAVE - 1) s_wsum[w] = incl;
-        __syncthreads();
-        uint32_t wbase_d = 0;
-#pragma unroll
-        for (int k = 0; k < SORT_WAVES; ++k) wbase_d += (k < w) ? s_wsum[k] : 0u;
-        const uint32_t excl = wbase_d + incl - total;
+        const uint32_t excl = block_exclusive_scan<SORT_THREADS>(total, s_wsum);
         s_gbase[d] = table[(size_t)d * nblocks + blockIdx.x] - excl;
-        uint32_t run = excl;
-#pragma unroll
-        for (int k = 0; k < SORT_WAVES; ++k) {
-            const uint32_t c = wave_hist[k][d];
-            wave_hist[k][d] = run;  // becomes the block-local base of (wave k, digit d)
-            run += c;
-        }
+        sort_bases(wave_hist, d, excl);   // block-local bases
     }
     __syncthreads();
 #pragma unroll
@@ -586,31 +563,8 @@ sort_sweep_kernel(int64_t n, const uint32_t* __restrict__ keys_in, const uint32_
 
     const int64_t wbase = (int64_t)bid * (SORT_THREADS * ITEMS) + (int64_t)w * (ITEMS * WAVE);
     uint32_t key[ITEMS], val[ITEMS], rank[ITEMS];
-    const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (WAVE - lane));
-#pragma unroll
-    for (int k = 0; k < ITEMS; ++k) {
-        const int64_t i = wbase + (int64_t)k * WAVE + lane;
-        const bool valid = i < n;
-        key[k] = valid ? keys_in[i] : 0u;
-        val[k] = valid ? vals_in[i] : 0u;
-    }
-#pragma unroll
-    for (int k = 0; k < ITEMS; ++k) {
-        const int64_t i = wbase + (int64_t)k * WAVE + lane;
-        const bool valid = i < n;
-        const uint32_t digit = (key[k] >> shift) & (RADIX - 1);
-        uint64_t mask = __ballot(valid);
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            const bool bit = (digit >> b) & 1u;
-            const uint64_t bal = __ballot(bit);
-            mask &= bit ? bal : ~bal;
-        }
-        uint32_t prev = 0;
-        if (valid) prev = wave_hist[w][digit];
-        rank[k] = prev + (uint32_t)__popcll(mask & lt_mask);
-        if (valid && (mask & lt_mask) == 0) wave_hist[w][digit] = prev + (uint32_t)__popcll(mask);
-    }
+    sort_load(n, wbase, keys_in, vals_in, key, val);
+    sort_rank(n, wbase, shift, key, wave_hist[w], rank);
     __syncthreads();
     {
         const int d = threadIdx.x;
@@ -660,18 +614,7 @@ sort_sweep_kernel(int64_t n, const uint32_t* __restrict__ keys_in, const uint32_
         }
         // exclusive scan of the digit totals across the 256 threads -> global base of digit d
         const uint32_t tot = st->totals[pass][d];
-        const uint32_t incl = wave_inclusive_scan(tot, lane);
-        if (lane == WAVE - 1) s_scan[w] = incl;
-        __syncthreads();
-        uint32_t woff = 0;
-        for (int k = 0; k < w; ++k) woff += s_scan[k];
-        uint32_t run = woff + incl - tot + excl;
-#pragma unroll
-        for (int k = 0; k < SORT_WAVES; ++k) {
-            const uint32_t c = wave_hist[k][d];
-            wave_hist[k][d] = run;  // becomes the global base of (wave k, digit d)
-            run += c;
-        }
+        sort_bases(wave_hist, d, block_exclusive_scan<SORT_THREADS>(tot, s_scan) + excl);   // global bases
     }
     __syncthreads();
 #pragma unroll

@@ -17,9 +17,9 @@
 //  * selection: sp_compact_kernel (a counting and a writing instantiation) and sp_offsets_kernel leave every image's
 //    candidates as (score bits, pixel) in row-major order (2048 pixels per workgroup, eight consecutive pixels per lane, a workgroup scan; one workgroup per image
 //    scans the chunk counts and writes n and min(n, K)).  sp_pick_kernel, one workgroup per image: n <= K copies the list out;
-//    otherwise four 8-bit digit passes over the list (LDS histogram, one wave picks the digit from the top) find the K-th largest
-//    score's bits T and how many of the scores equal to T are still needed, and a second walk keeps, in row-major order, every
-//    score above T and that many of the equal ones.  sp_rank_kernel then gives each of the K survivors its place by counting:
+//    otherwise four 8-bit digit passes over the list (scan.h's radix_select_block: LDS histogram, one wave picks the digit from the
+//    top) find the K-th largest score's bits T and its rank among the scores equal to T, and a second walk keeps, in row-major
+//    order, every score above T and the equal ones up to that rank.  sp_rank_kernel then gives each of the K survivors its place by counting:
 //    the survivors with a larger score plus the equal ones in front of it.  That is the stable descending sort, K^2 comparisons
 //    out of LDS (16 M at K = 4096), one launch for the whole batch, and it needs no segmented sort.  Candidates are positive
 //    floats, so their bits order as unsigned integers.
@@ -31,6 +31,7 @@
 //    1 KB per pixel with non-temporal stores.
 // Compiled without FP contraction: floor(ix) of a keypoint must agree with the CPU restatement (tests/superpoint_reference.py).
 #include "common.h"
+#include "scan.h"
 
 #include <math.h>
 
@@ -190,45 +191,13 @@ __device__ __forceinline__ bool sp_candidate(const SpSel& s, int64_t p, float v)
     return v > s.threshold && row >= s.border && row < s.H - s.border && col >= s.border && col < s.W - s.border;
 }
 
-// exclusive scan of one word per lane over the workgroup; s_wave: THREADS / 64 + 1 words.  Ends with a barrier: s_wave is free again.
-template <int THREADS>
-__device__ __forceinline__ uint32_t sp_block_scan(uint32_t v, uint32_t* s_wave, uint32_t* total)
-{
-    constexpr int NW = THREADS / 64;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t t = __shfl_up(incl, d);
-        if (lane >= d) incl += t;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    if (wave == 0) {
-        const uint32_t w = lane < NW ? s_wave[lane] : 0u;
-        uint32_t wi = w;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t t = __shfl_up(wi, d);
-            if (lane >= d) wi += t;
-        }
-        if (lane < NW) s_wave[lane] = wi - w;
-        if (lane == NW - 1) s_wave[NW] = wi;
-    }
-    __syncthreads();
-    const uint32_t res = s_wave[wave] + incl - v;
-    *total = s_wave[NW];
-    __syncthreads();
-    return res;
-}
-
 // workgroup g: chunk g % chunks of image g / chunks; lane t owns pixels [8 t, 8 t + 8) of the chunk
 template <bool WRITE>
 __global__ void __launch_bounds__(SP_SEL_THREADS)
 sp_compact_kernel(SpSel s, const float* __restrict__ nms, uint32_t* __restrict__ counts, uint32_t* __restrict__ ckey,
                   uint32_t* __restrict__ cidx)
 {
-    __shared__ uint32_t s_wave[SP_SEL_THREADS / 64 + 1];
+    __shared__ uint32_t s_wave[SP_SEL_THREADS / 64];
     const int b = blockIdx.x / s.chunks, chunk = blockIdx.x - b * s.chunks;
     const int64_t p0 = (int64_t)chunk * SP_SEL_CHUNK + (int64_t)threadIdx.x * SP_SEL_ITEMS;
     const float* src = nms + (int64_t)b * s.pixels;
@@ -241,7 +210,7 @@ sp_compact_kernel(SpSel s, const float* __restrict__ nms, uint32_t* __restrict__
         if (p < s.pixels && sp_candidate(s, p, v[e])) flags |= 1u << e;
     }
     uint32_t total;
-    const uint32_t at = sp_block_scan<SP_SEL_THREADS>((uint32_t)__popc(flags), s_wave, &total);
+    const uint32_t at = block_exclusive_scan<SP_SEL_THREADS>((uint32_t)__popc(flags), s_wave, &total);
     if (!WRITE) {
         if (threadIdx.x == 0) counts[blockIdx.x] = total;
         return;
@@ -260,16 +229,17 @@ sp_compact_kernel(SpSel s, const float* __restrict__ nms, uint32_t* __restrict__
 __global__ void __launch_bounds__(SP_PICK_THREADS)
 sp_offsets_kernel(int chunks, int K, uint32_t* __restrict__ counts, int32_t* __restrict__ count, int32_t* __restrict__ candidates)
 {
-    __shared__ uint32_t s_wave[SP_PICK_THREADS / 64 + 1];
+    __shared__ uint32_t s_wave[SP_PICK_THREADS / 64];
     uint32_t* c = counts + (int64_t)blockIdx.x * chunks;
     uint32_t run = 0;
     for (int i0 = 0; i0 < chunks; i0 += SP_PICK_THREADS) {
         const int i = i0 + threadIdx.x;
         const uint32_t v = i < chunks ? c[i] : 0u;
         uint32_t total;
-        const uint32_t at = sp_block_scan<SP_PICK_THREADS>(v, s_wave, &total);
+        const uint32_t at = block_exclusive_scan<SP_PICK_THREADS>(v, s_wave, &total);
         if (i < chunks) c[i] = run + at;
         run += total;
+        __syncthreads();   // (the next step overwrites the wave sums)
     }
     if (threadIdx.x == 0) {
         candidates[blockIdx.x] = (int32_t)run;   // n <= H W < 2^31
@@ -285,40 +255,27 @@ __device__ __forceinline__ void sp_write_keypoint(int W, uint32_t key, uint32_t 
     *score = __uint_as_float(key);
 }
 
-// All 64 lanes of one wave: the digit whose bin holds the k-th (1-based) of the 256 counts walked from digit 255 down, and the
-// rank left inside that bin.  k never exceeds the total here.
-__device__ __forceinline__ void sp_wave_pick_desc(const uint32_t* hist, uint32_t k, uint32_t* digit, uint32_t* rank)
+// The scan of sp_pick_kernel's walk, its own form (scan.h says why): exclusive scan of one word per lane over the workgroup, wave 0
+// scanning the wave sums; s_wave: THREADS / 64 + 1 words.  Ends with a barrier: s_wave is free again.
+template <int THREADS>
+__device__ __forceinline__ uint32_t sp_walk_scan(uint32_t v, uint32_t* s_wave, uint32_t* total)
 {
-    const int lane = threadIdx.x & 63;
-    uint32_t c[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) c[j] = hist[255 - (4 * lane + j)];
-    const uint32_t s = (c[0] + c[1]) + (c[2] + c[3]);
-    uint32_t incl = s;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t t = __shfl_up(incl, d);
-        if (lane >= d) incl += t;
+    constexpr int NW = THREADS / 64;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t incl = wave_inclusive_scan(v);
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    if (wave == 0) {
+        const uint32_t w = lane < NW ? s_wave[lane] : 0u;
+        const uint32_t wi = wave_inclusive_scan(w);
+        if (lane < NW) s_wave[lane] = wi - w;
+        if (lane == NW - 1) s_wave[NW] = wi;
     }
-    const uint32_t excl = incl - s;
-    const bool mine = excl < k && k <= incl;
-    uint32_t dg = 0, kr = 1;
-    if (mine) {
-        uint32_t cum = excl;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (k <= cum + c[j]) {
-                dg = 255 - (4 * lane + j);
-                kr = k - cum;
-                break;
-            }
-            cum += c[j];
-        }
-    }
-    const unsigned long long owners = __ballot(mine);
-    const int src = owners ? __ffsll((long long)owners) - 1 : 0;
-    *digit = __shfl(dg, src);
-    *rank = __shfl(kr, src);
+    __syncthreads();
+    const uint32_t res = s_wave[wave] + incl - v;
+    *total = s_wave[NW];
+    __syncthreads();
+    return res;
 }
 
 // one workgroup per image.  n <= K: the row-major list goes out, the rows behind it are zeroed.  n > K: the K survivors go to
@@ -348,29 +305,10 @@ sp_pick_kernel(SpSel s, const int32_t* __restrict__ candidates, const uint32_t* 
         }
         return;
     }
-    uint32_t prefix = 0, k = K;
-    for (int shift = 24; shift >= 0; shift -= 8) {
-        if (tid < 256) s_hist[tid] = 0;
-        __syncthreads();
-        const uint32_t hi = shift == 24 ? 0u : 0xFFFFFFFFu << (shift + 8);
-        for (uint32_t i = tid; i < n; i += SP_PICK_THREADS) {
-            const uint32_t u = key[i];
-            if ((u & hi) == prefix) atomicAdd(&s_hist[(u >> shift) & 255u], 1u);
-        }
-        __syncthreads();
-        if (tid < 64) {
-            uint32_t digit, rank;
-            sp_wave_pick_desc(s_hist, k, &digit, &rank);
-            if (tid == 0) {
-                s_sel[0] = prefix | (digit << shift);
-                s_sel[1] = rank;
-            }
-        }
-        __syncthreads();
-        prefix = s_sel[0];
-        k = s_sel[1];
-    }
-    // every score above `prefix`, and the first k of the equal ones
+    // the K-th largest score (the scores are positive floats: their bits order like they do), and its rank among its equals
+    uint32_t rank;
+    const uint32_t prefix = radix_select_block<SP_PICK_THREADS, true>(n, [&](uint32_t i) { return key[i]; }, K - 1, s_hist, s_sel, &rank);
+    // every score above `prefix`, and the equal ones up to that rank
     uint32_t* okey = selkey + (int64_t)b * K;
     uint32_t* oidx = selidx + (int64_t)b * K;
     uint32_t eq_run = 0, sel_run = 0;
@@ -379,9 +317,9 @@ sp_pick_kernel(SpSel s, const int32_t* __restrict__ candidates, const uint32_t* 
         const uint32_t u = i < n ? key[i] : 0u;
         const bool eq = i < n && u == prefix;
         uint32_t eq_total, sel_total;
-        const uint32_t eq_at = eq_run + sp_block_scan<SP_PICK_THREADS>(eq ? 1u : 0u, s_wave, &eq_total);
-        const bool sel = i < n && (u > prefix || (eq && eq_at < k));
-        const uint32_t at = sel_run + sp_block_scan<SP_PICK_THREADS>(sel ? 1u : 0u, s_wave, &sel_total);
+        const uint32_t eq_at = eq_run + sp_walk_scan<SP_PICK_THREADS>(eq ? 1u : 0u, s_wave, &eq_total);
+        const bool sel = i < n && (u > prefix || (eq && eq_at <= rank));
+        const uint32_t at = sel_run + sp_walk_scan<SP_PICK_THREADS>(sel ? 1u : 0u, s_wave, &sel_total);
         if (sel && at < K) {
             okey[at] = u;
             oidx[at] = idx[i];

@@ -2,6 +2,7 @@
 // radix front end; binsort.hip: the last block of the big-list launch runs it, one launch less per frame of the binned front end).
 #pragma once
 #include "common.h"
+#include "scan.h"
 
 namespace sr {
 
@@ -24,20 +25,7 @@ __device__ __forceinline__ void tile_order_block(int T, LenAt len_at, uint32_t* 
     }
     __syncthreads();
     // exclusive scan of the 1024 bucket counts (one per thread)
-    const uint32_t c = s_cnt[t];
-    uint32_t incl = c;
-    const int lane = t & (WAVE - 1), w = t / WAVE;
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) {
-        const uint32_t o = (uint32_t)__shfl_up((int)incl, d, WAVE);
-        if (lane >= d) incl += o;
-    }
-    if (lane == WAVE - 1) s_wsum[w] = incl;
-    __syncthreads();
-    uint32_t before = 0;
-    for (int k = 0; k < w; ++k) before += s_wsum[k];
-    __syncthreads();
-    s_cnt[t] = before + incl - c;
+    s_cnt[t] = block_exclusive_scan<ORDER_THREADS>(s_cnt[t], s_wsum);
     __syncthreads();
     for (int i = t; i < T; i += ORDER_THREADS) {
         const uint32_t len = len_at(i);

@@ -130,3 +130,21 @@ def test_loss_stage_kernels_keep_their_occupancy_and_lds():
         assert k["Occupancy"] >= waves and k["LDS Size"] <= lds, (name, k)
     assert _kernel(losses, "_ZN2sr17refine_fwd_kernelE")["VGPRs"] <= 115
     assert len(losses) == 6 and not [k for k in pose if "l1_rgbd_loss_kernel" in k], (list(losses), list(pose))
+
+
+def test_scan_and_sort_kernels_keep_their_registers_and_lds():
+    """The scan, radix-sort and tile-order kernels since they take their wave scan, workgroup scan and digit ranks from scan.h and
+    one rank body (HISTORY.md §29): nothing in scratch, no spill, and no kernel above the VGPRs or the LDS footprint, or below the
+    waves per SIMD, that it has with the shared forms.  While each carried its own copy the compiler reported (VGPRs / waves)
+    44 / 8 and 36 / 8 for the one-pass scans, 92 / 5 and 124 / 4 for the sweeps and 16 / 8 for the tile order, the rest as below:
+    the pins are the lower figures, so what the shared workgroup scan gained (a wave per SIMD in sort_sweep_kernel<8>) is held too."""
+    sort, binning = _usage("scan_sort.hip"), _usage("binning.hip")
+    pins = ((sort, "_ZN2sr19scan_onepass_kernelILb0EE", 42, 8, 32), (sort, "_ZN2sr19scan_onepass_kernelILb1EE", 34, 8, 32),
+            (sort, "_ZN2sr20sort_hist_all_kernelILi8EE", 11, 8, 4096), (sort, "_ZN2sr20sort_hist_all_kernelILi16EE", 11, 8, 4096),
+            (sort, "_ZN2sr17sort_sweep_kernelILi8EE", 74, 6, 4116), (sort, "_ZN2sr17sort_sweep_kernelILi16EE", 122, 4, 4116),
+            (sort, "_ZN2sr19sort_scatter_kernelIjjEE", 108, 4, 37904), (sort, "_ZN2sr19sort_scatter_kernelIttEE", 108, 4, 29712),
+            (sort, "_ZN2sr19sort_scatter_kernelItjEE", 108, 4, 29712), (binning, "_ZN2sr17tile_order_kernelE", 12, 8, 4160))
+    for u, name, vgprs, waves, lds in pins:
+        k = _kernel(u, name)
+        assert k["ScratchSize"] == 0 and k["VGPRs Spill"] == 0 and k["SGPRs Spill"] == 0, (name, k)
+        assert k["VGPRs"] <= vgprs and k["Occupancy"] >= waves and k["LDS Size"] <= lds, (name, k)
