@@ -569,10 +569,15 @@ size_t bin_table_entries(int32_t P, int32_t V, int tiles)
     return (size_t)(V > 0 ? V : 1) * (size_t)tiles * (size_t)bin_chunks(P, V, tiles);
 }
 
-size_t bin_scratch_bytes(int32_t P, int32_t V, int tiles)
+BinScratch bin_scratch_layout(void* base, int32_t P, int32_t V, int tiles)
 {
-    const size_t entries = bin_table_entries(P, V, tiles);
-    return align_up(entries * sizeof(uint32_t), 256) + scan_tmp_bytes((int64_t)entries);
+    BinScratch b;
+    Carver c{base};
+    b.entries = (int64_t)bin_table_entries(P, V, tiles);
+    b.table = c.take<uint32_t>((size_t)b.entries);
+    b.scan_tmp = c.take<char>(scan_tmp_bytes(b.entries));
+    b.bytes = c.o;
+    return b;
 }
 
 // geometry stage: per-(tile, chunk) counts and their exclusive scan (the state words of the scan at scan_tmp must be zero:

@@ -119,140 +119,97 @@ static inline int tile_bits(int tiles)
 struct TileGrid { int gx, gy; };
 static inline TileGrid tile_grid(int32_t W, int32_t H) { return TileGrid{(W + TILE - 1) / TILE, (H + TILE - 1) / TILE}; }
 
+// Both walks below note the offsets splatraster_get_*_layout publishes (and the two the binned front end's room check needs) on
+// their way past: `c.o` in front of a take is where that section starts.
 struct GeomLayout {
-    size_t rec0, rec1, tiles_touched, depth_order, offsets, rgb, clamped, sort_keys, keys_alt, vals_alt,
-        sort_tmp, scan_tmp, total, block_tiles, span_owner, bytes;
+    GeomView v;
+    uint32_t *keys_alt, *vals_alt;   // the depth sort's ping-pong twins
+    void* scan_tmp;
+    size_t rec0, tiles_touched, depth_order, offsets, rgb, clamped, sort_keys, total, bytes;
 };
 // n = V * P rows (V views of a window; V = 1 for the plain call)
-static GeomLayout geom_layout(int32_t P, int32_t V)
+static GeomLayout geom_layout(void* base, int32_t P, int32_t V)
 {
-    const size_t p1 = (size_t)(P > 0 ? P : 1);
-    const size_t n = p1 * (size_t)(V > 0 ? V : 1);
+    const size_t p1 = (size_t)(P > 0 ? P : 1), nv = (size_t)(V > 0 ? V : 1);
+    const size_t n = p1 * nv;
     GeomLayout L;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 256); return at; };
-    L.rec0 = take(32 * n);
-    L.rec1 = L.rec0 + 16;
-    L.tiles_touched = take(4 * n);
-    L.depth_order = take(4 * n);
-    L.offsets = take(4 * n);
-    L.rgb = take(12 * p1);       // SH colours: single-view calls only
-    L.clamped = take(3 * p1);
-    L.sort_keys = take(4 * n);
-    L.keys_alt = take(4 * n);
-    L.vals_alt = take(4 * n);
-    L.sort_tmp = take(sort_tmp_bytes((int64_t)n));
-    L.scan_tmp = take(scan_tmp_bytes((int64_t)n));
-    L.total = take(16);
-    L.block_tiles = take(4 * (size_t)preprocess_blocks((int32_t)p1) * (size_t)(V > 0 ? V : 1));
-    L.span_owner = take(4 * (size_t)SPAN_OWNER_CAP);
-    L.bytes = o;
+    Carver c{base};
+    L.rec0 = c.o;           L.v.rec = c.take<float4>(2 * n);
+    L.tiles_touched = c.o;  L.v.tiles_touched = c.take<uint32_t>(n);
+    L.depth_order = c.o;    L.v.depth_order = c.take<uint32_t>(n);
+    L.offsets = c.o;        L.v.offsets = c.take<uint32_t>(n);
+    L.rgb = c.o;            L.v.rgb = c.take<float>(3 * p1);       // SH colours: single-view calls only
+    L.clamped = c.o;        L.v.clamped = c.take<uint8_t>(3 * p1);
+    L.sort_keys = c.o;      L.v.sort_keys = c.take<uint32_t>(n);
+    L.keys_alt = c.take<uint32_t>(n);
+    L.vals_alt = c.take<uint32_t>(n);
+    L.v.sort_tmp = reinterpret_cast<uint32_t*>(c.take<char>(sort_tmp_bytes((int64_t)n)));
+    L.scan_tmp = c.take<char>(scan_tmp_bytes((int64_t)n));
+    L.total = c.o;          L.v.total = c.take<uint32_t>(4);
+    L.v.block_tiles = c.take<uint32_t>((size_t)preprocess_blocks((int32_t)p1) * nv);
+    L.v.span_owner = c.take<uint32_t>((size_t)SPAN_OWNER_CAP);
+    L.bytes = c.o;
     return L;
 }
+GeomView geom_view(void* base, int32_t P, int32_t V) { return geom_layout(base, P, V).v; }
 
-GeomView geom_view(void* base, int32_t P, int32_t V)
+struct BinLayout { BinView v; size_t point_list, tile_list, ranges, bytes; };
+static BinLayout bin_layout(void* base, int32_t P, int32_t V, int64_t R, int32_t W, int32_t H, int32_t C)
 {
-    const GeomLayout L = geom_layout(P, V);
-    char* b = reinterpret_cast<char*>(base);
-    GeomView g;
-    g.rec = reinterpret_cast<float4*>(b + L.rec0);
-    g.tiles_touched = reinterpret_cast<uint32_t*>(b + L.tiles_touched);
-    g.depth_order = reinterpret_cast<uint32_t*>(b + L.depth_order);
-    g.offsets = reinterpret_cast<uint32_t*>(b + L.offsets);
-    g.rgb = reinterpret_cast<float*>(b + L.rgb);
-    g.clamped = reinterpret_cast<uint8_t*>(b + L.clamped);
-    g.sort_keys = reinterpret_cast<uint32_t*>(b + L.sort_keys);
-    g.sort_tmp = reinterpret_cast<uint32_t*>(b + L.sort_tmp);
-    g.total = reinterpret_cast<uint32_t*>(b + L.total);
-    g.block_tiles = reinterpret_cast<uint32_t*>(b + L.block_tiles);
-    g.span_owner = reinterpret_cast<uint32_t*>(b + L.span_owner);
-    return g;
-}
-
-struct BinLayout {
-    size_t keysA, valsA, keysB, valsB, ranges, sort_tmp, irec, ipack, featp, gacc, pose_acc, ckpt, tile_order, nparts, bytes;
-};
-static BinLayout bin_layout(int32_t P, int32_t V, int64_t R, int32_t W, int32_t H, int32_t C)
-{
-    const size_t n = (size_t)(R > 0 ? R : 1);
-    const size_t nv = (size_t)(V > 0 ? V : 1);
+    const size_t n = (size_t)(R > 0 ? R : 1), p1 = (size_t)(P > 0 ? P : 1), nv = (size_t)(V > 0 ? V : 1);
     const TileGrid tg = tile_grid(W, H);
-    const size_t tiles = (size_t)tg.gx * (size_t)tg.gy * nv;
+    const size_t tiles = (size_t)tg.gx * (size_t)tg.gy * nv, tiles1 = tiles > 0 ? tiles : 1;
     BinLayout L;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 256); return at; };
-    L.valsA = take(4 * n);
-    L.keysA = take(4 * n);
-    L.keysB = take(4 * n);
-    L.valsB = take(4 * n);
-    L.ranges = take(8 * (tiles > 0 ? tiles : 1));
-    L.sort_tmp = take(sort_tmp_bytes((int64_t)n));
-    L.irec = take(32 * n);
-    L.ipack = take(4 * n);
+    Carver c{base};
+    L.point_list = c.o;  L.v.point_list = c.take<uint32_t>(n);
+    L.tile_list = c.o;   L.v.tile_list = c.take<uint32_t>(n);
+    L.v.keys_tmp = c.take<uint32_t>(n);
+    L.v.vals_tmp = c.take<uint32_t>(n);
+    L.ranges = c.o;      L.v.ranges = c.take<uint32_t>(2 * tiles1);
+    L.v.sort_tmp = c.take<char>(sort_tmp_bytes((int64_t)n));
+    L.v.irec = c.take<float4>(2 * n);
+    L.v.ipack = c.take<uint32_t>(n);
     // padded feature table only when the rows are not already 16-byte aligned (shared by the views)
-    L.featp = take((C % 4) ? (size_t)(P > 0 ? P : 1) * padded_channels(C) * sizeof(float) : 16);
+    L.v.featp = c.take<float>((C % 4) ? p1 * padded_channels(C) : 4);
     // (the shared colour rows and the per-(view, Gaussian) rows are ONE section: GaccLayout, common.h)
-    L.gacc = take(gacc_total_floats(C, (size_t)(P > 0 ? P : 1), nv) * sizeof(float));
-    L.pose_acc = take(POSE_ACC_BYTES);      // (directly behind gacc: the backward zeroes both with one fill)
+    L.v.gacc = c.take<float>(gacc_total_floats(C, p1, nv));
+    L.v.pose_acc = c.take<float>(POSE_ACC_FLOATS);      // (directly behind gacc: the backward zeroes both with one fill)
     // (the deterministic debug mode's 64-bit accumulator is NOT part of this buffer: it is a stream-ordered
     //  allocation made by the backward only while that mode is on)
     // mid-list checkpoints of the forward for split launches (small frames, narrow layouts): the maximum is reserved
     // whenever the shape qualifies, whatever the run-time knob says
     const bool ck = C <= 4 && 4 * (size_t)tiles <= (size_t)SPLIT_MAX_WAVES;
-    L.ckpt = take(ck ? nv * (size_t)SPLIT_PARTS_MAX * (size_t)(C + 2) * (size_t)W * (size_t)H * sizeof(float) : 16);
-    L.tile_order = take(4 * (tiles > 0 ? tiles : 1));
-    L.nparts = take(4 * (tiles > 0 ? tiles : 1));
-    L.bytes = o;
+    L.v.ckpt = c.take<float>(ck ? nv * (size_t)SPLIT_PARTS_MAX * (size_t)(C + 2) * (size_t)W * (size_t)H : 4);
+    L.v.tile_order = c.take<uint32_t>(tiles1);
+    L.v.nparts = c.take<uint32_t>(tiles1);
+    L.bytes = c.o;
     return L;
 }
-
 BinView bin_view(void* base, int32_t P, int32_t V, int64_t R, int32_t W, int32_t H, int32_t C)
 {
-    const BinLayout L = bin_layout(P, V, R, W, H, C);
-    char* b = reinterpret_cast<char*>(base);
-    BinView v;
-    v.point_list = reinterpret_cast<uint32_t*>(b + L.valsA);
-    v.tile_list = reinterpret_cast<uint32_t*>(b + L.keysA);
-    v.keys_tmp = reinterpret_cast<uint32_t*>(b + L.keysB);
-    v.vals_tmp = reinterpret_cast<uint32_t*>(b + L.valsB);
-    v.ranges = reinterpret_cast<uint32_t*>(b + L.ranges);
-    v.sort_tmp = b + L.sort_tmp;
-    v.irec = reinterpret_cast<float4*>(b + L.irec);
-    v.ipack = reinterpret_cast<uint32_t*>(b + L.ipack);
-    v.featp = reinterpret_cast<float*>(b + L.featp);
-    v.gacc = reinterpret_cast<float*>(b + L.gacc);
-    v.pose_acc = reinterpret_cast<float*>(b + L.pose_acc);
-    v.ckpt = reinterpret_cast<float*>(b + L.ckpt);
-    v.tile_order = reinterpret_cast<uint32_t*>(b + L.tile_order);
-    v.nparts = reinterpret_cast<uint32_t*>(b + L.nparts);
-    return v;
-}
-
-static size_t img_plane_bytes(int32_t W, int32_t H, int32_t V)
-{
-    return align_up((size_t)W * H * 4 * (size_t)(V > 0 ? V : 1), 256);
+    return bin_layout(base, P, V, R, W, H, C).v;
 }
 
 // final_T, n_contrib (where they always were), then what the compact payload adds: the plane n_contrib_c and the table cranges.
 // (The table belongs to the instance stream, but the binning buffer's size is pinned section by section
 //  — tests/test_accumulator_layout_sizes.py — while this buffer travels with it from the forward to the backward anyway.)
-static size_t img_cranges_bytes(int32_t W, int32_t H, int32_t V)
+struct ImgLayout { ImgView v; size_t n_contrib, bytes; };   // n_contrib: the offset splatraster_get_*_image_layout publishes
+static ImgLayout img_layout(void* base, int32_t W, int32_t H, int32_t V)
 {
+    const size_t nv = (size_t)(V > 0 ? V : 1);
+    const size_t plane = (size_t)W * H * nv;
     const TileGrid tg = tile_grid(W, H);
-    return align_up(8 * (size_t)tg.gx * (size_t)tg.gy * (size_t)(V > 0 ? V : 1), 256);
+    ImgLayout L;
+    Carver c{base};
+    L.v.final_T = c.take<float>(plane);
+    L.n_contrib = c.o;
+    L.v.n_contrib = c.take<uint32_t>(plane);
+    L.v.n_contrib_c = c.take<uint32_t>(plane);
+    L.v.cranges = c.take<uint32_t>(2 * (size_t)tg.gx * (size_t)tg.gy * nv);
+    L.bytes = c.o;
+    return L;
 }
-static size_t img_bytes(int32_t W, int32_t H, int32_t V) { return 3 * img_plane_bytes(W, H, V) + img_cranges_bytes(W, H, V); }
-
-ImgView img_view(void* base, int32_t W, int32_t H, int32_t V)
-{
-    char* b = reinterpret_cast<char*>(base);
-    ImgView v;
-    v.final_T = reinterpret_cast<float*>(b);
-    v.n_contrib = reinterpret_cast<uint32_t*>(b + img_plane_bytes(W, H, V));
-    v.n_contrib_c = reinterpret_cast<uint32_t*>(b + 2 * img_plane_bytes(W, H, V));
-    v.cranges = reinterpret_cast<uint32_t*>(b + 3 * img_plane_bytes(W, H, V));
-    return v;
-}
+ImgView img_view(void* base, int32_t W, int32_t H, int32_t V) { return img_layout(base, W, H, V).v; }
 
 // The compositing kernels index feature / accumulator rows with 24-bit x 24-bit multiplies (one
 // full-rate instruction instead of a 64-bit multiply-add pair per address): Gaussian ids must fit 24
@@ -298,22 +255,22 @@ const char* splatraster_error_string(int status)
 
 const char* splatraster_last_hip_error(void) { return g_last_error.c_str(); }
 
-size_t splatraster_geometry_bytes(int32_t P) { return geom_layout(P, 1).bytes; }
+size_t splatraster_geometry_bytes(int32_t P) { return geom_layout(nullptr, P, 1).bytes; }
 size_t splatraster_binning_bytes(int32_t P, int64_t R, int32_t width, int32_t height, int32_t channels)
 {
-    return bin_layout(P, 1, R, width, height, channels).bytes;
+    return bin_layout(nullptr, P, 1, R, width, height, channels).bytes;
 }
-size_t splatraster_image_bytes(int32_t width, int32_t height) { return img_bytes(width, height, 1); }
+size_t splatraster_image_bytes(int32_t width, int32_t height) { return img_layout(nullptr, width, height, 1).bytes; }
 
-size_t splatraster_window_geometry_bytes(int32_t P, int32_t n_views) { return geom_layout(P, n_views).bytes; }
+size_t splatraster_window_geometry_bytes(int32_t P, int32_t n_views) { return geom_layout(nullptr, P, n_views).bytes; }
 size_t splatraster_window_binning_bytes(int32_t P, int32_t n_views, int64_t R_total, int32_t width, int32_t height,
                                         int32_t channels)
 {
-    return bin_layout(P, n_views, R_total, width, height, channels).bytes;
+    return bin_layout(nullptr, P, n_views, R_total, width, height, channels).bytes;
 }
 size_t splatraster_window_image_bytes(int32_t width, int32_t height, int32_t n_views)
 {
-    return img_bytes(width, height, n_views);
+    return img_layout(nullptr, width, height, n_views).bytes;
 }
 
 int splatraster_get_geometry_layout(int32_t P, splatraster_geometry_layout* out)
@@ -323,8 +280,8 @@ int splatraster_get_geometry_layout(int32_t P, splatraster_geometry_layout* out)
 int splatraster_get_window_geometry_layout(int32_t P, int32_t n_views, splatraster_geometry_layout* out)
 {
     if (!out || n_views < 1 || n_views > MAX_VIEWS) return SPLATRASTER_ERR_BAD_ARG;
-    const GeomLayout L = geom_layout(P, n_views);
-    out->rec0 = L.rec0; out->rec1 = L.rec1; out->tiles_touched = L.tiles_touched;
+    const GeomLayout L = geom_layout(nullptr, P, n_views);
+    out->rec0 = L.rec0; out->rec1 = L.rec0 + 16; out->tiles_touched = L.tiles_touched;
     out->depth_order = L.depth_order; out->offsets = L.offsets; out->rgb = L.rgb;
     out->clamped = L.clamped; out->total = L.bytes;
     return SPLATRASTER_OK;
@@ -338,8 +295,8 @@ int splatraster_get_window_binning_layout(int32_t P, int32_t n_views, int64_t R_
                                           int32_t channels, splatraster_binning_layout* out)
 {
     if (!out || n_views < 1 || n_views > MAX_VIEWS) return SPLATRASTER_ERR_BAD_ARG;
-    const BinLayout L = bin_layout(P, n_views, R_total, width, height, channels);
-    out->point_list = L.valsA; out->tile_list = L.keysA; out->ranges = L.ranges; out->total = L.bytes;
+    const BinLayout L = bin_layout(nullptr, P, n_views, R_total, width, height, channels);
+    out->point_list = L.point_list; out->tile_list = L.tile_list; out->ranges = L.ranges; out->total = L.bytes;
     return SPLATRASTER_OK;
 }
 int splatraster_get_image_layout(int32_t width, int32_t height, splatraster_image_layout* out)
@@ -349,9 +306,8 @@ int splatraster_get_image_layout(int32_t width, int32_t height, splatraster_imag
 int splatraster_get_window_image_layout(int32_t width, int32_t height, int32_t n_views, splatraster_image_layout* out)
 {
     if (!out || n_views < 1 || n_views > MAX_VIEWS) return SPLATRASTER_ERR_BAD_ARG;
-    out->final_T = 0;
-    out->n_contrib = img_plane_bytes(width, height, n_views);
-    out->total = img_bytes(width, height, n_views);
+    const ImgLayout L = img_layout(nullptr, width, height, n_views);
+    out->final_T = 0; out->n_contrib = L.n_contrib; out->total = L.bytes;
     return SPLATRASTER_OK;
 }
 
@@ -381,9 +337,8 @@ static WinCams make_cams(int32_t V, const splatraster_window_view* views)
     return c;
 }
 
-// The binned front end (binsort.hip) keeps its (tile, chunk) table and the state of its scan where the radix front end
-// keeps the depth-sort buffers (sort_keys ... scan_tmp): the geometry buffer's size does not depend on the path.
-struct BinScratch { uint32_t* table; void* scan_tmp; int64_t entries; };
+// The binned front end (binsort.hip) keeps its (tile, chunk) table and the state of its scan (BinScratch, common.h) where the
+// radix front end keeps the depth-sort buffers (sort_keys ... scan_tmp): the geometry buffer's size does not depend on the path.
 
 // What a stage WROTE at a buffer: the next stage is a separate public call and must follow that, not re-derive it from the
 // process-wide debug switches as they stand by then (a switch flipped between two calls would otherwise make the render read a
@@ -423,9 +378,9 @@ static FramePlan frame_plan(int32_t W, int32_t H, int C, int32_t P, int32_t V, i
     const bool rendered = binning && written_find(binning, &w);   // (then no forward follows: no team)
     if (!rendered && !(geometry && written_find(geometry, &w))) {
         // binned front end (binsort.hip): where the shape allows and its table fits the depth-sort scratch of the geometry buffer
-        const GeomLayout L = geom_layout(P, V);
+        const GeomLayout L = geom_layout(nullptr, P, V);
         w.binned = g_bin_mode != 0 && P > 0 && p.tiles > 0 && p.tiles <= BIN_MAX_TILES && p.gx <= 255 && p.gy <= 255 &&
-                   bin_table_entries(P, V, p.tiles) < ((size_t)1 << 31) && bin_scratch_bytes(P, V, p.tiles) <= L.total - L.sort_keys &&
+                   bin_table_entries(P, V, p.tiles) < ((size_t)1 << 31) && bin_scratch_layout(nullptr, P, V, p.tiles).bytes <= L.total - L.sort_keys &&
                    (g_bin_mode == 1 || p.gtiles <= BIN_AUTO_MAX_TILES);
     }
     p.binned = w.binned;
@@ -455,14 +410,8 @@ static CompositeViews composite_views(const FramePlan& p, BinView b, ImgView im,
 
 static BinScratch bin_scratch(const FramePlan& p, void* geometry)
 {
-    BinScratch b{};
-    if (!p.binned) return b;
-    const GeomLayout L = geom_layout(p.P, p.V);
-    char* base = reinterpret_cast<char*>(geometry);
-    b.entries = (int64_t)bin_table_entries(p.P, p.V, p.tiles);
-    b.table = reinterpret_cast<uint32_t*>(base + L.sort_keys);
-    b.scan_tmp = base + L.sort_keys + align_up((size_t)b.entries * sizeof(uint32_t), 256);
-    return b;
+    if (!p.binned) return BinScratch{};
+    return bin_scratch_layout(geom_view(geometry, p.P, p.V).sort_keys, p.P, p.V, p.tiles);
 }
 
 // Stage 1 of the forward over a window of V views (V = 1: the plain call): one preprocess, ONE depth sort of the
@@ -503,9 +452,8 @@ static int window_geometry(const splatraster_settings* s, int32_t V, const splat
     st = lookback_error_init();
     if (st) return st;
     const int32_t n = P * V;
-    const GeomLayout L = geom_layout(P, V);
-    GeomView g = geom_view(geometry, P, V);
-    char* base = reinterpret_cast<char*>(geometry);
+    const GeomLayout L = geom_layout(geometry, P, V);
+    GeomView g = L.v;
     const WinCams cams = make_cams(V, views);
     const FramePlan plan = frame_plan(s->image_width, s->image_height, s->channels, P, V, 0, nullptr, nullptr);
     if (bounded && !plan.binned) return SPLATRASTER_ERR_UNSUPPORTED;   // (nothing launched yet)
@@ -535,7 +483,7 @@ static int window_geometry(const splatraster_settings* s, int32_t V, const splat
         else
             st = launch_preprocess(*s, P, V, cams, means3D, shs, opacities, scales, rotations, cov3D_precomp, g,
                                    g.sort_tmp, (uint32_t)(sort_zero_bytes(n, 32) / 4),
-                                   reinterpret_cast<uint32_t*>(base + L.scan_tmp), (uint32_t)(scan_state_bytes(n) / 4), stream, true, raw);
+                                   reinterpret_cast<uint32_t*>(L.scan_tmp), (uint32_t)(scan_state_bytes(n) / 4), stream, true, raw);
     }
     if (st) return st;
     if (!bounded) {
@@ -551,15 +499,13 @@ static int window_geometry(const splatraster_settings* s, int32_t V, const splat
     {
         StageTimer t(SPLATRASTER_STAGE_DEPTH_SORT, stream);
         bool in_alt = false;
-        uint32_t* keys_alt = reinterpret_cast<uint32_t*>(base + L.keys_alt);
-        uint32_t* vals_alt = reinterpret_cast<uint32_t*>(base + L.vals_alt);
-        st = sort_pairs_u32(n, g.sort_keys, g.depth_order, keys_alt, vals_alt, 32, g.sort_tmp, stream, &in_alt, true);
+        st = sort_pairs_u32(n, g.sort_keys, g.depth_order, L.keys_alt, L.vals_alt, 32, g.sort_tmp, stream, &in_alt, true);
         if (st) return st;
         if (in_alt) return SPLATRASTER_ERR_UNSUPPORTED;  // 4 passes: never
     }
     {
         StageTimer t(SPLATRASTER_STAGE_SCAN, stream);
-        st = inclusive_scan_u32(n, g.tiles_touched, g.depth_order, g.offsets, g.total, base + L.scan_tmp, stream, true,
+        st = inclusive_scan_u32(n, g.tiles_touched, g.depth_order, g.offsets, g.total, L.scan_tmp, stream, true,
                                 g.span_owner, (uint32_t)EMIT_SPAN, SPAN_OWNER_CAP);
     }
     if (st) return st;
@@ -1155,13 +1101,21 @@ int splatraster_debug_poison_lds(uint32_t pattern, void* stream)
     return launch_poison_lds(pattern, reinterpret_cast<hipStream_t>(stream));
 }
 
-size_t splatraster_sort_tmp_bytes(int64_t n)
+// keys / vals sorted in place: the alternate arrays are the first two sections of tmp, the sort's own scratch the third
+struct SortInPlace { uint32_t *keys_alt, *vals_alt; void* tmp; size_t bytes; };
+static SortInPlace sort_in_place_layout(void* base, int64_t n)
 {
     const size_t m = (size_t)(n > 0 ? n : 1);
-    return align_up(4 * m, 256) * 2 + sort_tmp_bytes(n);
+    SortInPlace L;
+    Carver c{base};
+    L.keys_alt = c.take<uint32_t>(m);
+    L.vals_alt = c.take<uint32_t>(m);
+    L.tmp = c.take<char>(sort_tmp_bytes(n));
+    L.bytes = c.o;
+    return L;
 }
+size_t splatraster_sort_tmp_bytes(int64_t n) { return sort_in_place_layout(nullptr, n).bytes; }
 
-// keys / vals sorted in place: the alternate arrays are the first two sections of tmp, the sort's own scratch the third
 static int sort_in_place(bool keys16, int64_t n, uint32_t* keys, uint32_t* vals, int32_t key_bits, void* tmp, void* stream_)
 {
     if (!keys || !vals || !tmp) return SPLATRASTER_ERR_BAD_ARG;
@@ -1170,13 +1124,11 @@ static int sort_in_place(bool keys16, int64_t n, uint32_t* keys, uint32_t* vals,
         if (st0) return st0;
     }
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    char* t = reinterpret_cast<char*>(tmp);
-    const size_t stride = align_up(4 * (size_t)n, 256);
-    uint32_t* ka = reinterpret_cast<uint32_t*>(t);
-    uint32_t* va = reinterpret_cast<uint32_t*>(t + stride);
+    const SortInPlace L = sort_in_place_layout(tmp, n);
+    uint32_t *ka = L.keys_alt, *va = L.vals_alt;
     bool in_alt = false;
-    int st = keys16 ? sort_pairs_k16(n, keys, vals, ka, va, key_bits, t + 2 * stride, stream, &in_alt)
-                    : sort_pairs_u32(n, keys, vals, ka, va, key_bits, t + 2 * stride, stream, &in_alt);
+    int st = keys16 ? sort_pairs_k16(n, keys, vals, ka, va, key_bits, L.tmp, stream, &in_alt)
+                    : sort_pairs_u32(n, keys, vals, ka, va, key_bits, L.tmp, stream, &in_alt);
     if (st) return st;
     if (in_alt) {
         SR_HIP_CHECK(hipMemcpyAsync(keys, ka, 4 * (size_t)n, hipMemcpyDeviceToDevice, stream));

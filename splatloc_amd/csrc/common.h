@@ -50,6 +50,22 @@ int launch_poison_lds(uint32_t pattern, hipStream_t stream);
     } while (0)
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+static inline bool misaligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }   // a: a power of two
+
+// ---- workspace carver -----------------------------------------------------------------------
+// Every caller-owned workspace is a row of 256-byte-aligned sections, padded after each one.  A stage's x_layout(base, shape...)
+// walks its buffer ONCE with this struct; the stage's *_bytes() query is the same walk with a null base (every pointer null,
+// `o` the size), so a size and the pointers it has to cover cannot drift apart.
+struct Carver {
+    void* base;        // null: sizes only
+    size_t o = 0;      // end of the sections taken so far: the bytes the walk needs
+    size_t off(size_t bytes) { const size_t at = o; o += align_up(bytes, 256); return at; }   // offset of the next section
+    template <class T> T* take(size_t count)                                                 // typed pointer to the next section
+    {
+        const size_t at = off(count * sizeof(T));
+        return base ? reinterpret_cast<T*>(static_cast<char*>(base) + at) : nullptr;
+    }
+};
 
 // ---- a window of views ------------------------------------------------------------------
 // SplatLoc.map renders `window_size` views of ONE Gaussian scene before a single backward
@@ -284,7 +300,10 @@ constexpr int BIN_SORT_BIG = 16384, BIN_BIG_BLOCKS = 128; // the launch for long
 constexpr int BIN_BIG_MINE = 1024;          // long lists one block of that launch can be handed (list k is block k % BIN_BIG_BLOCKS's)
 static_assert((size_t)BIN_MAX_TILES * MAX_VIEWS <= (size_t)BIN_BIG_MINE * BIN_BIG_BLOCKS, "every (view, tile) list could be a long one");
 size_t bin_table_entries(int32_t P, int32_t V, int tiles);
-size_t bin_scratch_bytes(int32_t P, int32_t V, int tiles);
+// the front end's (tile, chunk) table and the state of its scan: [table | scan_tmp], carved where the radix front end keeps the
+// depth-sort buffers of the geometry buffer (capi.hip); base null: `bytes` only
+struct BinScratch { uint32_t* table; void* scan_tmp; int64_t entries; size_t bytes; };
+BinScratch bin_scratch_layout(void* base, int32_t P, int32_t V, int tiles);
 int launch_bin_count(const FramePlan& p, const GeomView& g, uint32_t* table, void* scan_tmp, hipStream_t stream);
 // Bounded mode (splatraster_forward_window_bounded): the render stage runs into a binning buffer laid out for `capacity`
 // instances while R stays on the device.  The status block (splatraster_bounded_status: 16 words) exists twice: a device-resident

@@ -564,27 +564,26 @@ static int dec_bwd_groups(int64_t N) { const int t = dec_bwd_tiles(N); return t 
 static bool dec_n_ok(int64_t N) { return N >= 0 && N <= (int64_t(1) << 30); }
 
 struct DecWorkspace {
-    size_t slabs, loss_part, denc, total;   // byte offsets
+    float *slabs, *loss_part, *denc;
+    size_t total;
 };
-static DecWorkspace dec_workspace(const DecArgs& d, int64_t N)
+static DecWorkspace dec_workspace(void* base, const DecArgs& d, int64_t N)
 {
     DecWorkspace w;
-    size_t off = 0;
-    w.slabs = off;      off += align_up((size_t)dec_bwd_groups(N) * d.woff[d.n_layers] * sizeof(float), 256);
-    w.loss_part = off;  off += align_up((size_t)dec_bwd_tiles(N) * sizeof(float), 256);
-    w.denc = off;       off += align_up((size_t)N * d.dims[0] * sizeof(float), 256);
-    w.total = off;
+    Carver c{base};
+    w.slabs = c.take<float>((size_t)dec_bwd_groups(N) * d.woff[d.n_layers]);
+    w.loss_part = c.take<float>((size_t)dec_bwd_tiles(N));
+    w.denc = c.take<float>((size_t)N * d.dims[0]);
+    w.total = c.o;
     return w;
 }
-
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 static int dec_weights(const DecArgs& d, const float* const* weights, DecWeights* W)
 {
     if (!weights) return SPLATRASTER_ERR_BAD_ARG;
     for (int l = 0; l < DEC_MAX_LAYERS; ++l) {
         W->w[l] = l < d.n_layers ? weights[l] : nullptr;
-        if (l < d.n_layers && (!W->w[l] || !aligned16(W->w[l]))) return SPLATRASTER_ERR_BAD_ARG;
+        if (l < d.n_layers && (!W->w[l] || misaligned(W->w[l], 16))) return SPLATRASTER_ERR_BAD_ARG;
     }
     return SPLATRASTER_OK;
 }
@@ -633,7 +632,7 @@ int splatraster_decoder_workspace_bytes(const splatraster_decoder_layout* lay, i
     const int st = dec_args(lay, &a, &d);
     if (st) return st;
     if (!dec_n_ok(N)) return SPLATRASTER_ERR_BAD_ARG;
-    if (workspace_bytes) *workspace_bytes = dec_workspace(d, N).total;
+    if (workspace_bytes) *workspace_bytes = dec_workspace(nullptr, d, N).total;
     if (activation_bytes) *activation_bytes = (size_t)dec_acts_floats(d, N, lay->grid.n_dims) * sizeof(float);
     return SPLATRASTER_OK;
 }
@@ -651,7 +650,7 @@ int splatraster_decoder_forward(const splatraster_decoder_layout* lay, int64_t N
     if (st) return st;
     if (!dec_n_ok(N)) return SPLATRASTER_ERR_BAD_ARG;
     if (N == 0) return SPLATRASTER_OK;
-    if (!x || !table || !out || !aligned16(table) || !aligned16(out) || !aligned16(acts) ||
+    if (!x || !table || !out || misaligned(table, 16) || misaligned(out, 16) || misaligned(acts, 16) ||
         (reinterpret_cast<uintptr_t>(x) & (x_is_f64 ? 7u : 3u)))
         return SPLATRASTER_ERR_BAD_ARG;
     d.x_f64 = x_is_f64 != 0;
@@ -678,14 +677,11 @@ int splatraster_decoder_backward(const splatraster_decoder_layout* lay, int64_t 
     if ((dL_dout == nullptr) == (targets == nullptr)) return SPLATRASTER_ERR_BAD_ARG;   // exactly one of the two
     if (loss && !targets) return SPLATRASTER_ERR_BAD_ARG;
     if (N == 0) return SPLATRASTER_ERR_BAD_ARG;            // an empty batch has no mean; the caller returns zero gradients
-    if (!acts || !dL_dweights || !workspace || !aligned16(acts) || !aligned16(dL_dout) || !aligned16(targets) ||
-        !aligned16(dL_dweights) || !aligned16(dL_dtable) || !aligned16(workspace) || (dL_dx && (!table || !aligned16(table))))
+    if (!acts || !dL_dweights || !workspace || misaligned(acts, 16) || misaligned(dL_dout, 16) || misaligned(targets, 16) ||
+        misaligned(dL_dweights, 16) || misaligned(dL_dtable, 16) || misaligned(workspace, 16) || (dL_dx && (!table || misaligned(table, 16))))
         return SPLATRASTER_ERR_BAD_ARG;
-    const DecWorkspace w = dec_workspace(d, N);
-    char* base = static_cast<char*>(workspace);
-    float* slabs = reinterpret_cast<float*>(base + w.slabs);
-    float* loss_part = reinterpret_cast<float*>(base + w.loss_part);
-    float* denc = reinterpret_cast<float*>(base + w.denc);
+    const DecWorkspace w = dec_workspace(workspace, d, N);
+    float *slabs = w.slabs, *loss_part = w.loss_part, *denc = w.denc;
     const int tiles = dec_bwd_tiles(N), G = dec_bwd_groups(N);
     const float inv_N = 1.0f / (float)N;
     DecBwdArgs bd{};
@@ -719,8 +715,8 @@ int splatraster_decoder_adam(const splatraster_decoder_layout* lay, float* const
     st = dec_weights(d, weights, &W);
     if (st) return st;
     if (step < 1 || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return SPLATRASTER_ERR_BAD_ARG;
-    if (!w_grad || !w_m || !w_v || !table || !t_grad || !t_m || !t_v || !aligned16(table) || !aligned16(t_grad) || !aligned16(t_m) ||
-        !aligned16(t_v))
+    if (!w_grad || !w_m || !w_v || !table || !t_grad || !t_m || !t_v || misaligned(table, 16) || misaligned(t_grad, 16) || misaligned(t_m, 16) ||
+        misaligned(t_v, 16))
         return SPLATRASTER_ERR_BAD_ARG;
     DecAdam A{};
     for (int l = 0; l < d.n_layers; ++l) A.w[l] = weights[l];

@@ -175,22 +175,17 @@ densify_gather_kernel(int P, const uint32_t* __restrict__ flags, const uint32_t*
     }
 }
 
-size_t densify_workspace_bytes(int32_t P)
-{
-    const size_t n = 4 * (size_t)(P > 0 ? P : 1);
-    return align_up(4 * n, 256) * 2 + align_up(scan_tmp_bytes((int64_t)n), 256) + 256;
-}
-
-struct DensifyWs { uint32_t* flags; uint32_t* incl; void* scan_tmp; uint32_t* total; };
+struct DensifyWs { uint32_t* flags; uint32_t* incl; void* scan_tmp; uint32_t* total; size_t bytes; };
 static DensifyWs densify_ws(void* base, int32_t P)
 {
     const size_t n = 4 * (size_t)(P > 0 ? P : 1);
-    char* b = reinterpret_cast<char*>(base);
     DensifyWs w;
-    w.flags = reinterpret_cast<uint32_t*>(b);
-    w.incl = reinterpret_cast<uint32_t*>(b + align_up(4 * n, 256));
-    w.scan_tmp = b + 2 * align_up(4 * n, 256);
-    w.total = reinterpret_cast<uint32_t*>(b + 2 * align_up(4 * n, 256) + align_up(scan_tmp_bytes((int64_t)n), 256));
+    Carver c{base};
+    w.flags = c.take<uint32_t>(n);
+    w.incl = c.take<uint32_t>(n);
+    w.scan_tmp = c.take<char>(scan_tmp_bytes((int64_t)n));
+    w.total = c.take<uint32_t>(1);
+    w.bytes = c.o;
     return w;
 }
 
@@ -417,7 +412,7 @@ int adam_step(int n, const splatraster_adam_group* groups, double beta1, double 
         T.param[used] = g.param; T.grad[used] = g.grad; T.m[used] = g.exp_avg; T.v[used] = g.exp_avg_sq;
         T.gate[used] = g.row_gate; T.end[used] = total; T.row_width[used] = g.row_width;
         Q.qend[used] = total_quads; Q.numel[used] = g.numel;
-        aligned = aligned && (((uintptr_t)g.param | (uintptr_t)g.grad | (uintptr_t)g.exp_avg | (uintptr_t)g.exp_avg_sq) & 15u) == 0;
+        aligned = aligned && !misaligned(g.param, 16) && !misaligned(g.grad, 16) && !misaligned(g.exp_avg, 16) && !misaligned(g.exp_avg_sq, 16);
         const double bc1 = 1.0 - pow(beta1, g.step), bc2 = 1.0 - pow(beta2, g.step);
         T.step_size[used] = (float)((double)g.lr / bc1);
         T.inv_bc2_sqrt[used] = (float)(1.0 / sqrt(bc2));
@@ -515,7 +510,7 @@ using namespace sr;
 
 extern "C" {
 
-size_t splatraster_densify_workspace_bytes(int32_t P) { return densify_workspace_bytes(P); }
+size_t splatraster_densify_workspace_bytes(int32_t P) { return densify_ws(nullptr, P).bytes; }
 
 static int check_model(const splatraster_model* m, int need_all)
 {

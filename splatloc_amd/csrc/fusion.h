@@ -22,31 +22,32 @@ static inline bool bad_volume(const splatraster_fusion_volume* v, bool need_feat
     if ((int64_t)v->dim[0] * v->dim[1] > FUS_MAX_VOXELS || (int64_t)v->dim[0] * v->dim[1] * v->dim[2] > FUS_MAX_VOXELS) return true;
     if (v->feat_dim < 4 || v->feat_dim > FUS_MAX_FEAT || v->feat_dim % 4) return true;
     if (!v->tsdf || !v->weight || !v->color) return true;
-    if (need_feat && (!v->feat || (reinterpret_cast<uintptr_t>(v->feat) & 15))) return true;
+    if (need_feat && (!v->feat || misaligned(v->feat, 16))) return true;
     return false;
 }
 
 // ---- surface workspace --------------------------------------------------------------------------------------------------
+// [level, total | counts N | min/max partials | scan state]; level and total share the first section, at +0 and +128
 struct FusWs {
     float* level;
     uint64_t* total;
     uint32_t* counts;
     float* partial;
     void* scan_tmp;
+    size_t bytes;
 };
 
 static inline FusWs fus_layout(void* workspace, int64_t N)
 {
-    char* p = reinterpret_cast<char*>(workspace);
     FusWs w;
-    w.level = reinterpret_cast<float*>(p);
-    w.total = reinterpret_cast<uint64_t*>(p + 128);
-    p += 256;
-    w.counts = reinterpret_cast<uint32_t*>(p);
-    p += align_up((size_t)N * sizeof(uint32_t), 256);
-    w.partial = reinterpret_cast<float*>(p);
-    p += align_up(2 * FUS_MINMAX_BLOCKS * sizeof(float), 256);
-    w.scan_tmp = p;
+    Carver c{workspace};
+    char* head = c.take<char>(256);
+    w.level = reinterpret_cast<float*>(head);
+    w.total = head ? reinterpret_cast<uint64_t*>(head + 128) : nullptr;
+    w.counts = c.take<uint32_t>((size_t)N);
+    w.partial = c.take<float>(2 * FUS_MINMAX_BLOCKS);
+    w.scan_tmp = c.take<char>(scan_tmp_bytes(N));
+    w.bytes = c.o;
     return w;
 }
 

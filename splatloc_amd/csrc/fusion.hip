@@ -264,9 +264,7 @@ int splatraster_fusion_bytes(int32_t X, int32_t Y, int32_t Z, int32_t C, size_t*
     if (C < 4 || C > FUS_MAX_FEAT || C % 4) return SPLATRASTER_ERR_BAD_ARG;
     const size_t N = (size_t)X * Y * Z;
     *volume_bytes = N * sizeof(float) * (size_t)(1 + 1 + 3 + C);
-    // [level, total | counts N | min/max partials | scan state]
-    *surface_bytes = 256 + align_up(N * sizeof(uint32_t), 256) + align_up(2 * FUS_MINMAX_BLOCKS * sizeof(float), 256)
-                     + align_up(scan_tmp_bytes((int64_t)N), 256);
+    *surface_bytes = fus_layout(nullptr, (int64_t)N).bytes;
     return SPLATRASTER_OK;
 }
 
@@ -279,7 +277,7 @@ int splatraster_fusion_integrate(const splatraster_fusion_volume* v, int32_t F, 
     if (F < 0 || F > FUS_MAX_FRAMES || H < 1 || W < 1 || H > FUS_MAX_IMAGE || W > FUS_MAX_IMAGE) return SPLATRASTER_ERR_BAD_ARG;
     if (F == 0) return SPLATRASTER_OK;
     if (!depth || !color_im || !feat_im || !world2cam || !intrinsics) return SPLATRASTER_ERR_BAD_ARG;
-    if (reinterpret_cast<uintptr_t>(feat_im) & 15) return SPLATRASTER_ERR_BAD_ARG;
+    if (misaligned(feat_im, 16)) return SPLATRASTER_ERR_BAD_ARG;
     if (!(sdf_trunc > 0.f) || obs_weight != obs_weight) return SPLATRASTER_ERR_BAD_ARG;
     FusFrames fr;
     for (int f = 0; f < FUS_MAX_FRAMES; ++f) {
@@ -336,7 +334,7 @@ int splatraster_fusion_surface_extract(const splatraster_fusion_volume* v, const
     if (M > 3 * N) return SPLATRASTER_ERR_BAD_ARG;
     const FusWs w = fus_layout(const_cast<void*>(workspace), N);
     if (M == 0) return SPLATRASTER_OK;
-    if (!verts || !points || !index || !colors || !feats || (reinterpret_cast<uintptr_t>(feats) & 15)) return SPLATRASTER_ERR_BAD_ARG;
+    if (!verts || !points || !index || !colors || !feats || misaligned(feats, 16)) return SPLATRASTER_ERR_BAD_ARG;
     FusOrigin o;
     for (int k = 0; k < 3; ++k) o.o[k] = origin[k];
     SR_HIP_CHECK(hipMemsetAsync(index, 0xFF, (size_t)M * sizeof(int64_t), stream));   // -1: rows the write pass does not reach

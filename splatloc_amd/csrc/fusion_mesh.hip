@@ -28,21 +28,22 @@ static_assert(sizeof(McTable) == 4096 && MC_ROW == sizeof(uint4), "a case's row 
 
 constexpr int64_t MESH_MAX_CELLS = (int64_t)UINT32_MAX / MC_MAX_TRIANGLES;   // 5 triangles per cell stay below 2^32 in the scan
 
+// [total | counts cells | scan state]
 struct MeshWs {
     uint64_t* total;
     uint32_t* counts;
     void* scan_tmp;
+    size_t bytes;
 };
 
 static MeshWs mesh_layout(void* workspace, int64_t cells)
 {
-    char* p = reinterpret_cast<char*>(workspace);
     MeshWs w;
-    w.total = reinterpret_cast<uint64_t*>(p);
-    p += 256;
-    w.counts = reinterpret_cast<uint32_t*>(p);
-    p += align_up((size_t)cells * sizeof(uint32_t), 256);
-    w.scan_tmp = p;
+    Carver c{workspace};
+    w.total = c.take<uint64_t>(1);
+    w.counts = c.take<uint32_t>((size_t)cells);
+    w.scan_tmp = c.take<char>(scan_tmp_bytes(cells > 0 ? cells : 1));
+    w.bytes = c.o;
     return w;
 }
 
@@ -205,8 +206,7 @@ int splatraster_fusion_mesh_bytes(int32_t X, int32_t Y, int32_t Z, size_t* mesh_
     if ((int64_t)X * Y > FUS_MAX_VOXELS || (int64_t)X * Y * Z > FUS_MAX_VOXELS) return SPLATRASTER_ERR_BAD_ARG;
     const int64_t cells = mesh_cells(X, Y, Z);
     if (cells > MESH_MAX_CELLS) return SPLATRASTER_ERR_OVERFLOW;
-    // [total | counts cells | scan state]
-    *mesh_bytes = 256 + align_up((size_t)cells * sizeof(uint32_t), 256) + align_up(scan_tmp_bytes(cells > 0 ? cells : 1), 256);
+    *mesh_bytes = mesh_layout(nullptr, cells).bytes;
     return SPLATRASTER_OK;
 }
 

@@ -225,17 +225,13 @@ static int sel_blocks(int64_t n)
 
 static SelWs sel_layout(void* workspace, int32_t N, int64_t n)
 {
-    char* p = reinterpret_cast<char*>(workspace);   // null: sizes only
     SelWs w;
-    size_t off = 0;
-    w.hist = p ? reinterpret_cast<uint32_t*>(p + off) : nullptr;
-    off += align_up((size_t)N * 4 * 256 * sizeof(uint32_t), 256);
-    w.state = p ? reinterpret_cast<uint32_t*>(p + off) : nullptr;
-    off += align_up((size_t)N * SEL_STATE_WORDS * sizeof(uint32_t), 256);
-    w.zero_bytes = off;
-    w.partials = p ? reinterpret_cast<double*>(p + off) : nullptr;
-    off += align_up((size_t)N * sel_blocks(n) * 2 * sizeof(double), 256);
-    w.total = off;
+    Carver c{workspace};
+    w.hist = c.take<uint32_t>((size_t)N * 4 * 256);
+    w.state = c.take<uint32_t>((size_t)N * SEL_STATE_WORDS);
+    w.zero_bytes = c.o;
+    w.partials = c.take<double>((size_t)N * sel_blocks(n) * 2);
+    w.total = c.o;
     return w;
 }
 
@@ -382,20 +378,23 @@ static bool bad_frame(int32_t N, int32_t H, int32_t W)
 
 // what splatraster_grad_mask needs behind the caller's buffers: [frame select | medians N | intensities N H W]
 struct MaskWs {
-    size_t select, medians, intensity, total;
+    void* select;                // sel_layout's buffer (GLOBAL mode), else null
+    float *medians, *intensity;  // null where the mode / the caller's own intensity plane leaves the section out
+    size_t total;
 };
 
-static MaskWs mask_layout(int32_t N, int32_t H, int32_t W, int mode, bool have_intensity)
+static MaskWs mask_layout(void* workspace, int32_t N, int32_t H, int32_t W, int mode, bool have_intensity)
 {
-    MaskWs m = {0, 0, 0, 0};
+    MaskWs m{};
+    Carver c{workspace};
     const int64_t n = (int64_t)H * W;
     const bool scratch = !have_intensity && (mode == SPLATRASTER_GRAD_MASK_GLOBAL || image_ops_path(H, W) == IMG_PATH_GLOBAL);
     if (mode == SPLATRASTER_GRAD_MASK_GLOBAL) {
-        m.select = sel_layout(nullptr, N, n).total;
-        m.medians = align_up((size_t)N * sizeof(float), 256);
+        m.select = c.take<char>(sel_layout(nullptr, N, n).total);
+        m.medians = c.take<float>((size_t)N);
     }
-    if (scratch) m.intensity = align_up((size_t)N * n * sizeof(float), 256);
-    m.total = m.select + m.medians + m.intensity;
+    if (scratch) m.intensity = c.take<float>((size_t)N * n);
+    m.total = c.o;
     return m;
 }
 
@@ -423,7 +422,7 @@ int splatraster_grad_mask_workspace_bytes(int32_t N, int32_t H, int32_t W, int32
     if (!bytes || bad_frame(N, H, W)) return SPLATRASTER_ERR_BAD_ARG;
     if (mode != SPLATRASTER_GRAD_MASK_REPLICA && mode != SPLATRASTER_GRAD_MASK_GLOBAL) return SPLATRASTER_ERR_BAD_ARG;
     if (mode == SPLATRASTER_GRAD_MASK_REPLICA && image_ops_path(H, W) == IMG_PATH_NONE) return SPLATRASTER_ERR_BAD_ARG;
-    *bytes = mask_layout(N, H, W, mode, have_intensity != 0).total;
+    *bytes = mask_layout(nullptr, N, H, W, mode, have_intensity != 0).total;
     return SPLATRASTER_OK;
 }
 
@@ -438,17 +437,16 @@ int splatraster_grad_mask(int32_t N, int32_t H, int32_t W, const float* images, 
     const int path = image_ops_path(H, W);
     if (mode == SPLATRASTER_GRAD_MASK_REPLICA && path == IMG_PATH_NONE) return SPLATRASTER_ERR_BAD_ARG;   // an empty block: the reference raises
     if (mode == SPLATRASTER_GRAD_MASK_REPLICA && out_u8) return SPLATRASTER_ERR_UNSUPPORTED;   // the remainder keeps raw intensities
-    const MaskWs m = mask_layout(N, H, W, mode, intensity != nullptr);
+    const MaskWs m = mask_layout(workspace, N, H, W, mode, intensity != nullptr);
     if (m.total > 0 && (!workspace || workspace_bytes < m.total)) return SPLATRASTER_ERR_BAD_ARG;
-    char* ws = reinterpret_cast<char*>(workspace);
-    float* xs = intensity ? intensity : (m.intensity ? reinterpret_cast<float*>(ws + m.select + m.medians) : nullptr);
+    float* xs = intensity ? intensity : m.intensity;
     int st;
 
     if (mode == SPLATRASTER_GRAD_MASK_GLOBAL) {
         const int64_t n = (int64_t)H * W;
-        float* medians = reinterpret_cast<float*>(ws + m.select);
+        float* medians = m.medians;
         if ((st = launch_gradient(N, H, W, 0, 0, W, H, images, 1, eps, nullptr, nullptr, nullptr, xs, nullptr, stream))) return st;
-        if ((st = launch_frame_select(N, n, xs, 0, nullptr, 0.f, nullptr, medians, nullptr, nullptr, nullptr, ws, stream))) return st;
+        if ((st = launch_frame_select(N, n, xs, 0, nullptr, 0.f, nullptr, medians, nullptr, nullptr, nullptr, m.select, stream))) return st;
         hipLaunchKernelGGL(img_threshold_kernel, dim3(sel_blocks(n), N), dim3(IMG_THREADS), 0, stream, n, (const float*)xs,
                            (const float*)medians, edge_threshold, out_u8 ? nullptr : reinterpret_cast<float*>(out),
                            out_u8 ? reinterpret_cast<uint8_t*>(out) : nullptr, thresholds);

@@ -257,28 +257,6 @@ static uint32_t knn_max_cells(int N)
     return c;
 }
 
-struct KnnGridWs { KnnGrid* G; float* part; uint32_t* count; uint32_t* fill; uint32_t* incl; uint32_t* cell_of; float4* sorted; void* scan_tmp; size_t bytes, zero_bytes; };
-static KnnGridWs knn_grid_ws(void* base, int N)
-{
-    const size_t n = (size_t)(N > 0 ? N : 1), cells = knn_max_cells(N);
-    char* b = reinterpret_cast<char*>(base);
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 256); return at; };
-    KnnGridWs w;
-    // count and fill first: one memset clears both
-    w.count = reinterpret_cast<uint32_t*>(b + take(4 * cells));
-    w.fill = reinterpret_cast<uint32_t*>(b + take(4 * cells));
-    w.zero_bytes = o;
-    w.G = reinterpret_cast<KnnGrid*>(b + take(sizeof(KnnGrid)));
-    w.part = reinterpret_cast<float*>(b + take(sizeof(float) * 6 * KNN_BBOX_BLOCKS));
-    w.incl = reinterpret_cast<uint32_t*>(b + take(4 * cells));
-    w.cell_of = reinterpret_cast<uint32_t*>(b + take(4 * n));
-    w.sorted = reinterpret_cast<float4*>(b + take(16 * n));
-    w.scan_tmp = b + take(scan_tmp_bytes((int64_t)cells));
-    w.bytes = o;
-    return w;
-}
-
 static int knn_slices(int N)
 {
     const int qblocks = (N + KNN_THREADS - 1) / KNN_THREADS;
@@ -291,21 +269,46 @@ static int knn_slices(int N)
 }
 
 
-// flag word of the grid path (largest overloaded cell, see KnnGrid): the last 256 bytes of the workspace
-static uint32_t* knn_flag_word(void* workspace, int32_t N)
+// Either path may be taken (the threshold is a run-time knob), so the two share the front of the workspace: the grid path's
+// sections, or the brute force's partials; the flag word of the grid path (largest overloaded cell, see KnnGrid) lies behind
+// the longer of the two.
+struct KnnWs {
+    uint32_t *count, *fill; KnnGrid* G; float* part; uint32_t *incl, *cell_of; float4* sorted; void* scan_tmp;   // grid path
+    float* partial;   // brute force
+    uint32_t* flag;
+    size_t bytes, zero_bytes;
+};
+static KnnWs knn_layout(void* base, int N)
 {
-    return reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(workspace) + splatknn_workspace_bytes(N) - 256);
+    const size_t n = (size_t)(N > 0 ? N : 1), cells = knn_max_cells((int)n);
+    KnnWs w;
+    Carver c{base};
+    // count and fill first: one memset clears both
+    w.count = c.take<uint32_t>(cells);
+    w.fill = c.take<uint32_t>(cells);
+    w.zero_bytes = c.o;
+    w.G = c.take<KnnGrid>(1);
+    w.part = c.take<float>(6 * KNN_BBOX_BLOCKS);
+    w.incl = c.take<uint32_t>(cells);
+    w.cell_of = c.take<uint32_t>(n);
+    w.sorted = c.take<float4>(n);
+    w.scan_tmp = c.take<char>(scan_tmp_bytes((int64_t)cells));
+    Carver brute{base};
+    w.partial = brute.take<float>((size_t)knn_slices((int)n) * n * 3);
+    if (c.o < brute.o) c.o = brute.o;
+    w.flag = c.take<uint32_t>(1);
+    w.bytes = c.o;
+    return w;
 }
 
 // the tiled brute force; `gate` non-null: every block returns at once unless *gate > gate_limit
-static int knn_brute_dist2(int32_t N, const float* points, float* out, void* workspace, const uint32_t* gate, uint32_t gate_limit,
+static int knn_brute_dist2(int32_t N, const float* points, float* out, float* partial, const uint32_t* gate, uint32_t gate_limit,
                            hipStream_t stream)
 {
     const int slices = knn_slices(N);
     int slice_len = (N + slices - 1) / slices;
     slice_len = (slice_len + KNN_THREADS - 1) / KNN_THREADS * KNN_THREADS;
     const int qblocks = (N + KNN_THREADS - 1) / KNN_THREADS;
-    float* partial = reinterpret_cast<float*>(workspace);
     hipLaunchKernelGGL(knn_partial_kernel, dim3(qblocks, slices), dim3(KNN_THREADS), 0, stream, N, slice_len,
                        points, partial, gate, gate_limit);
     SR_LAUNCH_CHECK();
@@ -316,11 +319,11 @@ static int knn_brute_dist2(int32_t N, const float* points, float* out, void* wor
 
 static int knn_grid_dist2(int32_t N, const float* points, float* out, void* workspace, hipStream_t stream)
 {
-    KnnGridWs w = knn_grid_ws(workspace, N);
+    const KnnWs w = knn_layout(workspace, N);
     const uint32_t cells = knn_max_cells(N);
     const int blocks = (N + KNN_THREADS - 1) / KNN_THREADS;
     SR_HIP_CHECK(hipMemsetAsync(w.count, 0, w.zero_bytes, stream));
-    uint32_t* flag = knn_flag_word(workspace, N);
+    uint32_t* flag = w.flag;
     SR_HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(uint32_t), stream));
     hipLaunchKernelGGL(knn_bbox_kernel, dim3(KNN_BBOX_BLOCKS), dim3(KNN_THREADS), 0, stream, N, points, w.part);
     SR_LAUNCH_CHECK();
@@ -338,7 +341,7 @@ static int knn_grid_dist2(int32_t N, const float* points, float* out, void* work
     hipLaunchKernelGGL(knn_grid_query_kernel, dim3(blocks), dim3(KNN_THREADS), 0, stream, N, w.sorted, w.incl, w.G, flag, out);
     SR_LAUNCH_CHECK();
     // an overloaded grid (degenerate cloud) is answered by the brute force instead; otherwise these blocks return at once
-    return knn_brute_dist2(N, points, out, workspace, flag, knn_overload_limit(N), stream);
+    return knn_brute_dist2(N, points, out, w.partial, flag, knn_overload_limit(N), stream);
 }
 
 }  // namespace sr
@@ -347,13 +350,7 @@ using namespace sr;
 
 extern "C" {
 
-size_t splatknn_workspace_bytes(int32_t N)
-{
-    const size_t n = (size_t)(N > 0 ? N : 1);
-    const size_t brute = align_up((size_t)knn_slices((int)n) * n * 3 * sizeof(float), 256);
-    const size_t grid = knn_grid_ws(nullptr, (int)n).bytes;
-    return (brute > grid ? brute : grid) + 256;     // either path may be taken (the threshold is a run-time knob); + the flag word
-}
+size_t splatknn_workspace_bytes(int32_t N) { return knn_layout(nullptr, N).bytes; }
 
 int splatknn_debug_set_grid_min(int32_t n)
 {
@@ -368,7 +365,7 @@ int splatknn_dist2(int32_t N, const float* points, float* out, void* workspace, 
     if (!points || !out || !workspace) return SPLATRASTER_ERR_BAD_ARG;
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     if (N >= g_knn_grid_min && N >= 8) return knn_grid_dist2(N, points, out, workspace, stream);
-    return knn_brute_dist2(N, points, out, workspace, nullptr, 0u, stream);
+    return knn_brute_dist2(N, points, out, knn_layout(workspace, N).partial, nullptr, 0u, stream);
 }
 
 }  // extern "C"

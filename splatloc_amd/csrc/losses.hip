@@ -449,10 +449,17 @@ static RefineWindow refine_window()
     return win;
 }
 
-static size_t refinement_loss_workspace_bytes(int32_t C, int32_t H, int32_t W)
+// [three maps of C H W floats | block partials]
+struct RefineWs { float* maps; double* partial; size_t bytes; };
+static RefineWs refine_layout(void* workspace, int32_t C, int32_t H, int32_t W)
 {
     const size_t blocks = (size_t)((W + FW - 1) / FW) * ((H + FH - 1) / FH) * (size_t)C;
-    return align_up(3 * sizeof(float) * (size_t)C * H * W, 256) + blocks * 2 * sizeof(double);
+    RefineWs w;
+    Carver c{workspace};
+    w.maps = c.take<float>(3 * (size_t)C * H * W);
+    w.partial = c.take<double>(blocks * 2);
+    w.bytes = c.o;
+    return w;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -542,8 +549,9 @@ static int launch_refinement_loss(int32_t C, int32_t H, int32_t W, float lambda,
                            float* g_image, float* out, void* workspace, hipStream_t stream)
 {
     const size_t n = (size_t)C * H * W;
-    float* maps = reinterpret_cast<float*>(workspace);
-    double* partial = reinterpret_cast<double*>(reinterpret_cast<char*>(workspace) + align_up(3 * sizeof(float) * n, 256));
+    const RefineWs w = refine_layout(workspace, C, H, W);
+    float* maps = w.maps;
+    double* partial = w.partial;
     const dim3 grid((W + FW - 1) / FW, (H + FH - 1) / FH, C);
     const int blocks = (int)(grid.x * grid.y * grid.z);
     const RefineWindow win = refine_window();
@@ -594,7 +602,7 @@ int splatraster_mapping_loss_window(int32_t n_views, int32_t pixels, const splat
 size_t splatraster_refinement_loss_workspace_bytes(int32_t channels, int32_t height, int32_t width)
 {
     if (channels <= 0 || height <= 0 || width <= 0) return 0;
-    return refinement_loss_workspace_bytes(channels, height, width);
+    return refine_layout(nullptr, channels, height, width).bytes;
 }
 
 int splatraster_refinement_loss(int32_t channels, int32_t height, int32_t width, float lambda_dssim,

@@ -571,30 +571,29 @@ struct FrWs {
     size_t bytes;
 };
 
-static FrWs fr_layout(char* base, int64_t N, int64_t P)
+static FrWs fr_layout(void* base, int64_t N, int64_t P)
 {
     FrWs w;
-    size_t o = 0;
-    auto take = [&](size_t n) { char* p = base ? base + o : nullptr; o += align_up(n, 256); return p; };
+    Carver c{base};
     uint32_t nb = 1024;
     while ((int64_t)nb < N && nb < (1u << 22)) nb <<= 1;
     w.buckets = nb;
-    const size_t n4 = (size_t)(N > 0 ? N : 1) * 4, p4 = (size_t)(P > 0 ? P : 1) * 4;
-    w.flags = reinterpret_cast<uint32_t*>(take(n4));
-    w.uv = reinterpret_cast<double2*>(take(n4 * 4));
-    w.cand = reinterpret_cast<int32_t*>(take(n4));
-    w.cand_hash = reinterpret_cast<uint32_t*>(take(n4));
-    w.sorted = reinterpret_cast<uint32_t*>(take(n4));
-    w.counts = reinterpret_cast<uint32_t*>(take((size_t)nb * 4));
-    w.starts = reinterpret_cast<uint32_t*>(take((size_t)nb * 4));
-    w.cursor = reinterpret_cast<uint32_t*>(take((size_t)nb * 4));
-    w.found = reinterpret_cast<uint32_t*>(take(p4));
-    w.best = reinterpret_cast<int32_t*>(take(p4));
-    w.total = reinterpret_cast<uint64_t*>(take(sizeof(uint64_t)));
-    w.total2 = reinterpret_cast<uint64_t*>(take(sizeof(uint64_t)));
+    const size_t n = (size_t)(N > 0 ? N : 1), p = (size_t)(P > 0 ? P : 1);
+    w.flags = c.take<uint32_t>(n);
+    w.uv = c.take<double2>(n);
+    w.cand = c.take<int32_t>(n);
+    w.cand_hash = c.take<uint32_t>(n);
+    w.sorted = c.take<uint32_t>(n);
+    w.counts = c.take<uint32_t>(nb);
+    w.starts = c.take<uint32_t>(nb);
+    w.cursor = c.take<uint32_t>(nb);
+    w.found = c.take<uint32_t>(p);
+    w.best = c.take<int32_t>(p);
+    w.total = c.take<uint64_t>(1);
+    w.total2 = c.take<uint64_t>(1);
     const int64_t sn = std::max<int64_t>(std::max<int64_t>(N, P), (int64_t)nb);
-    w.scan_tmp = take(scan_tmp_bytes(sn));
-    w.bytes = o;
+    w.scan_tmp = c.take<char>(scan_tmp_bytes(sn));
+    w.bytes = c.o;
     return w;
 }
 
@@ -745,7 +744,7 @@ int splatraster_frustum_candidates(int64_t N, const float* points, const float* 
     cam.fy = key ? kp_K[1] : 1.0;
     cam.cx = key ? kp_K[2] : 0.0;
     cam.cy = key ? kp_K[3] : 0.0;
-    const FrWs w = fr_layout(reinterpret_cast<char*>(workspace), N, key ? P : 0);
+    const FrWs w = fr_layout(workspace, N, key ? P : 0);
     hipLaunchKernelGGL(fr_point_kernel, dim3(fr_blocks(N)), dim3(FR_THREADS), 0, stream, N, points, marker, marker_threshold,
                        cam, width, height, w.flags, w.uv);
     SR_LAUNCH_CHECK();

@@ -742,27 +742,28 @@ __global__ void __launch_bounds__(PNP_THREADS) pnp_final_kernel(const splatraste
 
 // ------------------------------------------------------------------------------------------------------------------- host
 struct PnpLayout {
-    size_t probs, state, models, nmod, count, sum, flag, total;
+    splatraster_pnp_problem* probs;
+    PnpState* state;
+    double* models;
+    int32_t *nmod, *count;
+    double* sum;
+    int32_t* flag;
+    size_t total;
 };
 
-static PnpLayout pnp_layout(int32_t B)
+static PnpLayout pnp_layout(void* base, int32_t B)
 {
     PnpLayout L;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = o;
-        o = align_up(o + bytes, 256);
-        return at;
-    };
+    Carver c{base};
     const size_t slots = (size_t)B * PNP_BATCH * PNP_SOL;
-    L.probs = take((size_t)B * sizeof(splatraster_pnp_problem));
-    L.state = take((size_t)B * sizeof(PnpState));
-    L.models = take(slots * PNP_MODEL * sizeof(double));
-    L.nmod = take((size_t)B * PNP_BATCH * sizeof(int32_t));
-    L.count = take(slots * sizeof(int32_t));
-    L.sum = take(slots * sizeof(double));
-    L.flag = take(sizeof(int32_t));
-    L.total = o;
+    L.probs = c.take<splatraster_pnp_problem>((size_t)B);
+    L.state = c.take<PnpState>((size_t)B);
+    L.models = c.take<double>(slots * PNP_MODEL);
+    L.nmod = c.take<int32_t>((size_t)B * PNP_BATCH);
+    L.count = c.take<int32_t>(slots);
+    L.sum = c.take<double>(slots);
+    L.flag = c.take<int32_t>(1);
+    L.total = c.o;
     return L;
 }
 
@@ -792,7 +793,7 @@ extern "C" {
 size_t splatraster_pnp_workspace_bytes(int32_t B, const splatraster_pnp_problem* problems, const splatraster_pnp_options* options)
 {
     if (pnp_check(B, problems, options) != SPLATRASTER_OK || B == 0) return 0;
-    return pnp_layout(B).total;
+    return pnp_layout(nullptr, B).total;
 }
 
 int splatraster_pnp_hypotheses(int32_t B, const splatraster_pnp_problem* problems, const splatraster_pnp_options* options,
@@ -807,9 +808,8 @@ int splatraster_pnp_hypotheses(int32_t B, const splatraster_pnp_problem* problem
         return SPLATRASTER_ERR_BAD_ARG;
     for (int32_t b = 0; b < B; ++b)
         if (problems[b].n < 4) return SPLATRASTER_ERR_BAD_ARG;
-    const PnpLayout L = pnp_layout(B);
-    char* ws = static_cast<char*>(workspace);
-    auto* probs = reinterpret_cast<splatraster_pnp_problem*>(ws + L.probs);
+    const PnpLayout L = pnp_layout(workspace, B);
+    splatraster_pnp_problem* probs = L.probs;
     SR_HIP_CHECK(hipMemcpyAsync(probs, problems, (size_t)B * sizeof(*problems), hipMemcpyHostToDevice, stream));
     hipLaunchKernelGGL(pnp_hyp_kernel, dim3(pnp_blocks((int64_t)B * ntrials, 256)), dim3(256), 0, stream, B, probs, options->seed,
                        trial0, ntrials, points2d, points3d, (const PnpState*)nullptr, samples, models, nmodels);
@@ -827,9 +827,8 @@ int splatraster_pnp_score(int32_t B, const splatraster_pnp_problem* problems, co
     if (M < 0 || (int64_t)B * M > (int64_t)PNP_BATCH * PNP_SOL * B) return SPLATRASTER_ERR_BAD_ARG;
     if (M == 0) return SPLATRASTER_OK;
     if (!models || !points2d || !points3d || !count || !sum || !workspace) return SPLATRASTER_ERR_BAD_ARG;
-    const PnpLayout L = pnp_layout(B);
-    char* ws = static_cast<char*>(workspace);
-    auto* probs = reinterpret_cast<splatraster_pnp_problem*>(ws + L.probs);
+    const PnpLayout L = pnp_layout(workspace, B);
+    splatraster_pnp_problem* probs = L.probs;
     SR_HIP_CHECK(hipMemcpyAsync(probs, problems, (size_t)B * sizeof(*problems), hipMemcpyHostToDevice, stream));
     const double thr2 = options->max_error_px * options->max_error_px;
     hipLaunchKernelGGL(pnp_score_kernel, dim3(pnp_blocks((int64_t)B * M, PNP_WAVES)), dim3(PNP_THREADS), 0, stream, B, probs, thr2,
@@ -849,15 +848,11 @@ int splatraster_pnp(int32_t B, const splatraster_pnp_problem* problems, const sp
     for (int32_t b = 0; b < B; ++b) total = std::max(total, problems[b].offset + problems[b].n);
     if (!R_out || !t_out || !num_inliers || !status || !trials || !workspace) return SPLATRASTER_ERR_BAD_ARG;
     if (total > 0 && (!points2d || !points3d || !inlier_mask)) return SPLATRASTER_ERR_BAD_ARG;
-    const PnpLayout L = pnp_layout(B);
-    char* ws = static_cast<char*>(workspace);
-    auto* probs = reinterpret_cast<splatraster_pnp_problem*>(ws + L.probs);
-    auto* state = reinterpret_cast<PnpState*>(ws + L.state);
-    auto* models = reinterpret_cast<double*>(ws + L.models);
-    auto* nmod = reinterpret_cast<int32_t*>(ws + L.nmod);
-    auto* count = reinterpret_cast<int32_t*>(ws + L.count);
-    auto* sum = reinterpret_cast<double*>(ws + L.sum);
-    auto* flag = reinterpret_cast<int32_t*>(ws + L.flag);
+    const PnpLayout L = pnp_layout(workspace, B);
+    splatraster_pnp_problem* probs = L.probs;
+    PnpState* state = L.state;
+    double *models = L.models, *sum = L.sum;
+    int32_t *nmod = L.nmod, *count = L.count, *flag = L.flag;
     const double thr2 = options->max_error_px * options->max_error_px;
     const int32_t M = PNP_BATCH * PNP_SOL;
     SR_HIP_CHECK(hipMemcpyAsync(probs, problems, (size_t)B * sizeof(*problems), hipMemcpyHostToDevice, stream));

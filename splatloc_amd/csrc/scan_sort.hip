@@ -647,15 +647,38 @@ static int64_t sweep_blocks(int64_t n)
     return tile ? (n + tile - 1) / tile : 0;
 }
 
+// words of the [digit][block] table that every histogram / scan / scatter pass scans
+static int64_t sort_table_words(int64_t nb) { return nb * RADIX; }
+
+// The sort's scratch in its two forms (base null: `bytes` only).  One-sweep: [SweepState | one status table per pass].
+struct SweepLayout { SweepState* st; uint32_t* status[MAX_PASSES]; size_t bytes; };
+static SweepLayout sweep_layout(void* tmp, int64_t n, int passes)
+{
+    const int64_t nbs = sweep_blocks(n);
+    SweepLayout L{};
+    Carver c{tmp};
+    L.st = c.take<SweepState>(1);
+    for (int p = 0; p < passes; ++p) L.status[p] = c.take<uint32_t>((size_t)(nbs > 0 ? nbs : 1) * RADIX);
+    L.bytes = c.o;
+    return L;
+}
+// Histogram passes over nb blocks: [table | state of the table's scan].
+struct HistLayout { uint32_t* table; void* scan_tmp; size_t bytes; };
+static HistLayout hist_layout(void* tmp, int64_t nb)
+{
+    HistLayout L;
+    Carver c{tmp};
+    L.table = c.take<uint32_t>((size_t)sort_table_words(nb));
+    L.scan_tmp = c.take<char>(scan_tmp_bytes(sort_table_words(nb)));
+    L.bytes = c.o;
+    return L;
+}
+
 size_t sort_tmp_bytes(int64_t n)
 {
     const int64_t nb = (n + SORT_TILE - 1) / SORT_TILE;
-    const size_t nbz = (size_t)(nb > 0 ? nb : 1);
-    const size_t table = align_up(nbz * RADIX * sizeof(uint32_t), 256);
-    const size_t legacy = table + scan_tmp_bytes((int64_t)nbz * RADIX);
-    const size_t stable = align_up((size_t)(sweep_blocks(n) > 0 ? sweep_blocks(n) : 1) * RADIX * sizeof(uint32_t), 256);
-    const size_t sweep = align_up(sizeof(SweepState), 256) + MAX_PASSES * stable;
-    return legacy > sweep ? legacy : sweep;
+    const size_t hist = hist_layout(nullptr, nb > 0 ? nb : 1).bytes, sweep = sweep_layout(nullptr, n, MAX_PASSES).bytes;
+    return hist > sweep ? hist : sweep;
 }
 
 // bytes at the start of tmp that must be zero before sort_pairs_u32 (0: none); a caller that
@@ -663,23 +686,20 @@ size_t sort_tmp_bytes(int64_t n)
 size_t sort_zero_bytes(int64_t n, int key_bits)
 {
     if (n <= 0 || key_bits <= 0 || !sweep_items(n)) return 0;
-    const int64_t nb = sweep_blocks(n);
-    const int passes = (key_bits + 7) / 8;
-    return align_up(sizeof(SweepState), 256) + (size_t)passes * align_up((size_t)nb * RADIX * sizeof(uint32_t), 256);
+    return sweep_layout(nullptr, n, (key_bits + 7) / 8).bytes;
 }
 
 // histogram / scan / scatter passes over 8-bit digits, ping-ponging between (kin, vin) and (kout, vout).  KIn = uint16_t:
 // the key arrays hold uint16_t (in the first half of their uint32_t storage) up to the input of the last pass, which
 // writes uint32_t keys — a pass never reads and writes the same buffer, so the two widths cannot overlap.
-// words of the [digit][block] table that every such pass scans
-static int64_t sort_table_words(int64_t nb) { return nb * RADIX; }
 
 template <typename KIn>
 static int sort_passes(int64_t n, int64_t nb, int passes, uint32_t* kin, uint32_t* vin, uint32_t* kout, uint32_t* vout, void* tmp,
                        hipStream_t stream, bool* result_in_alt)
 {
-    uint32_t* table = reinterpret_cast<uint32_t*>(tmp);
-    void* scan_tmp = reinterpret_cast<char*>(tmp) + align_up((size_t)nb * RADIX * sizeof(uint32_t), 256);
+    const HistLayout L = hist_layout(tmp, nb);
+    uint32_t* table = L.table;
+    void* scan_tmp = L.scan_tmp;
     for (int p = 0; p < passes; ++p) {
         const int shift = p * 8;
         const int64_t cnt = sort_table_words(nb);
@@ -726,18 +746,16 @@ int sort_pairs_u32(int64_t n, uint32_t* keys, uint32_t* vals, uint32_t* keys_alt
     if (sweep_items(n)) {
         const int items = sweep_items(n);
         const int64_t nbs = sweep_blocks(n);
-        const size_t table = align_up((size_t)nbs * RADIX * sizeof(uint32_t), 256);
-        const size_t head = align_up(sizeof(SweepState), 256);
-        SweepState* st = reinterpret_cast<SweepState*>(tmp);
-        char* status0 = reinterpret_cast<char*>(tmp) + head;
-        if (!tmp_zeroed) SR_HIP_CHECK(hipMemsetAsync(tmp, 0, head + (size_t)passes * table, stream));
+        const SweepLayout L = sweep_layout(tmp, n, passes);
+        SweepState* st = L.st;
+        if (!tmp_zeroed) SR_HIP_CHECK(hipMemsetAsync(tmp, 0, L.bytes, stream));
         if (items == 8)
             hipLaunchKernelGGL(sort_hist_all_kernel<8>, dim3((unsigned)nbs), dim3(SORT_THREADS), 0, stream, n, kin, passes, st);
         else
             hipLaunchKernelGGL(sort_hist_all_kernel<SORT_ITEMS>, dim3((unsigned)nbs), dim3(SORT_THREADS), 0, stream, n, kin, passes, st);
         SR_LAUNCH_CHECK();
         for (int p = 0; p < passes; ++p) {
-            uint32_t* status = reinterpret_cast<uint32_t*>(status0 + (size_t)p * table);
+            uint32_t* status = L.status[p];
             if (items == 8)
                 hipLaunchKernelGGL(sort_sweep_kernel<8>, dim3((unsigned)nbs), dim3(SORT_THREADS), 0, stream, n, kin, vin, kout,
                                    vout, p, st, status);

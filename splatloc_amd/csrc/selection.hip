@@ -322,26 +322,25 @@ struct SelWs {
     size_t bytes;
 };
 
-static SelWs sel_layout(char* base, int64_t N, int32_t num)
+static SelWs sel_layout(void* base, int64_t N, int32_t num)
 {
     SelWs w;
-    size_t o = 0;
-    auto take = [&](size_t n) { char* p = base ? base + o : nullptr; o += align_up(n, 256); return p; };
-    const size_t n4 = (size_t)(N > 0 ? N : 1) * 4;
-    w.keys = reinterpret_cast<uint32_t*>(take(n4));
-    w.vals = reinterpret_cast<uint32_t*>(take(n4));
-    w.keys_alt = reinterpret_cast<uint32_t*>(take(n4));
-    w.vals_alt = reinterpret_cast<uint32_t*>(take(n4));
-    w.flags = reinterpret_cast<uint32_t*>(take(n4));
-    w.surv = reinterpret_cast<uint32_t*>(take(n4));
-    w.order = reinterpret_cast<int32_t*>(take(n4));
-    w.pos = reinterpret_cast<float4*>(take(n4 * 4));
-    w.landmarks = reinterpret_cast<float4*>(take((size_t)(num > 0 ? num : 1) * sizeof(float4)));
-    w.count = reinterpret_cast<uint32_t*>(take(sizeof(uint32_t)));
-    w.total = reinterpret_cast<uint64_t*>(take(sizeof(uint64_t)));
-    w.sort_tmp = take(sort_tmp_bytes(N));
-    w.scan_tmp = take(scan_tmp_bytes(N));
-    w.bytes = o;
+    Carver c{base};
+    const size_t n = (size_t)(N > 0 ? N : 1);
+    w.keys = c.take<uint32_t>(n);
+    w.vals = c.take<uint32_t>(n);
+    w.keys_alt = c.take<uint32_t>(n);
+    w.vals_alt = c.take<uint32_t>(n);
+    w.flags = c.take<uint32_t>(n);
+    w.surv = c.take<uint32_t>(n);
+    w.order = c.take<int32_t>(n);
+    w.pos = c.take<float4>(n);
+    w.landmarks = c.take<float4>((size_t)(num > 0 ? num : 1));
+    w.count = c.take<uint32_t>(1);
+    w.total = c.take<uint64_t>(1);
+    w.sort_tmp = c.take<char>(sort_tmp_bytes(N));
+    w.scan_tmp = c.take<char>(scan_tmp_bytes(N));
+    w.bytes = c.o;
     return w;
 }
 
@@ -379,7 +378,7 @@ int splatraster_landmark_select(int64_t N, const float* points, const double* sc
     if (N < 1 || num < 1 || num > N || !points || !score || !out_idx || !workspace) return SPLATRASTER_ERR_BAD_ARG;
     if (!(radius > 0.0) || radius != radius || radius > 1e300) return SPLATRASTER_ERR_BAD_ARG;
     if (N >= ((int64_t)1 << 31)) return SPLATRASTER_ERR_OVERFLOW;
-    const SelWs w = sel_layout(reinterpret_cast<char*>(workspace), N, num);
+    const SelWs w = sel_layout(workspace, N, num);
     const unsigned nb = sel_blocks(N);
     bool alt = false;
     hipLaunchKernelGGL(sel_key_lo_kernel, dim3(nb), dim3(SEL_THREADS), 0, stream, N, score, w.keys, w.vals);

@@ -518,31 +518,26 @@ sp_dense_kernel(int Hc, int Wc, int row0, int64_t per_image /*rows W*/, int64_t 
 
 // workspace: [unit vectors B cells 256 f32 | chunk counts | candidate keys B H W | candidate pixels B H W | survivor keys B K | pixels B K]
 struct SpWs {
-    size_t dhat, counts, ckey, cidx, selkey, selidx, total;   // offsets; dhat is 0
-    size_t dhat_bytes;
+    float* dhat;
+    uint32_t *counts, *ckey, *cidx, *selkey, *selidx;
+    size_t dhat_bytes, total;   // dhat_bytes: the first section alone, all that sample / dense_descriptors use
 };
 
 static int sp_chunks(int64_t pixels) { return (int)((pixels + SP_SEL_CHUNK - 1) / SP_SEL_CHUNK); }
 
-static SpWs sp_layout(int64_t B, int64_t H, int64_t W, int64_t K)
+static SpWs sp_layout(void* base, int64_t B, int64_t H, int64_t W, int64_t K)
 {
     const int64_t cells = ((H + SP_CELL - 1) / SP_CELL) * ((W + SP_CELL - 1) / SP_CELL);
     SpWs w;
-    size_t off = 0;
-    w.dhat = off;
-    w.dhat_bytes = align_up((size_t)(B * cells) * SP_DESC * sizeof(float), 256);
-    off += w.dhat_bytes;
-    w.counts = off;
-    off += align_up((size_t)(B * sp_chunks(H * W)) * sizeof(uint32_t), 256);
-    w.ckey = off;
-    off += align_up((size_t)(B * H * W) * sizeof(uint32_t), 256);
-    w.cidx = off;
-    off += align_up((size_t)(B * H * W) * sizeof(uint32_t), 256);
-    w.selkey = off;
-    off += align_up((size_t)(B * K) * sizeof(uint32_t), 256);
-    w.selidx = off;
-    off += align_up((size_t)(B * K) * sizeof(uint32_t), 256);
-    w.total = off;
+    Carver c{base};
+    w.dhat = c.take<float>((size_t)(B * cells) * SP_DESC);
+    w.dhat_bytes = c.o;
+    w.counts = c.take<uint32_t>((size_t)(B * sp_chunks(H * W)));
+    w.ckey = c.take<uint32_t>((size_t)(B * H * W));
+    w.cidx = c.take<uint32_t>((size_t)(B * H * W));
+    w.selkey = c.take<uint32_t>((size_t)(B * K));
+    w.selidx = c.take<uint32_t>((size_t)(B * K));
+    w.total = c.o;
     return w;
 }
 
@@ -559,8 +554,6 @@ static int sp_check_cells(int32_t B, int32_t Hc, int32_t Wc)
     if (B < 1 || Hc < 1 || Wc < 1) return SPLATRASTER_ERR_BAD_ARG;
     return sp_check_pixels(B, (int64_t)Hc * SP_CELL, (int64_t)Wc * SP_CELL);
 }
-
-static bool sp_misaligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
 
 static int launch_sp_normalize(int32_t B, int32_t Hc, int32_t Wc, const float* coarse, float* dhat, hipStream_t stream)
 {
@@ -589,7 +582,7 @@ int splatraster_sp_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t max_
     if (bytes) *bytes = 0;
     if (!bytes || max_keypoints < 1 || max_keypoints > SP_MAX_KEYPOINTS) return SPLATRASTER_ERR_BAD_ARG;
     if (const int st = sp_check_pixels(B, H, W)) return st;
-    *bytes = sp_layout(B, H, W, max_keypoints).total;
+    *bytes = sp_layout(nullptr, B, H, W, max_keypoints).total;
     return SPLATRASTER_OK;
 }
 
@@ -598,7 +591,7 @@ int splatraster_sp_scores(int32_t B, int32_t Hc, int32_t Wc, const float* semi, 
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     if (!semi || !scores) return SPLATRASTER_ERR_BAD_ARG;
     if (const int st = sp_check_cells(B, Hc, Wc)) return st;
-    if (sp_misaligned(scores, 16)) return SPLATRASTER_ERR_BAD_ARG;   // float4 stores
+    if (misaligned(scores, 16)) return SPLATRASTER_ERR_BAD_ARG;   // float4 stores
     const int64_t total = (int64_t)B * Hc * Wc;
     hipLaunchKernelGGL(sp_scores_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, total, Hc, Wc, semi, scores);
     SR_LAUNCH_CHECK();
@@ -636,14 +629,9 @@ int splatraster_sp_select(int32_t B, int32_t H, int32_t W, const float* nms, flo
     if (!nms || !keypoints || !scores || !count || !candidates || !workspace) return SPLATRASTER_ERR_BAD_ARG;
     if (max_keypoints < 1 || max_keypoints > SP_MAX_KEYPOINTS || border < 0 || !(threshold >= 0.0f)) return SPLATRASTER_ERR_BAD_ARG;
     if (const int st = sp_check_pixels(B, H, W)) return st;
-    const SpWs w = sp_layout(B, H, W, max_keypoints);
-    if (workspace_bytes < w.total || sp_misaligned(workspace, 16)) return SPLATRASTER_ERR_BAD_ARG;
-    char* ws = reinterpret_cast<char*>(workspace);
-    uint32_t* counts = reinterpret_cast<uint32_t*>(ws + w.counts);
-    uint32_t* ckey = reinterpret_cast<uint32_t*>(ws + w.ckey);
-    uint32_t* cidx = reinterpret_cast<uint32_t*>(ws + w.cidx);
-    uint32_t* selkey = reinterpret_cast<uint32_t*>(ws + w.selkey);
-    uint32_t* selidx = reinterpret_cast<uint32_t*>(ws + w.selidx);
+    const SpWs w = sp_layout(workspace, B, H, W, max_keypoints);
+    if (workspace_bytes < w.total || misaligned(workspace, 16)) return SPLATRASTER_ERR_BAD_ARG;
+    uint32_t *counts = w.counts, *ckey = w.ckey, *cidx = w.cidx, *selkey = w.selkey, *selidx = w.selidx;
     SpSel s;
     s.H = H;
     s.W = W;
@@ -676,9 +664,9 @@ int splatraster_sp_sample(int32_t B, int32_t Hc, int32_t Wc, const float* coarse
     if (!coarse || !keypoints || !count || !descriptors || !workspace) return SPLATRASTER_ERR_BAD_ARG;
     if (K < 1 || K > SP_MAX_KEYPOINTS) return SPLATRASTER_ERR_BAD_ARG;
     if (const int st = sp_check_cells(B, Hc, Wc)) return st;
-    const SpWs w = sp_layout(B, (int64_t)Hc * SP_CELL, (int64_t)Wc * SP_CELL, K);
-    if (workspace_bytes < w.dhat_bytes || sp_misaligned(workspace, 16)) return SPLATRASTER_ERR_BAD_ARG;
-    float* dhat = reinterpret_cast<float*>(workspace);
+    const SpWs w = sp_layout(workspace, B, (int64_t)Hc * SP_CELL, (int64_t)Wc * SP_CELL, K);
+    if (workspace_bytes < w.dhat_bytes || misaligned(workspace, 16)) return SPLATRASTER_ERR_BAD_ARG;
+    float* dhat = w.dhat;
     if (const int st = launch_sp_normalize(B, Hc, Wc, coarse, dhat, stream)) return st;
     const int groups = (K + SP_SAMPLE_POINTS - 1) / SP_SAMPLE_POINTS;
     hipLaunchKernelGGL(sp_sample_kernel, dim3((unsigned)((int64_t)B * groups)), dim3(256), 0, stream, Hc, Wc, K, groups, (const float*)dhat,
@@ -694,9 +682,9 @@ int splatraster_sp_dense_descriptors(int32_t B, int32_t Hc, int32_t Wc, const fl
     if (!coarse || !out || !workspace) return SPLATRASTER_ERR_BAD_ARG;
     if (const int st = sp_check_cells(B, Hc, Wc)) return st;
     if (row0 < 0 || rows < 1 || (int64_t)row0 + rows > (int64_t)Hc * SP_CELL) return SPLATRASTER_ERR_BAD_ARG;
-    const SpWs w = sp_layout(B, (int64_t)Hc * SP_CELL, (int64_t)Wc * SP_CELL, 1);
-    if (workspace_bytes < w.dhat_bytes || sp_misaligned(workspace, 16) || sp_misaligned(out, 16)) return SPLATRASTER_ERR_BAD_ARG;
-    float* dhat = reinterpret_cast<float*>(workspace);
+    const SpWs w = sp_layout(workspace, B, (int64_t)Hc * SP_CELL, (int64_t)Wc * SP_CELL, 1);
+    if (workspace_bytes < w.dhat_bytes || misaligned(workspace, 16) || misaligned(out, 16)) return SPLATRASTER_ERR_BAD_ARG;
+    float* dhat = w.dhat;
     if (const int st = launch_sp_normalize(B, Hc, Wc, coarse, dhat, stream)) return st;
     const int64_t per_image = (int64_t)rows * Wc * SP_CELL, total = (int64_t)B * per_image;
     hipLaunchKernelGGL(sp_dense_kernel, dim3((unsigned)((total + SP_DENSE_PIXELS - 1) / SP_DENSE_PIXELS)), dim3(256), 0, stream, Hc, Wc, row0,

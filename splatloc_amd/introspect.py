@@ -79,7 +79,7 @@ def payload_state(fn_ctx_tensors, R: int, W: int, H: int, V: int = 1, compact: b
     the compact payload — splatraster_debug_set_payload_compact): only the LIVE entries of every list, in list order — what lies
     behind them in a list's span was never written and is not exposed —, with `cranges` [V * tiles, 2], `n_contrib_c` [V, H, W]
     and `back` [n]: every entry's position + 1 in its full list (the word irec[:, 3] carries).  The offsets mirror
-    csrc/capi.hip: bin_layout / img_view."""
+    csrc/capi.hip: bin_layout / img_layout."""
     lib = _native.load()
     _geom, binning, img = fn_ctx_tensors
     IL = _native.ImageLayout()
