@@ -19,13 +19,16 @@ __device__ __forceinline__ float act_quat_norm(const float4 q)
     return fmaxf(sqrtf(((q.x * q.x + q.y * q.y) + q.z * q.z) + q.w * q.w), 1e-12f);
 }
 
-// d normalize: (g - u (u . g)) / n with u = q / n
+// d normalize: (g - u (u . g)) / n with u = q / n; below the eps the clamped norm carries no gradient and what is left is g / 1e-12
+// (torch.nn.functional.normalize: `v / norm.clamp_min(eps)`, clamp_min passing the gradient at norm >= eps)
 __device__ __forceinline__ float4 act_normalize_bwd(const float4 q, const float4 g)
 {
 #pragma clang fp contract(fast)
-    const float n = act_quat_norm(q);
+    const float r = sqrtf(((q.x * q.x + q.y * q.y) + q.z * q.z) + q.w * q.w);
+    const float n = fmaxf(r, 1e-12f);
     const float ux = q.x / n, uy = q.y / n, uz = q.z / n, uw = q.w / n;
-    const float ug = ((ux * g.x + uy * g.y) + uz * g.z) + uw * g.w;
+    // (a select, not a branch: g - u * 0 is g, and n is 1e-12 there)
+    const float ug = r < 1e-12f ? 0.0f : ((ux * g.x + uy * g.y) + uz * g.z) + uw * g.w;
     return make_float4((g.x - ux * ug) / n, (g.y - uy * ug) / n, (g.z - uz * ug) / n, (g.w - uw * ug) / n);
 }
 

@@ -201,16 +201,13 @@ activate_bwd_kernel(int P, int K, int deg, int SC, int E, const float* __restric
     }
     if (t >= (size_t)P) return;
     const int i = (int)t;
-    // d exp
-    {
-        float acc = 0.f;
+    // d exp; an isotropic scale sums its three upstream gradients first, as the backward of `repeat` does: one expf, and a
+    // scale that overflowed gives (g0 + g1 + g2) * inf like torch, not the NaN of inf - inf
+    if (SC == 3) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float s = expf(scaling[(size_t)i * SC + (SC == 3 ? c : 0)]);
-            const float v = g_scales[3 * (size_t)i + c] * s;
-            if (SC == 3) d_scaling[3 * (size_t)i + c] = v; else acc += v;
-        }
-        if (SC != 3) d_scaling[i] = acc;
+        for (int c = 0; c < 3; ++c) d_scaling[3 * (size_t)i + c] = g_scales[3 * (size_t)i + c] * expf(scaling[3 * (size_t)i + c]);
+    } else {
+        d_scaling[i] = ((g_scales[3 * (size_t)i] + g_scales[3 * (size_t)i + 1]) + g_scales[3 * (size_t)i + 2]) * expf(scaling[i]);
     }
     // d normalize: (g - u (u . g)) / n
     {

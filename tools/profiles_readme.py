@@ -63,6 +63,7 @@ WHAT = [   # (file name regex, description; {placeholders} are filled by the ext
     (r"^bwd_shared_contract_ab\.json$", "`tools/ab.py`, base = the change (the backward takes its frame, alpha test, partition and segment records from `composite_common.h`, HISTORY §22), variant `parent` = the parent commit's library (differences are parent minus change): {ab}; the other runs that were made, `--stage refine_step`, the `composite_bwd` stage in ms and cycles and the bit-for-bit comparison of outputs and deterministic-mode gradients under `other_runs` / `outputs_parent_vs_change`"),
     (r"^loss_shared_bodies_ab\.json$", "the loss stage's shared bodies (HISTORY §23) against the parent commit's library: interleaved pairs of fresh `bench.py --stage loss` / `refine_step` / `eval_rendering` / `pose_refine` processes on one box (200 steps, 20 warm-up), every run, and per stage the medians, the parent's spread and the paired difference (head minus parent) with its 95 % interval under `summary`; per-kernel means of one `rocprofv3 --kernel-trace --stats` run per side under `kernel_trace`"),
     (r"^scan_shared_ab\.json$", "the shared integer scans, ranks and selects of `csrc/scan.h` (HISTORY §29) against the parent commit's library: interleaved pairs of fresh `bench.py --stage raster` / `map_step` processes on one box (200 steps, 20 warm-up), every run, and per stage the medians, the parent's spread and the paired difference (head minus parent) with its 95 % interval under `summary`; per-kernel means of one `rocprofv3 --kernel-trace --stats` run per side and workload under `kernel_trace`; the rows of `tools/time_superpoint_head.py` and `tools/time_image_ops.py` with either library under `tools`; the counts of the bit-for-bit comparison under `bit_for_bit`"),
+    (r"^activation_edges_ab\.json$", "the two activation fixes (HISTORY §31: `act_normalize_bwd` below the eps of normalize, the isotropic `d_scaling`) against the parent commit's library: eight interleaved pairs of fresh `bench.py --stage raster` / `map_step` processes in one session (200 steps, 20 warm-up), every run, and per stage the medians, the parent's own spread and the paired difference (head minus parent) with its 95 % interval under `summary`; the compiler's VGPR / scratch / occupancy figures of the nine touched kernels at parent and head; two earlier sessions (the header alone; a branching form that was not kept) under `earlier_sessions`"),
     (r"^workspace_carver_ab\.json$", "the host-side workspace carver (`Carver` in `csrc/common.h`, HISTORY §30; no kernel changes) against the parent commit's library: interleaved pairs of fresh `bench.py --stage raster` / `map_step` processes on one box (200 steps, 20 warm-up), every run, and per stage the medians, the parent's own spread and the paired difference (head minus parent) with its 95 % interval under `summary`"),
     (r"^dead_marks_share\.json$", "the forward's dead marks after one S2 window of five views, read through `introspect.payload_state` (`idead` against `imask`, bounded by `n_contrib_c`): {dm_share}"),
     (r"^dead_marks_share_room\.json$", "the same share on the reconstructed room of `tools/scene_lists.py`, its views rendered at C = 8 (colour table padded by zero columns) so that the wide forward marks: {dm_room}"),
