@@ -116,6 +116,19 @@ struct DensifyGroups {           // the 8 groups of GaussianModel.training_setup
 };
 enum { G_XYZ = 0, G_FDC, G_FREST, G_OPACITY, G_MARKER, G_KP, G_SCALING, G_ROTATION };
 
+// Adam moments of destination row d of group gq: those of source row i when `keep`, zero otherwise (every new row starts from
+// zero).  The source is read only under `keep`: m_in is NULL where an empty model with state is appended to
+__device__ __forceinline__ void moments_row(const DensifyGroups& G, int gq, size_t i, size_t d, bool keep)
+{
+    const int w = G.width[gq];
+    float* md = G.m_out[gq] + (size_t)w * d;
+    float* vd = G.v_out[gq] + (size_t)w * d;
+    for (int k = 0; k < w; ++k) {
+        md[k] = keep ? G.m_in[gq][(size_t)w * i + k] : 0.0f;
+        vd[k] = keep ? G.v_in[gq][(size_t)w * i + k] : 0.0f;
+    }
+}
+
 __global__ void __launch_bounds__(DN_BLOCK)
 densify_gather_kernel(int P, const uint32_t* __restrict__ flags, const uint32_t* __restrict__ incl, DensifyGroups G,
                       const float* __restrict__ unit_noise /*[2,P,3] or NULL*/, uint64_t seed, uint64_t stream_id,
@@ -162,16 +175,7 @@ densify_gather_kernel(int P, const uint32_t* __restrict__ flags, const uint32_t*
         } else {
             for (int k = 0; k < w; ++k) dst[k] = src[k];
         }
-        if (G.m_in[gq]) {   // Adam moments: originals keep theirs, every new row starts from zero
-            const float* ms = G.m_in[gq] + (size_t)w * i;
-            const float* vs = G.v_in[gq] + (size_t)w * i;
-            float* md = G.m_out[gq] + (size_t)w * d;
-            float* vd = G.v_out[gq] + (size_t)w * d;
-            for (int k = 0; k < w; ++k) {
-                md[k] = sec == 0 ? ms[k] : 0.0f;
-                vd[k] = sec == 0 ? vs[k] : 0.0f;
-            }
-        }
+        if (G.m_in[gq]) moments_row(G, gq, i, d, sec == 0);   // originals keep their moments
     }
 }
 
@@ -237,14 +241,7 @@ model_append_kernel(int P, int N, DensifyGroups G, AppendRows X)
         const float* src = (old ? G.in[gq] : X.extra[gq]) + (size_t)w * r;
         float* dst = G.out[gq] + (size_t)w * d;
         for (int k = 0; k < w; ++k) dst[k] = src[k];
-        if (G.m_out[gq]) {
-            float* md = G.m_out[gq] + (size_t)w * d;
-            float* vd = G.v_out[gq] + (size_t)w * d;
-            for (int k = 0; k < w; ++k) {
-                md[k] = old ? G.m_in[gq][(size_t)w * r + k] : 0.0f;
-                vd[k] = old ? G.v_in[gq][(size_t)w * r + k] : 0.0f;
-            }
-        }
+        if (G.m_out[gq]) moments_row(G, gq, r, d, old);
     }
 }
 
@@ -294,6 +291,18 @@ __device__ __forceinline__ void adam_element(const AdamTable& T, int gq, float g
     p -= T.step_size[gq] * (m / denom);
 }
 
+// element k of group gq at any alignment: the key gate of its row, adam_element, three stores
+__device__ __forceinline__ void adam_one(const AdamTable& T, int gq, unsigned long long k)
+{
+    float g = T.grad[gq][k];
+    if (T.gate[gq] && T.gate[gq][k / (unsigned)T.row_width[gq]] > T.gate_thr) g = 0.0f;   // train_gaussians.py:231-234
+    float m = T.m[gq][k], v = T.v[gq][k], p = T.param[gq][k];
+    adam_element(T, gq, g, m, v, p);
+    T.m[gq][k] = m;
+    T.v[gq][k] = v;
+    T.param[gq][k] = p;
+}
+
 // scalar form: any alignment
 // `Gate`: empty, or (const uint32_t* status) — the device copy of a bounded status block (splatraster_adam_step_gated): while its
 // overflow word is set every block leaves before it touches a parameter, a moment or max_radii2D
@@ -313,14 +322,7 @@ adam_kernel(AdamTable T, unsigned long long total, Gate... gate)
         int gq = 0;
 #pragma unroll 1
         while (gq + 1 < T.n && e >= T.end[gq]) ++gq;
-        const unsigned long long k = e - (gq ? T.end[gq - 1] : 0ull);
-        float g = T.grad[gq][k];
-        if (T.gate[gq] && T.gate[gq][k / (unsigned)T.row_width[gq]] > T.gate_thr) g = 0.0f;   // train_gaussians.py:231-234
-        float m = T.m[gq][k], v = T.v[gq][k], p = T.param[gq][k];
-        adam_element(T, gq, g, m, v, p);
-        T.m[gq][k] = m;
-        T.v[gq][k] = v;
-        T.param[gq][k] = p;
+        adam_one(T, gq, e - (gq ? T.end[gq - 1] : 0ull));
     }
 }
 
@@ -350,15 +352,15 @@ adam_quad_kernel(AdamTable T, AdamQuads Q, unsigned long long total_quads, Gate.
         while (gq + 1 < T.n && q >= Q.qend[gq]) ++gq;
         const unsigned long long k0 = (q - (gq ? Q.qend[gq - 1] : 0ull)) * 4ull;
         const long long left = Q.numel[gq] - (long long)k0;
-        const float* gate = T.gate[gq];
-        unsigned long long row = 0;
-        int rem = 0;
-        const int rw = T.row_width[gq];
-        if (gate) {
-            row = k0 / (unsigned)rw;
-            rem = (int)(k0 - row * (unsigned)rw);
-        }
         if (left >= 4) {
+            const float* gate = T.gate[gq];   // the key gate's row of the quad's first element, then a running counter: one division
+            unsigned long long row = 0;
+            int rem = 0;
+            const int rw = T.row_width[gq];
+            if (gate) {
+                row = k0 / (unsigned)rw;
+                rem = (int)(k0 - row * (unsigned)rw);
+            }
             float4 g4 = *reinterpret_cast<const float4*>(T.grad[gq] + k0);
             float4 m4 = *reinterpret_cast<const float4*>(T.m[gq] + k0);
             float4 v4 = *reinterpret_cast<const float4*>(T.v[gq] + k0);
@@ -376,20 +378,8 @@ adam_quad_kernel(AdamTable T, AdamQuads Q, unsigned long long total_quads, Gate.
             *reinterpret_cast<float4*>(T.m[gq] + k0) = make_float4(m[0], m[1], m[2], m[3]);
             *reinterpret_cast<float4*>(T.v[gq] + k0) = make_float4(v[0], v[1], v[2], v[3]);
             *reinterpret_cast<float4*>(T.param[gq] + k0) = make_float4(p[0], p[1], p[2], p[3]);
-        } else {
-            for (long long j = 0; j < left; ++j) {
-                const unsigned long long k = k0 + (unsigned long long)j;
-                float g = T.grad[gq][k];
-                if (gate) {
-                    if (gate[row] > T.gate_thr) g = 0.0f;
-                    if (++rem == rw) { rem = 0; ++row; }
-                }
-                float m = T.m[gq][k], v = T.v[gq][k], p = T.param[gq][k];
-                adam_element(T, gq, g, m, v, p);
-                T.m[gq][k] = m;
-                T.v[gq][k] = v;
-                T.param[gq][k] = p;
-            }
+        } else {   // the group's last, partial quad: at most three elements
+            for (long long j = 0; j < left; ++j) adam_one(T, gq, k0 + (unsigned long long)j);
         }
     }
 }
@@ -554,6 +544,36 @@ int splatraster_densify_plan_thresholds(const splatraster_model* model, const fl
     return st;
 }
 
+// slot k (G_XYZ ...) of a model struct, or of the moments struct of the same layout
+static float* model_slot(const splatraster_model* m, int k)
+{
+    float* const p[8] = {m->xyz, m->f_dc, m->f_rest, m->opacity, m->marker, m->kp_score, m->scaling, m->rotation};
+    return p[k];
+}
+
+// The group table of a model, its moments (both NULL, or both given) and the three outputs: widths, slots, and the rule that a
+// group carries Adam state only when BOTH moments are given (the marker never has any in map()).  State in but no state out:
+// SPLATRASTER_ERR_BAD_ARG.  Which parameter outputs a call needs is its caller's check.
+static int densify_groups(const splatraster_model* model, const splatraster_model* exp_avg, const splatraster_model* exp_avg_sq,
+                          const splatraster_model* out_model, const splatraster_model* out_exp_avg,
+                          const splatraster_model* out_exp_avg_sq, DensifyGroups& G)
+{
+    const int widths[8] = {3, 3, model->f_rest_width, 1, model->marker_width, model->kp_width, model->scaling_width, 4};
+    G = DensifyGroups{};
+    for (int k = 0; k < 8; ++k) {
+        G.width[k] = widths[k];
+        G.in[k] = model_slot(model, k);
+        G.out[k] = model_slot(out_model, k);
+        if (!exp_avg || !model_slot(exp_avg, k) || !model_slot(exp_avg_sq, k)) continue;
+        G.m_in[k] = model_slot(exp_avg, k);
+        G.v_in[k] = model_slot(exp_avg_sq, k);
+        G.m_out[k] = model_slot(out_exp_avg, k);
+        G.v_out[k] = model_slot(out_exp_avg_sq, k);
+        if (!G.m_out[k] || !G.v_out[k]) return SPLATRASTER_ERR_BAD_ARG;
+    }
+    return SPLATRASTER_OK;
+}
+
 int splatraster_densify_apply(const splatraster_model* model, const splatraster_model* exp_avg,
                               const splatraster_model* exp_avg_sq, const float* unit_noise, uint64_t seed,
                               uint64_t draw_id, void* workspace, int32_t new_P, splatraster_model* out_model,
@@ -566,29 +586,11 @@ int splatraster_densify_apply(const splatraster_model* model, const splatraster_
     if (model->P == 0 || new_P == 0) return SPLATRASTER_OK;
     if (!workspace || (exp_avg == nullptr) != (exp_avg_sq == nullptr)) return SPLATRASTER_ERR_BAD_ARG;
     if (exp_avg && (!out_exp_avg || !out_exp_avg_sq)) return SPLATRASTER_ERR_BAD_ARG;
-    const int widths[8] = {3, 3, model->f_rest_width, 1, model->marker_width, model->kp_width, model->scaling_width, 4};
-    auto ptrs = [](const splatraster_model* m, const float* (&p)[8]) {
-        p[0] = m->xyz; p[1] = m->f_dc; p[2] = m->f_rest; p[3] = m->opacity; p[4] = m->marker; p[5] = m->kp_score;
-        p[6] = m->scaling; p[7] = m->rotation;
-    };
-    DensifyGroups G{};
-    const float *in[8], *out[8], *mi[8] = {}, *vi[8] = {}, *mo[8] = {}, *vo[8] = {};
-    ptrs(model, in);
-    ptrs(out_model, out);
-    if (exp_avg) { ptrs(exp_avg, mi); ptrs(exp_avg_sq, vi); ptrs(out_exp_avg, mo); ptrs(out_exp_avg_sq, vo); }
-    for (int k = 0; k < 8; ++k) {
-        G.width[k] = widths[k];
-        G.in[k] = in[k];
-        G.out[k] = const_cast<float*>(out[k]);
-        if (widths[k] > 0 && in[k] && !out[k]) return SPLATRASTER_ERR_BAD_ARG;
-        // a group carries Adam state only when BOTH moments are given (the marker never has any in map())
-        const bool has = mi[k] && vi[k];
-        if (has && (!mo[k] || !vo[k])) return SPLATRASTER_ERR_BAD_ARG;
-        G.m_in[k] = has ? mi[k] : nullptr;
-        G.v_in[k] = has ? vi[k] : nullptr;
-        G.m_out[k] = has ? const_cast<float*>(mo[k]) : nullptr;
-        G.v_out[k] = has ? const_cast<float*>(vo[k]) : nullptr;
-    }
+    DensifyGroups G;
+    st = densify_groups(model, exp_avg, exp_avg_sq, out_model, out_exp_avg, out_exp_avg_sq, G);
+    if (st) return st;
+    for (int k = 0; k < 8; ++k)   // a group with rows in needs its output
+        if (G.width[k] > 0 && G.in[k] && !G.out[k]) return SPLATRASTER_ERR_BAD_ARG;
     return densify_apply(model->P, G, unit_noise, seed, draw_id, workspace, source_row, source_kind,
                          reinterpret_cast<hipStream_t>(stream));
 }
@@ -608,68 +610,53 @@ int splatraster_model_append(const splatraster_model* model, const splatraster_m
         model->kp_width != extra->kp_width || model->scaling_width != extra->scaling_width)
         return SPLATRASTER_ERR_BAD_ARG;
     if ((int64_t)model->P + (int64_t)extra->P >= ((int64_t)1 << 31)) return SPLATRASTER_ERR_OVERFLOW;
-    const int widths[8] = {3, 3, model->f_rest_width, 1, model->marker_width, model->kp_width, model->scaling_width, 4};
-    auto ptrs = [](const splatraster_model* m, const float* (&p)[8]) {
-        p[0] = m->xyz; p[1] = m->f_dc; p[2] = m->f_rest; p[3] = m->opacity; p[4] = m->marker; p[5] = m->kp_score;
-        p[6] = m->scaling; p[7] = m->rotation;
-    };
-    DensifyGroups G{};
+    DensifyGroups G;
+    st = densify_groups(model, exp_avg, exp_avg_sq, out_model, out_exp_avg, out_exp_avg_sq, G);
+    if (st) return st;
     AppendRows X{};
-    const float *in[8], *ex[8], *out[8], *mi[8] = {}, *vi[8] = {}, *mo[8] = {}, *vo[8] = {};
-    ptrs(model, in);
-    ptrs(extra, ex);
-    ptrs(out_model, out);
-    if (exp_avg) { ptrs(exp_avg, mi); ptrs(exp_avg_sq, vi); ptrs(out_exp_avg, mo); ptrs(out_exp_avg_sq, vo); }
     for (int k = 0; k < 8; ++k) {
-        G.width[k] = widths[k];
-        G.in[k] = in[k];
-        X.extra[k] = ex[k];
-        G.out[k] = const_cast<float*>(out[k]);
-        if (widths[k] > 0 && !out[k]) return SPLATRASTER_ERR_BAD_ARG;
-        // a group carries Adam state only when BOTH moments are given (the marker never has any in map())
-        const bool has = mi[k] && vi[k];
-        if (has && (!mo[k] || !vo[k])) return SPLATRASTER_ERR_BAD_ARG;
-        G.m_in[k] = has ? mi[k] : nullptr;
-        G.v_in[k] = has ? vi[k] : nullptr;
-        G.m_out[k] = has ? const_cast<float*>(mo[k]) : nullptr;
-        G.v_out[k] = has ? const_cast<float*>(vo[k]) : nullptr;
+        X.extra[k] = model_slot(extra, k);
+        if (G.width[k] > 0 && !G.out[k]) return SPLATRASTER_ERR_BAD_ARG;   // the model may be empty: the rows come from `extra`
     }
     return model_append(model->P, extra->P, G, X, reinterpret_cast<hipStream_t>(stream));
+}
+
+// the four Adam entry points: the groups, then P / radii / max_radii2D (absent: 0 and NULL), then the status block where the
+// entry point is a gated one
+static int adam_entry(int32_t n_groups, const splatraster_adam_group* groups, double beta1, double beta2, double eps,
+                      float row_gate_threshold, int32_t P, const int32_t* radii, float* max_radii2D, bool gated, const void* status,
+                      void* stream)
+{
+    if (n_groups < 0 || n_groups > ADAM_MAX_GROUPS || (n_groups > 0 && !groups)) return SPLATRASTER_ERR_BAD_ARG;
+    if (P < 0 || (P > 0 && (!radii || !max_radii2D))) return SPLATRASTER_ERR_BAD_ARG;
+    if (gated && !status) return SPLATRASTER_ERR_BAD_ARG;
+    return adam_step(n_groups, groups, beta1, beta2, eps, row_gate_threshold, P, radii, max_radii2D, reinterpret_cast<hipStream_t>(stream),
+                     gated ? reinterpret_cast<const BoundedStatus*>(status)->dev : nullptr);
 }
 
 int splatraster_adam_step(int32_t n_groups, const splatraster_adam_group* groups, double beta1, double beta2, double eps,
                           float row_gate_threshold, void* stream)
 {
-    if (n_groups < 0 || n_groups > ADAM_MAX_GROUPS || (n_groups > 0 && !groups)) return SPLATRASTER_ERR_BAD_ARG;
-    if (n_groups == 0) return SPLATRASTER_OK;
-    return adam_step(n_groups, groups, beta1, beta2, eps, row_gate_threshold, 0, nullptr, nullptr, reinterpret_cast<hipStream_t>(stream));
+    return adam_entry(n_groups, groups, beta1, beta2, eps, row_gate_threshold, 0, nullptr, nullptr, false, nullptr, stream);
 }
 
 int splatraster_adam_step_radii(int32_t n_groups, const splatraster_adam_group* groups, double beta1, double beta2, double eps,
                                 float row_gate_threshold, int32_t P, const int32_t* radii, float* max_radii2D, void* stream)
 {
-    if (n_groups < 0 || n_groups > ADAM_MAX_GROUPS || (n_groups > 0 && !groups) || P < 0 || (P > 0 && (!radii || !max_radii2D)))
-        return SPLATRASTER_ERR_BAD_ARG;
-    return adam_step(n_groups, groups, beta1, beta2, eps, row_gate_threshold, P, radii, max_radii2D, reinterpret_cast<hipStream_t>(stream));
+    return adam_entry(n_groups, groups, beta1, beta2, eps, row_gate_threshold, P, radii, max_radii2D, false, nullptr, stream);
 }
 
 int splatraster_adam_step_gated(int32_t n_groups, const splatraster_adam_group* groups, double beta1, double beta2, double eps,
                                 float row_gate_threshold, const void* status, void* stream)
 {
-    if (n_groups < 0 || n_groups > ADAM_MAX_GROUPS || (n_groups > 0 && !groups) || !status) return SPLATRASTER_ERR_BAD_ARG;
-    if (n_groups == 0) return SPLATRASTER_OK;
-    return adam_step(n_groups, groups, beta1, beta2, eps, row_gate_threshold, 0, nullptr, nullptr, reinterpret_cast<hipStream_t>(stream),
-                     reinterpret_cast<const BoundedStatus*>(status)->dev);
+    return adam_entry(n_groups, groups, beta1, beta2, eps, row_gate_threshold, 0, nullptr, nullptr, true, status, stream);
 }
 
 int splatraster_adam_step_radii_gated(int32_t n_groups, const splatraster_adam_group* groups, double beta1, double beta2, double eps,
                                       float row_gate_threshold, int32_t P, const int32_t* radii, float* max_radii2D,
                                       const void* status, void* stream)
 {
-    if (n_groups < 0 || n_groups > ADAM_MAX_GROUPS || (n_groups > 0 && !groups) || P < 0 || (P > 0 && (!radii || !max_radii2D)) || !status)
-        return SPLATRASTER_ERR_BAD_ARG;
-    return adam_step(n_groups, groups, beta1, beta2, eps, row_gate_threshold, P, radii, max_radii2D, reinterpret_cast<hipStream_t>(stream),
-                     reinterpret_cast<const BoundedStatus*>(status)->dev);
+    return adam_entry(n_groups, groups, beta1, beta2, eps, row_gate_threshold, P, radii, max_radii2D, true, status, stream);
 }
 
 size_t splatraster_isotropic_loss_workspace_bytes(int32_t P) { return isotropic_workspace_bytes(P); }

@@ -1,7 +1,10 @@
 """Device-side pieces of SplatLoc's densification bookkeeping."""
 from __future__ import annotations
 
+import ctypes as C
+
 import torch
+from torch import nn
 
 from . import _native
 from ._host import _ptr, _require_gpu, _stream, _on_device
@@ -38,7 +41,6 @@ def add_densification_stats_window(viewspace_grads, radii, xyz_gradient_accum, d
     """`add_densification_stats` for the views of a window in ONE launch (view order = the reference's loop order,
     train_gaussians.py:238-245).  `xyz_gradient_accum = denom = None`: only `max_radii2D` is updated — the statistics
     line of SplatLoc.color_refinement (train_gaussians.py:293-294); `viewspace_grads` may then be None."""
-    import ctypes as C
     radii = list(radii)
     V = len(radii)
     if V == 0:
@@ -89,7 +91,6 @@ def _row_width(t: torch.Tensor) -> int:
 
 
 def _model_struct(tensors: dict, P: int, widths: dict):
-    import ctypes as C
     m = _native.Model()
     m.P, m.f_rest_width, m.marker_width = P, widths["f_rest"], widths["marker"]
     m.kp_width, m.scaling_width = widths["kp_score"], widths["scaling"]
@@ -99,6 +100,43 @@ def _model_struct(tensors: dict, P: int, widths: dict):
     return m
 
 
+def _model_refs(rows: int, widths: dict, *sets):
+    """`Model` structs by reference for dicts by group name of tensors with `rows` rows, as splatraster_densify_apply and
+    splatraster_model_append take them; NULL for an empty dict (moments: no group has Adam state)."""
+    return [C.byref(_model_struct(t, rows, widths)) if t else None for t in sets]
+
+
+def _moments(opt, groups: dict):
+    """The optimizer's (exp_avg, exp_avg_sq) by group name; a group without Adam state is missing from both."""
+    m, v = {}, {}
+    for k in GROUPS:
+        st = opt.state.get(groups[k]["params"][0], None)
+        if st is not None and "exp_avg" in st:
+            m[k], v[k] = st["exp_avg"], st["exp_avg_sq"]
+    return m, v
+
+
+def _rebind(gaussians, groups: dict, k: str, new_param, new_m=None, new_v=None) -> None:
+    """The optimizer surgery for group `k`: `new_param` becomes a new `nn.Parameter` bound to the optimizer's group and to the
+    model; the old parameter's state moves to it with its `step` counter, and with `new_m` / `new_v` as moments where given."""
+    opt, grp = gaussians.optimizer, groups[k]
+    st = opt.state.pop(grp["params"][0], None)
+    p = nn.Parameter(new_param.requires_grad_(True))
+    grp["params"][0] = p
+    if st is not None:
+        if new_m is not None:
+            st["exp_avg"], st["exp_avg_sq"] = new_m, new_v
+        opt.state[p] = st
+    setattr(gaussians, ATTR[k], p)
+
+
+def _reset_stats(gaussians, n: int, dev) -> None:
+    """densification_postfix's last lines (gaussian_model.py:585-587): the statistics start over at the new row count"""
+    gaussians.xyz_gradient_accum = torch.zeros((n, 1), device=dev)
+    gaussians.denom = torch.zeros((n, 1), device=dev)
+    gaussians.max_radii2D = torch.zeros((n,), device=dev)
+
+
 def densify_tensors(params: dict, exp_avg: dict, exp_avg_sq: dict, xyz_gradient_accum, denom, max_grad, min_opacity,
                     extent, max_screen_size, percent_dense, primitive_reg, unit_noise=None, seed: int = 0,
                     draw_id: int = 0, return_sources: bool = False):
@@ -106,7 +144,6 @@ def densify_tensors(params: dict, exp_avg: dict, exp_avg_sq: dict, xyz_gradient_
     ROCm tensors [P, ...]; a group without Adam state is missing (or None) in the two moment dicts.
     Returns (new_params, new_exp_avg, new_exp_avg_sq[, source_row, source_kind]) — freshly allocated tensors
     in the reference's row order.  ONE device->host read (the new row count)."""
-    import ctypes as C
     lib = _native.load()
     xyz = params["xyz"]
     _require_gpu(xyz, "xyz")
@@ -147,17 +184,12 @@ def densify_tensors(params: dict, exp_avg: dict, exp_avg_sq: dict, xyz_gradient_
         if tuple(noise.shape) != (2, P, 3):
             raise RuntimeError("densify: unit_noise must be [2, P, 3]")
     if P and n:
-        m_in = _model_struct({k: exp_avg[k].contiguous() for k in has}, P, widths) if has else None
-        v_in = _model_struct({k: exp_avg_sq[k].contiguous() for k in has}, P, widths) if has else None
-        out = _model_struct(new_params, n, widths)
-        m_out = _model_struct(new_m, n, widths) if has else None
-        v_out = _model_struct(new_v, n, widths) if has else None
-        ref = lambda s: None if s is None else C.byref(s)  # noqa: E731
+        m_in, v_in = _model_refs(P, widths, {k: exp_avg[k].contiguous() for k in has}, {k: exp_avg_sq[k].contiguous() for k in has})
+        out, m_out, v_out = _model_refs(n, widths, new_params, new_m, new_v)
         with _on_device(dev):
             _native.check(lib.splatraster_densify_apply(
-                C.byref(src), ref(m_in), ref(v_in), _ptr(noise), C.c_uint64(int(seed)), C.c_uint64(int(draw_id)),
-                _ptr(ws), n, C.byref(out), ref(m_out), ref(v_out), _ptr(srow), _ptr(skind), _stream(dev)),
-                "densify_apply")
+                C.byref(src), m_in, v_in, _ptr(noise), C.c_uint64(int(seed)), C.c_uint64(int(draw_id)),
+                _ptr(ws), n, out, m_out, v_out, _ptr(srow), _ptr(skind), _stream(dev)), "densify_apply")
     if return_sources:
         return new_params, new_m, new_v, srow, skind
     return new_params, new_m, new_v
@@ -172,15 +204,10 @@ def densify_and_prune(gaussians, max_grad, min_opacity, extent, max_screen_size,
     `nn.Parameter`s bound to the model AND to the optimizer's groups, `exp_avg` / `exp_avg_sq` re-sized with
     zero rows for new points and the `step` counters carried over, statistics (incl. `max_radii2D`) zeroed.
     `draw_id` (default: an internal counter) distinguishes successive densifications under one `seed`."""
-    from torch import nn
     opt = gaussians.optimizer
     groups = {g["name"]: g for g in opt.param_groups}
     params = {k: getattr(gaussians, ATTR[k]).detach().contiguous() for k in GROUPS}
-    m, v = {}, {}
-    for k in GROUPS:
-        st = opt.state.get(groups[k]["params"][0], None)
-        if st is not None and "exp_avg" in st:
-            m[k], v[k] = st["exp_avg"], st["exp_avg_sq"]
+    m, v = _moments(opt, groups)
     if draw_id is None:
         draw_id = getattr(gaussians, "_splatloc_draws", 0)
         gaussians._splatloc_draws = draw_id + 1
@@ -188,21 +215,9 @@ def densify_and_prune(gaussians, max_grad, min_opacity, extent, max_screen_size,
                                           min_opacity, extent, max_screen_size, gaussians.percent_dense,
                                           gaussians.primitive_reg, unit_noise=unit_noise, seed=seed, draw_id=draw_id)
     for k in GROUPS:
-        grp = groups[k]
-        old = grp["params"][0]
-        st = opt.state.pop(old, None)
-        p = nn.Parameter(new_p[k].requires_grad_(True))
-        grp["params"][0] = p
-        if st is not None:
-            if k in new_m:
-                st["exp_avg"], st["exp_avg_sq"] = new_m[k], new_v[k]
-            opt.state[p] = st
-        setattr(gaussians, ATTR[k], p)
+        _rebind(gaussians, groups, k, new_p[k], new_m.get(k), new_v.get(k))
     n = new_p["xyz"].shape[0]
-    dev = new_p["xyz"].device
-    gaussians.xyz_gradient_accum = torch.zeros((n, 1), device=dev)
-    gaussians.denom = torch.zeros((n, 1), device=dev)
-    gaussians.max_radii2D = torch.zeros((n,), device=dev)
+    _reset_stats(gaussians, n, new_p["xyz"].device)
     return n
 
 
@@ -214,7 +229,6 @@ def reset_opacity_nonvisible(gaussians, visibility_filters) -> None:
     any of the filters keeps its ACTIVATED opacity as the new logit (`opacities_new[filter] = self.get_opacity[filter]`),
     every other one is reset to inverse_sigmoid(0.4).  A handful of elementwise device ops every ~2000 iterations:
     no kernel of its own, and no device->host synchronisation (the reference's boolean-mask stores each imply one)."""
-    from torch import nn
     op = gaussians._opacity.detach()
     act = torch.sigmoid(op)                                   # get_opacity
     x = torch.ones_like(act) * 0.4
@@ -225,19 +239,10 @@ def reset_opacity_nonvisible(gaussians, visibility_filters) -> None:
         seen = f if seen is None else (seen | f)
     if seen is not None:
         new = torch.where(seen.view(-1, 1), act, new)
-    opt = gaussians.optimizer
-    for grp in opt.param_groups:
-        if grp["name"] != "opacity":
-            continue
-        old = grp["params"][0]
-        st = opt.state.pop(old, None)
-        p = nn.Parameter(new.contiguous().requires_grad_(True))
-        grp["params"][0] = p
-        if st is not None:
-            st["exp_avg"] = torch.zeros_like(p)
-            st["exp_avg_sq"] = torch.zeros_like(p)
-            opt.state[p] = st
-        gaussians._opacity = p
+    groups = {g["name"]: g for g in gaussians.optimizer.param_groups}
+    if "opacity" in groups:
+        new = new.contiguous()
+        _rebind(gaussians, groups, "opacity", new, torch.zeros_like(new), torch.zeros_like(new))
 
 
 def extend_from_pcd(gaussians, fused_point_cloud, features, scales, rots, opacities, markers, kp_scores) -> int:
@@ -247,8 +252,6 @@ def extend_from_pcd(gaussians, fused_point_cloud, features, scales, rots, opacit
     that has state in ONE launch (the reference: a torch.cat per tensor and per moment), new `nn.Parameter`s are bound
     to the model and to the optimizer's groups with the `step` counters carried over, and the densification
     statistics are reset, exactly as densification_postfix does.  `features` is [N, 3, (max_sh_degree + 1)^2]."""
-    import ctypes as C
-    from torch import nn
     lib = _native.load()
     dev = fused_point_cloud.device
     _require_gpu(fused_point_cloud, "fused_point_cloud")
@@ -267,11 +270,7 @@ def extend_from_pcd(gaussians, fused_point_cloud, features, scales, rots, opacit
             raise RuntimeError(f"extend_from_pcd: group `{k}` has rows of {_row_width(params[k])} floats, the new rows {widths[k]}")
         if int(extra[k].shape[0]) != N:
             raise RuntimeError(f"extend_from_pcd: `{k}` has {int(extra[k].shape[0])} rows, expected {N}")
-    m, v = {}, {}
-    for k in GROUPS:
-        st = opt.state.get(groups[k]["params"][0], None)
-        if st is not None and "exp_avg" in st:
-            m[k], v[k] = st["exp_avg"].contiguous(), st["exp_avg_sq"].contiguous()
+    m, v = ({k: t.contiguous() for k, t in d.items()} for d in _moments(opt, groups))
     n = P + N
     f32 = dict(dtype=torch.float32, device=dev)
     new_p = {k: torch.empty((n,) + tuple(extra[k].shape[1:]), **f32) for k in GROUPS}
@@ -279,30 +278,12 @@ def extend_from_pcd(gaussians, fused_point_cloud, features, scales, rots, opacit
     new_m = {k: alloc(new_p[k]) for k in m}
     new_v = {k: alloc(new_p[k]) for k in m}
     if n:
-        src = _model_struct(params, P, widths)
-        ext = _model_struct(extra, N, widths)
-        out = _model_struct(new_p, n, widths)
-        has = bool(m)
-        m_in = _model_struct(m, P, widths) if has else None
-        v_in = _model_struct(v, P, widths) if has else None
-        m_out = _model_struct(new_m, n, widths) if has else None
-        v_out = _model_struct(new_v, n, widths) if has else None
-        ref = lambda s: None if s is None else C.byref(s)  # noqa: E731
+        src, m_in, v_in = _model_refs(P, widths, params, m, v)
+        ext, = _model_refs(N, widths, extra)
+        out, m_out, v_out = _model_refs(n, widths, new_p, new_m, new_v)
         with _on_device(dev):
-            _native.check(lib.splatraster_model_append(C.byref(src), ref(m_in), ref(v_in), C.byref(ext), C.byref(out),
-                                                       ref(m_out), ref(v_out), _stream(dev)), "model_append")
+            _native.check(lib.splatraster_model_append(src, m_in, v_in, ext, out, m_out, v_out, _stream(dev)), "model_append")
     for k in GROUPS:
-        grp = groups[k]
-        old = grp["params"][0]
-        st = opt.state.pop(old, None)
-        p = nn.Parameter(new_p[k].requires_grad_(True))
-        grp["params"][0] = p
-        if st is not None:
-            if k in new_m:
-                st["exp_avg"], st["exp_avg_sq"] = new_m[k], new_v[k]
-            opt.state[p] = st
-        setattr(gaussians, ATTR[k], p)
-    gaussians.xyz_gradient_accum = torch.zeros((n, 1), device=dev)
-    gaussians.denom = torch.zeros((n, 1), device=dev)
-    gaussians.max_radii2D = torch.zeros((n,), device=dev)
+        _rebind(gaussians, groups, k, new_p[k], new_m.get(k), new_v.get(k))
+    _reset_stats(gaussians, n, dev)
     return n

@@ -106,27 +106,17 @@ class Adam(torch.optim.Adam):
             gate = getattr(self, "_gate", None)
             if gate is not None and dev is not None and dev.index is not None and gate.device != dev:
                 raise RuntimeError(f"splatloc_amd.optim.Adam: the gate's status block lives on {gate.device}, the parameters on {dev}")
+            name, extra = "adam_step", []
             if radii_update is not None:      # the frame's max_radii2D line rides this launch (set_radii_update)
                 radii, max_radii = radii_update
                 dev = radii.device if dev is None else dev
-                with _on_device(dev):
-                    if gate is not None:
-                        _native.check(lib.splatraster_adam_step_radii_gated(
-                            len(entries), arr, C.c_double(betas[0]), C.c_double(betas[1]), C.c_double(eps), C.c_float(thr),
-                            int(radii.numel()), radii.data_ptr(), max_radii.data_ptr(), gate.handle, _stream(dev)), "adam_step_radii_gated")
-                    else:
-                        _native.check(lib.splatraster_adam_step_radii(len(entries), arr, C.c_double(betas[0]), C.c_double(betas[1]),
-                                                                      C.c_double(eps), C.c_float(thr), int(radii.numel()), radii.data_ptr(),
-                                                                      max_radii.data_ptr(), _stream(dev)), "adam_step_radii")
-            else:
-                with _on_device(dev):
-                    if gate is not None:
-                        _native.check(lib.splatraster_adam_step_gated(len(entries), arr, C.c_double(betas[0]), C.c_double(betas[1]),
-                                                                      C.c_double(eps), C.c_float(thr), gate.handle, _stream(dev)),
-                                      "adam_step_gated")
-                    else:
-                        _native.check(lib.splatraster_adam_step(len(entries), arr, C.c_double(betas[0]), C.c_double(betas[1]),
-                                                                C.c_double(eps), C.c_float(thr), _stream(dev)), "adam_step")
+                name, extra = name + "_radii", [int(radii.numel()), radii.data_ptr(), max_radii.data_ptr()]
+            if gate is not None:
+                name, extra = name + "_gated", extra + [gate.handle]
+            with _on_device(dev):
+                _native.check(getattr(lib, "splatraster_" + name)(
+                    len(entries), arr, C.c_double(betas[0]), C.c_double(betas[1]), C.c_double(eps), C.c_float(thr), *extra,
+                    _stream(dev)), name)
         del keep
         return loss
 

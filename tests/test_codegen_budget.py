@@ -132,6 +132,24 @@ def test_loss_stage_kernels_keep_their_occupancy_and_lds():
     assert len(losses) == 6 and not [k for k in pose if "l1_rgbd_loss_kernel" in k], (list(losses), list(pose))
 
 
+def test_model_update_kernels_keep_their_occupancy():
+    """densify.hip since the scalar Adam element, the moments row, the group table and the Adam entry are each written once
+    (HISTORY.md §32): the same nine kernels, and the seven of the model update with nothing in scratch, no spill, no LDS and the full
+    8 waves per SIMD.  They are HBM-bound and hold no LDS, so occupancy and scratch are what their speed depends on.  VGPRs, each
+    kernel with its own copy of those steps -> with the shared ones: adam_kernel 26 -> 26 (both forms), adam_quad_kernel
+    46 -> 48 (both forms), densify_gather_kernel 38 -> 38, model_append_kernel 16 -> 16,
+    densify_flags_kernel 25 -> 25.  The two isotropic kernels are pinned with the loss stage above."""
+    u = _usage("densify.hip")
+    assert len(u) == 9, list(u)
+    for name in ("_ZN2sr11adam_kernelIJEEE", "_ZN2sr11adam_kernelIJPKjEEE", "_ZN2sr16adam_quad_kernelIJEEE",
+                 "_ZN2sr16adam_quad_kernelIJPKjEEE", "_ZN2sr21densify_gather_kernelE", "_ZN2sr19model_append_kernelE",
+                 "_ZN2sr20densify_flags_kernelE"):
+        k = _kernel(u, name)
+        assert k["ScratchSize"] == 0 and k["VGPRs Spill"] == 0 and k["SGPRs Spill"] == 0 and k["LDS Size"] == 0, (name, k)
+        assert k["Occupancy"] >= 8, (name, k)
+    assert len([k for k in u if "isotropic" in k]) == 2, list(u)
+
+
 def test_scan_and_sort_kernels_keep_their_registers_and_lds():
     """The scan, radix-sort and tile-order kernels since they take their wave scan, workgroup scan and digit ranks from scan.h and
     one rank body (HISTORY.md §29): nothing in scratch, no spill, and no kernel above the VGPRs or the LDS footprint, or below the
