@@ -1208,6 +1208,54 @@ int splatraster_sp_sample(int32_t B, int32_t Hc, int32_t Wc, const float* coarse
 int splatraster_sp_dense_descriptors(int32_t B, int32_t Hc, int32_t Wc, const float* coarse, int32_t row0, int32_t rows, float* out,
                                      void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- NetVLAD head: soft assignment, VLAD aggregation, whitening (csrc/netvlad_head.hip) ----------- */
+
+/* Everything behind NetVLAD's convolution stack, for B images per call, asynchronous on `stream`, nothing read back, no host
+ * synchronisation.  All tensors are contiguous float32 device arrays.  hloc's NetVLAD layer is not part of the reference tree, so it
+ * is unpinned; these definitions are this project's own contract, modelled on that layer:
+ *  inputs     features [B,D,N], the backbone's map with N = h w locations, channel-major; score_w [K,D]; score_b [K] or NULL;
+ *             centers [D,K].
+ *  assign     inv[b,n] = 1 / max(sqrt(sum_d x[d,n]^2), 1e-12); xh[d,n] = x[d,n] * inv[b,n];
+ *             s[k,n] = sum_d score_w[k,d] * xh[d,n] (+ score_b[k]); a = softmax of s over k in float32: m = max, e_k = expf(s_k - m),
+ *             the sum in ascending k, a_k = e_k / sum.  Outputs assign [B,K,N] and inv_norm [B,N].  An all-zero location has xh = 0 and
+ *             takes part with a = softmax(score_b).
+ *  aggregate  V[d,k] = sum_n a[k,n] * xh[d,n] - centers[d,k] * sum_n a[k,n]: the GEMM form, which equals the literal
+ *             sum_n a[k,n] (xh[d,n] - centers[d,k]) up to rounding; the two differ in a column whose residuals cancel (the literal
+ *             form subtracts before it sums and keeps the small result's relative accuracy; this form's error is relative to
+ *             sum |a xh| + |c| sum a).  Flag INTRANORM: V[:,k] /= max(||V[:,k]||_2, 1e-12) over d.  Flattened as v[b, d * K + k].
+ *             Flag L2NORM: v /= max(||v||_2, 1e-12).  Flags 0: the raw V.  Reads features, assign, inv_norm and centers; never
+ *             recomputes the softmax.
+ *  project    y[b,o] = sum_i weight[o,i] * x[b,i] (+ bias[o]), weight [O,I] (nn.Linear's layout), bias [O] or NULL.  Flag L2NORM:
+ *             y /= max(||y||_2, 1e-12).  x must not alias y.
+ * Limits: 1 <= K <= SPLATRASTER_NETVLAD_MAX_K; D, N, O, I >= 1; B >= 0 (B = 0 returns SPLATRASTER_OK without a launch);
+ * D * K < 2^31; one workgroup per (image, step of locations), per (image, block of d rows) and per (tile of o rows, slice of I, block of
+ * images): each of these counts < 2^31.  Anything else, an unknown flag bit, a NULL or 4-byte-misaligned pointer, or a workspace
+ * below the query's answer: SPLATRASTER_ERR_BAD_ARG before any launch.  Non-finite inputs are outside the contract (no loop depends
+ * on data: they terminate).
+ * Determinism: no float atomics; every sum has an order fixed by the shape alone; results are bit-identical run to run, and row b
+ * of every output is bit-identical whatever B is. */
+#define SPLATRASTER_NETVLAD_MAX_K 64
+#define SPLATRASTER_NETVLAD_INTRANORM 1
+#define SPLATRASTER_NETVLAD_L2NORM 2
+/* Host only, never touches the device: the tile constants the launch geometry is built from.  n_step: locations per assign
+ * workgroup and per aggregation step; d_tile: d rows per aggregation workgroup; i_slice: columns of I per projection workgroup
+ * (the slices' partial sums are added in ascending order); o_tile / b_tile: weight rows and images of a projection tile. */
+int splatraster_netvlad_tiles(int32_t* n_step, int32_t* d_tile, int32_t* i_slice, int32_t* o_tile, int32_t* b_tile);
+/* Host only: bytes of workspace that serve every call below for B images of a [D,N] map, K clusters and an O x (D K) whitening
+ * (pass O = 1 for a head without one).  Only project uses it (I / i_slice partial sums per output, rounded up); assign and aggregate
+ * accept any workspace, NULL included.  (Named _size: the *_bytes queries are the ones tabulated in tests/test_host_workspace_sizes.py;
+ * this one's sizes are pinned by tests/test_host_netvlad_head.py.) */
+int splatraster_netvlad_workspace_size(int32_t B, int32_t D, int32_t K, int32_t N, int32_t O, size_t* bytes);
+int splatraster_netvlad_assign(int32_t B, int32_t D, int32_t K, int32_t N, const float* features, const float* score_w,
+                               const float* score_b, float* assign, float* inv_norm, void* workspace, size_t workspace_bytes,
+                               void* stream);
+int splatraster_netvlad_aggregate(int32_t B, int32_t D, int32_t K, int32_t N, const float* features, const float* assign,
+                                  const float* inv_norm, const float* centers, int32_t flags, float* v, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+/* float4 loads where I % 4 == 0 and x and weight are 16-byte aligned, scalar loads otherwise: the same sums either way. */
+int splatraster_netvlad_project(int32_t B, int32_t O, int64_t I, const float* x, const float* weight, const float* bias, int32_t flags,
+                                float* y, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- misc ---------------------------------------------------------------------------- */
 
 /* The decoupled look-backs of the one-pass scan and of the one-sweep radix sort never give up with a

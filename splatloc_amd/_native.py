@@ -235,6 +235,11 @@ SYMBOLS = {
     "splatraster_sp_select": (C.c_int, [_i32] * 3 + [_vp, C.c_float, _i32, _i32] + [_vp] * 5 + [_sz, _vp]),
     "splatraster_sp_sample": (C.c_int, [_i32] * 3 + [_vp, _i32] + [_vp] * 4 + [_sz, _vp]),
     "splatraster_sp_dense_descriptors": (C.c_int, [_i32] * 3 + [_vp, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "splatraster_netvlad_tiles": (C.c_int, [C.POINTER(_i32)] * 5),
+    "splatraster_netvlad_workspace_size": (C.c_int, [_i32] * 5 + [C.POINTER(_sz)]),
+    "splatraster_netvlad_assign": (C.c_int, [_i32] * 4 + [_vp] * 6 + [_sz, _vp]),
+    "splatraster_netvlad_aggregate": (C.c_int, [_i32] * 4 + [_vp] * 4 + [_i32, _vp, _vp, _sz, _vp]),
+    "splatraster_netvlad_project": (C.c_int, [_i32, _i32, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _sz, _vp]),
     "splatraster_lsap_workspace_bytes": (_sz, [_i32, _vp]),
     "splatraster_lsap": (C.c_int, [_i32, _vp, _vp, _i32] + [_vp] * 6),
     "splatraster_debug_set_lsap_lds": (C.c_int, [C.c_int]),
