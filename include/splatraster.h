@@ -1256,6 +1256,43 @@ int splatraster_netvlad_aggregate(int32_t B, int32_t D, int32_t K, int32_t N, co
 int splatraster_netvlad_project(int32_t B, int32_t O, int64_t I, const float* x, const float* weight, const float* bias, int32_t flags,
                                 float* y, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- convolution backbones: SuperPoint's encoder, NetVLAD's VGG16 trunk (csrc/conv2d.hip) --------- */
+
+/* The layer both networks repeat, for B images per call, asynchronous on `stream`, nothing read back, no host synchronisation, no
+ * float atomics.  All tensors are contiguous float32 NCHW device arrays.  Neither network's source is part of the reference tree, so
+ * parity is unpinned; the layer below and the two layer tables of splatloc_amd/convnet.py are this project's
+ * own contract.
+ *  conv2d      out[b,co,y,x] = sum_{ci,ky,kx} weight[co,ci,ky,kx] * xp[b,ci,y + ky - p,x + kx - p] (+ bias[co]): cross-correlation,
+ *              stride 1, ksize 1 or 3, p = (ksize - 1) / 2, xp = x padded with ZEROS; weight [Cout,Cin,ksize,ksize] (torch's layout),
+ *              bias [Cout] or NULL.  Flag RELU: max(out, 0).  Flag POOL2: a 2x2 max pool with stride 2 in floor mode, applied after
+ *              bias and ReLU, from the accumulators: out is [B,Cout,H/2,W/2], an odd last row or column is dropped, and the
+ *              unpooled map is never written.  out must not alias x.
+ *  THE CHAIN   every output is one float32 fmaf chain from zero, then + bias.  With C = ci_chunk of splatraster_conv2d_tiles:
+ *                  acc = 0
+ *                  for c0 = 0, C, 2 C, ... < Cin:  for ky = 0 .. ksize - 1:  for kx = 0 .. ksize - 1:  for ci = c0 .. c0 + C - 1:
+ *                      acc = fmaf(weight[co,ci,ky,kx], xp[b,ci,y + ky - p,x + kx - p], acc)
+ *                  out = acc + bias[co]
+ *              where a channel ci >= Cin and a padded tap contribute fmaf(0, 0, acc) and fmaf(w, 0, acc), which are acc exactly: a
+ *              border pixel and a channel tail follow the same statement.  The order is a function of (Cin, ksize) and C alone: not of
+ *              B, of the pixel's position, of Cout or of the launch.  Cin = 1 and Cin = 3 take the same path (a chunk padded with
+ *              zero channels), so there is no path hook.
+ * Limits: B >= 0 (B = 0 returns SPLATRASTER_OK without a launch); Cin, Cout, H, W >= 1 (H, W >= 2 with POOL2); Cin H W, Cout H W and
+ * ci_chunk H W < 2^31; one workgroup per (image, tile of channels, tile of pixels): that count < 2^31.  Anything else, a ksize outside
+ * {1, 3}, an unknown flag bit, a NULL x, weight or out, or a 4-byte-misaligned pointer: SPLATRASTER_ERR_BAD_ARG before any device work.
+ * The layer uses no workspace: any `workspace`, NULL included, is accepted.  All offsets are 64-bit.  Results are bit-identical run
+ * to run, and image b of the output is bit-identical whatever B is. */
+#define SPLATRASTER_CONV_RELU 1
+#define SPLATRASTER_CONV_POOL2 2
+/* Host only, never touches the device: the launch geometry.  co_tile: output channels per workgroup; px_rows x px_cols: its tile of
+ * output pixels (both even: a pool window never straddles a tile); ci_chunk: input channels staged per step, the C of the chain. */
+int splatraster_conv2d_tiles(int32_t* co_tile, int32_t* px_rows, int32_t* px_cols, int32_t* ci_chunk);
+int splatraster_conv2d(int32_t B, int32_t Cin, int32_t Cout, int32_t H, int32_t W, int32_t ksize, const float* x, const float* weight,
+                       const float* bias, int32_t flags, float* out, void* workspace, size_t workspace_bytes, void* stream);
+/* NetVLAD's input normalisation: rgb [B,3,H,W] in [0,1] -> out[b,c,y,x] = min(max(rgb * 255, 0), 255) - mean[c] with mean =
+ * (123.68, 116.779, 103.939) in R, G, B order; three float32 operations, each rounded on its own.  A pass of its own, so the first
+ * convolution pads with zeros and not with -mean.  B >= 0; H, W >= 1; 3 H W < 2^31; out may alias rgb. */
+int splatraster_netvlad_preprocess(int32_t B, int32_t H, int32_t W, const float* rgb, float* out, void* stream);
+
 /* ---- misc ---------------------------------------------------------------------------- */
 
 /* The decoupled look-backs of the one-pass scan and of the one-sweep radix sort never give up with a

@@ -240,6 +240,9 @@ SYMBOLS = {
     "splatraster_netvlad_assign": (C.c_int, [_i32] * 4 + [_vp] * 6 + [_sz, _vp]),
     "splatraster_netvlad_aggregate": (C.c_int, [_i32] * 4 + [_vp] * 4 + [_i32, _vp, _vp, _sz, _vp]),
     "splatraster_netvlad_project": (C.c_int, [_i32, _i32, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _sz, _vp]),
+    "splatraster_conv2d_tiles": (C.c_int, [C.POINTER(_i32)] * 4),
+    "splatraster_conv2d": (C.c_int, [_i32] * 6 + [_vp] * 3 + [_i32, _vp, _vp, _sz, _vp]),
+    "splatraster_netvlad_preprocess": (C.c_int, [_i32] * 3 + [_vp] * 3),
     "splatraster_lsap_workspace_bytes": (_sz, [_i32, _vp]),
     "splatraster_lsap": (C.c_int, [_i32, _vp, _vp, _i32] + [_vp] * 6),
     "splatraster_debug_set_lsap_lds": (C.c_int, [C.c_int]),

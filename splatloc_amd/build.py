@@ -36,10 +36,10 @@ COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-munsafe-fp-a
 # extra defines for experiments (tools/ablate.py sets this before build(force=True) into another LIB_DIR)
 EXTRA_FLAGS: list = []
 NO_CONTRACT = {"preprocess.hip", "binning.hip", "binsort.hip", "knn.hip", "selection.hip", "matching.hip", "pnp.hip", "fusion.hip",
-               "fusion_mesh.hip", "image_ops.hip", "superpoint_head.hip", "netvlad_head.hip"}
+               "fusion_mesh.hip", "image_ops.hip", "superpoint_head.hip", "netvlad_head.hip", "conv2d.hip"}
 SOURCES = ["preprocess.hip", "preprocess_bwd.hip", "camera_bwd.hip", "window_joint_bwd.hip", "scan_sort.hip", "binning.hip", "binsort.hip", "composite_fwd.hip",
            "composite_bwd.hip", "knn.hip", "activations.hip", "losses.hip", "densify.hip", "pose.hip", "grid_encoding.hip",
-           "decoder.hip", "selection.hip", "matching.hip", "pnp.hip", "fusion.hip", "fusion_mesh.hip", "image_ops.hip", "superpoint_head.hip", "netvlad_head.hip", "retrieval.hip", "bounded.hip", "capi.hip"]
+           "decoder.hip", "selection.hip", "matching.hip", "pnp.hip", "fusion.hip", "fusion_mesh.hip", "image_ops.hip", "superpoint_head.hip", "netvlad_head.hip", "conv2d.hip", "retrieval.hip", "bounded.hip", "capi.hip"]
 
 
 def have_hipcc() -> bool:

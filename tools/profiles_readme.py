@@ -36,6 +36,7 @@ WHAT = [   # (file name regex, description; {placeholders} are filled by the ext
     (r"^localize_time\.json$", "localisation (`tools/localize_time.py`), HIP events, interleaved medians: fused retrieval against `torch.einsum(...).topk` and the batched `Localizer.localize` against the per-query loop: {localize}"),
     (r"^image_ops_time\.json$", "frame preparation (`tools/time_image_ops.py`), HIP events, alternating medians, ms per call: `image_ops.compute_grad_masks` against the per-block loop of `Camera.compute_grad_mask` written with torch operators: {imageops}"),
     (r"^netvlad_head_time\.json$", "NetVLAD head (`tools/time_netvlad_head.py`), D = 512, K = 64, N = 1200, O = 4096, alternating medians of 10 rounds, ms per call, device events: `NetVLADHead` against the same head written with torch operators on the device (where two figures follow: hloc's literal form / the GEMM form); `project` with the byte floor 4 O I bytes over 6.29 TB/s: {nvhead}"),
+    (r"^convnet_time\.json$", "convolution backbones (`tools/time_convnet.py`), 480 x 640 frames, alternating medians of 10 rounds, ms per call, device events: `convnet` against `torch.nn.functional.conv2d` (+ relu, + max_pool2d) in float32 on the device, with the MFMA floor 2 k k Cin Cout H W B over 157.3 TF: {convnet}"),
     (r"^superpoint_head_time\.json$", "SuperPoint head (`tools/time_superpoint_head.py`), 480 x 640 frames, alternating medians of 10 rounds, ms per call, device events (host clock to the end of a synchronise in brackets): `superpoint.detect` against the same head written with torch operators on the device, its `nonzero` wait included; `dense_descriptors` with the bytes it writes: {sphead}"),
     (r"^pose_window_time\.json$", "pose refinement of 8 query frames at 640x480, `pose.refine_poses` per `window` against the loop of 8 `pose.refine_pose` calls, ms per frame-iteration, host clock around a device synchronise, alternating regions (`tools/pose_window_time.py`): {posewindow}"),
     (r"^refine_bounded_time\.json$", "`training.refine_bounded` (no host wait for the instance count) against this tree's plain loop of `color_refinement_step` calls (not a build of the parent commit), us per iteration, host clock around a device synchronise, interleaved regions in one process (`tools/refine_bounded_time.py`): {refinebounded}"),
@@ -301,6 +302,24 @@ def nvhead(path):
     return "; ".join(out) + f"; project B = 8 over B = 1: {j['project_B8_over_B1']:.3f}"
 
 
+def convnet(path):
+    j = _load(path) or {}
+    if not j.get("rows"):
+        return str(j.get("status", "not measured"))
+    out = []
+    for r in j["rows"]:
+        if r["what"] == "layer":
+            continue
+        out.append(f"{r['what']} B = {r['B']}: {r['hip']['median_ms']:.4f} vs {r['torch_conv2d']['median_ms']:.4f} (floor {r['mfma_floor_ms']:.4f}: "
+                   f"{r['fraction_of_floor']:.3f} of it)")
+    layers = [r for r in j["rows"] if r["what"] == "layer"]
+    if layers:
+        fr = [r["fraction_of_floor"] for r in layers]
+        ro = [r["hip_over_torch"] for r in layers]
+        out.append(f"{len(layers)} layer rows: fraction of the floor {min(fr):.3f} - {max(fr):.3f}, time over torch's {min(ro):.3f} - {max(ro):.3f}")
+    return "; ".join(out)
+
+
 def jointwindow(path):
     j = _load(path) or {}
     if not j.get("results"):
@@ -458,7 +477,7 @@ def fe_ab(path):
             f"{c['payload_ms']['change']:.4f} ms ({', '.join(f'{k} {v:.4f}' for k, v in c['payload_ms_of_band_variants'].items())})")
 
 
-EXTRACT = {"dm_share": dm_share, "dm_room": dm_room, "pc_kstats": pc_kstats, "pc_pmc": pc_pmc, "pc_ab": pc_ab, "fe_kstats": fe_kstats, "fe_pmc": fe_pmc, "fe_ab": fe_ab, "setup_pmc": setup_pmc, "kstats2": kstats2, "setup_ab": setup_ab, "scenelists": scenelists, "scene": scene, "ab": ab, "perview": perview, "mapidle": mapidle, "rccl": rccl, "kstats": kstats, "hbm": hbm, "sq": sq, "timeline": timeline, "bench": bench, "clocks": clocks, "gradbars": gradbars, "idle": idle, "landmark": landmark, "matching": matching, "pnp": pnp, "decoder": decoder, "fusion": fusion, "fusionmesh": fusionmesh, "localize": localize, "imageops": imageops, "sphead": sphead, "nvhead": nvhead, "jointwindow": jointwindow, "posewindow": posewindow, "refinebounded": refinebounded}
+EXTRACT = {"dm_share": dm_share, "dm_room": dm_room, "pc_kstats": pc_kstats, "pc_pmc": pc_pmc, "pc_ab": pc_ab, "fe_kstats": fe_kstats, "fe_pmc": fe_pmc, "fe_ab": fe_ab, "setup_pmc": setup_pmc, "kstats2": kstats2, "setup_ab": setup_ab, "scenelists": scenelists, "scene": scene, "ab": ab, "perview": perview, "mapidle": mapidle, "rccl": rccl, "kstats": kstats, "hbm": hbm, "sq": sq, "timeline": timeline, "bench": bench, "clocks": clocks, "gradbars": gradbars, "idle": idle, "landmark": landmark, "matching": matching, "pnp": pnp, "decoder": decoder, "fusion": fusion, "fusionmesh": fusionmesh, "localize": localize, "imageops": imageops, "sphead": sphead, "nvhead": nvhead, "convnet": convnet, "jointwindow": jointwindow, "posewindow": posewindow, "refinebounded": refinebounded}
 
 
 def describe(name, path):
