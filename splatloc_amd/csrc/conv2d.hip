@@ -3,18 +3,17 @@
 //   preprocess  NetVLAD's input normalisation clamp(x * 255, 0, 255) - mean[c]
 // The networks' definitions are not part of the reference tree: include/splatraster.h (splatraster_conv2d) and INTEGRATION.md §26
 // hold the layer's contract, which is this project's own.
-// Implicit GEMM on the exact-f32 MFMA: M = CV_CO output channels, N = a CV_ROWS x CV_COLS tile of output pixels, K = Cin k k walked
+// Implicit GEMM on the exact-f32 MFMA (mfma_tile.h has its operand and accumulator layout): M = CV_CO output channels, N = a CV_ROWS x CV_COLS tile of output pixels, K = Cin k k walked
 // in chunks of CV_CI input channels.  The im2col matrix never exists: a chunk's CV_CI planes of the pixel tile and its one-pixel
 // halo (zero outside the image) and the matching weight slab are staged in LDS, and the taps are shifted reads of that patch.
 // Determinism: no float atomics; every output is ONE fmaf chain from zero whose order is written down at the kernel and depends on
 // (Cin, ksize) and the tile constants alone, then + bias.  Built with -ffp-contract=off.
 #include "common.h"
+#include "mfma_tile.h"
 
 namespace sr {
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int CV_THREADS = 256;                       // four waves: wave w owns the tile's pixel rows 2 w and 2 w + 1
 constexpr int CV_CO = 64;                             // output channels of a workgroup: two 32-row MFMA blocks
@@ -30,9 +29,6 @@ constexpr int CV_WLD = 9 * CV_CI + 2;                 // row stride of the weigh
 static_assert(CV_PCH % 64 == 32 && CV_WLD % 64 == 10 && CV_CI % 2 == 0, "bank layout of the two operands");
 static_assert(CV_PLD == CV_PCOLS && CV_CO * 4 == CV_THREADS, "a plane is staged as it lies; four threads per weight row");
 static_assert(CV_ROWS % 2 == 0 && CV_COLS % 2 == 0 && CV_ROWS == 2 * (CV_THREADS / WAVE), "pool windows never straddle a tile or a wave");
-
-// row of a 32x32 accumulator register (decoder.hip's layout): column = lane & 31
-__device__ __forceinline__ int acc_row(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
 
 // One workgroup: image b, output channels [co0, co0 + CV_CO), output pixels [y0, y0 + CV_ROWS) x [x0, x0 + CV_COLS).
 // THE CHAIN of out[b, co, y, x], with xp the zero-padded input and p = (KS - 1) / 2:
@@ -124,9 +120,7 @@ conv2d_kernel(int32_t Cin, int32_t Cout, int32_t H, int32_t W, int32_t cotiles, 
 #pragma unroll
     for (int m = 0; m < 2; ++m)
 #pragma unroll
-        for (int n = 0; n < 2; ++n)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[m][n][i] = 0.f;
+        for (int n = 0; n < 2; ++n) acc_zero(acc[m][n]);
     const bool two = co0 + 32 < Cout;   // the second block of channels exists (wave-uniform)
     const float* wa = s_w + c * CV_WLD + half;
     const float* xa = s_x + half * CV_PCH + (2 * wave + 1 - P) * CV_PLD + (1 - P) + c;

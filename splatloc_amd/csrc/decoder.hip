@@ -4,7 +4,8 @@
 // Definition: include/splatraster.h (splatraster_decoder_layout) and INTEGRATION.md §19; design and measurements: DESIGN.md §18.
 //
 // Precision: f32 throughout.  Every matrix product runs on the exact f32-input MFMA v_mfma_f32_32x32x2_f32, whose result is a
-// k-ordered fmaf chain: each dot product starts from a zero accumulator and adds its products with k ascending.
+// k-ordered fmaf chain: each dot product starts from a zero accumulator and adds its products with k ascending (mfma_tile.h has
+// the operand and accumulator layout and the step of four k).
 //
 // Forward (decoder_fwd_kernel<D, F, RB>): one workgroup of 256 threads (4 waves) owns a tile of TM = 32 * RB points.
 //   1. x is normalised with the bounding box in f64 ((x - lo) / (hi - lo), from the f64 or the exactly widened f32 input) and rounded
@@ -41,6 +42,7 @@
 // backward 67 200 B; two workgroups (8 waves) per CU, i.e. 2 waves per SIMD, at most 256 VGPRs, no scratch.
 #include "common.h"
 #include "grid_encoding.h"
+#include "mfma_tile.h"
 
 #include <math.h>
 
@@ -53,8 +55,6 @@ constexpr int DEC_PAD = 4;         // floats of padding per panel row (keeps row
 constexpr int DEC_BWD_TM = 32;
 constexpr int DEC_BWD_MAX_WG = 64;
 constexpr int DEC_MAX_LAYERS = SPLATRASTER_DECODER_MAX_LAYERS;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct DecArgs {
     double lo[3], hi[3];
@@ -92,9 +92,6 @@ __host__ __device__ static inline int64_t acts_norm_offset(const A& d, int64_t N
 template <class A>
 __host__ __device__ static inline int64_t acts_xn_offset(const A& d, int64_t N) { return acts_norm_offset(d, N) + N; }
 
-// row of accumulator register `reg` in a 32x32 MFMA result (the column is lane & 31)
-__device__ __forceinline__ int acc_row(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
-
 // the value in a vector register the optimiser cannot see through: epilogue addresses built from it are computed per lane where they
 // are used, not hoisted out of the block loops as dozens of long-lived scalar registers
 __device__ __forceinline__ int in_vgpr(int v)
@@ -122,13 +119,10 @@ __device__ __forceinline__ void layer_block(f32x16 (&acc)[RB], const float* in, 
         for (int j = 0; j < 4; ++j) b[j] = *reinterpret_cast<const float4*>(wrow + k0 + 4 * j);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const float b0 = half ? b[j].y : b[j].x, b1 = half ? b[j].w : b[j].z;
+            const float2 bj = pick(b[j], half);   // once per j: every block of the tile shares it
 #pragma unroll
-            for (int rb = 0; rb < RB; ++rb) {
-                const float4 a = *reinterpret_cast<const float4*>(in + (rb * 32 + c) * ld_in + k0 + 4 * j);
-                acc[rb] = __builtin_amdgcn_mfma_f32_32x32x2f32(half ? a.y : a.x, b0, acc[rb], 0, 0, 0);
-                acc[rb] = __builtin_amdgcn_mfma_f32_32x32x2f32(half ? a.w : a.z, b1, acc[rb], 0, 0, 0);
-            }
+            for (int rb = 0; rb < RB; ++rb)
+                mfma_k4(acc[rb], pick(*reinterpret_cast<const float4*>(in + (rb * 32 + c) * ld_in + k0 + 4 * j), half), bj);
         }
     }
 }
@@ -207,9 +201,7 @@ decoder_fwd_kernel(int64_t N, GridArgs a, DecArgs d, const void* __restrict__ x,
         for (int cb = wave; cb < (No >> 5); cb += 4) {
             f32x16 acc[RB];
 #pragma unroll
-            for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) acc[rb][i] = 0.f;
+            for (int rb = 0; rb < RB; ++rb) acc_zero(acc[rb]);
             layer_block<RB>(acc, in, ld_in, W.w[l] + (size_t)(cb * 32 + c) * K, K, c, half);
             const int ldv = in_vgpr(ld_out), nov = in_vgpr(No), live = in_vgpr(h_out ? n_live : 0);
 #pragma unroll
@@ -234,6 +226,8 @@ decoder_fwd_kernel(int64_t N, GridArgs a, DecArgs d, const void* __restrict__ x,
         f32x16 acc[2][RB];
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
+            // element by element, not acc_zero(): zeroed as whole vectors, these 2 RB accumulators that live across the barrier give the
+            // forward another register assignment and schedule throughout; this form keeps its instructions as they were (HISTORY.md §35)
 #pragma unroll
             for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
@@ -382,8 +376,7 @@ decoder_bwd_kernel(int64_t N, int32_t n_tiles, DecBwdArgs d, DecWeights W, const
                 const int ob = b / nkb, kb = b - ob * nkb;
                 const bool kval = kb * 32 + c < K;
                 f32x16 acc;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+                acc_zero(acc);
 #pragma unroll 4
                 for (int p = 0; p < TM; p += 2) {
                     const float av = cur[(p + half) * ldp + ob * 32 + c];
@@ -405,14 +398,11 @@ decoder_bwd_kernel(int64_t N, int32_t n_tiles, DecBwdArgs d, DecWeights W, const
                 const bool kval = kb * 32 + c < K;
                 const float* wcol = W.w[l] + kb * 32 + (kval ? c : 0);
                 f32x16 acc;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+                acc_zero(acc);
 #pragma unroll 2
                 for (int o0 = 0; o0 < No; o0 += 4) {
-                    const float4 av = *reinterpret_cast<const float4*>(cur + c * ldp + o0);
                     const float b0 = wcol[(size_t)(o0 + half) * K], b1 = wcol[(size_t)(o0 + 2 + half) * K];
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(half ? av.y : av.x, kval ? b0 : 0.f, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(half ? av.w : av.z, kval ? b1 : 0.f, acc, 0, 0, 0);
+                    mfma_k4(acc, pick(*reinterpret_cast<const float4*>(cur + c * ldp + o0), half), make_float2(kval ? b0 : 0.f, kval ? b1 : 0.f));
                 }
                 if (kval) {
                     const int ldv = in_vgpr(ldh), kv = in_vgpr(K), live = in_vgpr(n_live);

@@ -5,15 +5,16 @@
 // hloc's NetVLAD layer is not part of the reference tree: include/splatraster.h (splatraster_netvlad_*) and INTEGRATION.md §25 hold
 // the definitions, which are this project's own.
 // Determinism: no float atomics; every sum has an order fixed by the shape alone (a contraction is the exact-f32 MFMA's fmaf chain
-// over ascending index, or two such chains added once; a reduction is a fixed tree), and a row b of any output never depends on the other rows of the batch.
+// over ascending index, mfma_tile.h, or two such chains added once; a reduction is a fixed tree, reduce.h's wave_sum_f32 among them),
+// and a row b of any output never depends on the other rows of the batch.
 // Built with -ffp-contract=off: the norms, the softmax and the centre term round operation by operation.
 #include "common.h"
+#include "mfma_tile.h"
+#include "reduce.h"
 
 namespace sr {
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int NV_MAX_K = SPLATRASTER_NETVLAD_MAX_K;
 constexpr int NV_T = 64;                        // locations of an assign workgroup / of an aggregation step
@@ -34,23 +35,10 @@ constexpr int PJ_BT = 32;                       // images that share one pass ov
 constexpr int PJ_KC = 32;                       // columns staged through LDS at a time
 constexpr int PJ_LD = PJ_KC + 4;
 constexpr int PJ_SLICE = 2048;                  // columns of a workgroup: 4096 x 32768 is 32 tiles x 16 slices = 2 workgroups per CU
-constexpr int PJ_ROWS = PJ_BT + PJ_OT;
-constexpr int PJ_PER_THREAD = PJ_ROWS * PJ_KC / PJ_THREADS;
 constexpr int PJ_FIN_THREADS = 256;
 constexpr float NV_EPS = 1e-12f;
 static_assert(NV_MAX_K == 64 && NV_T == 64, "two 32-wide blocks of clusters and of locations");
-static_assert(PJ_SLICE % PJ_KC == 0 && PJ_PER_THREAD % 4 == 0, "whole chunks, whole float4s");
-
-// row of a 32x32 accumulator register (decoder.hip's layout): column = lane & 31
-__device__ __forceinline__ int acc_row(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
-
-// ascending xor butterfly: every lane ends with the same total, the order is the lane count's alone
-__device__ __forceinline__ float wave_sum_f32(float v)
-{
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) v += __shfl_xor(v, d, WAVE);
-    return v;
-}
+static_assert(PJ_SLICE % PJ_KC == 0, "whole chunks");
 
 // One workgroup: image b, locations [n0, n0 + NV_T).  Column norms of the [D, NV_T] slab (four interleaved partial sums per
 // column, added in ascending order), then s = score_w xh over chunks of NV_DC channels, xh scaled on the way into LDS, then the
@@ -92,8 +80,7 @@ netvlad_assign_kernel(int32_t D, int32_t K, int32_t N, int32_t steps, const floa
     }
 
     f32x16 acc;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+    acc_zero(acc);
 #pragma unroll 1
     for (int d0 = 0; d0 < D; d0 += NV_DC) {
         __syncthreads();   // s_inv is written; the previous chunk's MFMAs have read the tiles
@@ -180,8 +167,7 @@ netvlad_aggregate_kernel(int32_t D, int32_t K, int32_t N, int32_t dblocks, const
     };
 
     f32x16 acc;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+    acc_zero(acc);
     fetch(0);
 #pragma unroll 1
     for (int step = 0; step < steps; ++step) {
@@ -194,12 +180,8 @@ netvlad_aggregate_kernel(int32_t D, int32_t K, int32_t N, int32_t dblocks, const
             const float* xa = s_t + c * NV_ALD + nh * 32;
             const float* aa = s_t + (NV_DT + kb * 32 + c) * NV_ALD + nh * 32;
 #pragma unroll
-            for (int j = 0; j < NV_T / 8; ++j) {
-                const float4 p = *reinterpret_cast<const float4*>(xa + 4 * j);
-                const float4 q = *reinterpret_cast<const float4*>(aa + 4 * j);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(half ? p.y : p.x, half ? q.y : q.x, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(half ? p.w : p.z, half ? q.w : q.z, acc, 0, 0, 0);
-            }
+            for (int j = 0; j < NV_T / 8; ++j)
+                mfma_k4(acc, pick(*reinterpret_cast<const float4*>(xa + 4 * j), half), pick(*reinterpret_cast<const float4*>(aa + 4 * j), half));
         }
     }
     __syncthreads();   // the tiles are free: the second halves travel through them, [kb][register][lane]
@@ -301,7 +283,9 @@ __global__ void __launch_bounds__(PJ_THREADS)
 netvlad_project_kernel(int32_t B, int32_t O, int64_t I, int32_t otiles, int32_t slices, const float* __restrict__ x,
                        const float* __restrict__ weight, float* __restrict__ partial)
 {
-    __shared__ __attribute__((aligned(16))) float s_stage[PJ_ROWS * PJ_LD];
+    using Tile = StackedTile<PJ_THREADS, PJ_BT, PJ_OT, PJ_KC, VEC>;   // image rows above the tile's weight rows (mfma_tile.h)
+    static_assert(Tile::LD == PJ_LD, "the staging area is declared with this stride");
+    __shared__ __attribute__((aligned(16))) float s_stage[Tile::ROWS * PJ_LD];
     const int tid = threadIdx.x, lane = tid & 63, c = lane & 31, half = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int ot = blockIdx.x % otiles, slice = (blockIdx.x / otiles) % slices, bc = blockIdx.x / otiles / slices;
@@ -310,68 +294,23 @@ netvlad_project_kernel(int32_t B, int32_t O, int64_t I, int32_t otiles, int32_t 
     const int64_t i1 = i0 + PJ_SLICE < I ? i0 + PJ_SLICE : I;
     const int nchunks = (int)((i1 - i0 + PJ_KC - 1) / PJ_KC);
 
-    float v[PJ_PER_THREAD];
-    // staged element e of a chunk: row = e / PJ_KC (image rows first, then weight rows), column = e % PJ_KC; zero outside B, O and I
-    auto fetch = [&](int chunk) {
-        const int64_t k0 = i0 + (int64_t)chunk * PJ_KC;
-        if (VEC) {
-#pragma unroll
-            for (int i = 0; i < PJ_PER_THREAD / 4; ++i) {
-                const int e = tid + PJ_THREADS * i, row = e >> 3;
-                const int64_t kk = k0 + 4 * (e & 7);
-                const bool isx = row < PJ_BT;
-                const int64_t rr = isx ? b0 + row : o0 + (row - PJ_BT);
-                float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (rr < (isx ? B : O) && kk < I) t = *reinterpret_cast<const float4*>((isx ? x : weight) + rr * I + kk);
-                v[4 * i] = t.x, v[4 * i + 1] = t.y, v[4 * i + 2] = t.z, v[4 * i + 3] = t.w;
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < PJ_PER_THREAD; ++i) {
-                const int e = tid + PJ_THREADS * i, row = e >> 5;
-                const int64_t kk = k0 + (e & 31);
-                const bool isx = row < PJ_BT;
-                const int64_t rr = isx ? b0 + row : o0 + (row - PJ_BT);
-                v[i] = (rr < (isx ? B : O) && kk < I) ? (isx ? x : weight)[rr * I + kk] : 0.f;
-            }
-        }
-    };
-    auto stage = [&]() {
-        if (VEC) {
-#pragma unroll
-            for (int i = 0; i < PJ_PER_THREAD / 4; ++i) {
-                const int e = tid + PJ_THREADS * i;
-                *reinterpret_cast<float4*>(s_stage + (e >> 3) * PJ_LD + 4 * (e & 7)) =
-                    make_float4(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]);
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < PJ_PER_THREAD; ++i) {
-                const int e = tid + PJ_THREADS * i;
-                s_stage[(e >> 5) * PJ_LD + (e & 31)] = v[i];
-            }
-        }
-    };
+    Tile tile;
+    auto fetch = [&](int chunk) { tile.fetch(x, b0, B, weight, o0, O, I, i0 + (int64_t)chunk * PJ_KC, tid); };
 
     f32x16 acc;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+    acc_zero(acc);
     fetch(0);
 #pragma unroll 1
     for (int chunk = 0; chunk < nchunks; ++chunk) {
         __syncthreads();   // the previous chunk's MFMAs have read the staging area
-        stage();
+        tile.stage(s_stage, tid);
         __syncthreads();
         if (chunk + 1 < nchunks) fetch(chunk + 1);   // in flight under the MFMAs
         const float* xa = s_stage + c * PJ_LD;
         const float* wa = s_stage + (PJ_BT + wave * 32 + c) * PJ_LD;
 #pragma unroll
-        for (int j = 0; j < PJ_KC / 4; ++j) {
-            const float4 p = *reinterpret_cast<const float4*>(xa + 4 * j);
-            const float4 q = *reinterpret_cast<const float4*>(wa + 4 * j);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(half ? p.y : p.x, half ? q.y : q.x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(half ? p.w : p.z, half ? q.w : q.z, acc, 0, 0, 0);
-        }
+        for (int j = 0; j < PJ_KC / 4; ++j)
+            mfma_k4(acc, pick(*reinterpret_cast<const float4*>(xa + 4 * j), half), pick(*reinterpret_cast<const float4*>(wa + 4 * j), half));
     }
     const int o = o0 + wave * 32 + c;
     if (o < O) {

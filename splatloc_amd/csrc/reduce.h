@@ -4,6 +4,8 @@
 //   block:    wave_sum per value, lane 0 of each wave stores s_red[wave][k], a barrier, then the wave partials are added in
 //             ascending wave index; all in double;
 //   partials: thread t adds partial[b][k] for b = t, t + THREADS, ... in that order, then the block (or wave) sum.
+// wave_sum_f32 is the same butterfly over floats, for the NetVLAD head's norms (netvlad_head.hip); it has a name of its own so that
+// no float argument of a wave_sum call, widened to double today, is ever captured by an overload.
 // NOT for sums that associate differently — a float butterfly in another order rounds differently, and these results are
 // compared bit for bit: pose.hip's L1 loss (descending float butterfly), decoder.hip's 32-lane butterfly32 and
 // grid_encoding.hip's reductions keep their own code, as do the min / max reductions of knn.hip and fusion.hip, and image_ops.hip's
@@ -22,6 +24,13 @@ __device__ __forceinline__ double wave_sum(double v)
 }
 
 __device__ __forceinline__ int wave_sum(int v)
+{
+#pragma unroll
+    for (int d = 1; d < WAVE; d <<= 1) v += __shfl_xor(v, d, WAVE);
+    return v;
+}
+
+__device__ __forceinline__ float wave_sum_f32(float v)
 {
 #pragma unroll
     for (int d = 1; d < WAVE; d <<= 1) v += __shfl_xor(v, d, WAVE);

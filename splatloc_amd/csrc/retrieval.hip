@@ -4,13 +4,12 @@
 //   pose_errors      utils/eval_utils.py:75-145                  SO3_to_quat, compute_quaternion_dist, eval_pose
 //   pose_invert      test.py:81-82                               camera-to-world from the world-to-camera PnP result
 #include "common.h"
+#include "mfma_tile.h"
 #include "scan.h"
 
 namespace sr {
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int RT_THREADS = 256;                 // four waves
 constexpr int RT_TN = 128;                      // database rows of a step: one 32-row block per wave
@@ -24,9 +23,6 @@ constexpr int RT_WIDE_RB = 4;                   // 128 query rows per workgroup 
 constexpr int RT_WIDE_MAX_K = 32;               // ... and the lists of 128 rows stay small
 static_assert((32 + RT_TN) * RT_LD >= 32 * RT_CLD, "the similarity tile must fit the staging area");
 static_assert(RT_MAX_K == 2 * WAVE, "a wave holds a list in two registers per lane");
-
-// row of a 32x32 accumulator register (decoder.hip's layout): column = lane & 31
-__device__ __forceinline__ int acc_row(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
 
 // (similarity, index) as one key: a larger key is a larger similarity, then a smaller index.  Never 0 for a real entry.
 __device__ __forceinline__ unsigned long long pack_key(float s, uint32_t n)
@@ -63,7 +59,8 @@ __device__ __forceinline__ void wave_insert(unsigned long long& l0, unsigned lon
 }
 
 // One workgroup: 32 * RB query rows against the database steps [blockIdx.y * steps_per_slice, ...).  Each wave accumulates RB
-// 32 x 32 blocks (query block x its 32 database rows of the step) over D with the exact-f32 MFMA; after a step the similarities
+// 32 x 32 blocks (query block x its 32 database rows of the step) over D with the exact-f32 MFMA (mfma_tile.h has the layout, the
+// chain and the staging, which is the same chain with float4 loads or scalar ones); after a step the similarities
 // of one query block at a time go through LDS to the wave that owns the query row (8 rows of the block per wave), which folds
 // them into the row's list (dynamic LDS: [32 * RB][k] keys).
 // direct: one slice, the lists are final -> idx / sims; else the slice's lists go to `partial` [Q][slices][k].
@@ -73,8 +70,10 @@ retrieval_kernel(int64_t Q, int64_t N, int32_t D, int32_t k, const float* __rest
                  int32_t steps_per_slice, int32_t direct, unsigned long long* __restrict__ partial, int64_t* __restrict__ idx,
                  float* __restrict__ sims, int32_t* __restrict__ status)
 {
-    constexpr int TQ = 32 * RB, ROWS = TQ + RT_TN, PER_THREAD = ROWS * RT_KC / RT_THREADS;
-    __shared__ __attribute__((aligned(16))) float s_stage[ROWS * RT_LD];
+    constexpr int TQ = 32 * RB;
+    using Tile = StackedTile<RT_THREADS, TQ, RT_TN, RT_KC, VEC>;   // query rows above the step's database rows (mfma_tile.h)
+    static_assert(Tile::LD == RT_LD, "the similarity tile is sized against this stride");
+    __shared__ __attribute__((aligned(16))) float s_stage[Tile::ROWS * RT_LD];
     extern __shared__ unsigned long long s_list[];   // [TQ][k]
     const int tid = threadIdx.x, lane = tid & 63, c = lane & 31, half = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -87,73 +86,29 @@ retrieval_kernel(int64_t Q, int64_t N, int32_t D, int32_t k, const float* __rest
 
     for (int i = tid; i < TQ * k; i += RT_THREADS) s_list[i] = 0;
 
-    float v[PER_THREAD];
-    // the staged element e of a chunk: row = e / RT_KC (query rows first), column = e % RT_KC; zero outside Q, N and D
+    Tile tile;
     auto fetch = [&](int64_t chunk) {
-        const int64_t n0 = (step0 + chunk / nkc) * RT_TN;
-        const int k0 = (int)(chunk % nkc) * RT_KC;
-        if (VEC) {
-#pragma unroll
-            for (int i = 0; i < PER_THREAD / 4; ++i) {
-                const int e = tid + RT_THREADS * i, row = e >> 3, kk = k0 + 4 * (e & 7);
-                const bool isq = row < TQ;
-                const int64_t r = isq ? q0 + row : n0 + (row - TQ);
-                const float* src = (isq ? query : db) + r * D + kk;
-                float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (r < (isq ? Q : N) && kk < D) x = *reinterpret_cast<const float4*>(src);
-                v[4 * i] = x.x, v[4 * i + 1] = x.y, v[4 * i + 2] = x.z, v[4 * i + 3] = x.w;
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < PER_THREAD; ++i) {
-                const int e = tid + RT_THREADS * i, row = e >> 5, kk = k0 + (e & 31);
-                const bool isq = row < TQ;
-                const int64_t r = isq ? q0 + row : n0 + (row - TQ);
-                v[i] = (r < (isq ? Q : N) && kk < D) ? (isq ? query : db)[r * D + kk] : 0.f;
-            }
-        }
+        tile.fetch(query, q0, Q, db, (step0 + chunk / nkc) * RT_TN, N, D, (int32_t)(chunk % nkc) * RT_KC, tid);
     };
-    auto stage = [&]() {
-        if (VEC) {
-#pragma unroll
-            for (int i = 0; i < PER_THREAD / 4; ++i) {
-                const int e = tid + RT_THREADS * i;
-                *reinterpret_cast<float4*>(s_stage + (e >> 3) * RT_LD + 4 * (e & 7)) =
-                    make_float4(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]);
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < PER_THREAD; ++i) {
-                const int e = tid + RT_THREADS * i;
-                s_stage[(e >> 5) * RT_LD + (e & 31)] = v[i];
-            }
-        }
-    };
-
     f32x16 acc[RB];
 #pragma unroll
-    for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[rb][i] = 0.f;
+    for (int rb = 0; rb < RB; ++rb) acc_zero(acc[rb]);
     bool nan_seen = false;
     if (nchunks > 0) fetch(0);
 #pragma unroll 1
     for (int64_t chunk = 0; chunk < nchunks; ++chunk) {
         __syncthreads();   // the previous chunk's MFMAs (or the previous step's merge) have read the staging area
-        stage();
+        tile.stage(s_stage, tid);
         __syncthreads();
         if (chunk + 1 < nchunks) fetch(chunk + 1);   // in flight under the MFMAs
         const float* qa = s_stage + c * RT_LD;
         const float* da = s_stage + (TQ + wave * 32 + c) * RT_LD;
 #pragma unroll
         for (int j = 0; j < RT_KC / 4; ++j) {
-            const float4 b = *reinterpret_cast<const float4*>(da + 4 * j);
+            const float2 b = pick(*reinterpret_cast<const float4*>(da + 4 * j), half);
 #pragma unroll
-            for (int rb = 0; rb < RB; ++rb) {
-                const float4 a = *reinterpret_cast<const float4*>(qa + rb * 32 * RT_LD + 4 * j);
-                acc[rb] = __builtin_amdgcn_mfma_f32_32x32x2f32(half ? a.y : a.x, half ? b.y : b.x, acc[rb], 0, 0, 0);
-                acc[rb] = __builtin_amdgcn_mfma_f32_32x32x2f32(half ? a.w : a.z, half ? b.w : b.z, acc[rb], 0, 0, 0);
-            }
+            for (int rb = 0; rb < RB; ++rb)
+                mfma_k4(acc[rb], pick(*reinterpret_cast<const float4*>(qa + rb * 32 * RT_LD + 4 * j), half), b);
         }
         if ((chunk + 1) % nkc != 0) continue;
         // the step is complete: per query block, similarities -> LDS [query row of the block][database row of the step]

@@ -23,6 +23,12 @@ RETRIEVAL_CASES = {
     5: (105, 33, 100, 64, 1),       # k == 1; Q one past a tile
     6: (106, 2, 64, 4096, 32),      # wide k
 }
+# the edges of the staging retrieval_kernel shares with the NetVLAD projection (csrc/mfma_tile.h), built like the cases above but
+# held to the oracle alone (no fixture entry): Q one past a query tile and N one past a database step, with
+EDGE_CASES = {
+    "d36": (111, 33, 129, 36, 5),   # D = a whole chunk and one float4: the float4 path where the base is aligned
+    "d33": (112, 33, 129, 33, 5),   # D = a whole chunk and one float: the scalar path
+}
 MAX_REDRAWS = 1000
 
 
@@ -52,7 +58,7 @@ def _noise(rng, shape, D):
 def retrieval_case(case):
     """(query f32 [Q, D], db f32 [N, D], k, draws): every consecutive gap among a row's top-(k + 1) f64 similarities exceeds
     4 gamma_D ||q|| max ||d||, twice what any f32 summation order can move a pair, so the indices are pinned."""
-    seed, Q, N, D, k = RETRIEVAL_CASES[case]
+    seed, Q, N, D, k = RETRIEVAL_CASES[case] if case in RETRIEVAL_CASES else EDGE_CASES[case]
     rng = np.random.default_rng(seed)
     db = _noise(rng, (N, D), D)
     db64 = db.astype(np.float64)

@@ -403,6 +403,13 @@ CASES = {
     "i2048_unaligned": lambda n: _project_case(n, "I = slice with an unaligned row base: scalar loads", 2, 5, I_SLICE, 15, unaligned=True),
     "i2049_o3": lambda n: _project_case(n, "I = slice + 1: a second slice of one column", 2, 3, I_SLICE + 1, 16),
     "i4100_b32": lambda n: _project_case(n, "I = 2 slice + 4 (float4 loads, three slices), B = b_tile", B_TILE, 5, 2 * I_SLICE + 4, 17),
+    # the edges of the staging the projection shares with retrieval (csrc/mfma_tile.h): a row tail of either operand at every I
+    "i36_o129_b33": lambda n: _project_case(n, "I = a chunk and one float4 (float4 loads), O = o_tile + 1, B = b_tile + 1", B_TILE + 1,
+                                            O_TILE + 1, 36, 18),
+    "i33_o129_b33": lambda n: _project_case(n, "I = a chunk and one float (scalar loads), O = o_tile + 1, B = b_tile + 1", B_TILE + 1,
+                                            O_TILE + 1, 33, 19),
+    "i2084_o129_b33": lambda n: _project_case(n, "I = slice + 36: the chunk and the float4 behind a slice edge", B_TILE + 1, O_TILE + 1,
+                                              I_SLICE + 36, 20),
     # the exact family
     "exact_k4": lambda n: exact_case(n, "exact: K = 4, N = T + 6, D = 8, O = 3, constant score bias", 2, 8, 4, T + 6, 3, 21, True),
     "exact_k64": lambda n: exact_case(n, "exact: K = 64, D = d_tile + 1, N = 2 T + 1, no biases", 1, D_TILE + 1, 64, 2 * T + 1, 2, 22, False),

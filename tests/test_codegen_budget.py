@@ -166,3 +166,23 @@ def test_scan_and_sort_kernels_keep_their_registers_and_lds():
         k = _kernel(u, name)
         assert k["ScratchSize"] == 0 and k["VGPRs Spill"] == 0 and k["SGPRs Spill"] == 0, (name, k)
         assert k["VGPRs"] <= vgprs and k["Occupancy"] >= waves and k["LDS Size"] <= lds, (name, k)
+
+
+def test_retrieval_kernels_keep_their_occupancy_lds_and_scratch():
+    """retrieval.hip since retrieval_kernel takes its accumulator layout, its step of four k and its staging from mfma_tile.h
+    (HISTORY.md §35): no spill, and retrieval_kernel<VEC, RB> at no fewer waves per SIMD, no more LDS and no more scratch than it
+    had with its own copy of each (159 / 219 / 86 / 138 VGPRs then; the two float4 forms kept 40 bytes per lane in scratch).  The
+    merge and the two pose kernels: the full 8 waves, nothing in scratch."""
+    u = _usage("retrieval.hip")
+    assert len(u) == 7, list(u)
+    for name, k in u.items():
+        assert k["VGPRs Spill"] == 0 and k["SGPRs Spill"] == 0, (name, k)
+    # <VEC, RB>: (waves per SIMD, LDS bytes, scratch bytes per lane)
+    pins = {(1, 4): (2, 36864, 40), (0, 4): (1, 36864, 0), (1, 1): (4, 23040, 40), (0, 1): (3, 23040, 0)}
+    for (vec, rb), (waves, lds, scratch) in pins.items():
+        k = _kernel(u, f"_ZN2sr12_GLOBAL__N_116retrieval_kernelILb{vec}ELi{rb}EE")
+        assert k["Occupancy"] >= waves and k["LDS Size"] <= lds and k["ScratchSize"] <= scratch, ((vec, rb), k)
+    for name in ("retrieval_merge_kernel", "pose_errors_kernel", "pose_invert_kernel"):
+        hits = [v for key, v in u.items() if name in key]
+        assert len(hits) == 1, (name, list(u))
+        assert hits[0]["Occupancy"] >= 8 and hits[0]["ScratchSize"] == 0, (name, hits[0])

@@ -1,7 +1,9 @@
 """The compiler's own resource report for csrc/conv2d.hip (`-Rpass-analysis=kernel-resource-usage`, read the way
 tests/test_codegen_budget.py reads it; hipcc cross-compiles gfx950 without a GPU): nothing in scratch, no VGPR or SGPR spill in any
 kernel of the file, and no kernel with more LDS than its arrays declare.  The convolution kernel holds 64 accumulator registers and
-prefetches a chunk of 16 patch and up to 20 weight values per thread: a spill there would put the prefetch into scratch memory."""
+prefetches a chunk of 16 patch and up to 20 weight values per thread: a spill there would put the prefetch into scratch memory.  The
+3x3 kernels are held at 2 waves per SIMD and the 1x1 kernels at 3, what each had with its own copy of the accumulator layout that is
+now csrc/mfma_tile.h's (HISTORY.md §35)."""
 from tests.test_codegen_budget import _usage
 
 # kernel -> bytes of LDS its __shared__ arrays declare: the patch, 8 planes of 10 x 34 pixels at a plane stride of 352 floats, and
@@ -34,8 +36,8 @@ def test_lds_is_no_more_than_declared():
     for key, lds in DECLARED.items():
         k = _find(u, key)
         assert k["LDS Size"] <= lds, (key, k, lds)
-    # two convolution workgroups per CU fit by LDS and by registers
+    # two convolution workgroups per CU fit by LDS and by registers; the 1x1 kernels, with a ninth of the weight prefetch, fit three
     for key in DECLARED:
         if key.startswith("conv2d"):
             k = _find(u, key)
-            assert 2 * k["LDS Size"] <= 160 * 1024 and k["Occupancy"] >= 2, (key, k)
+            assert 2 * k["LDS Size"] <= 160 * 1024 and k["Occupancy"] >= (3 if "ILi1E" in key else 2), (key, k)

@@ -64,6 +64,23 @@ def test_lds_and_occupancy_of_the_reference_configuration(compiled):
         assert k["VGPRs"] + k["AGPRs"] <= 256 and k["Occupancy"] >= 2, k
 
 
+def test_every_instantiation_keeps_its_waves_per_simd(compiled):
+    """What each kernel had with its own copy of the accumulator layout and of the step of four k that are now csrc/mfma_tile.h's
+    (HISTORY.md §35): every forward of tile height 64 at 2 waves per SIMD, every forward of tile height 32 at 4, the backward at 2
+    and within 115 VGPRs, and none above 256 registers per lane."""
+    usage, _, _ = compiled
+    fwd = {k: v for k, v in usage.items() if "decoder_fwd_kernel" in k}
+    tall = [v for k, v in fwd.items() if re.search(r"decoder_fwd_kernelILi\dELi\dELi2EE", k)]
+    low = [v for k, v in fwd.items() if re.search(r"decoder_fwd_kernelILi\dELi\dELi1EE", k)]
+    assert len(tall) == 8 and len(low) == 8, sorted(fwd)
+    for v in tall:
+        assert v["Occupancy"] >= 2 and v["VGPRs"] + v["AGPRs"] <= 256, v
+    for v in low:
+        assert v["Occupancy"] >= 4 and v["VGPRs"] + v["AGPRs"] <= 256, v
+    bwd = next(v for k, v in usage.items() if "decoder_bwd_kernel" in k)
+    assert bwd["Occupancy"] >= 2 and bwd["VGPRs"] <= 115 and bwd["VGPRs"] + bwd["AGPRs"] <= 256, bwd
+
+
 def test_mfma_in_forward_and_backward_and_no_compare_and_swap(compiled):
     _, bodies, text = compiled
     for name, body in bodies.items():

@@ -45,6 +45,34 @@ def test_retrieval_matches_the_reference(golden, case):
     assert np.all(err <= bound)
 
 
+@pytest.mark.parametrize("case", sorted(LR.EDGE_CASES))
+def test_retrieval_at_the_edges_of_the_shared_staging(case):
+    """Q = 33, N = 129 (a row tail of either operand) with D = 36 and D = 33: the oracle's indices (pinned by the cases' margin),
+    the similarities within the bound of the cases above; then the same numbers through views one float into their buffers, which
+    only the scalar loads can read: idx and sims bit for bit, D = 36 taking the float4 loads from its aligned buffers."""
+    q, db, k, _ = LR.retrieval_case(case)
+    assert (q.shape, db.shape) == ((33, db.shape[1]), (129, db.shape[1]))
+    i64, s64 = LR.retrieval_topk(q, db, k)
+    qd, dd = torch.from_numpy(q).cuda(), torch.from_numpy(db).cuda()
+    assert qd.data_ptr() % 16 == 0 and dd.data_ptr() % 16 == 0
+    idx, sims = L.retrieve(qd, dd, k=k)
+    assert np.array_equal(idx.cpu().numpy(), i64)
+    bound = LR.gamma(q.shape[1]) * _norms(q)[:, None] * _norms(db)[i64]
+    err = np.abs(sims.cpu().numpy().astype(np.float64) - s64)
+    print(f"case {case}: max |sims - f64| / bound = {float((err / bound).max()):.4f}")
+    assert np.all(err <= bound)
+
+    def shifted(t):
+        flat = torch.empty(t.numel() + 1, dtype=torch.float32, device="cuda")
+        view = flat[1:].view(t.shape)
+        view.copy_(t)
+        assert view.data_ptr() % 16 == 4 and view.is_contiguous()
+        return view
+
+    idx1, sims1 = L.retrieve(shifted(qd), shifted(dd), k=k)
+    assert torch.equal(idx1, idx) and torch.equal(sims1.view(torch.int32), sims.view(torch.int32))
+
+
 @pytest.mark.parametrize("which", (0, 1))
 def test_exact_cases_pin_the_tie_rule(which):
     q, db, k, idx_ref, sims_ref = LR.exact_case(which)

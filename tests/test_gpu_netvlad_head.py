@@ -14,9 +14,10 @@ Measured on the MI355X, error / bar (the bound is 1; for assign and inv_norm 1 m
   raw V      b32_d3_k2 0.254, n1_d3_k2 0.231, no_whitening 0.074, n63_d31_k63 0.052, n64_d32_k64 0.047, retrieval 0.044, the
              others below 0.025, layer 0.004; 0 on the exact family
   v          b32_d3_k2 0.086, no_whitening 0.041, n1_d3_k2 0.033, the others below 0.025
-  y raw      i3_otile_m1 0.348 (three terms), b32_d3_k2 0.183, zero_image 0.045, n65_d33_k1 0.041, n1_d3_k2 0.038, the others
-             below 0.03; the 2048- and 4100-column cases below 0.002; 0 on the exact family
-  y          b32_d3_k2 0.056, i3_otile_m1 0.028, the others below 0.02
+  y raw      i3_otile_m1 0.348 (three terms), b32_d3_k2 0.183, i36_o129_b33 0.084, i33_o129_b33 0.078, zero_image 0.045,
+             n65_d33_k1 0.041, n1_d3_k2 0.038, the others below 0.03; the 2048-, 2084- and 4100-column cases below 0.002; 0 on the
+             exact family
+  y          b32_d3_k2 0.056, i33_o129_b33 0.045, i36_o129_b33 0.035, i3_otile_m1 0.028, the others below 0.02
 """
 import ctypes as C
 import functools
@@ -86,26 +87,33 @@ def run_aggregate(x, a, inv, centers, flags):
     return v.done()
 
 
-def run_project(x, weight, bias, flags):
-    """`weight` as given: the caller decides its alignment"""
+def run_project(x, weight, bias, flags, partial=False):
+    """`weight` as given: the caller decides its alignment.  partial: also the slices' raw sums [slices][B][O], the workspace's
+    only section"""
     B, I = x.shape
     O = weight.shape[0]
     ws, nbytes = _ws(B, I, 1, 1, O)
     y = _Out(B, O)
     st = _native.load().splatraster_netvlad_project(B, O, I, _p(x), _p(weight), _p(bias), flags, _p(y.t), _p(ws), nbytes, _stream(x.device))
     assert st == 0
+    if partial:
+        slices = (I + R.I_SLICE - 1) // R.I_SLICE
+        return y.done(), ws[:slices * B * O * 4].view(torch.float32).view(slices, B, O)
     return y.done()
 
 
-def _weight(c):
-    w = c["whiten_w"]
-    if not c.get("unaligned"):
-        return w.cuda().contiguous()
+def _shifted(w):
+    """`w` on the device, one float into its buffer: only scalar loads can read it"""
     flat = torch.empty(w.numel() + 1, dtype=torch.float32, device="cuda")
     view = flat[1:].view(w.shape)
     view.copy_(w)
     assert view.data_ptr() % 16 == 4 and view.is_contiguous()
     return view
+
+
+def _weight(c):
+    w = c["whiten_w"]
+    return _shifted(w) if c.get("unaligned") else w.cuda().contiguous()
 
 
 @functools.lru_cache(maxsize=None)
@@ -206,6 +214,20 @@ def test_repeat_runs_are_bit_identical(name):
     assert first is not second and first.keys() == second.keys()
     for k in first:
         assert R.same_bits(first[k], second[k]), k
+
+
+@pytest.mark.parametrize("name", ("i36_o129_b33", "i2084_o129_b33"))
+def test_float4_and_scalar_loads_project_the_same_bits(name):
+    """the same numbers from 16-byte aligned buffers (I % 4 == 0: float4 loads) and through views one float into theirs (scalar
+    loads): the slices' raw sums and y, bit for bit"""
+    c = R.case(name)
+    x, W, wb = _dev(c["x"]), _dev(c["whiten_w"]), _dev(c["whiten_b"])
+    assert x.shape[1] % 4 == 0 and x.data_ptr() % 16 == 0 and W.data_ptr() % 16 == 0
+    y4, p4 = run_project(x, W, wb, R.L2NORM, partial=True)
+    y1, p1 = run_project(_shifted(c["x"]), _shifted(c["whiten_w"]), wb, R.L2NORM, partial=True)
+    assert p4.shape[0] == (2 if name.startswith("i2084") else 1)
+    assert R.same_bits(p4.cpu(), p1.cpu()) and R.same_bits(y4.cpu(), y1.cpu())
+    assert R.same_bits(y4.cpu(), device_run(name)["y"])
 
 
 @pytest.mark.parametrize("name", ("n63_d31_k63", "n65_d33_k1", "n129_d1_k2", "no_whitening", "zero_image"))

@@ -1,7 +1,9 @@
 """The compiler's own resource report for csrc/netvlad_head.hip (`-Rpass-analysis=kernel-resource-usage`, read the way
 tests/test_codegen_budget.py reads it; hipcc cross-compiles gfx950 without a GPU): nothing in scratch, no VGPR or SGPR spill in any
 kernel of the file, and no kernel with more LDS than its arrays declare.  The aggregation kernel prefetches a step of 24 rows per
-thread and the projection kernel a chunk of 20 floats: a spill there would put the prefetch into scratch memory."""
+thread and the projection kernel a chunk of 20 floats: a spill there would put the prefetch into scratch memory.  Every kernel is
+held at the waves per SIMD it had before the file took its accumulator layout, step of four k and projection staging from
+csrc/mfma_tile.h (HISTORY.md §35)."""
 from tests.test_codegen_budget import _usage
 
 # kernel -> bytes of LDS its __shared__ arrays declare
@@ -17,6 +19,17 @@ DECLARED = {
     "netvlad_project_kernelILb0E": (32 + 128) * 36 * 4,
     "netvlad_project_kernelILb1E": (32 + 128) * 36 * 4,
     "netvlad_project_finish_kernel": 4 * 4,
+}
+
+
+# kernel -> waves per SIMD
+WAVES = {
+    "netvlad_assign_kernel": 4,
+    "netvlad_aggregate_kernel": 6,
+    "netvlad_finish_kernel": 8,
+    "netvlad_project_kernelILb0E": 3,
+    "netvlad_project_kernelILb1E": 6,
+    "netvlad_project_finish_kernel": 8,
 }
 
 
@@ -42,3 +55,11 @@ def test_lds_is_no_more_than_declared():
     for key in ("netvlad_project_kernelILb0E", "netvlad_project_kernelILb1E"):
         k = _find(u, key)
         assert 2 * k["LDS Size"] <= 160 * 1024 and k["Occupancy"] >= 2, (key, k)
+
+
+def test_every_kernel_keeps_its_waves_per_simd():
+    u = _usage("netvlad_head.hip")
+    assert sorted(WAVES) == sorted(DECLARED)
+    for key, waves in WAVES.items():
+        k = _find(u, key)
+        assert k["Occupancy"] >= waves, (key, k, waves)
